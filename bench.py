@@ -9,6 +9,10 @@ that is already resident in HBM.  Workload = BASELINE.json's headline configurat
 
     python bench.py --gpus 1 --steps 1000 --warmup 50
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run times the headline only: set-up, warm-up, the timed sweeps, the result line.  --full adds everything else the
+line can carry (roofline and per-kernel tables, the further legs, the CPU baseline, the multi-rank pooling).  --dump-outputs DIR
+writes what the last timed sweep left for a caller (parameters, block structure, block states) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -93,6 +97,36 @@ def pmc_traffic(workload, kernel, key="bytes_fetch_doubled"):
         if len(hits) == 1:
             return hits[0][key]
     return None
+
+
+DUMP_LIMIT = 64 << 20     # bytes of all the files --dump-outputs writes
+
+
+def dump_outputs(chain, out_dir):
+    """What a caller of the timed path holds after its last sweep, as out_dir/<name>.npy: the parameters (theta = mean and
+    variance of every state, the transition matrix, the initial distribution) and the block structure of the sweep (block
+    starts, B + 1 of them, in float64 - exact for every uint32 position - and every block's state in float32).  Where the
+    block arrays would pass DUMP_LIMIT (weakly compressed workloads: ~10^8 blocks), a fixed, seeded sample of the blocks
+    is written instead, with its block indices (block_index.npy).  num_blocks.npy holds B either way."""
+    os.makedirs(out_dir, exist_ok=True)
+    A, pi = chain.transitions()
+    starts = chain.blocks()
+    states = chain.states()
+    B = states.size
+    arrays = {"theta": chain.theta().astype(np.float32), "transitions": A.astype(np.float32),
+              "initial": pi.astype(np.float32), "num_blocks": np.array([B], np.float64)}
+    per_block = 8 + 4                                          # a start (float64) and a state (float32)
+    if (B + 1) * per_block > DUMP_LIMIT - (1 << 20):
+        n = (DUMP_LIMIT - (1 << 20)) // (per_block + 8)        # ... and the block's index (float64)
+        idx = np.sort(np.random.default_rng(20240601).choice(B, size=n, replace=False))
+        arrays["block_index"] = idx.astype(np.float64)
+        arrays["block_starts"] = starts[idx].astype(np.float64)
+        arrays["block_states"] = states[idx].astype(np.float32)
+    else:
+        arrays["block_starts"] = starts.astype(np.float64)
+        arrays["block_states"] = states.astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def host_cpu():
@@ -206,6 +240,9 @@ def main():
     ap.add_argument("--no-scheme-legs", action="store_true", help="skip the recorded / config-2 mixture / config-2 static legs")
     ap.add_argument("--no-uncompressed-leg", action="store_true", help="skip the fourth leg (same trace, weights x 1e9: every position its own block)")
     ap.add_argument("--no-config-legs", action="store_true", help="skip the bounded legs of BASELINE configs 4 and 5 (one chain of each on this GPU)")
+    ap.add_argument("--full", action="store_true", help="beyond the headline: roofline and per-kernel tables, the further legs (each "
+                                                        "--no-*-leg still skips its own), the CPU baseline, the multi-rank pooling")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed sweep computed as DIR/<name>.npy")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -281,11 +318,13 @@ def main():
     DENSE_INST = dense_kernels(K, False)["trellis"]
     leg_steps = max(args.steps, LEG_MIN_STEPS)
     chain, elapsed, blocks, st0, st1 = run_leg(weight_summary=True, profile_level=1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(chain, args.dump_outputs)      # (before any further sweep of this chain)
     roof_family = "trellis" if dense_workload else "blocks_compact"
     scan_ms, scan_n = chain.profile_get(roof_family)           # HIP events around the kernel's launches
     null_ms, null_n = chain.profile_get("event_null")          # empty brackets recorded right behind them
     brackets_timed = scan_n
-    if scan_n < MIN_BRACKETS:
+    if args.full and scan_n < MIN_BRACKETS:
         # the timed region brackets every 32nd launch of the roofline kernel (a bracket costs ~5 us of stream time): with few
         # steps that is one sample or none.  A short pass OUTSIDE the timed region, same chain, same level, tops the sample
         # up to MIN_BRACKETS launches; kernel_avg_us is the average over all of them.
@@ -315,6 +354,27 @@ def main():
     out = None
     if rank == 0:
         B_avg = blocks / max(1, args.steps)
+        out = {
+            "metric": "block-updates/sec (Gibbs sweep) + HBM GB/s, 10^8 pos / 5 states",
+            "value": blocks_all / elapsed,
+            "unit": "block-updates/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": 1e3 * elapsed / args.steps,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic",
+            "config": {"workload": args.workload, "positions": T, "states": K, "blocks_per_sweep": B_avg,
+                       "compression": T / max(B_avg, 1.0), "block_structure": "dynamic", "chains": world,
+                       "parallelism": "chain-parallel x%d" % world,
+                       "cpu_baseline_sample": "port and reference binary: the same 10^8-position trace, a bounded number of sweeps"},
+            "forward_refits": st1["forward_refits"] - st0["forward_refits"],
+            "forward_serial": st1["forward_serial"] - st0["forward_serial"],
+        }
+    if rank == 0 and args.full:
         # an event pair measures ~3-5 us with nothing in between on this stack (marker packets + barrier): the
         # kernel's duration is the bracket minus the empty bracket (both reported; rocprofv3 agrees with the net)
         scan_raw_s = (scan_ms / max(1, scan_n)) * 1e-3
@@ -352,53 +412,33 @@ def main():
         frac = achieved / HBM_PEAK_GBS
         frac_upper = achieved_upper / HBM_PEAK_GBS
         assert frac <= frac_upper <= 1.0, "a roofline fraction above 1 means the byte count is not what the kernel moves"
-        out = {
-            "metric": "block-updates/sec (Gibbs sweep) + HBM GB/s, 10^8 pos / 5 states",
-            "value": blocks_all / elapsed,
-            "unit": "block-updates/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": args.workload, "positions": T, "states": K, "blocks_per_sweep": B_avg,
-                       "compression": T / max(B_avg, 1.0), "block_structure": "dynamic", "chains": world,
-                       "parallelism": "chain-parallel x%d" % world,
-                       "cpu_baseline_sample": "port and reference binary: the same 10^8-position trace, a bounded number of sweeps"},
-            "roofline": {"bound": "hbm", "kernel": DENSE_KERNEL + " (emission terms + forward filter + backward candidate maps)" if dense_workload
-                         else "hml_k_blocks_fused (block scan + block statistics + emission terms)",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": frac,
-                         "achieved_upper": achieved_upper, "frac_upper": frac_upper,
-                         "traffic": traffic, "traffic_source": PMC_FILES.get(args.workload) if traffic else None,
-                         "bytes_priced": ("frac: pmc FETCH_SIZE + WRITE_SIZE per launch as counted (lower bound); frac_upper: 2*FETCH_SIZE + "
-                                          "WRITE_SIZE (the guide's gfx950 correction; = `traffic`)") if traffic else "estimate (no committed profile)",
-                         "traffic_raw": traffic_raw,
-                         "kernel_avg_us": 1e6 * scan_avg_s, "kernel_bracket_us": 1e6 * scan_raw_s,
-                         "empty_bracket_us": 1e6 * null_s, "launches": scan_n, "launches_in_timed_region": brackets_timed,
-                         "launches_note": "HIP events on the chain's stream; launches beyond those of the timed region come from a "
-                                          "short extra pass of the same chain outside it (at least %d in all)" % MIN_BRACKETS,
-                         "limiter": "vector issue: about 530 VALU instructions per block-row, a third of them double precision (DESIGN.md 3a)" if dense_workload else
-                                    "latency: three dependent memory round trips + one inter-workgroup hand-off per launch",
-                         "profile_pair": None if dense_workload else
-                                         "rocprofv3 adds 1.5-2 us to every dispatch of this kernel: the line that pairs with "
-                                         "profiles/round5_kernel_stats_c3_bench.csv is profiles/round5_bench_c3_under_rocprof.json",
-                         "algorithmic_bytes_per_launch": algo_bytes,
-                         "algorithmic_equivalent_gbs": algo_bytes / scan_avg_s / 1e9,
-                         "algorithmic_speedup_vs_peak_float_stream": algo_bytes / scan_avg_s / 1e9 / HBM_PEAK_GBS,
-                         "sweep_frac": sweep_bytes / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS,
-                         "sweep_frac_note": "SURVEY.md 8d: algorithmic bytes of a whole sweep (4 T + B (36 + 8 K)) / sweep time / 8 TB/s"},
-            "forward_refits": st1["forward_refits"] - st0["forward_refits"],
-            "forward_serial": st1["forward_serial"] - st0["forward_serial"],
-        }
+        out["roofline"] = {"bound": "hbm", "kernel": DENSE_KERNEL + " (emission terms + forward filter + backward candidate maps)" if dense_workload
+                           else "hml_k_blocks_fused (block scan + block statistics + emission terms)",
+                           "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": frac,
+                           "achieved_upper": achieved_upper, "frac_upper": frac_upper,
+                           "traffic": traffic, "traffic_source": PMC_FILES.get(args.workload) if traffic else None,
+                           "bytes_priced": ("frac: pmc FETCH_SIZE + WRITE_SIZE per launch as counted (lower bound); frac_upper: 2*FETCH_SIZE + "
+                                            "WRITE_SIZE (the guide's gfx950 correction; = `traffic`)") if traffic else "estimate (no committed profile)",
+                           "traffic_raw": traffic_raw,
+                           "kernel_avg_us": 1e6 * scan_avg_s, "kernel_bracket_us": 1e6 * scan_raw_s,
+                           "empty_bracket_us": 1e6 * null_s, "launches": scan_n, "launches_in_timed_region": brackets_timed,
+                           "launches_note": "HIP events on the chain's stream; launches beyond those of the timed region come from a "
+                                            "short extra pass of the same chain outside it (at least %d in all)" % MIN_BRACKETS,
+                           "limiter": "vector issue: about 530 VALU instructions per block-row, a third of them double precision (DESIGN.md 3a)" if dense_workload else
+                                      "latency: three dependent memory round trips + one inter-workgroup hand-off per launch",
+                           "profile_pair": None if dense_workload else
+                                           "rocprofv3 adds 1.5-2 us to every dispatch of this kernel: the line that pairs with "
+                                           "profiles/round5_kernel_stats_c3_bench.csv is profiles/round5_bench_c3_under_rocprof.json",
+                           "algorithmic_bytes_per_launch": algo_bytes,
+                           "algorithmic_equivalent_gbs": algo_bytes / scan_avg_s / 1e9,
+                           "algorithmic_speedup_vs_peak_float_stream": algo_bytes / scan_avg_s / 1e9 / HBM_PEAK_GBS,
+                           "sweep_frac": sweep_bytes / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS,
+                           "sweep_frac_note": "SURVEY.md 8d: algorithmic bytes of a whole sweep (4 T + B (36 + 8 K)) / sweep time / 8 TB/s"}
         assert out["roofline"]["sweep_frac"] <= 1.0
 
     # per-kernel table (not part of the timed region): every launch of 200 further sweeps bracketed by HIP events on the
     # chain's stream, next to the PMC traffic of the committed profile
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         fam_kernel = dict(FAMILY_KERNEL)
         n_extra = 200
         if dense_workload:
@@ -444,7 +484,7 @@ def main():
 
     # what the other ranks cost this one: rank 0 repeats the timed region ALONE (the others wait at the barrier), so the line
     # carries the ratio the scaling curve should show if nothing but the shared host and power budget couples the chains
-    if dist_mode:
+    if args.full and dist_mode:
         if rank == 0:
             torch.cuda.synchronize()
             ta = time.perf_counter()
@@ -463,7 +503,7 @@ def main():
     # the collective run (round 5): the ranks' boundary lists through ncclAllGather (what the library picks for a strongly
     # compressed chain) on this rank's chain, and the dense int32 [K+1][T+1] payload through ncclAllReduce(sum) - the
     # gigabytes SURVEY.md section 5 prices - on a second chain attached to the same observations.
-    if dist_mode:
+    if args.full and dist_mode:
         # (the headline above is complete by now: a pooling that fails - the collective has never run on more than one GPU in the
         # build's environment - is reported in the line, it does not take the line away)
         try:
@@ -513,7 +553,7 @@ def main():
 
     # second leg: the same chain with the float weight stream (option weight_keys = 0): every sweep reads all T
     # float weights - the one genuinely bandwidth-bound kernel of the path, priced against the HBM roofline
-    if not args.no_stream_leg and world == 1:
+    if args.full and not args.no_stream_leg and world == 1:
         chain.close()
         chain, el2, bl2, c0, c1 = run_leg(weight_summary=False, profile_level=1, steps=leg_steps)
         f_ms, f_n = chain.profile_get("blocks_compact")
@@ -533,7 +573,7 @@ def main():
     # (-i F n 10, marginals on): hml_k_record inside the timed region.  (b) BASELINE config 2: 10^7 positions, scheme
     # M 100 0 S P F n 10 - mixture sweeps on dynamic blocks, then FB sweeps on a FIXED block structure (static blocks).
     # (c) steady state: 1000 sweeps of a chain that has 64 behind it (the forward warm-up of a young chain has settled).
-    if not args.no_scheme_legs and world == 1 and args.workload == "c3_1e8_k5_dynamic":
+    if args.full and not args.no_scheme_legs and world == 1 and args.workload == "c3_1e8_k5_dynamic":
         chain.close()
         ch = hammlet_amd.Chain(device=local_rank, seed=args.seed, chain_id=rank)
         ch.load(x)
@@ -642,7 +682,7 @@ def main():
     # third leg: several independent chains of the same workload on ONE GPU (chain-parallel inside the GPU: a single chain is
     # latency-bound and leaves most of the machine idle).  Two / three chains each on its own stream and host thread; eight
     # chains attached to ONE construction (hml_attach_observations) and batched through hml_iterate_many.
-    if not args.no_two_chain_leg and world == 1:
+    if args.full and not args.no_two_chain_leg and world == 1:
         import threading
         if chain is not None:
             chain.close()
@@ -786,7 +826,7 @@ def main():
 
     # fourth leg: SURVEY 8d's stress case C3u - the same trace with the breakpoint weights multiplied by 1e9, so that
     # every position is its own block (B = T): the regime in which the trellis itself, not the block scan, is the load
-    if not args.no_uncompressed_leg and world == 1 and args.workload == "c3_1e8_k5_dynamic":
+    if args.full and not args.no_uncompressed_leg and world == 1 and args.workload == "c3_1e8_k5_dynamic":
         if chain is not None:
             chain.close()
         chain = None
@@ -796,7 +836,7 @@ def main():
         out["uncompressed_c3u"] = leg
 
     # fifth leg: the other single-GPU workloads of BASELINE.json, bounded (their full lines: python bench.py --workload ...)
-    if not args.no_config_legs and world == 1 and args.workload == "c3_1e8_k5_dynamic":
+    if args.full and not args.no_config_legs and world == 1 and args.workload == "c3_1e8_k5_dynamic":
         if chain is not None:
             chain.close()
         chain = None
@@ -877,12 +917,12 @@ def main():
         leg["note"] = "BASELINE config 5's workload on ONE GPU (one of its 8 chains): simulated WGS read depth, the fused trellis path; sweeps 64..104"
         out["c5_2.5e8_depth_k5"] = leg
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(x, K, args.seed)
     elif rank == 0:
         out["cpu_baseline"] = None
 
-    if rank == 0:
+    if args.full and rank == 0:
         # the kernels SURVEY.md 8d and BASELINE.json's north star name, gathered into `roofline` from the legs that measured them
         roof = out["roofline"]
         if "float_stream" in out:   # 8d's literal roofline kernel: all T float weights streamed (bandwidth-bound; traffic = algorithmic bytes)
@@ -913,6 +953,7 @@ def main():
                            "compressed - latency-bound - and hml_k_trellis_rows (emission terms + filter + candidate maps in one pass) where they "
                            "are not - bound by vector issue; frac = counter bytes as counted / duration / 8 TB/s, frac_upper with the fetches doubled")
             roof["forward_trellis"] = fwd
+    if rank == 0:
         print(json.dumps(out))
     if dist is not None:
         dist.barrier()

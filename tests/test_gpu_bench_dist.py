@@ -25,7 +25,7 @@ def test_bench_multi_rank_branches_on_one_gpu():
     env = dict(os.environ, HML_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
-           "--workload", "c2_1e7_k5", "--no-stream-leg", "--no-two-chain-leg", "--no-uncompressed-leg", "--no-scheme-legs",
+           "--workload", "c2_1e7_k5", "--full", "--no-stream-leg", "--no-two-chain-leg", "--no-uncompressed-leg", "--no-scheme-legs",
            "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])

@@ -15,18 +15,18 @@ Q='simple_timer\|generateRocpd\|tool.cpp\|^$'
 
 PART=${2:-all}
 if [ "$PART" != "2" ]; then
-echo "== bench (driver settings)"; python3 $R/bench.py --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err
-echo "== bench (defaults)";        python3 $R/bench.py > $O/bench_default.json 2> $O/bench_default.err
-echo "== kernel stats";  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- python3 $R/bench.py --no-cpu-baseline --no-config-legs > $O/bench_under_rocprof.json 2> $O/stats.err
-echo "== pmc fetch";     HML_BENCH_NO_TORCH=1 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o run -- python3 $R/bench.py --steps 200 --warmup 50 --no-cpu-baseline --no-uncompressed-leg --no-config-legs > $O/pmc_fetch.json 2> $O/pmc_fetch.err
-echo "== pmc write";     HML_BENCH_NO_TORCH=1 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o run -- python3 $R/bench.py --steps 200 --warmup 50 --no-cpu-baseline --no-uncompressed-leg --no-config-legs > $O/pmc_write.json 2> $O/pmc_write.err
-echo "== c4 pmc fetch";  HML_BENCH_NO_TORCH=1 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/c4_fetch -o run -- python3 $R/bench.py --workload c4_1e8_k10 --steps 200 --warmup 64 --no-cpu-baseline --no-stream-leg --no-two-chain-leg > $O/c4_fetch.json 2> $O/c4_fetch.err
-echo "== c4 pmc write";  HML_BENCH_NO_TORCH=1 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/c4_write -o run -- python3 $R/bench.py --workload c4_1e8_k10 --steps 200 --warmup 64 --no-cpu-baseline --no-stream-leg --no-two-chain-leg > $O/c4_write.json 2> $O/c4_write.err
+echo "== bench (driver settings)"; python3 $R/bench.py --full --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err
+echo "== bench (defaults)";        python3 $R/bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+echo "== kernel stats";  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- python3 $R/bench.py --full --no-cpu-baseline --no-config-legs > $O/bench_under_rocprof.json 2> $O/stats.err
+echo "== pmc fetch";     HML_BENCH_NO_TORCH=1 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o run -- python3 $R/bench.py --full --steps 200 --warmup 50 --no-cpu-baseline --no-uncompressed-leg --no-config-legs > $O/pmc_fetch.json 2> $O/pmc_fetch.err
+echo "== pmc write";     HML_BENCH_NO_TORCH=1 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o run -- python3 $R/bench.py --full --steps 200 --warmup 50 --no-cpu-baseline --no-uncompressed-leg --no-config-legs > $O/pmc_write.json 2> $O/pmc_write.err
+echo "== c4 pmc fetch";  HML_BENCH_NO_TORCH=1 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/c4_fetch -o run -- python3 $R/bench.py --full --workload c4_1e8_k10 --steps 200 --warmup 64 --no-cpu-baseline --no-stream-leg --no-two-chain-leg > $O/c4_fetch.json 2> $O/c4_fetch.err
+echo "== c4 pmc write";  HML_BENCH_NO_TORCH=1 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/c4_write -o run -- python3 $R/bench.py --full --workload c4_1e8_k10 --steps 200 --warmup 64 --no-cpu-baseline --no-stream-leg --no-two-chain-leg > $O/c4_write.json 2> $O/c4_write.err
 fi
 if [ "$PART" = "1" ]; then
 cd $R
-python3 tools/pmc_summary.py $O/pmc_fetch $O/pmc_write $O/pmc_hbm_traffic.json "rocprofv3 --pmc <COUNTER> --output-format csv -- python3 bench.py --steps 200 --warmup 50 --no-cpu-baseline --no-uncompressed-leg --no-config-legs" > /dev/null
-python3 tools/pmc_summary.py $O/c4_fetch $O/c4_write $O/pmc_hbm_traffic_c4.json "rocprofv3 --pmc <COUNTER> --output-format csv -- python3 bench.py --workload c4_1e8_k10 --steps 200 --warmup 64 --no-cpu-baseline --no-stream-leg --no-two-chain-leg" > /dev/null
+python3 tools/pmc_summary.py $O/pmc_fetch $O/pmc_write $O/pmc_hbm_traffic.json "rocprofv3 --pmc <COUNTER> --output-format csv -- python3 bench.py --full --steps 200 --warmup 50 --no-cpu-baseline --no-uncompressed-leg --no-config-legs" > /dev/null
+python3 tools/pmc_summary.py $O/c4_fetch $O/c4_write $O/pmc_hbm_traffic_c4.json "rocprofv3 --pmc <COUNTER> --output-format csv -- python3 bench.py --full --workload c4_1e8_k10 --steps 200 --warmup 64 --no-cpu-baseline --no-stream-leg --no-two-chain-leg" > /dev/null
 python3 tools/kstats.py $O/stats > $O/kernel_stats_c3_bench.txt
 find $O/stats -name '*kernel_stats.csv' -exec cp {} $O/stats_kernel_stats.csv \;
 rm -rf $O/stats
@@ -42,7 +42,7 @@ echo "== c5 pmc write"; rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/c5_
 echo "== c5 stats";      rocprofv3 --kernel-trace --stats --output-format csv -d $O/c5_stats -o run -- python3 $R/tools/time_dense.py c5 20 > $O/dense_c5.txt 2> $O/c5_stats.err
 
 cd $R
-if [ "$PART" = "all" ]; then python3 tools/pmc_summary.py $O/pmc_fetch $O/pmc_write $O/pmc_hbm_traffic.json "rocprofv3 --pmc <COUNTER> --output-format csv -- python3 bench.py --steps 200 --warmup 50 --no-cpu-baseline --no-uncompressed-leg" > /dev/null; fi
+if [ "$PART" = "all" ]; then python3 tools/pmc_summary.py $O/pmc_fetch $O/pmc_write $O/pmc_hbm_traffic.json "rocprofv3 --pmc <COUNTER> --output-format csv -- python3 bench.py --full --steps 200 --warmup 50 --no-cpu-baseline --no-uncompressed-leg" > /dev/null; fi
 python3 tools/pmc_summary.py $O/dense_fetch $O/dense_write $O/pmc_hbm_traffic_c3u.json "rocprofv3 --pmc <COUNTER> --output-format csv -- python3 tools/time_dense.py c3u 20" > /dev/null
 python3 tools/pmc_summary.py $O/c5_fetch $O/c5_write $O/pmc_hbm_traffic_c5.json "rocprofv3 --pmc <COUNTER> --output-format csv -- python3 tools/time_dense.py c5 10" > /dev/null
 if [ "$PART" = "all" ]; then python3 tools/kstats.py $O/stats > $O/kernel_stats_c3_bench.txt; fi
@@ -73,7 +73,7 @@ rm -rf $O/sq_a_$W $O/sq_b_$W
 done
 cd $R
 # the other BASELINE configurations through the same script, end-to-end command lines, chains per GPU
-for W in c1_1e5_k3 c2_1e7_k5 c4_1e8_k10 c5_2.5e8_depth_k5; do python3 $R/bench.py --workload $W --no-cpu-baseline > $O/bench_$W.json 2> $O/bench_$W.err || true; done
+for W in c1_1e5_k3 c2_1e7_k5 c4_1e8_k10 c5_2.5e8_depth_k5; do python3 $R/bench.py --full --workload $W --no-cpu-baseline > $O/bench_$W.json 2> $O/bench_$W.err || true; done
 bash $R/tools/e2e_cli.sh > $O/cli_end_to_end_1e8.log 2>&1 || true
 bash $R/tools/e2e_small.sh > $O/cli_end_to_end_small.log 2>&1 || true
 cat $O/bench_driver.json; cat $O/dense_c3u.txt $O/dense_c5.txt; head -14 $O/kernel_stats_c3_bench.txt 2>/dev/null || true
