@@ -1,7 +1,9 @@
-"""Size-independent properties at BASELINE.json's full size (10^8 positions, 5 states, dynamic blocks), where the
-CPU checker is too slow to run inside the test suite: the block structure against an independent evaluation of
-its definition, conservation laws of the count pass and the marginals, run-to-run determinism, and equality of
-the two block-enumeration paths (group summary / float stream)."""
+"""Size-independent properties at BASELINE.json's full size (10^8 positions, 5 states, dynamic blocks), in addition to the
+bit-for-bit comparison with the CPU checker at that size (tests/test_gpu_fullsize_checker.py): the block structure
+against an independent evaluation of its definition, conservation laws of the count pass and the marginals,
+run-to-run determinism, and equality of the two block-enumeration paths (group summary / float stream).  They hold
+for chains far longer than the ones the checker follows (50 sweeps here), and they do not share the checker's
+arithmetic."""
 import numpy as np
 import pytest
 

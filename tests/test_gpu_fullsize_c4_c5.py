@@ -1,9 +1,11 @@
-"""Size-independent properties at the full sizes of BASELINE.json's configs 4 and 5, where the CPU checker is too slow
-to run inside the suite: C4 = 10^8 positions, 10 states (one of its 8 chains per GPU); C5 = 2.5*10^8
-simulated read-depth positions, 5-state model, compression ~1.5 (1.7*10^8 blocks per sweep: the dense forward
-geometry, the float weight stream, the two-level backward chain).  Checked: the block structure against its
-definition evaluated by numpy, the conservation laws of the count pass and of the marginals, equality of the chains
-that the alternative enumeration paths / forward geometries produce, bounded repair work, chain ids."""
+"""Size-independent properties at the full sizes of BASELINE.json's configs 4 and 5, in addition to the bit-for-bit
+comparison with the CPU checker (tests/test_gpu_fullsize_checker.py: C4 at full size, a 2.5*10^7 prefix of C5):
+C4 = 10^8 positions, 10 states (one of its 8 chains per GPU); C5 = 2.5*10^8 simulated read-depth positions, 5-state
+model, compression ~1.5 (1.7*10^8 blocks per sweep: the dense forward geometry, the float weight stream, the
+two-level backward chain).  Checked: the block structure against its definition evaluated by numpy, the conservation
+laws of the count pass and of the marginals, equality of the chains that the alternative enumeration paths / forward
+geometries produce, bounded repair work, chain ids - on longer chains than the checker follows, and at C5's whole
+length."""
 import numpy as np
 import pytest
 
