@@ -46,6 +46,7 @@ public:
     // length of the reference's count queue when all runs but the last have been added.
     uint64_t addSweep(const std::vector<uint32_t>& runStart, const std::vector<int16_t>& runState, uint64_t T) {
         const size_t R = runStart.size(), M = mStart.size();
+        if (R == 0 || T == 0) return 0;   // no runs or no positions: nothing was recorded, the segments stay what they were
         std::vector<uint32_t> start;
         std::vector<uint64_t> states;
         start.reserve(M + R);

@@ -7,6 +7,7 @@ import time
 
 import numpy as np
 
+from tests import hostile_inputs as hi
 from tests import oracle_lib as ol
 from tests.test_gpu_parity import run_both
 
@@ -16,21 +17,23 @@ ENV_KEYS = ("HML_DENSE_MIN_BLOCKS", "HML_FWD_CHUNK_DENSE", "HML_TRELLIS_FUSED", 
             "HML_WIDE_L", "HML_WIDE_LANES", "HML_MID_MIN_BLOCKS")
 
 
-def fuzz(hml, n_cfg, seed, log=None, many=False, compat=False, wide=False):
+def fuzz(hml, n_cfg, seed, log=None, many=False, compat=False, wide=False, data=None):
     """n_cfg random configurations; returns the number that ran identical (all, or an AssertionError names the first
     that differs).  The environment switches it sets are restored afterwards.  many: several chains through
     hml_iterate_many (_fuzz_many) instead of one through hml_iterate.  compat: the reference-compatible mode against the
     checker's REFERENCE mode (mt19937, libm, Kahan sums, size_t += float) - up to 64 states, chunk geometries that force
     wrong chunks.  wide: the default path's kernels for more than 16 states (hml_k_wide.h, hml_k_wide_lanes.h: the number of states at run
     time; a chunk a lane or a state a lane) against the checker's device mode - 2-64 states (HML_WIDE=1 sends models of up to 16 states there too), the
-    same chunk geometries."""
+    same chunk geometries.  data="hostile": the input comes from the families of tests/hostile_inputs.py (scaled, shifted, read depths of
+    1 to 5000, integer data full of ties, spikes) and T from a list that includes 1 ... 16, drawn from a random stream of their own -
+    without it every configuration is what it was before the argument existed."""
     saved = {k: os.environ.get(k) for k in ENV_KEYS}
     try:
         if many:
-            return _fuzz_many(hml, n_cfg, seed, log or (lambda *a, **k: None))
+            return _fuzz_many(hml, n_cfg, seed, log or (lambda *a, **k: None), data=data)
         if wide:
             os.environ["HML_WIDE"] = "1"
-        return _fuzz(hml, n_cfg, seed, log or (lambda *a, **k: None), compat=compat, wide=wide)
+        return _fuzz(hml, n_cfg, seed, log or (lambda *a, **k: None), compat=compat, wide=wide, data=data)
     finally:
         for k, v in saved.items():
             if v is None:
@@ -39,8 +42,9 @@ def fuzz(hml, n_cfg, seed, log=None, many=False, compat=False, wide=False):
                 os.environ[k] = v
 
 
-def _fuzz(hml, n_cfg, seed, log, compat=False, wide=False):
+def _fuzz(hml, n_cfg, seed, log, compat=False, wide=False, data=None):
     rng = np.random.default_rng(seed)
+    hrng = _hostile_rng(seed, data)
     bits = lambda a: np.ascontiguousarray(a, np.float32).view(np.uint32)
     t_start = time.time()
 
@@ -89,6 +93,14 @@ def _fuzz(hml, n_cfg, seed, log, compat=False, wide=False):
             x = ol.synth_depth(T, seed=int(rng.integers(1, 100)))
         else:
             x = np.stack([ol.trace(T, levels, int(rng.integers(1, 1000)) + d) for d in range(D)], axis=1).reshape(-1)
+        what = ""
+        if hrng is not None:   # one data dimension, the input and its length from tests/hostile_inputs.py
+            if D > 1:
+                D, P, K = 1, None, min(K, 16)
+            what, x = hi.fuzz_draw(hrng, T_max=65537 if K > 8 else 1 << 30)
+            T = x.size
+            if mult == 1e9 and T > 65537:
+                mult = kw["weight_mult"] = 1.0
         scheme = []
         for _ in range(int(rng.integers(1, 5))):
             tok = rng.choice(["F", "F", "M", "S", "D", "P"])
@@ -129,12 +141,20 @@ def _fuzz(hml, n_cfg, seed, log, compat=False, wide=False):
         run_both(o, g, scheme)
         ok = (np.array_equal(o.blocks(), g.blocks()) and np.array_equal(o.states(), g.states()) and np.array_equal(bits(o.theta()), bits(g.theta()))
               and hml.marginals_text(*g.marginals_rle()) == o.text("marginals"))
-        desc = "%3d %s T=%d K=%d D=%d dense=%d mult=%g self=%d scheme=%s  B=%d  %.0f s" % (it, "ok " if ok else "DIFF", T, K, D, dense, mult, self_trans, scheme, len(g.blocks()) - 1, time.time() - t_start)
+        desc = "%3d %s %s T=%d K=%d D=%d dense=%d mult=%g self=%d scheme=%s  B=%d  %.0f s" % (it, "ok " if ok else "DIFF", what, T, K, D, dense, mult, self_trans, scheme, len(g.blocks()) - 1, time.time() - t_start)
         log(desc)
         assert ok, desc
         g.close(); o.close()
 
     return n_cfg
+
+
+def _hostile_rng(seed, data):
+    """the random stream of the hostile draws - apart from the configurations' own, which stays what it was"""
+    if data is None:
+        return None
+    assert data == "hostile", data
+    return np.random.default_rng([seed, 0x686f7374])
 
 
 def _setenv(name, value):
@@ -144,11 +164,12 @@ def _setenv(name, value):
         os.environ[name] = str(value)
 
 
-def _fuzz_many(hml, n_cfg, seed, log):
+def _fuzz_many(hml, n_cfg, seed, log, data=None):
     """Several chains of one trace through hml_iterate_many - attached to one construction (hml_attach_observations: the
     many-chain block kernel) or with private ones, in 1-4 groups of chains, tiles of several batches, tiny block capacities,
     weakly compressed chains that leave the batch - each against the checker's chain of the same (seed, chain) run alone."""
     rng = np.random.default_rng(seed)
+    hrng = _hostile_rng(seed, data)
     bits = lambda a: np.ascontiguousarray(a, np.float32).view(np.uint32)
     t_start = time.time()
     for it in range(n_cfg):
@@ -172,6 +193,10 @@ def _fuzz_many(hml, n_cfg, seed, log):
             _setenv(k, v)
         seed_c = int(rng.integers(0, 1 << 30))
         x = ol.synth_depth(T, seed=int(rng.integers(1, 100))) if rng.random() < 0.15 else ol.trace(T, min(K, 5), int(rng.integers(1, 1000)))
+        what = ""
+        if hrng is not None:
+            what, x = hi.fuzz_draw(hrng, T_max=65537 if K > 8 else 1 << 30)
+            T = x.size
         scheme = []
         for _ in range(int(rng.integers(1, 5))):
             tok = rng.choice(["F", "F", "F", "M", "S", "D", "P"])
@@ -180,6 +205,7 @@ def _fuzz_many(hml, n_cfg, seed, log):
             scheme.append(("F", int(rng.integers(1, 5)), 1))
         pairs = []
         weights_key = int(rng.choice([1, 1, 2, 0]))
+        refused = None
         for chain in range(n):
             o = ol.OracleChain(K=K, seed=seed_c, chain=chain, rng=ol.RNG_CTR, math=ol.MATH_DEV, reduce=ol.REDUCE_DEV, **kw)
             g = hml.Chain(device=0, seed=seed_c, chain_id=chain)
@@ -191,13 +217,28 @@ def _fuzz_many(hml, n_cfg, seed, log):
                 g.load(x)
                 if mult != 1.0:
                     g.scale_weights(mult)
-            po = o.autoprior()
+            try:
+                po = o.autoprior()
+            except RuntimeError as err:   # the reference's own exception (one position, constant data): the GPU must raise it too
+                try:
+                    g.autoprior(kw["e_var"], kw["e_p"])
+                    raise AssertionError("configuration %d: the checker raised %r, the GPU did not" % (it, str(err)))
+                except hml.HmlError as gerr:
+                    assert str(err) in str(gerr), (str(err), str(gerr))
+                refused = str(err)
+                pairs.append((o, g))
+                break
             pg = g.autoprior(kw["e_var"], kw["e_p"])
             assert np.array_equal(bits(po), bits(pg)), ("autoprior", it, chain)
             o.init_model()
             g.set_model(K, pg, kw["t_off"], kw["t_diag"], kw["pi_alpha"], self_trans)
             o.set_record(marginals=True)
             pairs.append((o, g))
+        if refused is not None:
+            log("%3d ok  (both raise: %s)" % (it, refused))
+            for o, g in reversed(pairs):
+                g.close(); o.close()
+            continue
         gs = [g for _, g in pairs]
         pending = True
         for tok in scheme:
@@ -229,8 +270,8 @@ def _fuzz_many(hml, n_cfg, seed, log):
             if not ok:
                 break
         B = len(gs[0].blocks()) - 1
-        desc = "%3d %s T=%d K=%d chains=%d attached=%d mult=%g self=%d env=%s scheme=%s  B=%d  %.0f s" % (
-            it, "ok " if ok else "DIFF (chain %d)" % chain, T, K, n, attached, mult, self_trans,
+        desc = "%3d %s %s T=%d K=%d chains=%d attached=%d mult=%g self=%d env=%s scheme=%s  B=%d  %.0f s" % (
+            it, "ok " if ok else "DIFF (chain %d)" % chain, what, T, K, n, attached, mult, self_trans,
             {k[4:]: (None if v is None else int(v)) for k, v in env.items()}, scheme, B, time.time() - t_start)
         log(desc)
         assert ok, desc

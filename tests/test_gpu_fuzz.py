@@ -49,3 +49,15 @@ def test_bounded_fuzz_of_the_path_for_many_states(hml):
     tokens, read-depth input, and chunk geometries from the sequential form to chunks of one block without warm-up, where chunks
     start wrong and run again."""
     assert fuzz(hml, 160, 20261007, wide=True) == 160
+
+
+def test_bounded_fuzz_on_hostile_inputs(hml):
+    """The same differential runs on inputs that are not a unit-scale Gaussian trace (tests/hostile_inputs.py: scaled by 2^+-10,
+    2^+-40, 10^+-3, shifted by up to 1000, read depths of 1 to 5000, integer plateaus / alternation / ramp, spikes of +-10^3) and of
+    1 to 65537 positions, 1 ... 16 included (below one group of the weight summary, one wavefront, one chunk; where the reference
+    refuses the input, the GPU has to raise the same message): 100 single chains, 30 batches of chains, 30 configurations of the
+    path for many states against the checker's device mode, 30 of the reference-compatible mode against its reference mode."""
+    assert fuzz(hml, 100, 20261101, data="hostile") == 100
+    assert fuzz(hml, 30, 20261102, many=True, data="hostile") == 30
+    assert fuzz(hml, 30, 20261103, wide=True, data="hostile") == 30
+    assert fuzz(hml, 30, 20261104, compat=True, data="hostile") == 30
