@@ -84,6 +84,10 @@ SIGNATURES = {
     "hml_max_segmentation": (C.c_int, [_P, C.POINTER(C.c_uint64), _P, _P]),
     "hml_marginals_dense_device": (C.c_int, [_P, _P, _P]),
     "hml_recorded_sweeps": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "hml_set_level_recording": (C.c_int, [_P, C.c_int]),
+    "hml_levels_rle": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _P, _P, _P]),
+    "hml_levels_dense_device": (C.c_int, [_P, _P]),
+    "hml_levels_merge": (C.c_int, [_P, _P]),
     "hml_categorical_draw": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_uint32)]),
     "hml_relabel_permutation": (C.c_int, [_P, _P]),
     "hml_pool_payload_size": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
@@ -108,7 +112,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 3   # hml_abi_version() of include/hml.h this mirror was written against
+ABI_VERSION = 4   # hml_abi_version() of include/hml.h this mirror was written against
 
 
 def load_library(path=None):
@@ -422,6 +426,29 @@ class Chain:
             p = perm.ctypes.data
         _check(self.lib.hml_marginals_dense_device(self.h, out_ptr, p))
 
+    # ---- emission levels per position ---------------------------------------------------
+    def set_level_recording(self, on=True):
+        """accumulate the emission level mu(q_t) of every recorded sweep from now on (hml_set_level_recording)"""
+        _check(self.lib.hml_set_level_recording(self.h, 1 if on else 0))
+
+    def levels_rle(self):
+        """(seg_len[M], n_recorded, sum[D, M], sum_sq[D, M]): the sums of the level and of its square over the recorded sweeps"""
+        m, n = C.c_uint64(), C.c_uint64()
+        _check(self.lib.hml_levels_rle(self.h, C.byref(m), C.byref(n), None, None, None))
+        seg = np.empty(m.value, np.uint64)
+        s1 = np.empty((self.D, m.value), np.float64)
+        s2 = np.empty((self.D, m.value), np.float64)
+        _check(self.lib.hml_levels_rle(self.h, C.byref(m), C.byref(n), seg.ctypes.data, s1.ctypes.data, s2.ctypes.data))
+        return seg, n.value, s1, s2
+
+    def levels_dense_device(self, out_ptr):
+        """posterior mean (row 2 d) and standard deviation (row 2 d + 1) per position into a device buffer float32 [2 D][T]"""
+        _check(self.lib.hml_levels_dense_device(self.h, out_ptr))
+
+    def merge_levels(self, other):
+        """add `other`'s recorded levels into this chain's (same GPU, positions and dimensions); no relabelling involved"""
+        _check(self.lib.hml_levels_merge(self.h, other.h))
+
     # ---- chain-parallel pooling ---------------------------------------------------------
     def relabel_permutation(self):
         perm = np.empty(self.K, np.int32)
@@ -558,6 +585,19 @@ def iterate_many(chains, method, iterations, thinning=0):
     lib = load_library()
     arr = (_P * len(chains))(*[c.h for c in chains])
     _check(lib.hml_iterate_many(C.cast(arr, _P), len(chains), method.encode(), iterations, thinning))
+
+
+def levels_mean_sd(n, s1, s2):
+    """Posterior mean and standard deviation of the level from Chain.levels_rle()'s sums, as float32: S1 / N and
+    sqrt(max(0, S2 / N - (S1 / N)^2)) in double, rounded once - the formula of hml_levels_dense_device.  n = 0: NaN."""
+    s1 = np.asarray(s1, np.float64)
+    s2 = np.asarray(s2, np.float64)
+    if n == 0:
+        nan = np.full(s1.shape, np.nan, np.float32)
+        return nan, nan.copy()
+    mean = s1 / np.float64(n)
+    var = s2 / np.float64(n) - mean * mean
+    return mean.astype(np.float32), np.sqrt(np.maximum(var, 0.0)).astype(np.float32)
 
 
 def marginals_text(seg, cnt):

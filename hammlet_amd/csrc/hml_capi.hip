@@ -103,7 +103,8 @@ HML_KERNEL void hml_k_debug_eval(int fn, const float* __restrict__ a, const floa
 extern "C" {
 
 const char* hml_last_error(void) { return g_err.c_str(); }
-uint32_t hml_abi_version(void) { return 3; }   // 2: hml_stats.fused_fallbacks, hml_allreduce_marginals_perm, hml_pool_permutation, option "compat"; 3: hml_attach_observations
+uint32_t hml_abi_version(void) { return 4; }   // 2: hml_stats.fused_fallbacks, hml_allreduce_marginals_perm, hml_pool_permutation, option "compat"; 3: hml_attach_observations;
+                                                // 4: emission levels per position (hml_set_level_recording, hml_levels_rle, hml_levels_dense_device, hml_levels_merge)
 const char* hml_device_arch(void) { return "gfx950"; }
 int hml_device_count(int* n) {
     if (!n) return set_err(HML_ERR_ARG, "null argument");
@@ -172,6 +173,7 @@ int hml_create(hml_ctx** out, int device, uint64_t seed, uint32_t chain_id, void
     if (const char* e = getenv("HML_COMPAT")) c->compat = atoi(e) != 0;   // option "compat" for unmodified callers (`hammlet -compat`)
     if (const char* e = getenv("HML_TRELLIS_TUNE")) c->tre_autotune = atoi(e) != 0;
     if (const char* e = getenv("HML_FUSED_SPIN_LIMIT")) c->fused_spin_limit = (uint32_t)strtoul(e, nullptr, 10);
+    if (const char* e = getenv("HML_LEVELS")) c->rec_levels = c->levels_asked = atoi(e) != 0;   // hml_set_level_recording for unmodified callers (`hammlet -O L`)
     if (const char* e = getenv("HML_MAX_BLOCKS")) c->cap_opt = strtoull(e, nullptr, 10);   // option "max_blocks" (tests: a tiny capacity exercises the growth everywhere)
     if (device < 64) g_live_ctx[device].fetch_add(1);
     *out = c;
@@ -210,7 +212,7 @@ static void free_all(hml_ctx* c) {
     trace_release(c);
     free_sweep_buffers(c);
     void* ptrs[] = {c->d_group_word, c->d_wave_total, c->d_stage, c->d_span_count, c->d_starts, c->d_bstat, c->d_eprobe, c->d_aprobe, c->d_coarse1,
-                    c->d_diff, c->d_boundary, c->d_mdl, c->d_many};
+                    c->d_diff, c->d_boundary, c->d_levels, c->d_lev_boundary, c->d_mdl, c->d_many};
     for (void* p : ptrs) if (p) hipFree(p);
     if (c->h_B) hipHostFree(c->h_B);
     c->h_B = nullptr;
@@ -921,6 +923,15 @@ int hml_set_recording(hml_ctx* c, int marginals, hml_record_cb cb, void* user) {
     return 0;
 }
 
+int hml_set_level_recording(hml_ctx* c, int on) {
+    if (!c) return set_err(HML_ERR_ARG, "null context");
+    c->rec_levels = on != 0;
+    if (on) c->levels_asked = true;
+    // (recorded sweeps are never replayed from a captured graph - hml_iterate - but a graph captured under the other setting goes anyway)
+    if (c->graph_exec) { if (int r = ctx_bind(c)) return r; hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
+    return 0;
+}
+
 int hml_enable_probes(hml_ctx* c, int on) {
     if (!c || !c->model_set) return set_err(HML_ERR_ARG, "model not set");
     if (int r = ctx_bind(c)) return r;
@@ -1036,6 +1047,7 @@ static int sweep_compat(hml_ctx* c, char method, bool record) {
         if (int r = ensure_marginal_buffers(c)) return r;
         hipLaunchKernelGGL(hml_k_record, dim3(grid_for(hint, 256, 64, 16384)), dim3(256), 0, s, c->d_q, c->d_starts, c->d_mdl, c->d_diff, c->d_boundary);
     }
+    if (record && c->rec_levels) { if (int r = launch_levels_record(c, s, hint)) return r; }   // (hml_k_compat_update above is this sweep's parameter update)
     KLAUNCH_CHECK();
     return 0;
 }
@@ -1127,6 +1139,7 @@ static int sweep_wide(hml_ctx* c, char method, bool record) {
         ProfScope ps(c, "params");
         hipLaunchKernelGGL(hml_k_wide_params, dim3(1), dim3(1024), 0, s, c->d_mdl, c->d_partial, (hml_wide_acc*)c->d_wacc, 0);
     }
+    if (record && c->rec_levels) { if (int r = launch_levels_record(c, s, hint)) return r; }   // (after the update: hml_k_levels.h)
     KLAUNCH_CHECK();
     return 0;
 }
@@ -1537,6 +1550,127 @@ int hml_marginals_rle(hml_ctx* c, uint64_t* n_segments, int* n_columns, uint64_t
         seg_len[i] = (uint64_t)((i + 1 < M ? h_seg[i + 1] : T) - h_seg[i]);
         if (counts) for (int s = 0; s < ncol; ++s) counts[i * ncol + s] = cur[s];
     }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------- emission levels (hml_k_levels.h)
+}  // extern "C"
+
+// the levels' segments on the device: starts d_seg[M] and, per row, the inclusive sums over the segments d_sum[2 D][M]
+static int gather_level_segments(hml_ctx* c, uint64_t* M_out, DevBuf& d_seg, DevBuf& d_sum) {
+    const uint32_t T = (uint32_t)c->T;
+    const int rows = 2 * c->D;
+    DevBuf d_cnt, d_off, d_cs;
+    HIPCHK(hipMalloc(&d_cnt.p, c->n_spans * sizeof(uint32_t)));
+    HIPCHK(hipMalloc(&d_off.p, c->n_spans * sizeof(uint32_t)));
+    hipLaunchKernelGGL(hml_k_marg_count, dim3((c->n_spans + 3) / 4), dim3(256), 0, c->stream, c->d_lev_boundary, T, d_cnt.as<uint32_t>());
+    std::vector<uint32_t> h_cnt(c->n_spans), h_off(c->n_spans);
+    HIPCHK(hipMemcpyAsync(h_cnt.data(), d_cnt.p, c->n_spans * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    uint64_t M = 0;
+    for (uint32_t i = 0; i < c->n_spans; ++i) { h_off[i] = (uint32_t)M; M += h_cnt[i]; }
+    HIPCHK(hipMemcpyAsync(d_off.p, h_off.data(), c->n_spans * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMalloc(&d_seg.p, (M + 1) * sizeof(uint32_t)));
+    HIPCHK(hipMalloc(&d_sum.p, M * rows * sizeof(double)));
+    const uint32_t n_chunks = (uint32_t)((M + HML_LEV_CHUNK - 1) / HML_LEV_CHUNK);
+    HIPCHK(hipMalloc(&d_cs.p, (uint64_t)n_chunks * rows * sizeof(double)));
+    hipLaunchKernelGGL(hml_k_marg_scatter, dim3((c->n_spans + 3) / 4), dim3(256), 0, c->stream, c->d_lev_boundary, T, d_off.as<uint32_t>(), d_seg.as<uint32_t>());
+    hipLaunchKernelGGL(hml_k_levels_gather, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, c->stream, c->d_levels, T, rows, d_seg.as<uint32_t>(), (uint32_t)M, d_sum.as<double>());
+    const dim3 sgrid((unsigned)grid_for(n_chunks, 1, 1, 4096), (unsigned)rows);
+    hipLaunchKernelGGL(hml_k_levels_scan_partial, sgrid, dim3(256), 0, c->stream, d_sum.as<double>(), (uint32_t)M, n_chunks, d_cs.as<double>());
+    hipLaunchKernelGGL(hml_k_levels_scan_chunks, dim3(rows), dim3(1024), 0, c->stream, d_cs.as<double>(), n_chunks);
+    hipLaunchKernelGGL(hml_k_levels_scan_final, sgrid, dim3(256), 0, c->stream, d_sum.as<double>(), (uint32_t)M, n_chunks, d_cs.as<double>());
+    KLAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *M_out = M;
+    return 0;
+}
+
+static int levels_ready(hml_ctx* c, hml_model* m) {
+    if (!c->levels_asked) return set_err(HML_ERR_ARG, "no emission levels were recorded by this context: enable them with hml_set_level_recording (or HML_LEVELS=1) before the recorded sweeps");
+    if (int r = ensure_level_buffers(c)) return r;   // (asked for, but no sweep was recorded yet: one segment, zero sums)
+    if (int r = fetch_model(c, m)) return r;
+    if (m->err_code) { char buf[256]; return set_err(HML_ERR_MODEL, deverr_text(m->err_code, m->err_value, buf, sizeof buf)); }
+    return 0;
+}
+
+extern "C" {
+
+int hml_levels_rle(hml_ctx* c, uint64_t* n_segments, uint64_t* n_recorded, uint64_t* seg_len, double* sum, double* sum_sq) {
+    NEED_MODEL();
+    if (!n_segments) return set_err(HML_ERR_ARG, "null argument");
+    hml_model m; if (int r = levels_ready(c, &m)) return r;
+    const uint32_t T = (uint32_t)c->T;
+    const int D = c->D;
+    uint64_t M = 0;
+    DevBuf b_seg, b_sum;
+    if (int r = gather_level_segments(c, &M, b_seg, b_sum)) return r;
+    *n_segments = M;
+    if (n_recorded) *n_recorded = m.n_levels_recorded;
+    if (!seg_len) return 0;
+    std::vector<uint32_t> h_seg(M);
+    std::vector<double> h_sum(M * 2 * D);
+    HIPCHK(hipMemcpyAsync(h_seg.data(), b_seg.p, M * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(h_sum.data(), b_sum.p, M * 2 * D * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (uint64_t i = 0; i < M; ++i) seg_len[i] = (uint64_t)((i + 1 < M ? h_seg[i + 1] : T) - h_seg[i]);
+    for (int d = 0; d < D; ++d) {
+        if (sum) memcpy(sum + (uint64_t)d * M, h_sum.data() + (uint64_t)(2 * d) * M, M * sizeof(double));
+        if (sum_sq) memcpy(sum_sq + (uint64_t)d * M, h_sum.data() + (uint64_t)(2 * d + 1) * M, M * sizeof(double));
+    }
+    return 0;
+}
+
+int hml_levels_dense_device(hml_ctx* c, void* out_dev) {
+    NEED_MODEL();
+    if (!out_dev) return set_err(HML_ERR_ARG, "null argument");
+    hml_model m; if (int r = levels_ready(c, &m)) return r;
+    const uint32_t T = (uint32_t)c->T;
+    const int D = c->D;
+    uint64_t M = 0;
+    DevBuf b_seg, b_sum, b_ms;
+    if (int r = gather_level_segments(c, &M, b_seg, b_sum)) return r;
+    HIPCHK(hipMalloc(&b_ms.p, M * 2 * D * sizeof(float)));
+    hipLaunchKernelGGL(hml_k_levels_mean_sd, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, c->stream, b_sum.as<double>(), (uint32_t)M, D,
+                       m.n_levels_recorded, b_ms.as<float>());
+    hipLaunchKernelGGL(hml_k_levels_expand, dim3(grid_for(T, 256, 1, 65536)), dim3(256), 0, c->stream, b_ms.as<float>(), b_seg.as<uint32_t>(),
+                       (uint32_t)M, T, 2 * D, (float*)out_dev);
+    KLAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int hml_levels_merge(hml_ctx* dst, hml_ctx* src) {
+    if (!dst || !src || !dst->model_set || !src->model_set) return set_err(HML_ERR_ARG, "model not set");
+    if (dst == src) return set_err(HML_ERR_ARG, "a context cannot be merged into itself");
+    if (dst->device != src->device)
+        return set_err(HML_ERR_ARG, "the emission levels of chains on different GPUs are not merged yet: run the chains of one levels file on one GPU");
+    if (dst->T != src->T || dst->D != src->D) return set_err(HML_ERR_ARG, "emission levels can only be merged between chains over the same positions and dimensions");
+    if (int r = ctx_bind(dst)) return r;
+    if (int r = hml_settle(src)) return r;   // (both streams idle: the merge reads the source's accumulators on the destination's stream)
+    if (int r = hml_settle(dst)) return r;
+    if (!src->levels_asked) return set_err(HML_ERR_ARG, "no emission levels were recorded by the source context: enable them with hml_set_level_recording (or HML_LEVELS=1) before the recorded sweeps");
+    if (int r = ensure_level_buffers(src)) return r;
+    if (int r = ensure_level_buffers(dst)) return r;
+    dst->levels_asked = true;
+    const uint32_t T = (uint32_t)src->T;
+    // the source's segment starts (its cells are zero everywhere else), on the destination's stream
+    DevBuf d_cnt, d_off, d_seg;
+    HIPCHK(hipMalloc(&d_cnt.p, src->n_spans * sizeof(uint32_t)));
+    HIPCHK(hipMalloc(&d_off.p, src->n_spans * sizeof(uint32_t)));
+    hipLaunchKernelGGL(hml_k_marg_count, dim3((src->n_spans + 3) / 4), dim3(256), 0, dst->stream, src->d_lev_boundary, T, d_cnt.as<uint32_t>());
+    std::vector<uint32_t> h_cnt(src->n_spans), h_off(src->n_spans);
+    HIPCHK(hipMemcpyAsync(h_cnt.data(), d_cnt.p, src->n_spans * sizeof(uint32_t), hipMemcpyDeviceToHost, dst->stream));
+    HIPCHK(hipStreamSynchronize(dst->stream));
+    uint64_t M = 0;
+    for (uint32_t i = 0; i < src->n_spans; ++i) { h_off[i] = (uint32_t)M; M += h_cnt[i]; }
+    HIPCHK(hipMemcpyAsync(d_off.p, h_off.data(), src->n_spans * sizeof(uint32_t), hipMemcpyHostToDevice, dst->stream));
+    HIPCHK(hipMalloc(&d_seg.p, (M + 1) * sizeof(uint32_t)));
+    hipLaunchKernelGGL(hml_k_marg_scatter, dim3((src->n_spans + 3) / 4), dim3(256), 0, dst->stream, src->d_lev_boundary, T, d_off.as<uint32_t>(), d_seg.as<uint32_t>());
+    hipLaunchKernelGGL(hml_k_levels_merge, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, dst->stream, src->d_levels, d_seg.as<uint32_t>(), (uint32_t)M, T,
+                       2 * src->D, src->d_mdl, dst->d_levels, dst->d_lev_boundary, dst->d_mdl);
+    KLAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(dst->stream));
     return 0;
 }
 

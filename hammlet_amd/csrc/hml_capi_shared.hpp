@@ -30,6 +30,7 @@
 #include "hml_k_build.h"
 #include "hml_k_forward.h"
 #include "hml_k_marginals.h"
+#include "hml_k_levels.h"
 #include "hml_k_segment.h"
 #include "hml_k_trellis.h"
 #include "hml_k_trellis_rows.h"
@@ -234,6 +235,30 @@ static int ensure_marginal_buffers(hml_ctx* c) {
     const uint64_t words = (c->T + 1 + 31) / 32 + 1;
     HIPCHK(hipMalloc(&c->d_boundary, words * sizeof(uint32_t)));
     HIPCHK(hipMemsetAsync(c->d_boundary, 0, words * sizeof(uint32_t), c->stream));
+    return 0;
+}
+
+// the emission levels' accumulators (hml_k_levels.h): 2 D (T + 1) doubles and (T + 32) / 32 words, on first use.  Zeroed before
+// this returns: chains batched by hml_iterate_many run on their group's stream, not on their own.
+static int ensure_level_buffers(hml_ctx* c) {
+    if (c->d_levels) return 0;
+    const uint64_t n = 2ull * (uint64_t)c->D * (c->T + 1);
+    const uint64_t words = (c->T + 32) / 32;
+    HIPCHK(hipMalloc(&c->d_levels, n * sizeof(double)));
+    HIPCHK(hipMalloc(&c->d_lev_boundary, words * sizeof(uint32_t)));
+    HIPCHK(hipMemsetAsync(c->d_levels, 0, n * sizeof(double), c->stream));
+    HIPCHK(hipMemsetAsync(c->d_lev_boundary, 0, words * sizeof(uint32_t), c->stream));
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(c->stream, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone) HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// the level kernel of a recorded sweep, on stream `s`, BEHIND the sweep's parameter update: the level is mu under the theta
+// that hml_get_theta returns inside the sweep's record callback
+static int launch_levels_record(hml_ctx* c, hipStream_t s, uint32_t hint) {
+    if (int r = ensure_level_buffers(c)) return r;
+    ProfScope ps(c, "levels");
+    hipLaunchKernelGGL(hml_k_levels_record, dim3(grid_for(hint, 256, 64, 16384)), dim3(256), 0, s, c->d_q, c->d_starts, c->d_mdl, c->d_levels, c->d_lev_boundary);
     return 0;
 }
 

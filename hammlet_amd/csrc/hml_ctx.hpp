@@ -112,8 +112,13 @@ struct hml_ctx {
     bool params_spread = false;    // single-chain sweeps: the parameter kernel's tree over 16 workgroups (hml_k_params.h; HML_PARAMS_SPREAD)
     int32_t* d_diff = nullptr;
     uint32_t* d_boundary = nullptr;
+    // emission levels per position (hml_k_levels.h), allocated by the first recorded sweep that wants them
+    bool rec_levels = false;        // hml_set_level_recording / HML_LEVELS
+    bool levels_asked = false;      // ... was on at some time: the read-outs answer (with nothing recorded: one segment, zero sums)
+    double* d_levels = nullptr;     // [2 D][T + 1]: row 2 d the level's difference array, row 2 d + 1 its square's
+    uint32_t* d_lev_boundary = nullptr;   // the levels' own bitmap of segment boundaries
     hml_model* d_mdl = nullptr;
-    uint32_t* h_B = nullptr;        // pinned + mapped, four words: [0] the block count of the latest enumeration (grid sizing hint),
+    uint32_t* h_B = nullptr;       // pinned + mapped, four words: [0] the block count of the latest enumeration (grid sizing hint),
                                     // [1] set by the fused block kernel when a bounded wait expired, [2] the chain is HALTED: the number of
                                     // blocks an enumeration found beyond the capacity of the per-block buffers (hml_state.h)
     // Block capacity of the per-block buffers (0 until the observations are loaded; T = the worst case, every position a block).

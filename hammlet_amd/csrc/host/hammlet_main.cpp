@@ -3,12 +3,17 @@
 // flag semantics doc/hammlet-manpage.md:33-175); everything between reading the input and writing the
 // files runs on the GPU through libhammlet_hip.so.
 //
-// Extensions (not in the reference): `-O X` writes PREFIXmaxsegmentationSUFFIX; -raw FILE reads float32 values instead of text; -device N selects
+// Extensions (not in the reference): `-O X` writes PREFIXmaxsegmentationSUFFIX; `-O L` writes PREFIXlevelsSUFFIX, the denoised
+// trace: per segment its length and, per data dimension, the posterior mean and standard deviation of the emission level
+// over the recorded sweeps (include/hml.h, hml_levels_rle; with -chains N the chains of the GPU are merged first - no
+// relabelling is involved); -raw FILE reads float32 values instead of text; -device N selects
 // the GPU; -chain N selects the Philox sub-key of an independent chain; -chains N runs N independent chains (sub-keys
 // chain .. chain+N-1), chain k on GPU (device + k) mod #GPUs in its own host thread, and pools their recorded marginals
 // with one all-reduce over RCCL before PREFIXmarginalsSUFFIX is written (hml_allreduce_marginals); the per-sweep side
 // files of chain k >= 1 are PREFIXchainK.{sequences,...}SUFFIX.
+#include <cmath>
 #include <condition_variable>
+#include <cstdio>
 #include <cstdlib>
 #include <ctime>
 #include <exception>
@@ -39,6 +44,8 @@ static const char* kHelp =
     "  -o, -output-pattern PRE SUF    output files are PRE{marginals,...}SUF (default: hammlet- .csv)\n"
     "  -O, -output-data M S P B C G   marginals sequences parameters blocks compression segments\n"
     "                    X            maxsegmentation: the maxSegmentation tool's output for the marginals (extension)\n"
+    "                    L            levels: length, then posterior mean and standard deviation of the emission level\n"
+    "                                 per data dimension, one line per segment - the denoised trace (extension)\n"
     "  -w, -overwrite                 allow overwriting output files\n"
     "  -s, -states K | C P D          number of states (default 3), or P parameters shared by P^D states over D dimensions\n"
     "  -e, -emissions normal VAR P    automatic prior: P(variance < VAR) = P (default normal 0.2 0.9)\n"
@@ -129,6 +136,40 @@ public:
         mCv.notify_all();
     }
 };
+
+static const char* kLevelsDevicesMessage =
+    "The emission levels of chains on different GPUs are not merged yet: run -O L with -chains N on one GPU!";
+
+static string levelsFileName(const Job& job) { return job.opref + "levels" + job.osuff; }
+
+// PREFIXlevelsSUFFIX from the context's recorded levels: "length mean_0 sd_0 [mean_1 sd_1 ...]" per segment, %.9g
+static void writeLevels(const Job& job, hml_ctx* ctx) {
+    uint64_t M = 0, N = 0;
+    hml_check(hml_levels_rle(ctx, &M, &N, nullptr, nullptr, nullptr));
+    const size_t D = job.nrDataDim;
+    vector<uint64_t> len(M);
+    vector<double> s1(M * D), s2(M * D);
+    hml_check(hml_levels_rle(ctx, &M, &N, len.data(), s1.data(), s2.data()));
+    const string fn = levelsFileName(job);
+    FILE* out = fopen(fn.c_str(), "w");
+    if (!out) throw std::runtime_error("Cannot write to file " + fn + "!");
+    for (uint64_t i = 0; i < M; ++i) {
+        fprintf(out, "%llu", (unsigned long long)len[i]);
+        for (size_t d = 0; d < D; ++d) {
+            // (the formula of hml_levels_dense_device: double arithmetic, one rounding to float; nothing recorded: nan)
+            float mean = NAN, sd = NAN;
+            if (N > 0) {
+                const double m = s1[d * M + i] / (double)N;
+                const double var = s2[d * M + i] / (double)N - m * m;
+                mean = (float)m;
+                sd = (float)std::sqrt(var > 0.0 ? var : 0.0);
+            }
+            fprintf(out, " %.9g %.9g", (double)mean, (double)sd);
+        }
+        fputc('\n', out);
+    }
+    if (fclose(out) != 0) throw std::runtime_error("Cannot write to file " + fn + "!");
+}
 
 // One chain from its device context to its output files.  `index` > 0 (chains of `-chains N` beyond the first): the
 // per-sweep side files carry the infix "chainK." and the (pooled) marginals are left to chain 0.
@@ -233,6 +274,7 @@ static void runChain(const Job& job, vector<real_t>& inputValues, bool steal, in
     for (const Step& st : job.scheme)
         if (run.token(st)) run.sweeps(st);
     hml_check(hml_sync(run.RNG.ctx()));
+    if (!rendezvous && job.outputs.at("levels")) writeLevels(job, run.RNG.ctx());   // (several chains: the main thread merges and writes)
     if (rendezvous && !rendezvous->arrive(index, run.RNG.ctx())) run.records.discardMarginals();   // pooling failed elsewhere
     run.records.close();
 }
@@ -384,6 +426,7 @@ int main(int argc, const char* argv[]) {
         outputArgs.registerFlags({"D", "mapping"});
         outputArgs.registerFlags({"G", "segments"});
         outputArgs.registerFlags({"X", "maxsegmentation"});   // extension
+        outputArgs.registerFlags({"L", "levels"});            // extension
         outputArgs.parseArgs();
 
         // ---- input
@@ -456,8 +499,14 @@ int main(int argc, const char* argv[]) {
         job.weightMultiplier = weightMultiplier; job.useSelfTrans = useSelfTrans;
         job.thetaParams = thetaParams; job.trans = trans; job.selfTrans = selfTrans; job.initialAlpha = initialAlpha;
         job.scheme = scheme;
-        for (const char* o : {"sequences", "parameters", "blocks", "compression", "marginals", "segments", "maxsegmentation"})
+        for (const char* o : {"sequences", "parameters", "blocks", "compression", "marginals", "segments", "maxsegmentation", "levels"})
             job.outputs[o] = outputArgs.isSet(o);
+        if (job.outputs.at("levels")) {
+            // every context of this process accumulates the emission levels of its recorded sweeps (include/hml.h)
+            setenv("HML_LEVELS", "1", 1);
+            const string fn = levelsFileName(job);
+            if (!overwrite) { std::ifstream probe(fn); if (probe.good()) throw std::runtime_error("File " + fn + " already exists! Use -w to allow overwrite!"); }
+        }
 
         if (nrChains <= 1) {
             // the device context is created once every argument has been parsed and the input has been read
@@ -467,6 +516,7 @@ int main(int argc, const char* argv[]) {
             // nothing is exchanged while sampling; the recorded marginals are pooled by one all-reduce (RCCL) at the end
             int nDev = 1;
             hml_check(hml_device_count(&nDev));
+            if (job.outputs.at("levels") && nDev > 1) throw std::runtime_error(kLevelsDevicesMessage);   // (before anything runs)
             Rendezvous rv(nrChains);
             // chain k lives on GPU (device + k) mod #GPUs; the chains of one GPU are driven by ONE host thread in lockstep and
             // share the construction of the observations
@@ -510,6 +560,13 @@ int main(int argc, const char* argv[]) {
                         for (size_t j = 0; j < job.nrStates; ++j) out << (j ? "\t" : "") << perms[(size_t)k * job.nrStates + j];
                         out << "\n";
                     }
+                } catch (...) { poolError = std::current_exception(); }
+            }
+            if ((int)ctxs.size() == nrChains && job.outputs.at("levels") && !poolError) {
+                // the chains share the GPU: their levels add up in the first chain's context, which the file is written from
+                try {
+                    for (int k = 1; k < nrChains; ++k) hml_check(hml_levels_merge(ctxs[0], ctxs[k]));
+                    writeLevels(job, ctxs[0]);
                 } catch (...) { poolError = std::current_exception(); }
             }
             rv.release(poolError == nullptr && (int)ctxs.size() == nrChains);

@@ -238,6 +238,34 @@ int hml_max_segmentation(hml_ctx* ctx, uint64_t* n_runs, uint64_t* run_len /*n_r
 int hml_marginals_dense_device(hml_ctx* ctx, void* out_dev, const int32_t* perm);
 int hml_recorded_sweeps(hml_ctx* ctx, uint64_t* n);
 
+/* ---- emission levels per position: the denoised trace.  No counterpart in the reference. ----
+ * The LEVEL of a recorded sweep at position t and data dimension d is the mean of the emission parameter of the state
+ * that covers t - parameter (s / P^d) % P of state s, the mapping of hml_set_dimensions - under the theta that is current
+ * AFTER that sweep's parameter update: what hml_get_theta returns inside the sweep's record callback and what the
+ * parameters file prints for the sweep.  The context accumulates, per position, the sum of the levels and the sum of their
+ * squares over the recorded sweeps, in double; posterior mean S1 / N and standard deviation sqrt(max(0, S2 / N - (S1 / N)^2)).
+ * Memory: 2 D (T + 1) doubles and (T + 32) / 32 words, allocated by the first recorded sweep that needs them; cost per
+ * recorded sweep: proportional to the number of changes of state, like the marginals.
+ * hml_set_level_recording: at any time before a recorded sweep; turning it off keeps what was accumulated.  Off by
+ * default (a sweep then launches what it launched before ABI 4).  Environment: HML_LEVELS=1. */
+int hml_set_level_recording(hml_ctx* ctx, int on);
+/* Run-length form: segments are cut wherever any recorded sweep had a boundary between runs of equal states.  sum[d *
+ * n_segments + i] = S1 and sum_sq[...] = S2 of dimension d on segment i; n_recorded = N.  Call with seg_len == NULL to
+ * obtain n_segments and n_recorded.  The sums are the same bits on every run of the same chain (fixed summation tree).
+ * HML_ERR_ARG on a context that never recorded levels. */
+int hml_levels_rle(hml_ctx* ctx, uint64_t* n_segments, uint64_t* n_recorded, uint64_t* seg_len /*n_segments*/,
+                   double* sum /*D*n_segments, dimension-major*/, double* sum_sq /*D*n_segments*/);
+/* Dense form on the DEVICE: float [2 D][T], row 2 d the posterior mean of dimension d, row 2 d + 1 its standard deviation
+ * (both computed in double, then rounded once; not-a-number when nothing was recorded). */
+int hml_levels_dense_device(hml_ctx* ctx, void* out_dev /* float [2D][T] */);
+/* Adds `src`'s accumulators, boundary bits and count of recorded sweeps into `dst`; `src` is unchanged and `dst` may go on
+ * recording.  Same device, T and D, otherwise HML_ERR_ARG (chains on different GPUs are not merged yet).  Unlike the pooled
+ * marginals (hml_pool_*, below) this needs NO common labels: the marginals count states, and two chains - or two halves of
+ * one - may call the same level "state 1" and "state 3", so pooling them relies on hml_relabel_permutation's ordering by
+ * the last sampled means; the level itself is the same number whatever the state is called, so sums over sweeps and
+ * chains are exact statements about the posterior, also with twin or unused states. */
+int hml_levels_merge(hml_ctx* dst, hml_ctx* src);
+
 /* Trellis::sample(t) (src/Trellis.hpp:61-66): one draw of std::discrete_distribution over K weights - p_i = w_i / sum in
  * double, first i whose cumulative probability reaches u - with u from the chain's Philox key (sub-stream HOST,
  * one counter step per call).  Runs on the host (shared arithmetic of the kernels, hml_dist.h). */
@@ -309,7 +337,7 @@ int hml_get_stats(hml_ctx* ctx, hml_stats* out);
 
 /* HIP-event timing of one named kernel family accumulated since the last reset (milliseconds and
  * launches); name is one of "blocks_compact", "blocks_scatter", "block_stats", "stats_emission", "emission", "forward",
- * "backward_maps", "backward_chain", "mixture", "counts", "params", "marginals", "event_null".  level 0 = off, 1 = only the dominant kernel
+ * "backward_maps", "backward_chain", "mixture", "counts", "params", "marginals", "levels", "event_null".  level 0 = off, 1 = only the dominant kernel
  * ("blocks_compact", two events per sweep), 2 = every family. */
 int hml_profile_enable(hml_ctx* ctx, int level);
 int hml_profile_get(hml_ctx* ctx, const char* name, double* total_ms, uint64_t* launches);
