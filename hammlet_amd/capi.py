@@ -88,6 +88,12 @@ SIGNATURES = {
     "hml_levels_rle": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _P, _P, _P]),
     "hml_levels_dense_device": (C.c_int, [_P, _P]),
     "hml_levels_merge": (C.c_int, [_P, _P]),
+    "hml_levels_on_segments": (C.c_int, [_P, C.c_uint64, _P, _P, _P]),
+    "hml_set_break_recording": (C.c_int, [_P, C.c_int]),
+    "hml_breaks_list": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _P, _P]),
+    "hml_breaks_dense_device": (C.c_int, [_P, _P, C.c_uint32]),
+    "hml_breaks_merge": (C.c_int, [_P, _P]),
+    "hml_breaks_consensus": (C.c_int, [_P, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), _P, _P, _P]),
     "hml_categorical_draw": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_uint32)]),
     "hml_relabel_permutation": (C.c_int, [_P, _P]),
     "hml_pool_payload_size": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
@@ -112,7 +118,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 4   # hml_abi_version() of include/hml.h this mirror was written against
+ABI_VERSION = 5   # hml_abi_version() of include/hml.h this mirror was written against
 
 
 def load_library(path=None):
@@ -448,6 +454,51 @@ class Chain:
     def merge_levels(self, other):
         """add `other`'s recorded levels into this chain's (same GPU, positions and dimensions); no relabelling involved"""
         _check(self.lib.hml_levels_merge(self.h, other.h))
+
+    def levels_on_segments(self, cuts):
+        """(sum[D, n + 1], sum_sq[D, n + 1]): S1 and S2 of the recorded levels summed over the positions of the n + 1 segments
+        that the n ascending cuts in (0, T) leave (hml_levels_on_segments); a segment's mean is sum / (N * length)"""
+        cuts = np.ascontiguousarray(cuts, np.uint32)
+        n = cuts.size
+        s1 = np.empty((self.D, n + 1), np.float64)
+        s2 = np.empty((self.D, n + 1), np.float64)
+        _check(self.lib.hml_levels_on_segments(self.h, n, cuts.ctypes.data if n else None, s1.ctypes.data, s2.ctypes.data))
+        return s1, s2
+
+    # ---- breakpoint posteriors per position -----------------------------------------------
+    def set_break_recording(self, on=True):
+        """count the breakpoints of every recorded sweep from now on (hml_set_break_recording)"""
+        _check(self.lib.hml_set_break_recording(self.h, 1 if on else 0))
+
+    def breaks_list(self):
+        """(pos[M], count[M], n_recorded): the positions where a recorded sweep changed state, ascending, and how many did"""
+        m, n = C.c_uint64(), C.c_uint64()
+        _check(self.lib.hml_breaks_list(self.h, C.byref(m), C.byref(n), None, None))
+        pos = np.empty(m.value, np.uint32)
+        cnt = np.empty(m.value, np.uint32)
+        if m.value:
+            _check(self.lib.hml_breaks_list(self.h, C.byref(m), C.byref(n), pos.ctypes.data, cnt.ctypes.data))
+        return pos, cnt, n.value
+
+    def breaks_dense(self, out_ptr, window=0):
+        """(sum of the counts within `window` positions of t) / n_recorded per position into a device buffer float32 [T]"""
+        _check(self.lib.hml_breaks_dense_device(self.h, out_ptr, window))
+
+    def breaks_merge(self, other):
+        """add `other`'s breakpoint counts into this chain's (same GPU and positions); no relabelling involved"""
+        _check(self.lib.hml_breaks_merge(self.h, other.h))
+
+    def breaks_consensus(self, window, min_count):
+        """(pos[S], mass[S], peak[S]): the candidates whose windowed mass reaches min_count and that no neighbour within
+        the window beats (hml_breaks_consensus), ascending"""
+        s = C.c_uint64()
+        _check(self.lib.hml_breaks_consensus(self.h, window, min_count, C.byref(s), None, None, None))
+        pos = np.empty(s.value, np.uint32)
+        mass = np.empty(s.value, np.uint64)
+        peak = np.empty(s.value, np.uint32)
+        if s.value:
+            _check(self.lib.hml_breaks_consensus(self.h, window, min_count, C.byref(s), pos.ctypes.data, mass.ctypes.data, peak.ctypes.data))
+        return pos, mass, peak
 
     # ---- chain-parallel pooling ---------------------------------------------------------
     def relabel_permutation(self):

@@ -103,8 +103,10 @@ HML_KERNEL void hml_k_debug_eval(int fn, const float* __restrict__ a, const floa
 extern "C" {
 
 const char* hml_last_error(void) { return g_err.c_str(); }
-uint32_t hml_abi_version(void) { return 4; }   // 2: hml_stats.fused_fallbacks, hml_allreduce_marginals_perm, hml_pool_permutation, option "compat"; 3: hml_attach_observations;
+uint32_t hml_abi_version(void) { return 5; }   // 2: hml_stats.fused_fallbacks, hml_allreduce_marginals_perm, hml_pool_permutation, option "compat"; 3: hml_attach_observations;
                                                 // 4: emission levels per position (hml_set_level_recording, hml_levels_rle, hml_levels_dense_device, hml_levels_merge)
+                                                // 5: breakpoint posteriors (hml_set_break_recording, hml_breaks_list, hml_breaks_dense_device, hml_breaks_merge,
+                                                //    hml_breaks_consensus) and hml_levels_on_segments
 const char* hml_device_arch(void) { return "gfx950"; }
 int hml_device_count(int* n) {
     if (!n) return set_err(HML_ERR_ARG, "null argument");
@@ -174,6 +176,7 @@ int hml_create(hml_ctx** out, int device, uint64_t seed, uint32_t chain_id, void
     if (const char* e = getenv("HML_TRELLIS_TUNE")) c->tre_autotune = atoi(e) != 0;
     if (const char* e = getenv("HML_FUSED_SPIN_LIMIT")) c->fused_spin_limit = (uint32_t)strtoul(e, nullptr, 10);
     if (const char* e = getenv("HML_LEVELS")) c->rec_levels = c->levels_asked = atoi(e) != 0;   // hml_set_level_recording for unmodified callers (`hammlet -O L`)
+    if (const char* e = getenv("HML_BREAKS")) c->rec_breaks = c->breaks_asked = atoi(e) != 0;   // hml_set_break_recording for unmodified callers (`hammlet -O breakpoints`)
     if (const char* e = getenv("HML_MAX_BLOCKS")) c->cap_opt = strtoull(e, nullptr, 10);   // option "max_blocks" (tests: a tiny capacity exercises the growth everywhere)
     if (device < 64) g_live_ctx[device].fetch_add(1);
     *out = c;
@@ -212,7 +215,7 @@ static void free_all(hml_ctx* c) {
     trace_release(c);
     free_sweep_buffers(c);
     void* ptrs[] = {c->d_group_word, c->d_wave_total, c->d_stage, c->d_span_count, c->d_starts, c->d_bstat, c->d_eprobe, c->d_aprobe, c->d_coarse1,
-                    c->d_diff, c->d_boundary, c->d_levels, c->d_lev_boundary, c->d_mdl, c->d_many};
+                    c->d_diff, c->d_boundary, c->d_levels, c->d_lev_boundary, c->d_breaks, c->d_brk_boundary, c->d_mdl, c->d_many};
     for (void* p : ptrs) if (p) hipFree(p);
     if (c->h_B) hipHostFree(c->h_B);
     c->h_B = nullptr;
@@ -932,6 +935,15 @@ int hml_set_level_recording(hml_ctx* c, int on) {
     return 0;
 }
 
+int hml_set_break_recording(hml_ctx* c, int on) {
+    if (!c) return set_err(HML_ERR_ARG, "null context");
+    c->rec_breaks = on != 0;
+    if (on) c->breaks_asked = true;
+    // (as in hml_set_level_recording: a graph captured under the other setting goes)
+    if (c->graph_exec) { if (int r = ctx_bind(c)) return r; hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
+    return 0;
+}
+
 int hml_enable_probes(hml_ctx* c, int on) {
     if (!c || !c->model_set) return set_err(HML_ERR_ARG, "model not set");
     if (int r = ctx_bind(c)) return r;
@@ -1048,6 +1060,7 @@ static int sweep_compat(hml_ctx* c, char method, bool record) {
         hipLaunchKernelGGL(hml_k_record, dim3(grid_for(hint, 256, 64, 16384)), dim3(256), 0, s, c->d_q, c->d_starts, c->d_mdl, c->d_diff, c->d_boundary);
     }
     if (record && c->rec_levels) { if (int r = launch_levels_record(c, s, hint)) return r; }   // (hml_k_compat_update above is this sweep's parameter update)
+    if (record && c->rec_breaks) { if (int r = launch_breaks_record(c, s, hint)) return r; }
     KLAUNCH_CHECK();
     return 0;
 }
@@ -1140,6 +1153,7 @@ static int sweep_wide(hml_ctx* c, char method, bool record) {
         hipLaunchKernelGGL(hml_k_wide_params, dim3(1), dim3(1024), 0, s, c->d_mdl, c->d_partial, (hml_wide_acc*)c->d_wacc, 0);
     }
     if (record && c->rec_levels) { if (int r = launch_levels_record(c, s, hint)) return r; }   // (after the update: hml_k_levels.h)
+    if (record && c->rec_breaks) { if (int r = launch_breaks_record(c, s, hint)) return r; }
     KLAUNCH_CHECK();
     return 0;
 }
@@ -1671,6 +1685,203 @@ int hml_levels_merge(hml_ctx* dst, hml_ctx* src) {
                        2 * src->D, src->d_mdl, dst->d_levels, dst->d_lev_boundary, dst->d_mdl);
     KLAUNCH_CHECK();
     HIPCHK(hipStreamSynchronize(dst->stream));
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------- breakpoints (hml_k_breaks.h)
+}  // extern "C"
+
+// exclusive 64-bit prefix sums of M 32-bit values on `s`: d_pre[M + 1] (allocated here), d_pre[M] = the total
+static int breaks_scan(hipStream_t s, const uint32_t* d_v, uint64_t M, DevBuf& d_pre) {
+    DevBuf d_cs;
+    const uint32_t n_chunks = (uint32_t)((M + HML_BRK_CHUNK - 1) / HML_BRK_CHUNK);
+    HIPCHK(hipMalloc(&d_pre.p, (M + 1) * sizeof(unsigned long long)));
+    HIPCHK(hipMalloc(&d_cs.p, ((uint64_t)n_chunks + 1) * sizeof(unsigned long long)));
+    const int grid = grid_for(n_chunks, 1, 1, 4096);
+    hipLaunchKernelGGL(hml_k_breaks_scan_partial, dim3(grid), dim3(256), 0, s, d_v, (uint32_t)M, n_chunks, d_cs.as<unsigned long long>());
+    hipLaunchKernelGGL(hml_k_breaks_scan_chunks, dim3(1), dim3(1024), 0, s, d_cs.as<unsigned long long>(), n_chunks);
+    hipLaunchKernelGGL(hml_k_breaks_scan_final, dim3(grid), dim3(256), 0, s, d_v, (uint32_t)M, n_chunks, d_cs.as<unsigned long long>(), d_pre.as<unsigned long long>());
+    KLAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(s));   // (d_cs goes with this frame)
+    return 0;
+}
+
+// the positions with a count, ascending, on the device: d_list[1 + M] - entry 0 is the position 0 that the compaction kernels
+// always emit (never a breakpoint), the M break positions follow - on stream `s` from the bitmap of context `c`
+static int compact_break_positions(hml_ctx* c, hipStream_t s, uint64_t* M_out, DevBuf& d_list) {
+    const uint32_t T = (uint32_t)c->T;
+    DevBuf d_cnt, d_off;
+    HIPCHK(hipMalloc(&d_cnt.p, c->n_spans * sizeof(uint32_t)));
+    HIPCHK(hipMalloc(&d_off.p, c->n_spans * sizeof(uint32_t)));
+    hipLaunchKernelGGL(hml_k_marg_count, dim3((c->n_spans + 3) / 4), dim3(256), 0, s, c->d_brk_boundary, T, d_cnt.as<uint32_t>());
+    std::vector<uint32_t> h_cnt(c->n_spans), h_off(c->n_spans);
+    HIPCHK(hipMemcpyAsync(h_cnt.data(), d_cnt.p, c->n_spans * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    uint64_t n = 0;
+    for (uint32_t i = 0; i < c->n_spans; ++i) { h_off[i] = (uint32_t)n; n += h_cnt[i]; }
+    HIPCHK(hipMemcpyAsync(d_off.p, h_off.data(), c->n_spans * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMalloc(&d_list.p, (n + 1) * sizeof(uint32_t)));
+    hipLaunchKernelGGL(hml_k_marg_scatter, dim3((c->n_spans + 3) / 4), dim3(256), 0, s, c->d_brk_boundary, T, d_off.as<uint32_t>(), d_list.as<uint32_t>());
+    KLAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(s));
+    *M_out = n - 1;   // (position 0 always counts)
+    return 0;
+}
+
+// break positions d_list[1 + M] (see above), their counts d_cnt[M] and the exclusive sums of the counts d_pre[M + 1]
+static int gather_breaks(hml_ctx* c, uint64_t* M_out, DevBuf& d_list, DevBuf& d_cnt, DevBuf& d_pre) {
+    uint64_t M = 0;
+    if (int r = compact_break_positions(c, c->stream, &M, d_list)) return r;
+    HIPCHK(hipMalloc(&d_cnt.p, (M + 1) * sizeof(uint32_t)));
+    if (M) hipLaunchKernelGGL(hml_k_breaks_gather, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, c->stream, c->d_breaks, d_list.as<uint32_t>() + 1, (uint32_t)M, d_cnt.as<uint32_t>());
+    if (int r = breaks_scan(c->stream, d_cnt.as<uint32_t>(), M, d_pre)) return r;
+    *M_out = M;
+    return 0;
+}
+
+static const char* kNoBreaks = "no breakpoints were recorded by this context: enable them with hml_set_break_recording (or HML_BREAKS=1) before the recorded sweeps";
+
+static int breaks_ready(hml_ctx* c, hml_model* m) {
+    if (!c->breaks_asked) return set_err(HML_ERR_ARG, kNoBreaks);
+    if (int r = ensure_break_buffers(c)) return r;   // (asked for, but no sweep was recorded yet: an empty list)
+    if (int r = fetch_model(c, m)) return r;
+    if (m->err_code) { char buf[256]; return set_err(HML_ERR_MODEL, deverr_text(m->err_code, m->err_value, buf, sizeof buf)); }
+    return 0;
+}
+
+extern "C" {
+
+int hml_breaks_list(hml_ctx* c, uint64_t* n_breaks, uint64_t* n_recorded, uint32_t* pos, uint32_t* count) {
+    NEED_MODEL();
+    if (!n_breaks) return set_err(HML_ERR_ARG, "null argument");
+    hml_model m; if (int r = breaks_ready(c, &m)) return r;
+    uint64_t M = 0;
+    DevBuf b_list, b_cnt;
+    if (int r = compact_break_positions(c, c->stream, &M, b_list)) return r;
+    *n_breaks = M;
+    if (n_recorded) *n_recorded = m.n_breaks_recorded;
+    if (!pos || M == 0) return 0;
+    HIPCHK(hipMemcpyAsync(pos, b_list.as<uint32_t>() + 1, M * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (count) {
+        HIPCHK(hipMalloc(&b_cnt.p, M * sizeof(uint32_t)));
+        hipLaunchKernelGGL(hml_k_breaks_gather, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, c->stream, c->d_breaks, b_list.as<uint32_t>() + 1, (uint32_t)M, b_cnt.as<uint32_t>());
+        KLAUNCH_CHECK();
+        HIPCHK(hipMemcpyAsync(count, b_cnt.p, M * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int hml_breaks_dense_device(hml_ctx* c, void* out_dev, uint32_t window) {
+    NEED_MODEL();
+    if (!out_dev) return set_err(HML_ERR_ARG, "null argument");
+    hml_model m; if (int r = breaks_ready(c, &m)) return r;
+    uint64_t M = 0;
+    DevBuf b_list, b_cnt, b_pre;
+    if (int r = gather_breaks(c, &M, b_list, b_cnt, b_pre)) return r;
+    const uint32_t T = (uint32_t)c->T;
+    hipLaunchKernelGGL(hml_k_breaks_dense, dim3(grid_for(T, 256, 1, 65536)), dim3(256), 0, c->stream, b_list.as<uint32_t>() + 1, b_pre.as<unsigned long long>(),
+                       (uint32_t)M, T, window, m.n_breaks_recorded, (float*)out_dev);
+    KLAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int hml_breaks_consensus(hml_ctx* c, uint32_t window, uint64_t min_count, uint64_t* n_selected, uint32_t* pos, uint64_t* mass, uint32_t* peak) {
+    NEED_MODEL();
+    if (!n_selected) return set_err(HML_ERR_ARG, "null argument");
+    hml_model m; if (int r = breaks_ready(c, &m)) return r;
+    uint64_t M = 0;
+    DevBuf b_list, b_cnt, b_pre, b_mass, b_sel, b_where, b_opos, b_omass, b_opeak;
+    if (int r = gather_breaks(c, &M, b_list, b_cnt, b_pre)) return r;
+    *n_selected = 0;
+    if (M == 0) return 0;
+    HIPCHK(hipMalloc(&b_mass.p, M * sizeof(unsigned long long)));
+    HIPCHK(hipMalloc(&b_sel.p, M * sizeof(uint32_t)));
+    const uint32_t* d_pos = b_list.as<uint32_t>() + 1;
+    hipLaunchKernelGGL(hml_k_breaks_select, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, c->stream, d_pos, b_cnt.as<uint32_t>(), b_pre.as<unsigned long long>(),
+                       (uint32_t)M, window, (unsigned long long)(min_count > 1 ? min_count : 1), b_mass.as<unsigned long long>(), b_sel.as<uint32_t>());
+    KLAUNCH_CHECK();
+    if (int r = breaks_scan(c->stream, b_sel.as<uint32_t>(), M, b_where)) return r;
+    unsigned long long S = 0;
+    HIPCHK(hipMemcpyAsync(&S, b_where.as<unsigned long long>() + M, sizeof S, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *n_selected = S;
+    if (!pos || S == 0) return 0;
+    HIPCHK(hipMalloc(&b_opos.p, S * sizeof(uint32_t)));
+    HIPCHK(hipMalloc(&b_omass.p, S * sizeof(unsigned long long)));
+    HIPCHK(hipMalloc(&b_opeak.p, S * sizeof(uint32_t)));
+    hipLaunchKernelGGL(hml_k_breaks_compact, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, c->stream, d_pos, b_cnt.as<uint32_t>(), b_mass.as<unsigned long long>(),
+                       b_sel.as<uint32_t>(), b_where.as<unsigned long long>(), (uint32_t)M, b_opos.as<uint32_t>(), b_omass.as<unsigned long long>(), b_opeak.as<uint32_t>());
+    KLAUNCH_CHECK();
+    HIPCHK(hipMemcpyAsync(pos, b_opos.p, S * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (mass) HIPCHK(hipMemcpyAsync(mass, b_omass.p, S * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (peak) HIPCHK(hipMemcpyAsync(peak, b_opeak.p, S * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int hml_breaks_merge(hml_ctx* dst, hml_ctx* src) {
+    if (!dst || !src || !dst->model_set || !src->model_set) return set_err(HML_ERR_ARG, "model not set");
+    if (dst == src) return set_err(HML_ERR_ARG, "a context cannot be merged into itself");
+    if (dst->device != src->device)
+        return set_err(HML_ERR_ARG, "the breakpoints of chains on different GPUs are not merged yet: run the chains of one breakpoints file on one GPU");
+    if (dst->T != src->T) return set_err(HML_ERR_ARG, "breakpoints can only be merged between chains over the same positions");
+    if (int r = ctx_bind(dst)) return r;
+    if (int r = hml_settle(src)) return r;   // (both streams idle: the merge reads the source's counts on the destination's stream)
+    if (int r = hml_settle(dst)) return r;
+    if (!src->breaks_asked) return set_err(HML_ERR_ARG, "no breakpoints were recorded by the source context: enable them with hml_set_break_recording (or HML_BREAKS=1) before the recorded sweeps");
+    if (int r = ensure_break_buffers(src)) return r;
+    if (int r = ensure_break_buffers(dst)) return r;
+    dst->breaks_asked = true;
+    uint64_t M = 0;
+    DevBuf b_list;
+    if (int r = compact_break_positions(src, dst->stream, &M, b_list)) return r;
+    // (M = 0 still adds the source's count of recorded sweeps)
+    hipLaunchKernelGGL(hml_k_breaks_merge, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, dst->stream, src->d_breaks, b_list.as<uint32_t>() + 1, (uint32_t)M,
+                       src->d_mdl, dst->d_breaks, dst->d_brk_boundary, dst->d_mdl);
+    KLAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(dst->stream));
+    return 0;
+}
+
+int hml_levels_on_segments(hml_ctx* c, uint64_t n_cuts, const uint32_t* cuts, double* sum, double* sum_sq) {
+    NEED_MODEL();
+    if (n_cuts && !cuts) return set_err(HML_ERR_ARG, "null argument");
+    const uint32_t T = (uint32_t)c->T;
+    if (n_cuts >= T) return set_err(HML_ERR_ARG, "more cuts than positions");
+    for (uint64_t i = 0; i < n_cuts; ++i) {
+        if (cuts[i] == 0 || cuts[i] >= T) return set_err(HML_ERR_ARG, "a cut must lie inside (0, T)");
+        if (i > 0 && cuts[i] <= cuts[i - 1]) return set_err(HML_ERR_ARG, "the cuts must be strictly ascending");
+    }
+    hml_model m; if (int r = levels_ready(c, &m)) return r;
+    const int D = c->D, rows = 2 * D;
+    uint64_t M = 0;
+    DevBuf b_seg, b_val, b_w, b_cs, b_cuts, b_out;
+    if (int r = gather_level_segments(c, &M, b_seg, b_val)) return r;
+    const uint64_t n_seg = n_cuts + 1;
+    const uint32_t n_chunks = (uint32_t)((M + HML_LEV_CHUNK - 1) / HML_LEV_CHUNK);
+    HIPCHK(hipMalloc(&b_w.p, M * rows * sizeof(double)));
+    HIPCHK(hipMalloc(&b_cs.p, (uint64_t)n_chunks * rows * sizeof(double)));
+    HIPCHK(hipMalloc(&b_cuts.p, (n_cuts + 1) * sizeof(uint32_t)));
+    HIPCHK(hipMalloc(&b_out.p, n_seg * rows * sizeof(double)));
+    if (n_cuts) HIPCHK(hipMemcpyAsync(b_cuts.p, cuts, n_cuts * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(hml_k_levels_weigh, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, c->stream, b_val.as<double>(), b_seg.as<uint32_t>(), (uint32_t)M, T, rows, b_w.as<double>());
+    // the fixed-shape scan of the levels' read-out (hml_k_levels.h), now over len_i * value_i
+    const dim3 sgrid((unsigned)grid_for(n_chunks, 1, 1, 4096), (unsigned)rows);
+    hipLaunchKernelGGL(hml_k_levels_scan_partial, sgrid, dim3(256), 0, c->stream, b_w.as<double>(), (uint32_t)M, n_chunks, b_cs.as<double>());
+    hipLaunchKernelGGL(hml_k_levels_scan_chunks, dim3(rows), dim3(1024), 0, c->stream, b_cs.as<double>(), n_chunks);
+    hipLaunchKernelGGL(hml_k_levels_scan_final, sgrid, dim3(256), 0, c->stream, b_w.as<double>(), (uint32_t)M, n_chunks, b_cs.as<double>());
+    hipLaunchKernelGGL(hml_k_levels_on_segments, dim3(grid_for(n_seg, 256, 1, 16384)), dim3(256), 0, c->stream, b_val.as<double>(), b_w.as<double>(), b_seg.as<uint32_t>(),
+                       (uint32_t)M, T, rows, b_cuts.as<uint32_t>(), (uint32_t)n_cuts, b_out.as<double>());
+    KLAUNCH_CHECK();
+    std::vector<double> h_out(n_seg * rows);
+    HIPCHK(hipMemcpyAsync(h_out.data(), b_out.p, n_seg * rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int d = 0; d < D; ++d) {
+        if (sum) memcpy(sum + (uint64_t)d * n_seg, h_out.data() + (uint64_t)(2 * d) * n_seg, n_seg * sizeof(double));
+        if (sum_sq) memcpy(sum_sq + (uint64_t)d * n_seg, h_out.data() + (uint64_t)(2 * d + 1) * n_seg, n_seg * sizeof(double));
+    }
     return 0;
 }
 

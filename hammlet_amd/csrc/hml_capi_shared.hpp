@@ -31,6 +31,7 @@
 #include "hml_k_forward.h"
 #include "hml_k_marginals.h"
 #include "hml_k_levels.h"
+#include "hml_k_breaks.h"
 #include "hml_k_segment.h"
 #include "hml_k_trellis.h"
 #include "hml_k_trellis_rows.h"
@@ -259,6 +260,28 @@ static int launch_levels_record(hml_ctx* c, hipStream_t s, uint32_t hint) {
     if (int r = ensure_level_buffers(c)) return r;
     ProfScope ps(c, "levels");
     hipLaunchKernelGGL(hml_k_levels_record, dim3(grid_for(hint, 256, 64, 16384)), dim3(256), 0, s, c->d_q, c->d_starts, c->d_mdl, c->d_levels, c->d_lev_boundary);
+    return 0;
+}
+
+// the breakpoint counts (hml_k_breaks.h): T + 1 words and (T + 32) / 32 words of bitmap, on first use; zeroed before this
+// returns, like the levels' accumulators
+static int ensure_break_buffers(hml_ctx* c) {
+    if (c->d_breaks) return 0;
+    const uint64_t words = (c->T + 32) / 32;
+    HIPCHK(hipMalloc(&c->d_breaks, (c->T + 1) * sizeof(uint32_t)));
+    HIPCHK(hipMalloc(&c->d_brk_boundary, words * sizeof(uint32_t)));
+    HIPCHK(hipMemsetAsync(c->d_breaks, 0, (c->T + 1) * sizeof(uint32_t), c->stream));
+    HIPCHK(hipMemsetAsync(c->d_brk_boundary, 0, words * sizeof(uint32_t), c->stream));
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(c->stream, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone) HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// the breakpoint kernel of a recorded sweep, on stream `s` (it reads the sweep's states and block starts, not theta)
+static int launch_breaks_record(hml_ctx* c, hipStream_t s, uint32_t hint) {
+    if (int r = ensure_break_buffers(c)) return r;
+    ProfScope ps(c, "breaks");
+    hipLaunchKernelGGL(hml_k_breaks_record, dim3(grid_for(hint, 256, 64, 16384)), dim3(256), 0, s, c->d_q, c->d_starts, c->d_mdl, c->d_breaks, c->d_brk_boundary);
     return 0;
 }
 

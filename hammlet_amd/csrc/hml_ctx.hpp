@@ -117,6 +117,11 @@ struct hml_ctx {
     bool levels_asked = false;      // ... was on at some time: the read-outs answer (with nothing recorded: one segment, zero sums)
     double* d_levels = nullptr;     // [2 D][T + 1]: row 2 d the level's difference array, row 2 d + 1 its square's
     uint32_t* d_lev_boundary = nullptr;   // the levels' own bitmap of segment boundaries
+    // breakpoint counts per position (hml_k_breaks.h), allocated by the first recorded sweep that wants them
+    bool rec_breaks = false;        // hml_set_break_recording / HML_BREAKS
+    bool breaks_asked = false;      // ... was on at some time: the read-outs answer (with nothing recorded: an empty list)
+    uint32_t* d_breaks = nullptr;   // [T + 1]: recorded sweeps with a breakpoint at t
+    uint32_t* d_brk_boundary = nullptr;   // the breaks' own bitmap of the positions with a count
     hml_model* d_mdl = nullptr;
     uint32_t* h_B = nullptr;       // pinned + mapped, four words: [0] the block count of the latest enumeration (grid sizing hint),
                                     // [1] set by the fused block kernel when a bounded wait expired, [2] the chain is HALTED: the number of

@@ -129,6 +129,7 @@ struct hml_model {
     uint32_t wl_W_need, wl_need_age;   // ... a warm-up that failed on a settled chain, and the sweeps since (the adaptation stays above twice that for a while)
     uint32_t wl_retry;           // ... this sweep's filter runs once more with a longer warm-up (hml_k_wl_retry_decide): the warm-up, or 0
     unsigned long long n_levels_recorded;   // sweeps whose emission levels were accumulated (hml_k_levels.h), merged chains included
+    unsigned long long n_breaks_recorded;   // sweeps whose breakpoints were counted (hml_k_breaks.h), merged chains included
 };
 
 #if defined(__HIPCC__)

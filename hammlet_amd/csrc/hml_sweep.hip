@@ -276,6 +276,7 @@ static int sweep_k(hml_ctx* c, char method, bool record) {
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_params<KK>), dim3(1), dim3(1024), 0, s, c->d_mdl, c->d_partial, 0);
     }
     if (record && c->rec_levels) { if (int r = launch_levels_record(c, s, hint)) return r; }   // (after the update: hml_k_levels.h)
+    if (record && c->rec_breaks) { if (int r = launch_breaks_record(c, s, hint)) return r; }
     KLAUNCH_CHECK();
     return 0;
 }
@@ -293,6 +294,7 @@ static int iterate_many_k(hml_ctx* const* cs, int n, uint64_t first, uint64_t it
     unsigned long long rec_mask = 0ull;
     for (int i = 0; i < n; ++i) {
         if (records && cs[i]->rec_levels) { if (int r = ensure_level_buffers(cs[i])) return r; }
+        if (records && cs[i]->rec_breaks) { if (int r = ensure_break_buffers(cs[i])) return r; }
         if (records && cs[i]->rec_marginals) {
             if (cs[i]->pooled) return set_err(HML_ERR_ARG, "the marginals of a context are pooled (common labels, several chains): further sweeps cannot be recorded into them");
             if (int r = ensure_marginal_buffers(cs[i])) return r;
@@ -454,6 +456,11 @@ static int iterate_many_k(hml_ctx* const* cs, int n, uint64_t first, uint64_t it
             if (record) for (int k = g0; k < g0 + gn; ++k) if (cs[k]->rec_levels) {
                 hml_ctx* c = cs[k];
                 hipLaunchKernelGGL(hml_k_levels_record, dim3(gB), dim3(256), 0, s, c->d_q, c->d_starts, c->d_mdl, c->d_levels, c->d_lev_boundary);
+            }
+            // ... and those that count their breakpoints (hml_k_breaks.h)
+            if (record) for (int k = g0; k < g0 + gn; ++k) if (cs[k]->rec_breaks) {
+                hml_ctx* c = cs[k];
+                hipLaunchKernelGGL(hml_k_breaks_record, dim3(gB), dim3(256), 0, s, c->d_q, c->d_starts, c->d_mdl, c->d_breaks, c->d_brk_boundary);
             }
         }
         KLAUNCH_CHECK();

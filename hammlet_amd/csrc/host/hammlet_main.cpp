@@ -6,7 +6,10 @@
 // Extensions (not in the reference): `-O X` writes PREFIXmaxsegmentationSUFFIX; `-O L` writes PREFIXlevelsSUFFIX, the denoised
 // trace: per segment its length and, per data dimension, the posterior mean and standard deviation of the emission level
 // over the recorded sweeps (include/hml.h, hml_levels_rle; with -chains N the chains of the GPU are merged first - no
-// relabelling is involved); -raw FILE reads float32 values instead of text; -device N selects
+// relabelling is involved); `-O breakpoints` (BP) writes PREFIXbreakpointsSUFFIX, per position where a recorded sweep changed
+// state how many did and that share of the recorded sweeps; `-O consensus` (CS) writes PREFIXconsensusSUFFIX, the consensus
+// segmentation under `-consensus W P` with each segment's support and level (hml_breaks_consensus, hml_levels_on_segments);
+// -raw FILE reads float32 values instead of text; -device N selects
 // the GPU; -chain N selects the Philox sub-key of an independent chain; -chains N runs N independent chains (sub-keys
 // chain .. chain+N-1), chain k on GPU (device + k) mod #GPUs in its own host thread, and pools their recorded marginals
 // with one all-reduce over RCCL before PREFIXmarginalsSUFFIX is written (hml_allreduce_marginals); the per-sweep side
@@ -46,6 +49,11 @@ static const char* kHelp =
     "                    X            maxsegmentation: the maxSegmentation tool's output for the marginals (extension)\n"
     "                    L            levels: length, then posterior mean and standard deviation of the emission level\n"
     "                                 per data dimension, one line per segment - the denoised trace (extension)\n"
+    "                    BP           breakpoints: position, number of recorded sweeps that change state there, and that\n"
+    "                                 number over the recorded sweeps, one line per such position (extension)\n"
+    "                    CS           consensus: start, length, support of the left boundary, then mean and standard\n"
+    "                                 deviation of the emission level per data dimension, one line per consensus segment;\n"
+    "                                 turns the recording of the levels on (extension; see -consensus)\n"
     "  -w, -overwrite                 allow overwriting output files\n"
     "  -s, -states K | C P D          number of states (default 3), or P parameters shared by P^D states over D dimensions\n"
     "  -e, -emissions normal VAR P    automatic prior: P(variance < VAR) = P (default normal 0.2 0.9)\n"
@@ -61,6 +69,9 @@ static const char* kHelp =
     "                                 summation orders on the GPU - the same files as the reference for the same -R\n"
     "                                 (any model the default path takes: up to 64 states, -s C P D; about a hundred times\n"
     "                                 slower per sweep than the default path, ten times faster than the reference)\n"
+    "  -consensus W P                 consensus segmentation (-O CS): a breakpoint is kept when the sweeps with a breakpoint\n"
+    "                                 within W positions of it number at least P of the recorded ones and none of those\n"
+    "                                 positions was a breakpoint more often (default 16 0.5) (extension)\n"
     "  -chains N                      N independent chains, one per GPU, marginals pooled over RCCL (extension);\n"
     "                                 chains beyond the number of GPUs share a GPU and the construction it holds.\n"
     "                                 The pooled marginals / maxsegmentation files use common labels (states by\n"
@@ -84,6 +95,8 @@ struct Job {
     vector<vector<real_t>> thetaParams;
     vector<Step> scheme;
     std::map<string, bool> outputs;
+    uint32_t consensusWindow = 16;   // -consensus W P
+    double consensusShare = 0.5;
 };
 
 // Meeting point of the chain threads of `-chains N` and the main thread: a chain arrives with its context once its
@@ -169,6 +182,71 @@ static void writeLevels(const Job& job, hml_ctx* ctx) {
         fputc('\n', out);
     }
     if (fclose(out) != 0) throw std::runtime_error("Cannot write to file " + fn + "!");
+}
+
+static const char* kBreaksDevicesMessage =
+    "The breakpoints of chains on different GPUs are not merged yet: run -O breakpoints / -O consensus with -chains N on one GPU!";
+
+static string breaksFileName(const Job& job) { return job.opref + "breakpoints" + job.osuff; }
+static string consensusFileName(const Job& job) { return job.opref + "consensus" + job.osuff; }
+
+// PREFIXbreakpointsSUFFIX from the context's breakpoint counts: "position count probability" per listed position, the
+// probability count / N in double as %.9g
+static void writeBreakpoints(const Job& job, hml_ctx* ctx) {
+    uint64_t M = 0, N = 0;
+    hml_check(hml_breaks_list(ctx, &M, &N, nullptr, nullptr));
+    vector<uint32_t> pos(M), cnt(M);
+    if (M) hml_check(hml_breaks_list(ctx, &M, &N, pos.data(), cnt.data()));
+    const string fn = breaksFileName(job);
+    FILE* out = fopen(fn.c_str(), "w");
+    if (!out) throw std::runtime_error("Cannot write to file " + fn + "!");
+    for (uint64_t i = 0; i < M; ++i) fprintf(out, "%u %u %.9g\n", pos[i], cnt[i], (double)cnt[i] / (double)N);
+    if (fclose(out) != 0) throw std::runtime_error("Cannot write to file " + fn + "!");
+}
+
+// PREFIXconsensusSUFFIX: "start length support mean_0 sd_0 [mean_1 sd_1 ...]" per segment between consensus breakpoints;
+// support = windowed mass / N of the segment's left boundary (1 for the first segment); mean and standard deviation of the
+// level pooled over the segment's positions and the recorded sweeps (double arithmetic, one rounding to float, %.9g)
+static void writeConsensus(const Job& job, hml_ctx* ctx) {
+    uint64_t M = 0, N = 0, S = 0, Mlev = 0, Nlev = 0;
+    hml_check(hml_breaks_list(ctx, &M, &N, nullptr, nullptr));
+    const double need = std::ceil(job.consensusShare * (double)N);
+    const uint64_t minCount = need > 1.0 ? (uint64_t)need : 1;
+    hml_check(hml_breaks_consensus(ctx, job.consensusWindow, minCount, &S, nullptr, nullptr, nullptr));
+    vector<uint32_t> pos(S), peak(S);
+    vector<uint64_t> mass(S);
+    if (S) hml_check(hml_breaks_consensus(ctx, job.consensusWindow, minCount, &S, pos.data(), mass.data(), peak.data()));
+    hml_check(hml_levels_rle(ctx, &Mlev, &Nlev, nullptr, nullptr, nullptr));
+    const size_t D = job.nrDataDim;
+    vector<double> s1((S + 1) * D), s2((S + 1) * D);
+    hml_check(hml_levels_on_segments(ctx, S, pos.data(), s1.data(), s2.data()));
+    const string fn = consensusFileName(job);
+    FILE* out = fopen(fn.c_str(), "w");
+    if (!out) throw std::runtime_error("Cannot write to file " + fn + "!");
+    for (uint64_t k = 0; k <= S; ++k) {
+        const uint64_t start = k == 0 ? 0 : pos[k - 1], end = k == S ? job.T : pos[k];
+        fprintf(out, "%llu %llu %.9g", (unsigned long long)start, (unsigned long long)(end - start), k == 0 ? 1.0 : (double)mass[k - 1] / (double)N);
+        for (size_t d = 0; d < D; ++d) {
+            float mean = NAN, sd = NAN;
+            if (Nlev > 0) {
+                const double w = (double)Nlev * (double)(end - start);
+                const double m = s1[d * (S + 1) + k] / w;
+                const double var = s2[d * (S + 1) + k] / w - m * m;
+                mean = (float)m;
+                sd = (float)std::sqrt(var > 0.0 ? var : 0.0);
+            }
+            fprintf(out, " %.9g %.9g", (double)mean, (double)sd);
+        }
+        fputc('\n', out);
+    }
+    if (fclose(out) != 0) throw std::runtime_error("Cannot write to file " + fn + "!");
+}
+
+// the files written from a finished context (one chain, or the first of several after the others were merged into it)
+static void writeContextFiles(const Job& job, hml_ctx* ctx) {
+    if (job.outputs.at("levels")) writeLevels(job, ctx);
+    if (job.outputs.at("breakpoints")) writeBreakpoints(job, ctx);
+    if (job.outputs.at("consensus")) writeConsensus(job, ctx);
 }
 
 // One chain from its device context to its output files.  `index` > 0 (chains of `-chains N` beyond the first): the
@@ -274,7 +352,7 @@ static void runChain(const Job& job, vector<real_t>& inputValues, bool steal, in
     for (const Step& st : job.scheme)
         if (run.token(st)) run.sweeps(st);
     hml_check(hml_sync(run.RNG.ctx()));
-    if (!rendezvous && job.outputs.at("levels")) writeLevels(job, run.RNG.ctx());   // (several chains: the main thread merges and writes)
+    if (!rendezvous) writeContextFiles(job, run.RNG.ctx());   // (several chains: the main thread merges and writes)
     if (rendezvous && !rendezvous->arrive(index, run.RNG.ctx())) run.records.discardMarginals();   // pooling failed elsewhere
     run.records.close();
 }
@@ -346,6 +424,7 @@ int main(int argc, const char* argv[]) {
         args.registerFlags({"-chain"}, "0");
         args.registerFlags({"-chains"}, "1");
         args.registerFlags({"-compat"});
+        args.registerFlags({"-consensus"}, "16 0.5");
         args.parseArgs();
 
         if (args.isSet("-g")) args.print();
@@ -427,6 +506,8 @@ int main(int argc, const char* argv[]) {
         outputArgs.registerFlags({"G", "segments"});
         outputArgs.registerFlags({"X", "maxsegmentation"});   // extension
         outputArgs.registerFlags({"L", "levels"});            // extension
+        outputArgs.registerFlags({"BP", "breakpoints"});      // extension (B and C are the reference's blocks and compression)
+        outputArgs.registerFlags({"CS", "consensus"});        // extension
         outputArgs.parseArgs();
 
         // ---- input
@@ -499,13 +580,24 @@ int main(int argc, const char* argv[]) {
         job.weightMultiplier = weightMultiplier; job.useSelfTrans = useSelfTrans;
         job.thetaParams = thetaParams; job.trans = trans; job.selfTrans = selfTrans; job.initialAlpha = initialAlpha;
         job.scheme = scheme;
-        for (const char* o : {"sequences", "parameters", "blocks", "compression", "marginals", "segments", "maxsegmentation", "levels"})
+        for (const char* o : {"sequences", "parameters", "blocks", "compression", "marginals", "segments", "maxsegmentation", "levels", "breakpoints", "consensus"})
             job.outputs[o] = outputArgs.isSet(o);
-        if (job.outputs.at("levels")) {
-            // every context of this process accumulates the emission levels of its recorded sweeps (include/hml.h)
-            setenv("HML_LEVELS", "1", 1);
-            const string fn = levelsFileName(job);
+        auto refuseExisting = [&](const string& fn) {
             if (!overwrite) { std::ifstream probe(fn); if (probe.good()) throw std::runtime_error("File " + fn + " already exists! Use -w to allow overwrite!"); }
+        };
+        const bool wantsBreaks = job.outputs.at("breakpoints") || job.outputs.at("consensus");
+        const bool wantsLevels = job.outputs.at("levels") || job.outputs.at("consensus");   // (a consensus segment carries its level)
+        if (wantsLevels) setenv("HML_LEVELS", "1", 1);   // every context of this process accumulates the emission levels of its recorded sweeps (include/hml.h)
+        if (wantsBreaks) setenv("HML_BREAKS", "1", 1);   // ... and counts their breakpoints
+        if (job.outputs.at("levels")) refuseExisting(levelsFileName(job));
+        if (job.outputs.at("breakpoints")) refuseExisting(breaksFileName(job));
+        if (job.outputs.at("consensus")) {
+            refuseExisting(consensusFileName(job));
+            const double w = args.parse<double>("-consensus", 0);
+            job.consensusShare = args.parse<double>("-consensus", 1);
+            if (!(w >= 0 && w <= 4294967295.0)) throw std::runtime_error("The window of -consensus must be a number of positions!");
+            if (!(job.consensusShare >= 0 && job.consensusShare <= 1)) throw std::runtime_error("The share of -consensus must lie in [0, 1]!");
+            job.consensusWindow = (uint32_t)w;
         }
 
         if (nrChains <= 1) {
@@ -517,6 +609,7 @@ int main(int argc, const char* argv[]) {
             int nDev = 1;
             hml_check(hml_device_count(&nDev));
             if (job.outputs.at("levels") && nDev > 1) throw std::runtime_error(kLevelsDevicesMessage);   // (before anything runs)
+            if (wantsBreaks && nDev > 1) throw std::runtime_error(kBreaksDevicesMessage);
             Rendezvous rv(nrChains);
             // chain k lives on GPU (device + k) mod #GPUs; the chains of one GPU are driven by ONE host thread in lockstep and
             // share the construction of the observations
@@ -562,11 +655,15 @@ int main(int argc, const char* argv[]) {
                     }
                 } catch (...) { poolError = std::current_exception(); }
             }
-            if ((int)ctxs.size() == nrChains && job.outputs.at("levels") && !poolError) {
-                // the chains share the GPU: their levels add up in the first chain's context, which the file is written from
+            if ((int)ctxs.size() == nrChains && (wantsLevels || wantsBreaks) && !poolError) {
+                // the chains share the GPU: their levels and breakpoint counts add up in the first chain's context, which the
+                // files are written from
                 try {
-                    for (int k = 1; k < nrChains; ++k) hml_check(hml_levels_merge(ctxs[0], ctxs[k]));
-                    writeLevels(job, ctxs[0]);
+                    for (int k = 1; k < nrChains; ++k) {
+                        if (wantsLevels) hml_check(hml_levels_merge(ctxs[0], ctxs[k]));
+                        if (wantsBreaks) hml_check(hml_breaks_merge(ctxs[0], ctxs[k]));
+                    }
+                    writeContextFiles(job, ctxs[0]);
                 } catch (...) { poolError = std::current_exception(); }
             }
             rv.release(poolError == nullptr && (int)ctxs.size() == nrChains);

@@ -265,6 +265,42 @@ int hml_levels_dense_device(hml_ctx* ctx, void* out_dev /* float [2D][T] */);
  * the last sampled means; the level itself is the same number whatever the state is called, so sums over sweeps and
  * chains are exact statements about the posterior, also with twin or unused states. */
 int hml_levels_merge(hml_ctx* dst, hml_ctx* src);
+/* Sums of the recorded levels over caller-given segments (ABI 5): the n_cuts ascending cuts in (0, T) divide the positions
+ * into n_cuts + 1 segments; sum[d * (n_cuts + 1) + k] = the sum over the positions t of segment k of S1[t], sum_sq[...] of
+ * S2[t].  The cuts need not be boundaries of the levels: a fine segment that a cut splits contributes by length.  A
+ * segment's mean level is sum / (N len) and its pooled spread sqrt(max(0, sum_sq / (N len) - mean^2)) with N of
+ * hml_levels_rle.  Same bits on every run (the fixed summation tree of hml_levels_rle over length x value).  HML_ERR_ARG on
+ * unsorted or out-of-range cuts and on a context that never recorded levels. */
+int hml_levels_on_segments(hml_ctx* ctx, uint64_t n_cuts, const uint32_t* cuts /*n_cuts, ascending, in (0, T)*/,
+                           double* sum /*D*(n_cuts+1), dimension-major*/, double* sum_sq /*D*(n_cuts+1)*/);
+
+/* ---- breakpoint posteriors per position and the consensus segmentation (ABI 5).  No counterpart in the reference. ----
+ * A recorded sweep has a BREAKPOINT at position t (0 < t < T) iff a block starts at t whose state differs from the state of
+ * the block before it; position 0 is never one.  The context counts, per position, the recorded sweeps with a breakpoint
+ * there (C[t]) and the sweeps recorded while the recording was on (N).  Like the emission level the indicator does not
+ * depend on what the states are called, so it adds over sweeps and chains without relabelling; all of it is integers, so
+ * every result below is exact.  Memory: T + 1 words and (T + 32) / 32 words, allocated by the first recorded sweep that
+ * needs them; cost per recorded sweep: one launch, proportional to the number of blocks.
+ * hml_set_break_recording: at any time before a recorded sweep; turning it off keeps what was accumulated.  Off by
+ * default (a sweep then launches what it launched before ABI 5).  Environment: HML_BREAKS=1. */
+int hml_set_break_recording(hml_ctx* ctx, int on);
+/* The positions with C > 0, ascending, and their counts; n_recorded = N.  Call with pos == NULL to obtain n_breaks and
+ * n_recorded.  A context that recorded but saw no breakpoint returns n_breaks = 0; HML_ERR_ARG on a context that never
+ * recorded breaks. */
+int hml_breaks_list(hml_ctx* ctx, uint64_t* n_breaks, uint64_t* n_recorded, uint32_t* pos /*n_breaks*/, uint32_t* count /*n_breaks*/);
+/* Dense form on the DEVICE: out[t] = (sum of C[u] over |u - t| <= window) / N - the posterior probability of a breakpoint
+ * at t for window 0, the expected number of breakpoints near t otherwise.  The sum is exact (64-bit integers), the quotient
+ * is taken in double and rounded once to float; not-a-number when N = 0. */
+int hml_breaks_dense_device(hml_ctx* ctx, void* out_dev /* float [T] */, uint32_t window);
+/* Adds `src`'s counts, positions and N into `dst`; `src` is unchanged and `dst` may go on recording.  Same device and T,
+ * otherwise HML_ERR_ARG (chains on different GPUs are not merged yet).  No common labels are needed. */
+int hml_breaks_merge(hml_ctx* dst, hml_ctx* src);
+/* Consensus breakpoints.  The candidates are the listed positions t_i with counts C_i; mass_i = the sum of C_j over
+ * |t_j - t_i| <= window.  Candidate i is SELECTED iff mass_i >= max(min_count, 1) and no other candidate j within the
+ * window has C_j > C_i, or C_j == C_i with t_j < t_i - whether j is selected itself plays no part, so every candidate is
+ * decided on its own.  Output, ascending: position, mass and peak = C_i.  Call with pos == NULL to obtain n_selected. */
+int hml_breaks_consensus(hml_ctx* ctx, uint32_t window, uint64_t min_count, uint64_t* n_selected, uint32_t* pos /*n_selected*/,
+                         uint64_t* mass /*n_selected*/, uint32_t* peak /*n_selected*/);
 
 /* Trellis::sample(t) (src/Trellis.hpp:61-66): one draw of std::discrete_distribution over K weights - p_i = w_i / sum in
  * double, first i whose cumulative probability reaches u - with u from the chain's Philox key (sub-stream HOST,
@@ -337,7 +373,7 @@ int hml_get_stats(hml_ctx* ctx, hml_stats* out);
 
 /* HIP-event timing of one named kernel family accumulated since the last reset (milliseconds and
  * launches); name is one of "blocks_compact", "blocks_scatter", "block_stats", "stats_emission", "emission", "forward",
- * "backward_maps", "backward_chain", "mixture", "counts", "params", "marginals", "levels", "event_null".  level 0 = off, 1 = only the dominant kernel
+ * "backward_maps", "backward_chain", "mixture", "counts", "params", "marginals", "levels", "breaks", "event_null".  level 0 = off, 1 = only the dominant kernel
  * ("blocks_compact", two events per sweep), 2 = every family. */
 int hml_profile_enable(hml_ctx* ctx, int level);
 int hml_profile_get(hml_ctx* ctx, const char* name, double* total_ms, uint64_t* launches);
