@@ -94,6 +94,12 @@ SIGNATURES = {
     "hml_breaks_dense_device": (C.c_int, [_P, _P, C.c_uint32]),
     "hml_breaks_merge": (C.c_int, [_P, _P]),
     "hml_breaks_consensus": (C.c_int, [_P, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), _P, _P, _P]),
+    "hml_set_level_bands": (C.c_int, [_P, C.c_int, _P]),
+    "hml_get_level_bands": (C.c_int, [_P, C.POINTER(C.c_int), _P]),
+    "hml_bands_rle": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_uint64), _P, _P]),
+    "hml_bands_dense_device": (C.c_int, [_P, _P, C.c_int]),
+    "hml_bands_call": (C.c_int, [_P, C.c_uint64, C.POINTER(C.c_uint64), _P, _P]),
+    "hml_bands_merge": (C.c_int, [_P, _P]),
     "hml_categorical_draw": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_uint32)]),
     "hml_relabel_permutation": (C.c_int, [_P, _P]),
     "hml_pool_payload_size": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
@@ -500,6 +506,48 @@ class Chain:
             _check(self.lib.hml_breaks_consensus(self.h, window, min_count, C.byref(s), pos.ctypes.data, mass.ctypes.data, peak.ctypes.data))
         return pos, mass, peak
 
+    # ---- label-free marginals: the level's posterior in bands -------------------------------
+    def set_level_bands(self, edges):
+        """count, per position, the recorded sweeps whose emission level falls into each of the len(edges) + 1 bands that the
+        ascending `edges` define (hml_set_level_bands); an empty list turns the recording off and keeps the counts"""
+        edges = np.ascontiguousarray(edges, np.float32)
+        _check(self.lib.hml_set_level_bands(self.h, edges.size, edges.ctypes.data if edges.size else None))
+
+    def level_bands(self):
+        """the edges last set, float32"""
+        n = C.c_int()
+        edges = np.zeros(31, np.float32)
+        _check(self.lib.hml_get_level_bands(self.h, C.byref(n), edges.ctypes.data))
+        return edges[:n.value].copy()
+
+    def bands_rle(self):
+        """(seg_len[M], counts[M, D * (n_edges + 1)], n_recorded): per band segment, the recorded sweeps whose level lay in
+        band b of dimension d, in column d * (n_edges + 1) + b"""
+        m, ncol, n = C.c_uint64(), C.c_int(), C.c_uint64()
+        _check(self.lib.hml_bands_rle(self.h, C.byref(m), C.byref(ncol), C.byref(n), None, None))
+        seg = np.empty(m.value, np.uint64)
+        cnt = np.empty((m.value, ncol.value), np.int32)
+        _check(self.lib.hml_bands_rle(self.h, C.byref(m), C.byref(ncol), C.byref(n), seg.ctypes.data, cnt.ctypes.data))
+        return seg, cnt, n.value
+
+    def bands_dense_device(self, out_ptr, cumulative=False):
+        """counts per position into a device buffer int32 [D * (n_edges + 1)][T]; cumulative: the sweeps in band b or above"""
+        _check(self.lib.hml_bands_dense_device(self.h, out_ptr, 1 if cumulative else 0))
+
+    def bands_call(self, rank=0):
+        """(run_len[R], run_band[D, R]): the most probable band (rank 0) or the band of the rank-th smallest recorded level
+        (1 <= rank <= n_recorded) per dimension, adjacent segments with the same call merged (hml_bands_call)"""
+        r = C.c_uint64()
+        _check(self.lib.hml_bands_call(self.h, rank, C.byref(r), None, None))
+        ln = np.empty(r.value, np.uint64)
+        band = np.empty((self.D, r.value), np.int32)
+        _check(self.lib.hml_bands_call(self.h, rank, C.byref(r), ln.ctypes.data, band.ctypes.data))
+        return ln, band
+
+    def merge_bands(self, other):
+        """add `other`'s band counts into this chain's (same GPU, positions, dimensions and edges); no relabelling involved"""
+        _check(self.lib.hml_bands_merge(self.h, other.h))
+
     # ---- chain-parallel pooling ---------------------------------------------------------
     def relabel_permutation(self):
         perm = np.empty(self.K, np.int32)
@@ -649,6 +697,16 @@ def levels_mean_sd(n, s1, s2):
     mean = s1 / np.float64(n)
     var = s2 / np.float64(n) - mean * mean
     return mean.astype(np.float32), np.sqrt(np.maximum(var, 0.0)).astype(np.float32)
+
+
+def bands_exceedance(counts, n_edges, D):
+    """Per-edge exceedance counts from Chain.bands_rle()'s counts [M, D * (n_edges + 1)]: out[i, d * n_edges + j] = the
+    recorded sweeps whose level of dimension d on segment i was >= edges[j] (the sum of the bands above the edge), int64."""
+    counts = np.asarray(counts, np.int64)
+    nb = n_edges + 1
+    per_dim = counts.reshape(counts.shape[0], D, nb)
+    above = np.cumsum(per_dim[:, :, ::-1], axis=2)[:, :, ::-1]   # [.., b] = the bands b and above
+    return np.ascontiguousarray(above[:, :, 1:]).reshape(counts.shape[0], D * n_edges)
 
 
 def marginals_text(seg, cnt):

@@ -100,6 +100,8 @@ HML_KERNEL void hml_k_debug_eval(int fn, const float* __restrict__ a, const floa
     }
 }
 
+static int bands_from_env(hml_ctx* c);   // (the level bands' section)
+
 extern "C" {
 
 const char* hml_last_error(void) { return g_err.c_str(); }
@@ -179,6 +181,7 @@ int hml_create(hml_ctx** out, int device, uint64_t seed, uint32_t chain_id, void
     if (const char* e = getenv("HML_BREAKS")) c->rec_breaks = c->breaks_asked = atoi(e) != 0;   // hml_set_break_recording for unmodified callers (`hammlet -O breakpoints`)
     if (const char* e = getenv("HML_MAX_BLOCKS")) c->cap_opt = strtoull(e, nullptr, 10);   // option "max_blocks" (tests: a tiny capacity exercises the growth everywhere)
     if (device < 64) g_live_ctx[device].fetch_add(1);
+    if (int r = bands_from_env(c)) { hml_destroy(c); return r; }   // HML_BANDS=e0,e1,...: hml_set_level_bands for unmodified callers (`hammlet -bands`)
     *out = c;
     return 0;
 }
@@ -215,7 +218,7 @@ static void free_all(hml_ctx* c) {
     trace_release(c);
     free_sweep_buffers(c);
     void* ptrs[] = {c->d_group_word, c->d_wave_total, c->d_stage, c->d_span_count, c->d_starts, c->d_bstat, c->d_eprobe, c->d_aprobe, c->d_coarse1,
-                    c->d_diff, c->d_boundary, c->d_levels, c->d_lev_boundary, c->d_breaks, c->d_brk_boundary, c->d_mdl, c->d_many};
+                    c->d_diff, c->d_boundary, c->d_levels, c->d_lev_boundary, c->d_breaks, c->d_brk_boundary, c->d_bands, c->d_band_boundary, c->d_mdl, c->d_many};
     for (void* p : ptrs) if (p) hipFree(p);
     if (c->h_B) hipHostFree(c->h_B);
     c->h_B = nullptr;
@@ -1061,6 +1064,7 @@ static int sweep_compat(hml_ctx* c, char method, bool record) {
     }
     if (record && c->rec_levels) { if (int r = launch_levels_record(c, s, hint)) return r; }   // (hml_k_compat_update above is this sweep's parameter update)
     if (record && c->rec_breaks) { if (int r = launch_breaks_record(c, s, hint)) return r; }
+    if (record && c->rec_bands) { if (int r = launch_bands_record(c, s, hint)) return r; }
     KLAUNCH_CHECK();
     return 0;
 }
@@ -1154,6 +1158,7 @@ static int sweep_wide(hml_ctx* c, char method, bool record) {
     }
     if (record && c->rec_levels) { if (int r = launch_levels_record(c, s, hint)) return r; }   // (after the update: hml_k_levels.h)
     if (record && c->rec_breaks) { if (int r = launch_breaks_record(c, s, hint)) return r; }
+    if (record && c->rec_bands) { if (int r = launch_bands_record(c, s, hint)) return r; }
     KLAUNCH_CHECK();
     return 0;
 }
@@ -1882,6 +1887,245 @@ int hml_levels_on_segments(hml_ctx* c, uint64_t n_cuts, const uint32_t* cuts, do
         if (sum) memcpy(sum + (uint64_t)d * n_seg, h_out.data() + (uint64_t)(2 * d) * n_seg, n_seg * sizeof(double));
         if (sum_sq) memcpy(sum_sq + (uint64_t)d * n_seg, h_out.data() + (uint64_t)(2 * d + 1) * n_seg, n_seg * sizeof(double));
     }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------- level bands (hml_k_bands.h)
+}  // extern "C"
+
+static bool parse_band_edges(const char* text, int* n, float* edges) {
+    // "e0,e1,..." (HML_BANDS); false on anything else
+    *n = 0;
+    const char* p = text;
+    while (*p) {
+        char* end = nullptr;
+        const float v = strtof(p, &end);
+        if (end == p || *n >= HML_MAX_BAND_EDGES) return false;
+        edges[(*n)++] = v;
+        p = end;
+        if (*p == ',') ++p; else if (*p) return false;
+    }
+    return *n > 0;
+}
+
+static const char* band_edges_fault(int n, const float* edges) {
+    if (n < 1 || n > HML_MAX_BAND_EDGES) return "level bands take 1 to 31 edges";
+    for (int j = 0; j < n; ++j) {
+        if (!std::isfinite(edges[j])) return "the edges of the level bands must be finite";
+        if (j > 0 && !(edges[j - 1] < edges[j])) return "the edges of the level bands must be strictly ascending";
+    }
+    return nullptr;
+}
+
+static bool same_band_edges(const hml_ctx* a, int n, const float* edges) {
+    return a->n_band_edges == n && memcmp(a->band_edges, edges, (size_t)n * sizeof(float)) == 0;   // (bit for bit)
+}
+
+static const char* kNoBands = "no level bands were recorded by this context: give the edges with hml_set_level_bands (or HML_BANDS=e0,e1,...) before the recorded sweeps";
+
+static int bands_ready(hml_ctx* c, hml_model* m) {
+    if (!c->bands_asked) return set_err(HML_ERR_ARG, kNoBands);
+    if (int r = ensure_band_buffers(c)) return r;   // (asked for, but no sweep was recorded yet: one segment of zeros)
+    if (int r = fetch_model(c, m)) return r;
+    if (m->err_code) { char buf[256]; return set_err(HML_ERR_MODEL, deverr_text(m->err_code, m->err_value, buf, sizeof buf)); }
+    return 0;
+}
+
+// the band segments of context `c` on stream `s`: starts d_seg[M] and, with `d_g`, the count differences at the starts
+// d_g[M][columns] (segment-major, hml_k_marg_gather)
+static int gather_band_segments(hml_ctx* c, hipStream_t s, uint64_t* M_out, DevBuf& d_seg, DevBuf* d_g) {
+    const uint32_t T = (uint32_t)c->T;
+    const int ncol = c->D * (c->n_band_edges + 1);
+    DevBuf d_cnt, d_off;
+    HIPCHK(hipMalloc(&d_cnt.p, c->n_spans * sizeof(uint32_t)));
+    HIPCHK(hipMalloc(&d_off.p, c->n_spans * sizeof(uint32_t)));
+    hipLaunchKernelGGL(hml_k_marg_count, dim3((c->n_spans + 3) / 4), dim3(256), 0, s, c->d_band_boundary, T, d_cnt.as<uint32_t>());
+    std::vector<uint32_t> h_cnt(c->n_spans), h_off(c->n_spans);
+    HIPCHK(hipMemcpyAsync(h_cnt.data(), d_cnt.p, c->n_spans * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    uint64_t M = 0;
+    for (uint32_t i = 0; i < c->n_spans; ++i) { h_off[i] = (uint32_t)M; M += h_cnt[i]; }
+    HIPCHK(hipMemcpyAsync(d_off.p, h_off.data(), c->n_spans * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMalloc(&d_seg.p, (M + 1) * sizeof(uint32_t)));
+    hipLaunchKernelGGL(hml_k_marg_scatter, dim3((c->n_spans + 3) / 4), dim3(256), 0, s, c->d_band_boundary, T, d_off.as<uint32_t>(), d_seg.as<uint32_t>());
+    if (d_g) {
+        HIPCHK(hipMalloc(&d_g->p, std::max<uint64_t>(M, 1) * ncol * sizeof(int32_t)));
+        hipLaunchKernelGGL(hml_k_marg_gather, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, s, c->d_bands, T, ncol, d_seg.as<uint32_t>(), (uint32_t)M, d_g->as<int32_t>());
+    }
+    KLAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(s));
+    *M_out = M;
+    return 0;
+}
+
+static int bands_from_env(hml_ctx* c) {
+    if (const char* e = getenv("HML_BANDS")) {
+        int n = 0; float edges[HML_MAX_BAND_EDGES];
+        if (!parse_band_edges(e, &n, edges)) return set_err(HML_ERR_ARG, "HML_BANDS: expected up to 31 comma-separated numbers");
+        if (const char* why = band_edges_fault(n, edges)) return set_err(HML_ERR_ARG, std::string("HML_BANDS: ") + why);
+        c->n_band_edges = n;
+        memcpy(c->band_edges, edges, (size_t)n * sizeof(float));
+        c->rec_bands = c->bands_asked = true;
+    }
+    return 0;
+}
+
+extern "C" {
+
+int hml_set_level_bands(hml_ctx* c, int n_edges, const float* edges) {
+    if (!c) return set_err(HML_ERR_ARG, "null context");
+    // (as in hml_set_level_recording: a graph captured under the other setting goes)
+    if (c->graph_exec) { if (int r = ctx_bind(c)) return r; hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
+    if (n_edges == 0) { c->rec_bands = false; return 0; }   // (what was accumulated stays, and so do its edges)
+    if (!edges) return set_err(HML_ERR_ARG, "null argument");
+    if (const char* why = band_edges_fault(n_edges, edges)) return set_err(HML_ERR_ARG, why);
+    if (c->model_set && (uint64_t)c->D * (uint64_t)(n_edges + 1) > HML_CAP_K)
+        return set_err(HML_ERR_ARG, "level bands: the data dimensions times (edges + 1) exceed 64 columns");
+    if (!same_band_edges(c, n_edges, edges) && c->d_bands) {
+        // buffers of other edges: they go if they hold nothing
+        if (int r = ctx_bind(c)) return r;
+        if (int r = hml_settle(c)) return r;
+        hml_model m; if (int r = fetch_model(c, &m)) return r;
+        if (m.n_bands_recorded != 0ull) return set_err(HML_ERR_ARG, "level bands were already recorded under other edges: they cannot be changed any more");
+        HIPCHK(hipFree(c->d_bands)); c->d_bands = nullptr;
+        HIPCHK(hipFree(c->d_band_boundary)); c->d_band_boundary = nullptr;
+    }
+    c->n_band_edges = n_edges;
+    memcpy(c->band_edges, edges, (size_t)n_edges * sizeof(float));
+    c->rec_bands = c->bands_asked = true;
+    return 0;
+}
+
+int hml_get_level_bands(hml_ctx* c, int* n_edges, float* edges) {
+    if (!c || !n_edges) return set_err(HML_ERR_ARG, "null argument");
+    *n_edges = c->n_band_edges;
+    if (edges) memcpy(edges, c->band_edges, (size_t)c->n_band_edges * sizeof(float));
+    return 0;
+}
+
+int hml_bands_rle(hml_ctx* c, uint64_t* n_segments, int* n_columns, uint64_t* n_recorded, uint64_t* seg_len, int32_t* counts) {
+    NEED_MODEL();
+    if (!n_segments) return set_err(HML_ERR_ARG, "null argument");
+    hml_model m; if (int r = bands_ready(c, &m)) return r;
+    const uint32_t T = (uint32_t)c->T;
+    const int ncol = c->D * (c->n_band_edges + 1);
+    uint64_t M = 0;
+    DevBuf b_seg, b_g;
+    if (int r = gather_band_segments(c, c->stream, &M, b_seg, &b_g)) return r;
+    *n_segments = M;
+    if (n_columns) *n_columns = ncol;
+    if (n_recorded) *n_recorded = m.n_bands_recorded;
+    if (!seg_len) return 0;
+    std::vector<uint32_t> h_seg(M);
+    std::vector<int32_t> h_g(M * ncol);
+    HIPCHK(hipMemcpyAsync(h_seg.data(), b_seg.p, M * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(h_g.data(), b_g.p, M * ncol * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    // running sums over segments, as in hml_marginals_rle
+    std::vector<int32_t> cur(ncol, 0);
+    for (uint64_t i = 0; i < M; ++i) {
+        for (int s = 0; s < ncol; ++s) cur[s] += h_g[i * ncol + s];
+        seg_len[i] = (uint64_t)((i + 1 < M ? h_seg[i + 1] : T) - h_seg[i]);
+        if (counts) for (int s = 0; s < ncol; ++s) counts[i * ncol + s] = cur[s];
+    }
+    return 0;
+}
+
+int hml_bands_dense_device(hml_ctx* c, void* out_dev, int cumulative) {
+    NEED_MODEL();
+    if (!out_dev) return set_err(HML_ERR_ARG, "null argument");
+    hml_model m; if (int r = bands_ready(c, &m)) return r;
+    const uint32_t T = (uint32_t)c->T;
+    const int nb = c->n_band_edges + 1, ncol = c->D * nb;
+    int32_t* out = (int32_t*)out_dev;
+    const uint32_t n_chunks = c->n_spans;
+    DevBuf b_cs;
+    HIPCHK(hipMalloc(&b_cs.p, (uint64_t)ncol * n_chunks * sizeof(int32_t)));
+    hipLaunchKernelGGL(hml_k_dense_partial, dim3(n_chunks, ncol), dim3(256), 0, c->stream, c->d_bands, T, ncol, b_cs.as<int32_t>(), n_chunks);
+    hipLaunchKernelGGL(hml_k_dense_chunkscan, dim3(ncol), dim3(1024), 0, c->stream, b_cs.as<int32_t>(), n_chunks);
+    hipLaunchKernelGGL(hml_k_dense_final, dim3(n_chunks, ncol), dim3(256), 0, c->stream, c->d_bands, T, ncol, b_cs.as<int32_t>(), n_chunks, (const int32_t*)nullptr, out);
+    if (cumulative) hipLaunchKernelGGL(hml_k_bands_cumulate, dim3(grid_for(T, 256, 1, 65536)), dim3(256), 0, c->stream, out, T, c->D, nb);
+    KLAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int hml_bands_call(hml_ctx* c, uint64_t rank, uint64_t* n_runs, uint64_t* run_len, int32_t* run_band) {
+    NEED_MODEL();
+    if (!n_runs) return set_err(HML_ERR_ARG, "null argument");
+    hml_model m; if (int r = bands_ready(c, &m)) return r;
+    if (rank > m.n_bands_recorded) return set_err(HML_ERR_ARG, "hml_bands_call: the rank must be 0 (the most probable band) or between 1 and the number of recorded sweeps");
+    const uint32_t T = (uint32_t)c->T;
+    const int D = c->D, nb = c->n_band_edges + 1, ncol = D * nb;
+    uint64_t M = 0;
+    DevBuf b_seg, b_g, b_cs, b_rc, b_key;
+    if (int r = gather_band_segments(c, c->stream, &M, b_seg, &b_g)) return r;
+    const uint32_t n_chunks = (uint32_t)((M + 255) / 256);
+    HIPCHK(hipMalloc(&b_cs.p, (uint64_t)ncol * n_chunks * sizeof(int32_t)));
+    HIPCHK(hipMalloc(&b_rc.p, ((uint64_t)n_chunks + 1) * sizeof(int32_t)));
+    HIPCHK(hipMalloc(&b_key.p, M * sizeof(int16_t)));
+    int32_t *const d_cs = b_cs.as<int32_t>(), *const d_rc = b_rc.as<int32_t>();
+    int16_t* const d_key = b_key.as<int16_t>();
+    HIPCHK(hipMemsetAsync(d_rc + n_chunks, 0, sizeof(int32_t), c->stream));
+    hipLaunchKernelGGL(hml_k_seg_partial, dim3(n_chunks), dim3(256), 0, c->stream, b_g.as<int32_t>(), (uint32_t)M, ncol, d_cs, n_chunks);
+    hipLaunchKernelGGL(hml_k_dense_chunkscan, dim3(ncol), dim3(1024), 0, c->stream, d_cs, n_chunks);
+    hipLaunchKernelGGL(hml_k_bands_pick, dim3(n_chunks), dim3(256), 0, c->stream, b_g.as<int32_t>(), (uint32_t)M, D, nb, d_cs, n_chunks, (unsigned long long)rank, d_key);
+    hipLaunchKernelGGL(hml_k_seg_run_count, dim3(n_chunks), dim3(256), 0, c->stream, d_key, (uint32_t)M, d_rc);
+    hipLaunchKernelGGL(hml_k_dense_chunkscan, dim3(1), dim3(1024), 0, c->stream, d_rc, n_chunks + 1u);   // d_rc[n_chunks] = total
+    KLAUNCH_CHECK();
+    int32_t R = 0;
+    HIPCHK(hipMemcpyAsync(&R, d_rc + n_chunks, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *n_runs = (uint64_t)R;
+    if (!run_len) return 0;
+    DevBuf b_rs, b_rq;
+    HIPCHK(hipMalloc(&b_rs.p, (uint64_t)R * sizeof(uint32_t)));
+    HIPCHK(hipMalloc(&b_rq.p, (uint64_t)R * sizeof(int16_t)));
+    hipLaunchKernelGGL(hml_k_seg_run_scatter, dim3(n_chunks), dim3(256), 0, c->stream, d_key, b_seg.as<uint32_t>(), (uint32_t)M, d_rc, b_rs.as<uint32_t>(), b_rq.as<int16_t>());
+    KLAUNCH_CHECK();
+    std::vector<uint32_t> h_rs(R);
+    std::vector<int16_t> h_rq(R);
+    HIPCHK(hipMemcpyAsync(h_rs.data(), b_rs.p, (uint64_t)R * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(h_rq.data(), b_rq.p, (uint64_t)R * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int32_t r = 0; r < R; ++r) {
+        run_len[r] = (uint64_t)((r + 1 < R ? h_rs[r + 1] : T) - h_rs[r]);
+        if (run_band) {
+            uint32_t key = (uint16_t)h_rq[r];   // (hml_k_bands_pick: the D calls as digits to the base of the bands per dimension)
+            for (int d = 0; d < D; ++d) { run_band[(uint64_t)d * R + r] = (int32_t)(key % (uint32_t)nb); key /= (uint32_t)nb; }
+        }
+    }
+    return 0;
+}
+
+int hml_bands_merge(hml_ctx* dst, hml_ctx* src) {
+    if (!dst || !src || !dst->model_set || !src->model_set) return set_err(HML_ERR_ARG, "model not set");
+    if (dst == src) return set_err(HML_ERR_ARG, "a context cannot be merged into itself");
+    if (dst->device != src->device)
+        return set_err(HML_ERR_ARG, "the level bands of chains on different GPUs are not merged yet: run the chains of one bands file on one GPU");
+    if (dst->T != src->T || dst->D != src->D) return set_err(HML_ERR_ARG, "level bands can only be merged between chains over the same positions and dimensions");
+    if (!src->bands_asked) return set_err(HML_ERR_ARG, "no level bands were recorded by the source context: give the edges with hml_set_level_bands (or HML_BANDS=e0,e1,...) before the recorded sweeps");
+    if (!same_band_edges(dst, src->n_band_edges, src->band_edges)) {
+        // a destination that was never asked takes the source's edges; any other difference is refused
+        if (dst->bands_asked || dst->d_bands) return set_err(HML_ERR_ARG, "level bands can only be merged between chains with the same edges, bit for bit");
+        dst->n_band_edges = src->n_band_edges;
+        memcpy(dst->band_edges, src->band_edges, sizeof dst->band_edges);
+    }
+    if (int r = ctx_bind(dst)) return r;
+    if (int r = hml_settle(src)) return r;   // (both streams idle: the merge reads the source's accumulators on the destination's stream)
+    if (int r = hml_settle(dst)) return r;
+    if (int r = ensure_band_buffers(src)) return r;
+    if (int r = ensure_band_buffers(dst)) return r;
+    dst->bands_asked = true;
+    const uint32_t T = (uint32_t)src->T;
+    const int ncol = src->D * (src->n_band_edges + 1);
+    uint64_t M = 0;
+    DevBuf b_seg;
+    if (int r = gather_band_segments(src, dst->stream, &M, b_seg, nullptr)) return r;
+    hipLaunchKernelGGL(hml_k_bands_merge, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, dst->stream, src->d_bands, b_seg.as<uint32_t>(), (uint32_t)M, T,
+                       ncol, src->d_mdl, dst->d_bands, dst->d_band_boundary, dst->d_mdl);
+    KLAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(dst->stream));
     return 0;
 }
 

@@ -32,6 +32,7 @@
 #include "hml_k_marginals.h"
 #include "hml_k_levels.h"
 #include "hml_k_breaks.h"
+#include "hml_k_bands.h"
 #include "hml_k_segment.h"
 #include "hml_k_trellis.h"
 #include "hml_k_trellis_rows.h"
@@ -286,6 +287,38 @@ static int launch_breaks_record(hml_ctx* c, hipStream_t s, uint32_t hint) {
 }
 
 
+// the level bands' accumulators (hml_k_bands.h): D (n_edges + 1) (T + 1) int32 and (T + 32) / 32 words of bitmap, on first
+// use; zeroed before this returns, like the levels' accumulators
+static int ensure_band_buffers(hml_ctx* c) {
+    if (c->d_bands) return 0;
+    const uint64_t ncol = (uint64_t)c->D * (uint64_t)(c->n_band_edges + 1);
+    if (c->n_band_edges < 1 || ncol > HML_CAP_K) return set_err(HML_ERR_ARG, "level bands: the data dimensions times (edges + 1) must be between 2 and 64 columns");
+    const uint64_t n = ncol * (c->T + 1);
+    const uint64_t words = (c->T + 32) / 32;
+    HIPCHK(hipMalloc(&c->d_bands, n * sizeof(int32_t)));
+    HIPCHK(hipMalloc(&c->d_band_boundary, words * sizeof(uint32_t)));
+    HIPCHK(hipMemsetAsync(c->d_bands, 0, n * sizeof(int32_t), c->stream));
+    HIPCHK(hipMemsetAsync(c->d_band_boundary, 0, words * sizeof(uint32_t), c->stream));
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(c->stream, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone) HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+static hml_band_edges band_edges_of(const hml_ctx* c) {
+    hml_band_edges ed;
+    memset(&ed, 0, sizeof ed);
+    ed.n = c->n_band_edges;
+    for (int j = 0; j < c->n_band_edges; ++j) ed.e[j] = c->band_edges[j];
+    return ed;
+}
+
+// the band kernel of a recorded sweep, on stream `s`, BEHIND the sweep's parameter update like the level kernel
+static int launch_bands_record(hml_ctx* c, hipStream_t s, uint32_t hint) {
+    if (int r = ensure_band_buffers(c)) return r;
+    ProfScope ps(c, "bands");
+    hipLaunchKernelGGL(hml_k_bands_record, dim3(grid_for(hint, 256, 64, 16384)), dim3(256), 0, s, c->d_q, c->d_starts, c->d_mdl, band_edges_of(c), c->d_bands, c->d_band_boundary);
+    return 0;
+}
 
 
 // ---- chunk length of the fused trellis path (hml_ctx.hpp: tre_autotune)

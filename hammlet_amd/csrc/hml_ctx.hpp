@@ -122,6 +122,13 @@ struct hml_ctx {
     bool breaks_asked = false;      // ... was on at some time: the read-outs answer (with nothing recorded: an empty list)
     uint32_t* d_breaks = nullptr;   // [T + 1]: recorded sweeps with a breakpoint at t
     uint32_t* d_brk_boundary = nullptr;   // the breaks' own bitmap of the positions with a count
+    // level bands per position (hml_k_bands.h), allocated by the first recorded sweep that wants them
+    bool rec_bands = false;         // hml_set_level_bands / HML_BANDS
+    bool bands_asked = false;       // ... was on at some time: the read-outs answer (with nothing recorded: one segment of zeros)
+    int n_band_edges = 0;           // the edges last set (they stay when the recording is turned off)
+    float band_edges[31] = {};
+    int32_t* d_bands = nullptr;     // [D (n_band_edges + 1)][T + 1]: difference arrays of the counts per band
+    uint32_t* d_band_boundary = nullptr;   // the bands' own bitmap of segment boundaries
     hml_model* d_mdl = nullptr;
     uint32_t* h_B = nullptr;       // pinned + mapped, four words: [0] the block count of the latest enumeration (grid sizing hint),
                                     // [1] set by the fused block kernel when a bounded wait expired, [2] the chain is HALTED: the number of

@@ -130,6 +130,7 @@ struct hml_model {
     uint32_t wl_retry;           // ... this sweep's filter runs once more with a longer warm-up (hml_k_wl_retry_decide): the warm-up, or 0
     unsigned long long n_levels_recorded;   // sweeps whose emission levels were accumulated (hml_k_levels.h), merged chains included
     unsigned long long n_breaks_recorded;   // sweeps whose breakpoints were counted (hml_k_breaks.h), merged chains included
+    unsigned long long n_bands_recorded;    // sweeps whose level bands were counted (hml_k_bands.h), merged chains included
 };
 
 #if defined(__HIPCC__)

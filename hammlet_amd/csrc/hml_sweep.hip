@@ -277,6 +277,7 @@ static int sweep_k(hml_ctx* c, char method, bool record) {
     }
     if (record && c->rec_levels) { if (int r = launch_levels_record(c, s, hint)) return r; }   // (after the update: hml_k_levels.h)
     if (record && c->rec_breaks) { if (int r = launch_breaks_record(c, s, hint)) return r; }
+    if (record && c->rec_bands) { if (int r = launch_bands_record(c, s, hint)) return r; }
     KLAUNCH_CHECK();
     return 0;
 }
@@ -295,6 +296,7 @@ static int iterate_many_k(hml_ctx* const* cs, int n, uint64_t first, uint64_t it
     for (int i = 0; i < n; ++i) {
         if (records && cs[i]->rec_levels) { if (int r = ensure_level_buffers(cs[i])) return r; }
         if (records && cs[i]->rec_breaks) { if (int r = ensure_break_buffers(cs[i])) return r; }
+        if (records && cs[i]->rec_bands) { if (int r = ensure_band_buffers(cs[i])) return r; }
         if (records && cs[i]->rec_marginals) {
             if (cs[i]->pooled) return set_err(HML_ERR_ARG, "the marginals of a context are pooled (common labels, several chains): further sweeps cannot be recorded into them");
             if (int r = ensure_marginal_buffers(cs[i])) return r;
@@ -461,6 +463,11 @@ static int iterate_many_k(hml_ctx* const* cs, int n, uint64_t first, uint64_t it
             if (record) for (int k = g0; k < g0 + gn; ++k) if (cs[k]->rec_breaks) {
                 hml_ctx* c = cs[k];
                 hipLaunchKernelGGL(hml_k_breaks_record, dim3(gB), dim3(256), 0, s, c->d_q, c->d_starts, c->d_mdl, c->d_breaks, c->d_brk_boundary);
+            }
+            // ... and those that count their level bands (hml_k_bands.h; behind the parameter kernels, like the levels)
+            if (record) for (int k = g0; k < g0 + gn; ++k) if (cs[k]->rec_bands) {
+                hml_ctx* c = cs[k];
+                hipLaunchKernelGGL(hml_k_bands_record, dim3(gB), dim3(256), 0, s, c->d_q, c->d_starts, c->d_mdl, band_edges_of(c), c->d_bands, c->d_band_boundary);
             }
         }
         KLAUNCH_CHECK();

@@ -9,6 +9,10 @@
 // relabelling is involved); `-O breakpoints` (BP) writes PREFIXbreakpointsSUFFIX, per position where a recorded sweep changed
 // state how many did and that share of the recorded sweeps; `-O consensus` (CS) writes PREFIXconsensusSUFFIX, the consensus
 // segmentation under `-consensus W P` with each segment's support and level (hml_breaks_consensus, hml_levels_on_segments);
+// `-bands E0 [E1 ...]` gives ascending edges of the emission level, and `-O LB` (bands) writes PREFIXbandsSUFFIX, per band segment
+// its length and per data dimension and band the number of recorded sweeps whose level lay in it - marginals that need no
+// labels - and `-O LC` (bandcalls) writes PREFIXbandcallsSUFFIX, the band called per run under `-bandcall P` (hml_bands_rle,
+// hml_bands_call);
 // -raw FILE reads float32 values instead of text; -device N selects
 // the GPU; -chain N selects the Philox sub-key of an independent chain; -chains N runs N independent chains (sub-keys
 // chain .. chain+N-1), chain k on GPU (device + k) mod #GPUs in its own host thread, and pools their recorded marginals
@@ -54,6 +58,10 @@ static const char* kHelp =
     "                    CS           consensus: start, length, support of the left boundary, then mean and standard\n"
     "                                 deviation of the emission level per data dimension, one line per consensus segment;\n"
     "                                 turns the recording of the levels on (extension; see -consensus)\n"
+    "                    LB           bands: length, then per data dimension and band of -bands the number of recorded sweeps\n"
+    "                                 whose emission level lay in the band, one line per band segment (extension)\n"
+    "                    LC           bandcalls: start, length, then the band called per data dimension, one line per run\n"
+    "                                 of equal calls (extension; see -bandcall)\n"
     "  -w, -overwrite                 allow overwriting output files\n"
     "  -s, -states K | C P D          number of states (default 3), or P parameters shared by P^D states over D dimensions\n"
     "  -e, -emissions normal VAR P    automatic prior: P(variance < VAR) = P (default normal 0.2 0.9)\n"
@@ -72,6 +80,11 @@ static const char* kHelp =
     "  -consensus W P                 consensus segmentation (-O CS): a breakpoint is kept when the sweeps with a breakpoint\n"
     "                                 within W positions of it number at least P of the recorded ones and none of those\n"
     "                                 positions was a breakpoint more often (default 16 0.5) (extension)\n"
+    "  -bands E0 [E1 ...]             up to 31 ascending edges of the emission level, e.g. -0.5 0.5 for loss / neutral / gain:\n"
+    "                                 band b holds the levels in [E(b-1), E(b)); counted per position over the recorded\n"
+    "                                 sweeps, whatever the states are called (-O LB, -O LC) (extension)\n"
+    "  -bandcall P                    the call of -O LC: 0 (default) the most probable band, 0 < P <= 1 the band of the\n"
+    "                                 P-quantile of the recorded levels (0.5: the median) (extension)\n"
     "  -chains N                      N independent chains, one per GPU, marginals pooled over RCCL (extension);\n"
     "                                 chains beyond the number of GPUs share a GPU and the construction it holds.\n"
     "                                 The pooled marginals / maxsegmentation files use common labels (states by\n"
@@ -97,6 +110,8 @@ struct Job {
     std::map<string, bool> outputs;
     uint32_t consensusWindow = 16;   // -consensus W P
     double consensusShare = 0.5;
+    size_t nrBandEdges = 0;          // -bands
+    double bandCall = 0;             // -bandcall P
 };
 
 // Meeting point of the chain threads of `-chains N` and the main thread: a chain arrives with its context once its
@@ -242,11 +257,69 @@ static void writeConsensus(const Job& job, hml_ctx* ctx) {
     if (fclose(out) != 0) throw std::runtime_error("Cannot write to file " + fn + "!");
 }
 
+static const char* kBandsDevicesMessage =
+    "The level bands of chains on different GPUs are not merged yet: run -O bands / -O bandcalls with -chains N on one GPU!";
+
+static string bandsFileName(const Job& job) { return job.opref + "bands" + job.osuff; }
+static string bandCallsFileName(const Job& job) { return job.opref + "bandcalls" + job.osuff; }
+
+// PREFIXbandsSUFFIX from the context's band counts: "length c_0 ... c_{n_columns-1}" per band segment, tab-separated like
+// the marginals file; column d (edges + 1) + b = the recorded sweeps whose level of dimension d lay in band b
+static void writeBands(const Job& job, hml_ctx* ctx) {
+    uint64_t M = 0, N = 0;
+    int ncol = 0;
+    hml_check(hml_bands_rle(ctx, &M, &ncol, &N, nullptr, nullptr));
+    vector<uint64_t> len(M);
+    vector<int32_t> cnt(M * (size_t)ncol);
+    hml_check(hml_bands_rle(ctx, &M, &ncol, &N, len.data(), cnt.data()));
+    const string fn = bandsFileName(job);
+    FILE* out = fopen(fn.c_str(), "w");
+    if (!out) throw std::runtime_error("Cannot write to file " + fn + "!");
+    for (uint64_t i = 0; i < M; ++i) {
+        fprintf(out, "%llu", (unsigned long long)len[i]);
+        for (int s = 0; s < ncol; ++s) fprintf(out, "\t%d", cnt[i * (size_t)ncol + s]);
+        fputc('\n', out);
+    }
+    if (fclose(out) != 0) throw std::runtime_error("Cannot write to file " + fn + "!");
+}
+
+// PREFIXbandcallsSUFFIX: "start length band_0 [band_1 ...]" per run of equal calls; -bandcall 0: the most probable band,
+// 0 < P <= 1: the band of the rank max(1, ceil(P N))-th smallest of the N recorded levels
+static void writeBandCalls(const Job& job, hml_ctx* ctx) {
+    uint64_t M = 0, N = 0, R = 0;
+    int ncol = 0;
+    hml_check(hml_bands_rle(ctx, &M, &ncol, &N, nullptr, nullptr));
+    uint64_t rank = 0;
+    if (job.bandCall > 0 && N > 0) {
+        const double r = std::ceil(job.bandCall * (double)N);
+        rank = r > 1.0 ? (uint64_t)r : 1;
+        if (rank > N) rank = N;
+    }
+    hml_check(hml_bands_call(ctx, rank, &R, nullptr, nullptr));
+    const size_t D = job.nrDataDim;
+    vector<uint64_t> len(R);
+    vector<int32_t> band(R * D);
+    hml_check(hml_bands_call(ctx, rank, &R, len.data(), band.data()));
+    const string fn = bandCallsFileName(job);
+    FILE* out = fopen(fn.c_str(), "w");
+    if (!out) throw std::runtime_error("Cannot write to file " + fn + "!");
+    uint64_t start = 0;
+    for (uint64_t r = 0; r < R; ++r) {
+        fprintf(out, "%llu %llu", (unsigned long long)start, (unsigned long long)len[r]);
+        for (size_t d = 0; d < D; ++d) fprintf(out, " %d", band[d * R + r]);
+        fputc('\n', out);
+        start += len[r];
+    }
+    if (fclose(out) != 0) throw std::runtime_error("Cannot write to file " + fn + "!");
+}
+
 // the files written from a finished context (one chain, or the first of several after the others were merged into it)
 static void writeContextFiles(const Job& job, hml_ctx* ctx) {
     if (job.outputs.at("levels")) writeLevels(job, ctx);
     if (job.outputs.at("breakpoints")) writeBreakpoints(job, ctx);
     if (job.outputs.at("consensus")) writeConsensus(job, ctx);
+    if (job.outputs.at("bands")) writeBands(job, ctx);
+    if (job.outputs.at("bandcalls")) writeBandCalls(job, ctx);
 }
 
 // One chain from its device context to its output files.  `index` > 0 (chains of `-chains N` beyond the first): the
@@ -425,6 +498,8 @@ int main(int argc, const char* argv[]) {
         args.registerFlags({"-chains"}, "1");
         args.registerFlags({"-compat"});
         args.registerFlags({"-consensus"}, "16 0.5");
+        args.registerFlags({"-bands"});
+        args.registerFlags({"-bandcall"}, "0");
         args.parseArgs();
 
         if (args.isSet("-g")) args.print();
@@ -508,6 +583,8 @@ int main(int argc, const char* argv[]) {
         outputArgs.registerFlags({"L", "levels"});            // extension
         outputArgs.registerFlags({"BP", "breakpoints"});      // extension (B and C are the reference's blocks and compression)
         outputArgs.registerFlags({"CS", "consensus"});        // extension
+        outputArgs.registerFlags({"LB", "bands"});            // extension
+        outputArgs.registerFlags({"LC", "bandcalls"});        // extension
         outputArgs.parseArgs();
 
         // ---- input
@@ -580,7 +657,7 @@ int main(int argc, const char* argv[]) {
         job.weightMultiplier = weightMultiplier; job.useSelfTrans = useSelfTrans;
         job.thetaParams = thetaParams; job.trans = trans; job.selfTrans = selfTrans; job.initialAlpha = initialAlpha;
         job.scheme = scheme;
-        for (const char* o : {"sequences", "parameters", "blocks", "compression", "marginals", "segments", "maxsegmentation", "levels", "breakpoints", "consensus"})
+        for (const char* o : {"sequences", "parameters", "blocks", "compression", "marginals", "segments", "maxsegmentation", "levels", "breakpoints", "consensus", "bands", "bandcalls"})
             job.outputs[o] = outputArgs.isSet(o);
         auto refuseExisting = [&](const string& fn) {
             if (!overwrite) { std::ifstream probe(fn); if (probe.good()) throw std::runtime_error("File " + fn + " already exists! Use -w to allow overwrite!"); }
@@ -589,6 +666,34 @@ int main(int argc, const char* argv[]) {
         const bool wantsLevels = job.outputs.at("levels") || job.outputs.at("consensus");   // (a consensus segment carries its level)
         if (wantsLevels) setenv("HML_LEVELS", "1", 1);   // every context of this process accumulates the emission levels of its recorded sweeps (include/hml.h)
         if (wantsBreaks) setenv("HML_BREAKS", "1", 1);   // ... and counts their breakpoints
+        const bool wantsBands = job.outputs.at("bands") || job.outputs.at("bandcalls");
+        if (wantsBands && !args.isSet("-bands")) throw std::runtime_error("The outputs bands (LB) and bandcalls (LC) need the edges of the bands: give them with -bands E0 [E1 ...]!");
+        if (args.isSet("-bands")) {
+            // the edges as floats, handed to every context of this process (include/hml.h, HML_BANDS)
+            const vector<string> toks = args.tokens("-bands");
+            if (toks.empty()) throw std::runtime_error("Not enough arguments for flag -bands!");
+            if (toks.size() > 31) throw std::runtime_error("Too many edges for -bands: at most 31!");
+            string env;
+            float prev = 0;
+            for (size_t j = 0; j < toks.size(); ++j) {
+                char* end = nullptr;
+                const float e = strtof(toks[j].c_str(), &end);
+                if (end == toks[j].c_str() || *end) throw std::runtime_error("Conversion failed for string \"" + toks[j] + "\"!");
+                if (!std::isfinite(e)) throw std::runtime_error("The edges of -bands must be finite!");
+                if (j > 0 && !(prev < e)) throw std::runtime_error("The edges of -bands must be strictly ascending!");
+                prev = e;
+                char buf[32];
+                snprintf(buf, sizeof buf, "%.9g", (double)e);   // (nine digits give the float back)
+                env += (j ? "," : "") + string(buf);
+            }
+            if (nrDataDim * (toks.size() + 1) > 64) throw std::runtime_error("Too many bands: data dimensions times (edges + 1) may not exceed 64!");
+            job.nrBandEdges = toks.size();
+            job.bandCall = args.parse<double>("-bandcall", 0);
+            if (!(job.bandCall >= 0 && job.bandCall <= 1)) throw std::runtime_error("The quantile of -bandcall must lie in [0, 1]!");
+            if (wantsBands) setenv("HML_BANDS", env.c_str(), 1);
+        }
+        if (job.outputs.at("bands")) refuseExisting(bandsFileName(job));
+        if (job.outputs.at("bandcalls")) refuseExisting(bandCallsFileName(job));
         if (job.outputs.at("levels")) refuseExisting(levelsFileName(job));
         if (job.outputs.at("breakpoints")) refuseExisting(breaksFileName(job));
         if (job.outputs.at("consensus")) {
@@ -610,6 +715,7 @@ int main(int argc, const char* argv[]) {
             hml_check(hml_device_count(&nDev));
             if (job.outputs.at("levels") && nDev > 1) throw std::runtime_error(kLevelsDevicesMessage);   // (before anything runs)
             if (wantsBreaks && nDev > 1) throw std::runtime_error(kBreaksDevicesMessage);
+            if (wantsBands && nDev > 1) throw std::runtime_error(kBandsDevicesMessage);
             Rendezvous rv(nrChains);
             // chain k lives on GPU (device + k) mod #GPUs; the chains of one GPU are driven by ONE host thread in lockstep and
             // share the construction of the observations
@@ -655,13 +761,14 @@ int main(int argc, const char* argv[]) {
                     }
                 } catch (...) { poolError = std::current_exception(); }
             }
-            if ((int)ctxs.size() == nrChains && (wantsLevels || wantsBreaks) && !poolError) {
-                // the chains share the GPU: their levels and breakpoint counts add up in the first chain's context, which the
+            if ((int)ctxs.size() == nrChains && (wantsLevels || wantsBreaks || wantsBands) && !poolError) {
+                // the chains share the GPU: their levels, breakpoint counts and band counts add up in the first chain's context, which the
                 // files are written from
                 try {
                     for (int k = 1; k < nrChains; ++k) {
                         if (wantsLevels) hml_check(hml_levels_merge(ctxs[0], ctxs[k]));
                         if (wantsBreaks) hml_check(hml_breaks_merge(ctxs[0], ctxs[k]));
+                        if (wantsBands) hml_check(hml_bands_merge(ctxs[0], ctxs[k]));
                     }
                     writeContextFiles(job, ctxs[0]);
                 } catch (...) { poolError = std::current_exception(); }

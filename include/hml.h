@@ -302,6 +302,43 @@ int hml_breaks_merge(hml_ctx* dst, hml_ctx* src);
 int hml_breaks_consensus(hml_ctx* ctx, uint32_t window, uint64_t min_count, uint64_t* n_selected, uint32_t* pos /*n_selected*/,
                          uint64_t* mass /*n_selected*/, uint32_t* peak /*n_selected*/);
 
+/* ---- label-free marginals: the posterior of the emission level in caller-given bands.  No counterpart in the reference. ----
+ * EDGES: n_edges floats, 1 <= n_edges <= 31, finite and strictly ascending; they define n_edges + 1 BANDS.  band(mu) = the
+ * number of j with edges[j] <= mu, compared in float: band 0 lies below edges[0], band b is [edges[b-1], edges[b]), a level
+ * equal to an edge belongs to the band above it, a level that is not a number to band 0.  The LEVEL of a recorded sweep at
+ * position t and dimension d is the one of the emission levels above: mu of parameter (s / P^d) % P of the state s that
+ * covers t, under the theta that is current after that sweep's parameter update.  COLUMNS: n_columns = D (n_edges + 1),
+ * column d (n_edges + 1) + b; more than 64 columns are refused.  The context counts, per position and column, the recorded
+ * sweeps whose level fell into the band, and N, the sweeps recorded while the recording was on.  The counts do not depend on
+ * what a state is called - twin states, label switching and pooled chains need no relabelling - and they are integers, so
+ * every result below is exact.  Segments: a boundary lies where the band of any dimension changes in any recorded sweep;
+ * adjacent runs of different states in the same bands leave none, so the band segments are coarser than the levels' and the
+ * marginals'.  Memory: 4 n_columns (T + 1) bytes and (T + 32) / 32 words, allocated by the first recorded sweep that needs
+ * them; cost per recorded sweep: one launch, proportional to the number of blocks.
+ * hml_set_level_bands sets the edges and turns the recording on, at any time before a recorded sweep; n_edges = 0 turns it
+ * off and keeps what was accumulated, and its edges.  Once a sweep has been recorded, edges that differ in any bit are
+ * HML_ERR_ARG.  Off by default (a sweep then launches what it launched before).  Environment: HML_BANDS="e0,e1,...".
+ * hml_get_level_bands: the edges last set (edges may be NULL). */
+int hml_set_level_bands(hml_ctx* ctx, int n_edges, const float* edges /*n_edges*/);
+int hml_get_level_bands(hml_ctx* ctx, int* n_edges, float* edges /*31*/);
+/* Run-length form, in the shape of hml_marginals_rle: counts[i * n_columns + col] of segment i; n_recorded = N.  Call with
+ * seg_len == NULL to obtain the sizes.  Per segment the columns of a dimension sum to N.  A context that was asked but recorded
+ * nothing answers one segment of zeros with N = 0; HML_ERR_ARG on a context that never recorded bands. */
+int hml_bands_rle(hml_ctx* ctx, uint64_t* n_segments, int* n_columns, uint64_t* n_recorded, uint64_t* seg_len /*n_segments*/,
+                  int32_t* counts /*n_segments * n_columns, segment-major*/);
+/* Dense form on the DEVICE: int32 [n_columns][T].  cumulative = 0: the count per band.  cumulative = 1: row b of dimension d
+ * holds the sweeps whose level lay in band b or above - the exceedance count of edge b - 1; row 0 is N everywhere. */
+int hml_bands_dense_device(hml_ctx* ctx, void* out_dev /* int32 [n_columns][T] */, int cumulative);
+/* A call per band segment and dimension; adjacent segments whose call agrees in every dimension form one run.  rank = 0: the
+ * band with the largest count (the first maximum wins, hml_max_segmentation's rule).  1 <= rank <= N: the band of the
+ * rank-th smallest recorded level, i.e. the smallest b whose cumulative count over bands 0 .. b reaches rank (rank =
+ * ceil(N / 2): the median's band).  Any other rank is HML_ERR_ARG.  run_band[d * n_runs + r].  Call with run_len == NULL to
+ * obtain n_runs. */
+int hml_bands_call(hml_ctx* ctx, uint64_t rank, uint64_t* n_runs, uint64_t* run_len /*n_runs*/, int32_t* run_band /*D*n_runs, dimension-major*/);
+/* Adds `src`'s cells, boundary bits and N into `dst`; `src` is unchanged and `dst` may go on recording.  Same device, T, D and
+ * bit-identical edges, otherwise HML_ERR_ARG; a `dst` that was never given edges takes `src`'s. */
+int hml_bands_merge(hml_ctx* dst, hml_ctx* src);
+
 /* Trellis::sample(t) (src/Trellis.hpp:61-66): one draw of std::discrete_distribution over K weights - p_i = w_i / sum in
  * double, first i whose cumulative probability reaches u - with u from the chain's Philox key (sub-stream HOST,
  * one counter step per call).  Runs on the host (shared arithmetic of the kernels, hml_dist.h). */
@@ -373,7 +410,7 @@ int hml_get_stats(hml_ctx* ctx, hml_stats* out);
 
 /* HIP-event timing of one named kernel family accumulated since the last reset (milliseconds and
  * launches); name is one of "blocks_compact", "blocks_scatter", "block_stats", "stats_emission", "emission", "forward",
- * "backward_maps", "backward_chain", "mixture", "counts", "params", "marginals", "levels", "breaks", "event_null".  level 0 = off, 1 = only the dominant kernel
+ * "backward_maps", "backward_chain", "mixture", "counts", "params", "marginals", "levels", "breaks", "bands", "event_null".  level 0 = off, 1 = only the dominant kernel
  * ("blocks_compact", two events per sweep), 2 = every family. */
 int hml_profile_enable(hml_ctx* ctx, int level);
 int hml_profile_get(hml_ctx* ctx, const char* name, double* total_ms, uint64_t* launches);
