@@ -101,6 +101,7 @@ HML_KERNEL void hml_k_debug_eval(int fn, const float* __restrict__ a, const floa
 }
 
 static int bands_from_env(hml_ctx* c);   // (the level bands' section)
+static bool same_band_edges(const hml_ctx* a, int n, const float* edges);
 
 extern "C" {
 
@@ -177,8 +178,8 @@ int hml_create(hml_ctx** out, int device, uint64_t seed, uint32_t chain_id, void
     if (const char* e = getenv("HML_COMPAT")) c->compat = atoi(e) != 0;   // option "compat" for unmodified callers (`hammlet -compat`)
     if (const char* e = getenv("HML_TRELLIS_TUNE")) c->tre_autotune = atoi(e) != 0;
     if (const char* e = getenv("HML_FUSED_SPIN_LIMIT")) c->fused_spin_limit = (uint32_t)strtoul(e, nullptr, 10);
-    if (const char* e = getenv("HML_LEVELS")) c->rec_levels = c->levels_asked = atoi(e) != 0;   // hml_set_level_recording for unmodified callers (`hammlet -O L`)
-    if (const char* e = getenv("HML_BREAKS")) c->rec_breaks = c->breaks_asked = atoi(e) != 0;   // hml_set_break_recording for unmodified callers (`hammlet -O breakpoints`)
+    if (const char* e = getenv("HML_LEVELS")) c->rec[HML_REC_LEVELS].on = c->rec[HML_REC_LEVELS].asked = atoi(e) != 0;   // hml_set_level_recording for unmodified callers (`hammlet -O L`)
+    if (const char* e = getenv("HML_BREAKS")) c->rec[HML_REC_BREAKS].on = c->rec[HML_REC_BREAKS].asked = atoi(e) != 0;   // hml_set_break_recording for unmodified callers (`hammlet -O breakpoints`)
     if (const char* e = getenv("HML_MAX_BLOCKS")) c->cap_opt = strtoull(e, nullptr, 10);   // option "max_blocks" (tests: a tiny capacity exercises the growth everywhere)
     if (device < 64) g_live_ctx[device].fetch_add(1);
     if (int r = bands_from_env(c)) { hml_destroy(c); return r; }   // HML_BANDS=e0,e1,...: hml_set_level_bands for unmodified callers (`hammlet -bands`)
@@ -218,8 +219,9 @@ static void free_all(hml_ctx* c) {
     trace_release(c);
     free_sweep_buffers(c);
     void* ptrs[] = {c->d_group_word, c->d_wave_total, c->d_stage, c->d_span_count, c->d_starts, c->d_bstat, c->d_eprobe, c->d_aprobe, c->d_coarse1,
-                    c->d_diff, c->d_boundary, c->d_levels, c->d_lev_boundary, c->d_breaks, c->d_brk_boundary, c->d_bands, c->d_band_boundary, c->d_mdl, c->d_many};
+                    c->d_diff, c->d_boundary, c->d_mdl, c->d_many};
     for (void* p : ptrs) if (p) hipFree(p);
+    for (hml_recorder& r : c->rec) { if (r.d_acc) hipFree(r.d_acc); if (r.d_boundary) hipFree(r.d_boundary); }
     if (c->h_B) hipHostFree(c->h_B);
     c->h_B = nullptr;
 }
@@ -929,23 +931,16 @@ int hml_set_recording(hml_ctx* c, int marginals, hml_record_cb cb, void* user) {
     return 0;
 }
 
-int hml_set_level_recording(hml_ctx* c, int on) {
+static int set_recorder(hml_ctx* c, int kind, int on) {
     if (!c) return set_err(HML_ERR_ARG, "null context");
-    c->rec_levels = on != 0;
-    if (on) c->levels_asked = true;
+    c->rec[kind].on = on != 0;
+    if (on) c->rec[kind].asked = true;
     // (recorded sweeps are never replayed from a captured graph - hml_iterate - but a graph captured under the other setting goes anyway)
     if (c->graph_exec) { if (int r = ctx_bind(c)) return r; hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
     return 0;
 }
-
-int hml_set_break_recording(hml_ctx* c, int on) {
-    if (!c) return set_err(HML_ERR_ARG, "null context");
-    c->rec_breaks = on != 0;
-    if (on) c->breaks_asked = true;
-    // (as in hml_set_level_recording: a graph captured under the other setting goes)
-    if (c->graph_exec) { if (int r = ctx_bind(c)) return r; hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
-    return 0;
-}
+int hml_set_level_recording(hml_ctx* c, int on) { return set_recorder(c, HML_REC_LEVELS, on); }
+int hml_set_break_recording(hml_ctx* c, int on) { return set_recorder(c, HML_REC_BREAKS, on); }
 
 int hml_enable_probes(hml_ctx* c, int on) {
     if (!c || !c->model_set) return set_err(HML_ERR_ARG, "model not set");
@@ -1062,9 +1057,7 @@ static int sweep_compat(hml_ctx* c, char method, bool record) {
         if (int r = ensure_marginal_buffers(c)) return r;
         hipLaunchKernelGGL(hml_k_record, dim3(grid_for(hint, 256, 64, 16384)), dim3(256), 0, s, c->d_q, c->d_starts, c->d_mdl, c->d_diff, c->d_boundary);
     }
-    if (record && c->rec_levels) { if (int r = launch_levels_record(c, s, hint)) return r; }   // (hml_k_compat_update above is this sweep's parameter update)
-    if (record && c->rec_breaks) { if (int r = launch_breaks_record(c, s, hint)) return r; }
-    if (record && c->rec_bands) { if (int r = launch_bands_record(c, s, hint)) return r; }
+    if (record) { if (int r = launch_recorders(c, s, hint)) return r; }   // (hml_k_compat_update above is this sweep's parameter update)
     KLAUNCH_CHECK();
     return 0;
 }
@@ -1156,9 +1149,7 @@ static int sweep_wide(hml_ctx* c, char method, bool record) {
         ProfScope ps(c, "params");
         hipLaunchKernelGGL(hml_k_wide_params, dim3(1), dim3(1024), 0, s, c->d_mdl, c->d_partial, (hml_wide_acc*)c->d_wacc, 0);
     }
-    if (record && c->rec_levels) { if (int r = launch_levels_record(c, s, hint)) return r; }   // (after the update: hml_k_levels.h)
-    if (record && c->rec_breaks) { if (int r = launch_breaks_record(c, s, hint)) return r; }
-    if (record && c->rec_bands) { if (int r = launch_bands_record(c, s, hint)) return r; }
+    if (record) { if (int r = launch_recorders(c, s, hint)) return r; }   // (after the update: hml_k_levels.h)
     KLAUNCH_CHECK();
     return 0;
 }
@@ -1511,23 +1502,53 @@ int hml_recorded_sweeps(hml_ctx* c, uint64_t* n) {
     *n = m.n_recorded; return 0;
 }
 
+}  // extern "C"
+
+// The positions whose bit is set in a boundary bitmap over T positions (n_spans spans of HML_SPAN), ascending, on stream `s`:
+// d_seg[M + 1] is allocated here, position 0 is always the first entry.  Counts per span, their prefix sums on the host, scatter.
+static int compact_boundaries(hipStream_t s, const uint32_t* d_boundary, uint32_t T, uint32_t n_spans, uint64_t* M_out, DevBuf& d_seg) {
+    DevBuf d_cnt, d_off;
+    HIPCHK(hipMalloc(&d_cnt.p, n_spans * sizeof(uint32_t)));
+    HIPCHK(hipMalloc(&d_off.p, n_spans * sizeof(uint32_t)));
+    hipLaunchKernelGGL(hml_k_marg_count, dim3((n_spans + 3) / 4), dim3(256), 0, s, d_boundary, T, d_cnt.as<uint32_t>());
+    std::vector<uint32_t> h_cnt(n_spans), h_off(n_spans);
+    HIPCHK(hipMemcpyAsync(h_cnt.data(), d_cnt.p, n_spans * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    uint64_t M = 0;
+    for (uint32_t i = 0; i < n_spans; ++i) { h_off[i] = (uint32_t)M; M += h_cnt[i]; }
+    HIPCHK(hipMemcpyAsync(d_off.p, h_off.data(), n_spans * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMalloc(&d_seg.p, (M + 1) * sizeof(uint32_t)));
+    hipLaunchKernelGGL(hml_k_marg_scatter, dim3((n_spans + 3) / 4), dim3(256), 0, s, d_boundary, T, d_off.as<uint32_t>(), d_seg.as<uint32_t>());
+    KLAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(s));   // (d_cnt and d_off go with this frame)
+    *M_out = M;
+    return 0;
+}
+
+// The fixed-shape scan of hml_k_scan.h over `rows` rows of M entries on stream `s`: inclusive into d_out[rows][M] (d_out may
+// be d_in), or exclusive into d_out[rows][M + 1] with the totals last.
+template <typename In, typename Acc, bool Exclusive>
+static int scan_rows(hipStream_t s, const In* d_in, uint64_t M, int rows, Acc* d_out) {
+    DevBuf d_cs;
+    const uint32_t n_chunks = (uint32_t)((M + HML_SCAN_CHUNK - 1) / HML_SCAN_CHUNK);
+    HIPCHK(hipMalloc(&d_cs.p, ((uint64_t)n_chunks * rows + 1) * sizeof(Acc)));
+    const dim3 grid((unsigned)grid_for(n_chunks, 1, 1, 4096), (unsigned)rows);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_scan_partial<In, Acc>), grid, dim3(256), 0, s, d_in, (uint32_t)M, n_chunks, d_cs.as<Acc>());
+    hipLaunchKernelGGL(hml_k_scan_chunks<Acc>, dim3(rows), dim3(1024), 0, s, d_cs.as<Acc>(), n_chunks);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_scan_final<In, Acc, Exclusive>), grid, dim3(256), 0, s, d_in, (uint32_t)M, n_chunks, (const Acc*)d_cs.as<Acc>(), d_out);
+    KLAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(s));   // (d_cs goes with this frame)
+    return 0;
+}
+
 // marginal segments on the device: starts d_seg[M] and count differences d_g[M*K] at the starts (caller frees)
 static int gather_marginal_segments(hml_ctx* c, uint64_t* M_out, uint32_t** d_seg_out, int32_t** d_g_out) {
     const uint32_t T = (uint32_t)c->T;
     const int K = c->K;
-    DevBuf d_cnt, d_off, d_seg, d_g;   // (released on every early return; the two results are handed over at the end)
-    HIPCHK(hipMalloc(&d_cnt.p, c->n_spans * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&d_off.p, c->n_spans * sizeof(uint32_t)));
-    hipLaunchKernelGGL(hml_k_marg_count, dim3((c->n_spans + 3) / 4), dim3(256), 0, c->stream, c->d_boundary, T, d_cnt.as<uint32_t>());
-    std::vector<uint32_t> h_cnt(c->n_spans), h_off(c->n_spans);
-    HIPCHK(hipMemcpyAsync(h_cnt.data(), d_cnt.p, c->n_spans * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    DevBuf d_seg, d_g;   // (released on every early return; the two results are handed over at the end)
     uint64_t M = 0;
-    for (uint32_t i = 0; i < c->n_spans; ++i) { h_off[i] = (uint32_t)M; M += h_cnt[i]; }
-    HIPCHK(hipMemcpyAsync(d_off.p, h_off.data(), c->n_spans * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMalloc(&d_seg.p, (M + 1) * sizeof(uint32_t)));
+    if (int r = compact_boundaries(c->stream, c->d_boundary, T, c->n_spans, &M, d_seg)) return r;
     HIPCHK(hipMalloc(&d_g.p, std::max<uint64_t>(M, 1) * K * sizeof(int32_t)));
-    hipLaunchKernelGGL(hml_k_marg_scatter, dim3((c->n_spans + 3) / 4), dim3(256), 0, c->stream, c->d_boundary, T, d_off.as<uint32_t>(), d_seg.as<uint32_t>());
     hipLaunchKernelGGL(hml_k_marg_gather, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, c->stream, c->d_diff, T, K, d_seg.as<uint32_t>(),
                        (uint32_t)M, d_g.as<int32_t>());
     KLAUNCH_CHECK();
@@ -1536,7 +1557,6 @@ static int gather_marginal_segments(hml_ctx* c, uint64_t* M_out, uint32_t** d_se
     return 0;
 }
 
-}  // extern "C"
 int hml_ctx_gather_marginal_segments(hml_ctx* c, uint64_t* M, uint32_t** d_seg, int32_t** d_g) { return gather_marginal_segments(c, M, d_seg, d_g); }
 extern "C" {
 
@@ -1575,41 +1595,72 @@ int hml_marginals_rle(hml_ctx* c, uint64_t* n_segments, int* n_columns, uint64_t
 // ---------------------------------------------------------------------------------------- emission levels (hml_k_levels.h)
 }  // extern "C"
 
+// a recording's read-out may begin: it was asked for, its buffers exist (asked for, but no sweep was recorded yet: the empty
+// answer of its kind, hml_ctx.hpp), the model is fetched and carries no device error
+static int recorder_ready(hml_ctx* c, int kind, hml_model* m) {
+    if (!c->rec[kind].asked) return recorder_none(kind, "this");
+    if (int r = ensure_recorder_buffers(c, kind)) return r;
+    if (int r = fetch_model(c, m)) return r;
+    if (m->err_code) { char buf[256]; return set_err(HML_ERR_MODEL, deverr_text(m->err_code, m->err_value, buf, sizeof buf)); }
+    return 0;
+}
+
+// hml_levels_merge / hml_breaks_merge / hml_bands_merge: the source's cells at the source's boundaries into the destination,
+// on the destination's stream
+static int recorder_merge(hml_ctx* dst, hml_ctx* src, int kind) {
+    const hml_recorder_kind& rk = hml_recorder_kinds[kind];
+    const bool per_dimension = kind != HML_REC_BREAKS;
+    if (!dst || !src || !dst->model_set || !src->model_set) return set_err(HML_ERR_ARG, "model not set");
+    if (dst == src) return set_err(HML_ERR_ARG, "a context cannot be merged into itself");
+    if (dst->device != src->device)
+        return set_err(HML_ERR_ARG, std::string("the ") + rk.noun + " of chains on different GPUs are not merged yet: run the chains of one " + rk.file + " file on one GPU");
+    if (dst->T != src->T || (per_dimension && dst->D != src->D))
+        return set_err(HML_ERR_ARG, std::string(rk.noun) + " can only be merged between chains over the same positions" + (per_dimension ? " and dimensions" : ""));
+    if (!src->rec[kind].asked) return recorder_none(kind, "the source");
+    if (kind == HML_REC_BANDS && !same_band_edges(dst, src->n_band_edges, src->band_edges)) {
+        // a destination that was never asked takes the source's edges; any other difference is refused
+        if (dst->rec[kind].asked || dst->rec[kind].d_acc) return set_err(HML_ERR_ARG, "level bands can only be merged between chains with the same edges, bit for bit");
+        dst->n_band_edges = src->n_band_edges;
+        memcpy(dst->band_edges, src->band_edges, sizeof dst->band_edges);
+    }
+    if (int r = ctx_bind(dst)) return r;
+    if (int r = hml_settle(src)) return r;   // (both streams idle: the merge reads the source's accumulators on the destination's stream)
+    if (int r = hml_settle(dst)) return r;
+    if (int r = ensure_recorder_buffers(src, kind)) return r;
+    if (int r = ensure_recorder_buffers(dst, kind)) return r;
+    dst->rec[kind].asked = true;
+    const hml_recorder &rs = src->rec[kind], &rd = dst->rec[kind];
+    const uint32_t T = (uint32_t)src->T;
+    const int rows = recorder_rows(src, kind);
+    uint64_t M = 0;
+    DevBuf b_seg;
+    if (int r = compact_boundaries(dst->stream, rs.d_boundary, T, src->n_spans, &M, b_seg)) return r;
+    const uint32_t* d_pos = b_seg.as<uint32_t>();
+    if (kind == HML_REC_BREAKS) { ++d_pos; --M; }   // (position 0 is never a breakpoint; M = 0 still adds the source's count of recorded sweeps)
+    const dim3 grid(grid_for(M, 256, 1, 16384));
+    unsigned long long *const src_n = recorder_counter(src, kind), *const dst_n = recorder_counter(dst, kind);
+    if (kind == HML_REC_LEVELS)
+        hipLaunchKernelGGL(hml_k_rec_merge<double>, grid, dim3(256), 0, dst->stream, rs.acc<double>(), d_pos, (uint32_t)M, T, rows, src_n, rd.acc<double>(), rd.d_boundary, dst_n);
+    else if (kind == HML_REC_BREAKS)
+        hipLaunchKernelGGL(hml_k_rec_merge<uint32_t>, grid, dim3(256), 0, dst->stream, rs.acc<uint32_t>(), d_pos, (uint32_t)M, T, rows, src_n, rd.acc<uint32_t>(), rd.d_boundary, dst_n);
+    else
+        hipLaunchKernelGGL(hml_k_rec_merge<int32_t>, grid, dim3(256), 0, dst->stream, rs.acc<int32_t>(), d_pos, (uint32_t)M, T, rows, src_n, rd.acc<int32_t>(), rd.d_boundary, dst_n);
+    KLAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(dst->stream));
+    return 0;
+}
+
 // the levels' segments on the device: starts d_seg[M] and, per row, the inclusive sums over the segments d_sum[2 D][M]
 static int gather_level_segments(hml_ctx* c, uint64_t* M_out, DevBuf& d_seg, DevBuf& d_sum) {
     const uint32_t T = (uint32_t)c->T;
     const int rows = 2 * c->D;
-    DevBuf d_cnt, d_off, d_cs;
-    HIPCHK(hipMalloc(&d_cnt.p, c->n_spans * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&d_off.p, c->n_spans * sizeof(uint32_t)));
-    hipLaunchKernelGGL(hml_k_marg_count, dim3((c->n_spans + 3) / 4), dim3(256), 0, c->stream, c->d_lev_boundary, T, d_cnt.as<uint32_t>());
-    std::vector<uint32_t> h_cnt(c->n_spans), h_off(c->n_spans);
-    HIPCHK(hipMemcpyAsync(h_cnt.data(), d_cnt.p, c->n_spans * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    const hml_recorder& rec = c->rec[HML_REC_LEVELS];
     uint64_t M = 0;
-    for (uint32_t i = 0; i < c->n_spans; ++i) { h_off[i] = (uint32_t)M; M += h_cnt[i]; }
-    HIPCHK(hipMemcpyAsync(d_off.p, h_off.data(), c->n_spans * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMalloc(&d_seg.p, (M + 1) * sizeof(uint32_t)));
+    if (int r = compact_boundaries(c->stream, rec.d_boundary, T, c->n_spans, &M, d_seg)) return r;
     HIPCHK(hipMalloc(&d_sum.p, M * rows * sizeof(double)));
-    const uint32_t n_chunks = (uint32_t)((M + HML_LEV_CHUNK - 1) / HML_LEV_CHUNK);
-    HIPCHK(hipMalloc(&d_cs.p, (uint64_t)n_chunks * rows * sizeof(double)));
-    hipLaunchKernelGGL(hml_k_marg_scatter, dim3((c->n_spans + 3) / 4), dim3(256), 0, c->stream, c->d_lev_boundary, T, d_off.as<uint32_t>(), d_seg.as<uint32_t>());
-    hipLaunchKernelGGL(hml_k_levels_gather, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, c->stream, c->d_levels, T, rows, d_seg.as<uint32_t>(), (uint32_t)M, d_sum.as<double>());
-    const dim3 sgrid((unsigned)grid_for(n_chunks, 1, 1, 4096), (unsigned)rows);
-    hipLaunchKernelGGL(hml_k_levels_scan_partial, sgrid, dim3(256), 0, c->stream, d_sum.as<double>(), (uint32_t)M, n_chunks, d_cs.as<double>());
-    hipLaunchKernelGGL(hml_k_levels_scan_chunks, dim3(rows), dim3(1024), 0, c->stream, d_cs.as<double>(), n_chunks);
-    hipLaunchKernelGGL(hml_k_levels_scan_final, sgrid, dim3(256), 0, c->stream, d_sum.as<double>(), (uint32_t)M, n_chunks, d_cs.as<double>());
-    KLAUNCH_CHECK();
-    HIPCHK(hipStreamSynchronize(c->stream));
+    hipLaunchKernelGGL(hml_k_rec_gather<double>, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, c->stream, rec.acc<double>(), T, rows, d_seg.as<uint32_t>(), (uint32_t)M, d_sum.as<double>());
+    if (int r = scan_rows<double, double, false>(c->stream, d_sum.as<double>(), M, rows, d_sum.as<double>())) return r;
     *M_out = M;
-    return 0;
-}
-
-static int levels_ready(hml_ctx* c, hml_model* m) {
-    if (!c->levels_asked) return set_err(HML_ERR_ARG, "no emission levels were recorded by this context: enable them with hml_set_level_recording (or HML_LEVELS=1) before the recorded sweeps");
-    if (int r = ensure_level_buffers(c)) return r;   // (asked for, but no sweep was recorded yet: one segment, zero sums)
-    if (int r = fetch_model(c, m)) return r;
-    if (m->err_code) { char buf[256]; return set_err(HML_ERR_MODEL, deverr_text(m->err_code, m->err_value, buf, sizeof buf)); }
     return 0;
 }
 
@@ -1618,7 +1669,7 @@ extern "C" {
 int hml_levels_rle(hml_ctx* c, uint64_t* n_segments, uint64_t* n_recorded, uint64_t* seg_len, double* sum, double* sum_sq) {
     NEED_MODEL();
     if (!n_segments) return set_err(HML_ERR_ARG, "null argument");
-    hml_model m; if (int r = levels_ready(c, &m)) return r;
+    hml_model m; if (int r = recorder_ready(c, HML_REC_LEVELS, &m)) return r;
     const uint32_t T = (uint32_t)c->T;
     const int D = c->D;
     uint64_t M = 0;
@@ -1643,7 +1694,7 @@ int hml_levels_rle(hml_ctx* c, uint64_t* n_segments, uint64_t* n_recorded, uint6
 int hml_levels_dense_device(hml_ctx* c, void* out_dev) {
     NEED_MODEL();
     if (!out_dev) return set_err(HML_ERR_ARG, "null argument");
-    hml_model m; if (int r = levels_ready(c, &m)) return r;
+    hml_model m; if (int r = recorder_ready(c, HML_REC_LEVELS, &m)) return r;
     const uint32_t T = (uint32_t)c->T;
     const int D = c->D;
     uint64_t M = 0;
@@ -1659,98 +1710,42 @@ int hml_levels_dense_device(hml_ctx* c, void* out_dev) {
     return 0;
 }
 
-int hml_levels_merge(hml_ctx* dst, hml_ctx* src) {
-    if (!dst || !src || !dst->model_set || !src->model_set) return set_err(HML_ERR_ARG, "model not set");
-    if (dst == src) return set_err(HML_ERR_ARG, "a context cannot be merged into itself");
-    if (dst->device != src->device)
-        return set_err(HML_ERR_ARG, "the emission levels of chains on different GPUs are not merged yet: run the chains of one levels file on one GPU");
-    if (dst->T != src->T || dst->D != src->D) return set_err(HML_ERR_ARG, "emission levels can only be merged between chains over the same positions and dimensions");
-    if (int r = ctx_bind(dst)) return r;
-    if (int r = hml_settle(src)) return r;   // (both streams idle: the merge reads the source's accumulators on the destination's stream)
-    if (int r = hml_settle(dst)) return r;
-    if (!src->levels_asked) return set_err(HML_ERR_ARG, "no emission levels were recorded by the source context: enable them with hml_set_level_recording (or HML_LEVELS=1) before the recorded sweeps");
-    if (int r = ensure_level_buffers(src)) return r;
-    if (int r = ensure_level_buffers(dst)) return r;
-    dst->levels_asked = true;
-    const uint32_t T = (uint32_t)src->T;
-    // the source's segment starts (its cells are zero everywhere else), on the destination's stream
-    DevBuf d_cnt, d_off, d_seg;
-    HIPCHK(hipMalloc(&d_cnt.p, src->n_spans * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&d_off.p, src->n_spans * sizeof(uint32_t)));
-    hipLaunchKernelGGL(hml_k_marg_count, dim3((src->n_spans + 3) / 4), dim3(256), 0, dst->stream, src->d_lev_boundary, T, d_cnt.as<uint32_t>());
-    std::vector<uint32_t> h_cnt(src->n_spans), h_off(src->n_spans);
-    HIPCHK(hipMemcpyAsync(h_cnt.data(), d_cnt.p, src->n_spans * sizeof(uint32_t), hipMemcpyDeviceToHost, dst->stream));
-    HIPCHK(hipStreamSynchronize(dst->stream));
-    uint64_t M = 0;
-    for (uint32_t i = 0; i < src->n_spans; ++i) { h_off[i] = (uint32_t)M; M += h_cnt[i]; }
-    HIPCHK(hipMemcpyAsync(d_off.p, h_off.data(), src->n_spans * sizeof(uint32_t), hipMemcpyHostToDevice, dst->stream));
-    HIPCHK(hipMalloc(&d_seg.p, (M + 1) * sizeof(uint32_t)));
-    hipLaunchKernelGGL(hml_k_marg_scatter, dim3((src->n_spans + 3) / 4), dim3(256), 0, dst->stream, src->d_lev_boundary, T, d_off.as<uint32_t>(), d_seg.as<uint32_t>());
-    hipLaunchKernelGGL(hml_k_levels_merge, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, dst->stream, src->d_levels, d_seg.as<uint32_t>(), (uint32_t)M, T,
-                       2 * src->D, src->d_mdl, dst->d_levels, dst->d_lev_boundary, dst->d_mdl);
-    KLAUNCH_CHECK();
-    HIPCHK(hipStreamSynchronize(dst->stream));
-    return 0;
-}
+int hml_levels_merge(hml_ctx* dst, hml_ctx* src) { return recorder_merge(dst, src, HML_REC_LEVELS); }
 
 // ---------------------------------------------------------------------------------------- breakpoints (hml_k_breaks.h)
 }  // extern "C"
 
 // exclusive 64-bit prefix sums of M 32-bit values on `s`: d_pre[M + 1] (allocated here), d_pre[M] = the total
 static int breaks_scan(hipStream_t s, const uint32_t* d_v, uint64_t M, DevBuf& d_pre) {
-    DevBuf d_cs;
-    const uint32_t n_chunks = (uint32_t)((M + HML_BRK_CHUNK - 1) / HML_BRK_CHUNK);
     HIPCHK(hipMalloc(&d_pre.p, (M + 1) * sizeof(unsigned long long)));
-    HIPCHK(hipMalloc(&d_cs.p, ((uint64_t)n_chunks + 1) * sizeof(unsigned long long)));
-    const int grid = grid_for(n_chunks, 1, 1, 4096);
-    hipLaunchKernelGGL(hml_k_breaks_scan_partial, dim3(grid), dim3(256), 0, s, d_v, (uint32_t)M, n_chunks, d_cs.as<unsigned long long>());
-    hipLaunchKernelGGL(hml_k_breaks_scan_chunks, dim3(1), dim3(1024), 0, s, d_cs.as<unsigned long long>(), n_chunks);
-    hipLaunchKernelGGL(hml_k_breaks_scan_final, dim3(grid), dim3(256), 0, s, d_v, (uint32_t)M, n_chunks, d_cs.as<unsigned long long>(), d_pre.as<unsigned long long>());
-    KLAUNCH_CHECK();
-    HIPCHK(hipStreamSynchronize(s));   // (d_cs goes with this frame)
-    return 0;
+    return scan_rows<uint32_t, unsigned long long, true>(s, d_v, M, 1, d_pre.as<unsigned long long>());
 }
 
 // the positions with a count, ascending, on the device: d_list[1 + M] - entry 0 is the position 0 that the compaction kernels
-// always emit (never a breakpoint), the M break positions follow - on stream `s` from the bitmap of context `c`
-static int compact_break_positions(hml_ctx* c, hipStream_t s, uint64_t* M_out, DevBuf& d_list) {
-    const uint32_t T = (uint32_t)c->T;
-    DevBuf d_cnt, d_off;
-    HIPCHK(hipMalloc(&d_cnt.p, c->n_spans * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&d_off.p, c->n_spans * sizeof(uint32_t)));
-    hipLaunchKernelGGL(hml_k_marg_count, dim3((c->n_spans + 3) / 4), dim3(256), 0, s, c->d_brk_boundary, T, d_cnt.as<uint32_t>());
-    std::vector<uint32_t> h_cnt(c->n_spans), h_off(c->n_spans);
-    HIPCHK(hipMemcpyAsync(h_cnt.data(), d_cnt.p, c->n_spans * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+// always emit (never a breakpoint), the M break positions follow
+static int compact_break_positions(hml_ctx* c, uint64_t* M_out, DevBuf& d_list) {
     uint64_t n = 0;
-    for (uint32_t i = 0; i < c->n_spans; ++i) { h_off[i] = (uint32_t)n; n += h_cnt[i]; }
-    HIPCHK(hipMemcpyAsync(d_off.p, h_off.data(), c->n_spans * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMalloc(&d_list.p, (n + 1) * sizeof(uint32_t)));
-    hipLaunchKernelGGL(hml_k_marg_scatter, dim3((c->n_spans + 3) / 4), dim3(256), 0, s, c->d_brk_boundary, T, d_off.as<uint32_t>(), d_list.as<uint32_t>());
-    KLAUNCH_CHECK();
-    HIPCHK(hipStreamSynchronize(s));
+    if (int r = compact_boundaries(c->stream, c->rec[HML_REC_BREAKS].d_boundary, (uint32_t)c->T, c->n_spans, &n, d_list)) return r;
     *M_out = n - 1;   // (position 0 always counts)
+    return 0;
+}
+
+// C[pos] for the M break positions of d_list into d_cnt[M] (allocated here with one spare entry)
+static int gather_break_counts(hml_ctx* c, const DevBuf& d_list, uint64_t M, DevBuf& d_cnt) {
+    HIPCHK(hipMalloc(&d_cnt.p, (M + 1) * sizeof(uint32_t)));
+    if (M) hipLaunchKernelGGL(hml_k_rec_gather<uint32_t>, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, c->stream, c->rec[HML_REC_BREAKS].acc<uint32_t>(), (uint32_t)c->T, 1,
+                              d_list.as<uint32_t>() + 1, (uint32_t)M, d_cnt.as<uint32_t>());
+    KLAUNCH_CHECK();
     return 0;
 }
 
 // break positions d_list[1 + M] (see above), their counts d_cnt[M] and the exclusive sums of the counts d_pre[M + 1]
 static int gather_breaks(hml_ctx* c, uint64_t* M_out, DevBuf& d_list, DevBuf& d_cnt, DevBuf& d_pre) {
     uint64_t M = 0;
-    if (int r = compact_break_positions(c, c->stream, &M, d_list)) return r;
-    HIPCHK(hipMalloc(&d_cnt.p, (M + 1) * sizeof(uint32_t)));
-    if (M) hipLaunchKernelGGL(hml_k_breaks_gather, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, c->stream, c->d_breaks, d_list.as<uint32_t>() + 1, (uint32_t)M, d_cnt.as<uint32_t>());
+    if (int r = compact_break_positions(c, &M, d_list)) return r;
+    if (int r = gather_break_counts(c, d_list, M, d_cnt)) return r;
     if (int r = breaks_scan(c->stream, d_cnt.as<uint32_t>(), M, d_pre)) return r;
     *M_out = M;
-    return 0;
-}
-
-static const char* kNoBreaks = "no breakpoints were recorded by this context: enable them with hml_set_break_recording (or HML_BREAKS=1) before the recorded sweeps";
-
-static int breaks_ready(hml_ctx* c, hml_model* m) {
-    if (!c->breaks_asked) return set_err(HML_ERR_ARG, kNoBreaks);
-    if (int r = ensure_break_buffers(c)) return r;   // (asked for, but no sweep was recorded yet: an empty list)
-    if (int r = fetch_model(c, m)) return r;
-    if (m->err_code) { char buf[256]; return set_err(HML_ERR_MODEL, deverr_text(m->err_code, m->err_value, buf, sizeof buf)); }
     return 0;
 }
 
@@ -1759,18 +1754,16 @@ extern "C" {
 int hml_breaks_list(hml_ctx* c, uint64_t* n_breaks, uint64_t* n_recorded, uint32_t* pos, uint32_t* count) {
     NEED_MODEL();
     if (!n_breaks) return set_err(HML_ERR_ARG, "null argument");
-    hml_model m; if (int r = breaks_ready(c, &m)) return r;
+    hml_model m; if (int r = recorder_ready(c, HML_REC_BREAKS, &m)) return r;
     uint64_t M = 0;
     DevBuf b_list, b_cnt;
-    if (int r = compact_break_positions(c, c->stream, &M, b_list)) return r;
+    if (int r = compact_break_positions(c, &M, b_list)) return r;
     *n_breaks = M;
     if (n_recorded) *n_recorded = m.n_breaks_recorded;
     if (!pos || M == 0) return 0;
     HIPCHK(hipMemcpyAsync(pos, b_list.as<uint32_t>() + 1, M * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     if (count) {
-        HIPCHK(hipMalloc(&b_cnt.p, M * sizeof(uint32_t)));
-        hipLaunchKernelGGL(hml_k_breaks_gather, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, c->stream, c->d_breaks, b_list.as<uint32_t>() + 1, (uint32_t)M, b_cnt.as<uint32_t>());
-        KLAUNCH_CHECK();
+        if (int r = gather_break_counts(c, b_list, M, b_cnt)) return r;
         HIPCHK(hipMemcpyAsync(count, b_cnt.p, M * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1780,7 +1773,7 @@ int hml_breaks_list(hml_ctx* c, uint64_t* n_breaks, uint64_t* n_recorded, uint32
 int hml_breaks_dense_device(hml_ctx* c, void* out_dev, uint32_t window) {
     NEED_MODEL();
     if (!out_dev) return set_err(HML_ERR_ARG, "null argument");
-    hml_model m; if (int r = breaks_ready(c, &m)) return r;
+    hml_model m; if (int r = recorder_ready(c, HML_REC_BREAKS, &m)) return r;
     uint64_t M = 0;
     DevBuf b_list, b_cnt, b_pre;
     if (int r = gather_breaks(c, &M, b_list, b_cnt, b_pre)) return r;
@@ -1795,7 +1788,7 @@ int hml_breaks_dense_device(hml_ctx* c, void* out_dev, uint32_t window) {
 int hml_breaks_consensus(hml_ctx* c, uint32_t window, uint64_t min_count, uint64_t* n_selected, uint32_t* pos, uint64_t* mass, uint32_t* peak) {
     NEED_MODEL();
     if (!n_selected) return set_err(HML_ERR_ARG, "null argument");
-    hml_model m; if (int r = breaks_ready(c, &m)) return r;
+    hml_model m; if (int r = recorder_ready(c, HML_REC_BREAKS, &m)) return r;
     uint64_t M = 0;
     DevBuf b_list, b_cnt, b_pre, b_mass, b_sel, b_where, b_opos, b_omass, b_opeak;
     if (int r = gather_breaks(c, &M, b_list, b_cnt, b_pre)) return r;
@@ -1826,29 +1819,7 @@ int hml_breaks_consensus(hml_ctx* c, uint32_t window, uint64_t min_count, uint64
     return 0;
 }
 
-int hml_breaks_merge(hml_ctx* dst, hml_ctx* src) {
-    if (!dst || !src || !dst->model_set || !src->model_set) return set_err(HML_ERR_ARG, "model not set");
-    if (dst == src) return set_err(HML_ERR_ARG, "a context cannot be merged into itself");
-    if (dst->device != src->device)
-        return set_err(HML_ERR_ARG, "the breakpoints of chains on different GPUs are not merged yet: run the chains of one breakpoints file on one GPU");
-    if (dst->T != src->T) return set_err(HML_ERR_ARG, "breakpoints can only be merged between chains over the same positions");
-    if (int r = ctx_bind(dst)) return r;
-    if (int r = hml_settle(src)) return r;   // (both streams idle: the merge reads the source's counts on the destination's stream)
-    if (int r = hml_settle(dst)) return r;
-    if (!src->breaks_asked) return set_err(HML_ERR_ARG, "no breakpoints were recorded by the source context: enable them with hml_set_break_recording (or HML_BREAKS=1) before the recorded sweeps");
-    if (int r = ensure_break_buffers(src)) return r;
-    if (int r = ensure_break_buffers(dst)) return r;
-    dst->breaks_asked = true;
-    uint64_t M = 0;
-    DevBuf b_list;
-    if (int r = compact_break_positions(src, dst->stream, &M, b_list)) return r;
-    // (M = 0 still adds the source's count of recorded sweeps)
-    hipLaunchKernelGGL(hml_k_breaks_merge, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, dst->stream, src->d_breaks, b_list.as<uint32_t>() + 1, (uint32_t)M,
-                       src->d_mdl, dst->d_breaks, dst->d_brk_boundary, dst->d_mdl);
-    KLAUNCH_CHECK();
-    HIPCHK(hipStreamSynchronize(dst->stream));
-    return 0;
-}
+int hml_breaks_merge(hml_ctx* dst, hml_ctx* src) { return recorder_merge(dst, src, HML_REC_BREAKS); }
 
 int hml_levels_on_segments(hml_ctx* c, uint64_t n_cuts, const uint32_t* cuts, double* sum, double* sum_sq) {
     NEED_MODEL();
@@ -1859,24 +1830,19 @@ int hml_levels_on_segments(hml_ctx* c, uint64_t n_cuts, const uint32_t* cuts, do
         if (cuts[i] == 0 || cuts[i] >= T) return set_err(HML_ERR_ARG, "a cut must lie inside (0, T)");
         if (i > 0 && cuts[i] <= cuts[i - 1]) return set_err(HML_ERR_ARG, "the cuts must be strictly ascending");
     }
-    hml_model m; if (int r = levels_ready(c, &m)) return r;
+    hml_model m; if (int r = recorder_ready(c, HML_REC_LEVELS, &m)) return r;
     const int D = c->D, rows = 2 * D;
     uint64_t M = 0;
-    DevBuf b_seg, b_val, b_w, b_cs, b_cuts, b_out;
+    DevBuf b_seg, b_val, b_w, b_cuts, b_out;
     if (int r = gather_level_segments(c, &M, b_seg, b_val)) return r;
     const uint64_t n_seg = n_cuts + 1;
-    const uint32_t n_chunks = (uint32_t)((M + HML_LEV_CHUNK - 1) / HML_LEV_CHUNK);
     HIPCHK(hipMalloc(&b_w.p, M * rows * sizeof(double)));
-    HIPCHK(hipMalloc(&b_cs.p, (uint64_t)n_chunks * rows * sizeof(double)));
     HIPCHK(hipMalloc(&b_cuts.p, (n_cuts + 1) * sizeof(uint32_t)));
     HIPCHK(hipMalloc(&b_out.p, n_seg * rows * sizeof(double)));
     if (n_cuts) HIPCHK(hipMemcpyAsync(b_cuts.p, cuts, n_cuts * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(hml_k_levels_weigh, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, c->stream, b_val.as<double>(), b_seg.as<uint32_t>(), (uint32_t)M, T, rows, b_w.as<double>());
-    // the fixed-shape scan of the levels' read-out (hml_k_levels.h), now over len_i * value_i
-    const dim3 sgrid((unsigned)grid_for(n_chunks, 1, 1, 4096), (unsigned)rows);
-    hipLaunchKernelGGL(hml_k_levels_scan_partial, sgrid, dim3(256), 0, c->stream, b_w.as<double>(), (uint32_t)M, n_chunks, b_cs.as<double>());
-    hipLaunchKernelGGL(hml_k_levels_scan_chunks, dim3(rows), dim3(1024), 0, c->stream, b_cs.as<double>(), n_chunks);
-    hipLaunchKernelGGL(hml_k_levels_scan_final, sgrid, dim3(256), 0, c->stream, b_w.as<double>(), (uint32_t)M, n_chunks, b_cs.as<double>());
+    // the fixed-shape scan of the levels' read-out, now over len_i * value_i
+    if (int r = scan_rows<double, double, false>(c->stream, b_w.as<double>(), M, rows, b_w.as<double>())) return r;
     hipLaunchKernelGGL(hml_k_levels_on_segments, dim3(grid_for(n_seg, 256, 1, 16384)), dim3(256), 0, c->stream, b_val.as<double>(), b_w.as<double>(), b_seg.as<uint32_t>(),
                        (uint32_t)M, T, rows, b_cuts.as<uint32_t>(), (uint32_t)n_cuts, b_out.as<double>());
     KLAUNCH_CHECK();
@@ -1921,39 +1887,18 @@ static bool same_band_edges(const hml_ctx* a, int n, const float* edges) {
     return a->n_band_edges == n && memcmp(a->band_edges, edges, (size_t)n * sizeof(float)) == 0;   // (bit for bit)
 }
 
-static const char* kNoBands = "no level bands were recorded by this context: give the edges with hml_set_level_bands (or HML_BANDS=e0,e1,...) before the recorded sweeps";
-
-static int bands_ready(hml_ctx* c, hml_model* m) {
-    if (!c->bands_asked) return set_err(HML_ERR_ARG, kNoBands);
-    if (int r = ensure_band_buffers(c)) return r;   // (asked for, but no sweep was recorded yet: one segment of zeros)
-    if (int r = fetch_model(c, m)) return r;
-    if (m->err_code) { char buf[256]; return set_err(HML_ERR_MODEL, deverr_text(m->err_code, m->err_value, buf, sizeof buf)); }
-    return 0;
-}
-
-// the band segments of context `c` on stream `s`: starts d_seg[M] and, with `d_g`, the count differences at the starts
-// d_g[M][columns] (segment-major, hml_k_marg_gather)
-static int gather_band_segments(hml_ctx* c, hipStream_t s, uint64_t* M_out, DevBuf& d_seg, DevBuf* d_g) {
+// the band segments of context `c`: starts d_seg[M] and the count differences at the starts d_g[M][columns] (segment-major,
+// hml_k_marg_gather)
+static int gather_band_segments(hml_ctx* c, uint64_t* M_out, DevBuf& d_seg, DevBuf& d_g) {
     const uint32_t T = (uint32_t)c->T;
     const int ncol = c->D * (c->n_band_edges + 1);
-    DevBuf d_cnt, d_off;
-    HIPCHK(hipMalloc(&d_cnt.p, c->n_spans * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&d_off.p, c->n_spans * sizeof(uint32_t)));
-    hipLaunchKernelGGL(hml_k_marg_count, dim3((c->n_spans + 3) / 4), dim3(256), 0, s, c->d_band_boundary, T, d_cnt.as<uint32_t>());
-    std::vector<uint32_t> h_cnt(c->n_spans), h_off(c->n_spans);
-    HIPCHK(hipMemcpyAsync(h_cnt.data(), d_cnt.p, c->n_spans * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    const hml_recorder& rec = c->rec[HML_REC_BANDS];
     uint64_t M = 0;
-    for (uint32_t i = 0; i < c->n_spans; ++i) { h_off[i] = (uint32_t)M; M += h_cnt[i]; }
-    HIPCHK(hipMemcpyAsync(d_off.p, h_off.data(), c->n_spans * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMalloc(&d_seg.p, (M + 1) * sizeof(uint32_t)));
-    hipLaunchKernelGGL(hml_k_marg_scatter, dim3((c->n_spans + 3) / 4), dim3(256), 0, s, c->d_band_boundary, T, d_off.as<uint32_t>(), d_seg.as<uint32_t>());
-    if (d_g) {
-        HIPCHK(hipMalloc(&d_g->p, std::max<uint64_t>(M, 1) * ncol * sizeof(int32_t)));
-        hipLaunchKernelGGL(hml_k_marg_gather, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, s, c->d_bands, T, ncol, d_seg.as<uint32_t>(), (uint32_t)M, d_g->as<int32_t>());
-    }
+    if (int r = compact_boundaries(c->stream, rec.d_boundary, T, c->n_spans, &M, d_seg)) return r;
+    HIPCHK(hipMalloc(&d_g.p, std::max<uint64_t>(M, 1) * ncol * sizeof(int32_t)));
+    hipLaunchKernelGGL(hml_k_marg_gather, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, c->stream, rec.acc<int32_t>(), T, ncol, d_seg.as<uint32_t>(), (uint32_t)M, d_g.as<int32_t>());
     KLAUNCH_CHECK();
-    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipStreamSynchronize(c->stream));
     *M_out = M;
     return 0;
 }
@@ -1965,7 +1910,7 @@ static int bands_from_env(hml_ctx* c) {
         if (const char* why = band_edges_fault(n, edges)) return set_err(HML_ERR_ARG, std::string("HML_BANDS: ") + why);
         c->n_band_edges = n;
         memcpy(c->band_edges, edges, (size_t)n * sizeof(float));
-        c->rec_bands = c->bands_asked = true;
+        c->rec[HML_REC_BANDS].on = c->rec[HML_REC_BANDS].asked = true;
     }
     return 0;
 }
@@ -1976,23 +1921,24 @@ int hml_set_level_bands(hml_ctx* c, int n_edges, const float* edges) {
     if (!c) return set_err(HML_ERR_ARG, "null context");
     // (as in hml_set_level_recording: a graph captured under the other setting goes)
     if (c->graph_exec) { if (int r = ctx_bind(c)) return r; hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
-    if (n_edges == 0) { c->rec_bands = false; return 0; }   // (what was accumulated stays, and so do its edges)
+    if (n_edges == 0) { c->rec[HML_REC_BANDS].on = false; return 0; }   // (what was accumulated stays, and so do its edges)
     if (!edges) return set_err(HML_ERR_ARG, "null argument");
     if (const char* why = band_edges_fault(n_edges, edges)) return set_err(HML_ERR_ARG, why);
     if (c->model_set && (uint64_t)c->D * (uint64_t)(n_edges + 1) > HML_CAP_K)
         return set_err(HML_ERR_ARG, "level bands: the data dimensions times (edges + 1) exceed 64 columns");
-    if (!same_band_edges(c, n_edges, edges) && c->d_bands) {
+    if (!same_band_edges(c, n_edges, edges) && c->rec[HML_REC_BANDS].d_acc) {
         // buffers of other edges: they go if they hold nothing
         if (int r = ctx_bind(c)) return r;
         if (int r = hml_settle(c)) return r;
         hml_model m; if (int r = fetch_model(c, &m)) return r;
         if (m.n_bands_recorded != 0ull) return set_err(HML_ERR_ARG, "level bands were already recorded under other edges: they cannot be changed any more");
-        HIPCHK(hipFree(c->d_bands)); c->d_bands = nullptr;
-        HIPCHK(hipFree(c->d_band_boundary)); c->d_band_boundary = nullptr;
+        hml_recorder& rec = c->rec[HML_REC_BANDS];
+        HIPCHK(hipFree(rec.d_acc)); rec.d_acc = nullptr;
+        HIPCHK(hipFree(rec.d_boundary)); rec.d_boundary = nullptr;
     }
     c->n_band_edges = n_edges;
     memcpy(c->band_edges, edges, (size_t)n_edges * sizeof(float));
-    c->rec_bands = c->bands_asked = true;
+    c->rec[HML_REC_BANDS].on = c->rec[HML_REC_BANDS].asked = true;
     return 0;
 }
 
@@ -2006,12 +1952,12 @@ int hml_get_level_bands(hml_ctx* c, int* n_edges, float* edges) {
 int hml_bands_rle(hml_ctx* c, uint64_t* n_segments, int* n_columns, uint64_t* n_recorded, uint64_t* seg_len, int32_t* counts) {
     NEED_MODEL();
     if (!n_segments) return set_err(HML_ERR_ARG, "null argument");
-    hml_model m; if (int r = bands_ready(c, &m)) return r;
+    hml_model m; if (int r = recorder_ready(c, HML_REC_BANDS, &m)) return r;
     const uint32_t T = (uint32_t)c->T;
     const int ncol = c->D * (c->n_band_edges + 1);
     uint64_t M = 0;
     DevBuf b_seg, b_g;
-    if (int r = gather_band_segments(c, c->stream, &M, b_seg, &b_g)) return r;
+    if (int r = gather_band_segments(c, &M, b_seg, b_g)) return r;
     *n_segments = M;
     if (n_columns) *n_columns = ncol;
     if (n_recorded) *n_recorded = m.n_bands_recorded;
@@ -2034,16 +1980,16 @@ int hml_bands_rle(hml_ctx* c, uint64_t* n_segments, int* n_columns, uint64_t* n_
 int hml_bands_dense_device(hml_ctx* c, void* out_dev, int cumulative) {
     NEED_MODEL();
     if (!out_dev) return set_err(HML_ERR_ARG, "null argument");
-    hml_model m; if (int r = bands_ready(c, &m)) return r;
+    hml_model m; if (int r = recorder_ready(c, HML_REC_BANDS, &m)) return r;
     const uint32_t T = (uint32_t)c->T;
     const int nb = c->n_band_edges + 1, ncol = c->D * nb;
     int32_t* out = (int32_t*)out_dev;
     const uint32_t n_chunks = c->n_spans;
     DevBuf b_cs;
     HIPCHK(hipMalloc(&b_cs.p, (uint64_t)ncol * n_chunks * sizeof(int32_t)));
-    hipLaunchKernelGGL(hml_k_dense_partial, dim3(n_chunks, ncol), dim3(256), 0, c->stream, c->d_bands, T, ncol, b_cs.as<int32_t>(), n_chunks);
-    hipLaunchKernelGGL(hml_k_dense_chunkscan, dim3(ncol), dim3(1024), 0, c->stream, b_cs.as<int32_t>(), n_chunks);
-    hipLaunchKernelGGL(hml_k_dense_final, dim3(n_chunks, ncol), dim3(256), 0, c->stream, c->d_bands, T, ncol, b_cs.as<int32_t>(), n_chunks, (const int32_t*)nullptr, out);
+    hipLaunchKernelGGL(hml_k_dense_partial, dim3(n_chunks, ncol), dim3(256), 0, c->stream, c->rec[HML_REC_BANDS].acc<int32_t>(), T, ncol, b_cs.as<int32_t>(), n_chunks);
+    hipLaunchKernelGGL(hml_k_scan_chunks<int32_t>, dim3(ncol), dim3(1024), 0, c->stream, b_cs.as<int32_t>(), n_chunks);
+    hipLaunchKernelGGL(hml_k_dense_final, dim3(n_chunks, ncol), dim3(256), 0, c->stream, c->rec[HML_REC_BANDS].acc<int32_t>(), T, ncol, b_cs.as<int32_t>(), n_chunks, (const int32_t*)nullptr, out);
     if (cumulative) hipLaunchKernelGGL(hml_k_bands_cumulate, dim3(grid_for(T, 256, 1, 65536)), dim3(256), 0, c->stream, out, T, c->D, nb);
     KLAUNCH_CHECK();
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -2053,13 +1999,13 @@ int hml_bands_dense_device(hml_ctx* c, void* out_dev, int cumulative) {
 int hml_bands_call(hml_ctx* c, uint64_t rank, uint64_t* n_runs, uint64_t* run_len, int32_t* run_band) {
     NEED_MODEL();
     if (!n_runs) return set_err(HML_ERR_ARG, "null argument");
-    hml_model m; if (int r = bands_ready(c, &m)) return r;
+    hml_model m; if (int r = recorder_ready(c, HML_REC_BANDS, &m)) return r;
     if (rank > m.n_bands_recorded) return set_err(HML_ERR_ARG, "hml_bands_call: the rank must be 0 (the most probable band) or between 1 and the number of recorded sweeps");
     const uint32_t T = (uint32_t)c->T;
     const int D = c->D, nb = c->n_band_edges + 1, ncol = D * nb;
     uint64_t M = 0;
     DevBuf b_seg, b_g, b_cs, b_rc, b_key;
-    if (int r = gather_band_segments(c, c->stream, &M, b_seg, &b_g)) return r;
+    if (int r = gather_band_segments(c, &M, b_seg, b_g)) return r;
     const uint32_t n_chunks = (uint32_t)((M + 255) / 256);
     HIPCHK(hipMalloc(&b_cs.p, (uint64_t)ncol * n_chunks * sizeof(int32_t)));
     HIPCHK(hipMalloc(&b_rc.p, ((uint64_t)n_chunks + 1) * sizeof(int32_t)));
@@ -2068,10 +2014,10 @@ int hml_bands_call(hml_ctx* c, uint64_t rank, uint64_t* n_runs, uint64_t* run_le
     int16_t* const d_key = b_key.as<int16_t>();
     HIPCHK(hipMemsetAsync(d_rc + n_chunks, 0, sizeof(int32_t), c->stream));
     hipLaunchKernelGGL(hml_k_seg_partial, dim3(n_chunks), dim3(256), 0, c->stream, b_g.as<int32_t>(), (uint32_t)M, ncol, d_cs, n_chunks);
-    hipLaunchKernelGGL(hml_k_dense_chunkscan, dim3(ncol), dim3(1024), 0, c->stream, d_cs, n_chunks);
+    hipLaunchKernelGGL(hml_k_scan_chunks<int32_t>, dim3(ncol), dim3(1024), 0, c->stream, d_cs, n_chunks);
     hipLaunchKernelGGL(hml_k_bands_pick, dim3(n_chunks), dim3(256), 0, c->stream, b_g.as<int32_t>(), (uint32_t)M, D, nb, d_cs, n_chunks, (unsigned long long)rank, d_key);
     hipLaunchKernelGGL(hml_k_seg_run_count, dim3(n_chunks), dim3(256), 0, c->stream, d_key, (uint32_t)M, d_rc);
-    hipLaunchKernelGGL(hml_k_dense_chunkscan, dim3(1), dim3(1024), 0, c->stream, d_rc, n_chunks + 1u);   // d_rc[n_chunks] = total
+    hipLaunchKernelGGL(hml_k_scan_chunks<int32_t>, dim3(1), dim3(1024), 0, c->stream, d_rc, n_chunks + 1u);   // d_rc[n_chunks] = total
     KLAUNCH_CHECK();
     int32_t R = 0;
     HIPCHK(hipMemcpyAsync(&R, d_rc + n_chunks, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -2098,36 +2044,7 @@ int hml_bands_call(hml_ctx* c, uint64_t rank, uint64_t* n_runs, uint64_t* run_le
     return 0;
 }
 
-int hml_bands_merge(hml_ctx* dst, hml_ctx* src) {
-    if (!dst || !src || !dst->model_set || !src->model_set) return set_err(HML_ERR_ARG, "model not set");
-    if (dst == src) return set_err(HML_ERR_ARG, "a context cannot be merged into itself");
-    if (dst->device != src->device)
-        return set_err(HML_ERR_ARG, "the level bands of chains on different GPUs are not merged yet: run the chains of one bands file on one GPU");
-    if (dst->T != src->T || dst->D != src->D) return set_err(HML_ERR_ARG, "level bands can only be merged between chains over the same positions and dimensions");
-    if (!src->bands_asked) return set_err(HML_ERR_ARG, "no level bands were recorded by the source context: give the edges with hml_set_level_bands (or HML_BANDS=e0,e1,...) before the recorded sweeps");
-    if (!same_band_edges(dst, src->n_band_edges, src->band_edges)) {
-        // a destination that was never asked takes the source's edges; any other difference is refused
-        if (dst->bands_asked || dst->d_bands) return set_err(HML_ERR_ARG, "level bands can only be merged between chains with the same edges, bit for bit");
-        dst->n_band_edges = src->n_band_edges;
-        memcpy(dst->band_edges, src->band_edges, sizeof dst->band_edges);
-    }
-    if (int r = ctx_bind(dst)) return r;
-    if (int r = hml_settle(src)) return r;   // (both streams idle: the merge reads the source's accumulators on the destination's stream)
-    if (int r = hml_settle(dst)) return r;
-    if (int r = ensure_band_buffers(src)) return r;
-    if (int r = ensure_band_buffers(dst)) return r;
-    dst->bands_asked = true;
-    const uint32_t T = (uint32_t)src->T;
-    const int ncol = src->D * (src->n_band_edges + 1);
-    uint64_t M = 0;
-    DevBuf b_seg;
-    if (int r = gather_band_segments(src, dst->stream, &M, b_seg, nullptr)) return r;
-    hipLaunchKernelGGL(hml_k_bands_merge, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, dst->stream, src->d_bands, b_seg.as<uint32_t>(), (uint32_t)M, T,
-                       ncol, src->d_mdl, dst->d_bands, dst->d_band_boundary, dst->d_mdl);
-    KLAUNCH_CHECK();
-    HIPCHK(hipStreamSynchronize(dst->stream));
-    return 0;
-}
+int hml_bands_merge(hml_ctx* dst, hml_ctx* src) { return recorder_merge(dst, src, HML_REC_BANDS); }
 
 int hml_max_segmentation(hml_ctx* c, uint64_t* n_runs, uint64_t* run_len, int32_t* run_state) {
     NEED_MODEL();
@@ -2155,11 +2072,11 @@ int hml_max_segmentation(hml_ctx* c, uint64_t* n_runs, uint64_t* run_len, int32_
     int16_t* const d_st = b_st.as<int16_t>();
     HIPCHK(hipMemsetAsync(d_rc + n_chunks, 0, sizeof(int32_t), c->stream));
     hipLaunchKernelGGL(hml_k_seg_partial, dim3(n_chunks), dim3(256), 0, c->stream, d_g, (uint32_t)M, K, d_cs, n_chunks);
-    hipLaunchKernelGGL(hml_k_dense_chunkscan, dim3(K), dim3(1024), 0, c->stream, d_cs, n_chunks);
+    hipLaunchKernelGGL(hml_k_scan_chunks<int32_t>, dim3(K), dim3(1024), 0, c->stream, d_cs, n_chunks);
     if (K <= HML_MAX_K) hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_seg_argmax<HML_MAX_K>), dim3(n_chunks), dim3(256), 0, c->stream, d_g, (uint32_t)M, K, d_cs, n_chunks, d_st);
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_seg_argmax<HML_CAP_K>), dim3(n_chunks), dim3(256), 0, c->stream, d_g, (uint32_t)M, K, d_cs, n_chunks, d_st);
     hipLaunchKernelGGL(hml_k_seg_run_count, dim3(n_chunks), dim3(256), 0, c->stream, d_st, (uint32_t)M, d_rc);
-    hipLaunchKernelGGL(hml_k_dense_chunkscan, dim3(1), dim3(1024), 0, c->stream, d_rc, n_chunks + 1u);   // d_rc[n_chunks] = total
+    hipLaunchKernelGGL(hml_k_scan_chunks<int32_t>, dim3(1), dim3(1024), 0, c->stream, d_rc, n_chunks + 1u);   // d_rc[n_chunks] = total
     KLAUNCH_CHECK();
     int32_t R = 0;
     HIPCHK(hipMemcpyAsync(&R, d_rc + n_chunks, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -2210,7 +2127,7 @@ int hml_marginals_dense_device(hml_ctx* c, void* out_dev, const int32_t* perm) {
         HIPCHK(hipMemcpyAsync(d_perm, perm, K * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     }
     hipLaunchKernelGGL(hml_k_dense_partial, dim3(n_chunks, K), dim3(256), 0, c->stream, c->d_diff, T, K, d_cs, n_chunks);
-    hipLaunchKernelGGL(hml_k_dense_chunkscan, dim3(K), dim3(1024), 0, c->stream, d_cs, n_chunks);
+    hipLaunchKernelGGL(hml_k_scan_chunks<int32_t>, dim3(K), dim3(1024), 0, c->stream, d_cs, n_chunks);
     hipLaunchKernelGGL(hml_k_dense_final, dim3(n_chunks, K), dim3(256), 0, c->stream, c->d_diff, T, K, d_cs, n_chunks, d_perm, out);
     hipLaunchKernelGGL(hml_k_dense_boundary, dim3(grid_for(T, 256, 1, 65536)), dim3(256), 0, c->stream, c->d_boundary, T,
                        out + (uint64_t)K * T);

@@ -30,6 +30,7 @@
 #include "hml_k_build.h"
 #include "hml_k_forward.h"
 #include "hml_k_marginals.h"
+#include "hml_k_scan.h"
 #include "hml_k_levels.h"
 #include "hml_k_breaks.h"
 #include "hml_k_bands.h"
@@ -240,67 +241,56 @@ static int ensure_marginal_buffers(hml_ctx* c) {
     return 0;
 }
 
-// the emission levels' accumulators (hml_k_levels.h): 2 D (T + 1) doubles and (T + 32) / 32 words, on first use.  Zeroed before
-// this returns: chains batched by hml_iterate_many run on their group's stream, not on their own.
-static int ensure_level_buffers(hml_ctx* c) {
-    if (c->d_levels) return 0;
-    const uint64_t n = 2ull * (uint64_t)c->D * (c->T + 1);
+// ---- the per-position recordings beside the marginals (hml_recorder, hml_ctx.hpp): what differs between the three ----
+struct hml_recorder_kind {
+    const char* family;   // profile family of its record kernel
+    size_t elem;          // bytes of an accumulator cell
+    size_t counter;       // offset in hml_model of its count of recorded sweeps
+    const char* none;     // "nothing was recorded" (%s: "this" / "the source")
+    const char* noun;     // what the merge messages call it
+    const char* file;     // ... and its output file
+};
+static const hml_recorder_kind hml_recorder_kinds[HML_REC_KINDS] = {
+    {"levels", sizeof(double), offsetof(hml_model, n_levels_recorded),
+     "no emission levels were recorded by %s context: enable them with hml_set_level_recording (or HML_LEVELS=1) before the recorded sweeps", "emission levels", "levels"},
+    {"breaks", sizeof(uint32_t), offsetof(hml_model, n_breaks_recorded),
+     "no breakpoints were recorded by %s context: enable them with hml_set_break_recording (or HML_BREAKS=1) before the recorded sweeps", "breakpoints", "breakpoints"},
+    {"bands", sizeof(int32_t), offsetof(hml_model, n_bands_recorded),
+     "no level bands were recorded by %s context: give the edges with hml_set_level_bands (or HML_BANDS=e0,e1,...) before the recorded sweeps", "level bands", "bands"},
+};
+static int recorder_rows(const hml_ctx* c, int kind) {
+    return kind == HML_REC_LEVELS ? 2 * c->D : kind == HML_REC_BREAKS ? 1 : c->D * (c->n_band_edges + 1);
+}
+static unsigned long long* recorder_counter(const hml_ctx* c, int kind) {
+    return (unsigned long long*)((char*)c->d_mdl + hml_recorder_kinds[kind].counter);
+}
+static int recorder_none(int kind, const char* whose) {
+    char buf[256];
+    snprintf(buf, sizeof buf, hml_recorder_kinds[kind].none, whose);
+    return set_err(HML_ERR_ARG, buf);
+}
+
+// a recording's accumulators - rows (T + 1) cells and (T + 32) / 32 words of bitmap - on first use.  Zeroed before this
+// returns: chains batched by hml_iterate_many run on their group's stream, not on their own.
+static int ensure_recorder_buffers(hml_ctx* c, int kind) {
+    hml_recorder& r = c->rec[kind];
+    if (r.d_acc) return 0;
+    if (kind == HML_REC_BANDS && (c->n_band_edges < 1 || recorder_rows(c, kind) > HML_CAP_K))
+        return set_err(HML_ERR_ARG, "level bands: the data dimensions times (edges + 1) must be between 2 and 64 columns");
+    const uint64_t bytes = (uint64_t)recorder_rows(c, kind) * (c->T + 1) * hml_recorder_kinds[kind].elem;
     const uint64_t words = (c->T + 32) / 32;
-    HIPCHK(hipMalloc(&c->d_levels, n * sizeof(double)));
-    HIPCHK(hipMalloc(&c->d_lev_boundary, words * sizeof(uint32_t)));
-    HIPCHK(hipMemsetAsync(c->d_levels, 0, n * sizeof(double), c->stream));
-    HIPCHK(hipMemsetAsync(c->d_lev_boundary, 0, words * sizeof(uint32_t), c->stream));
+    HIPCHK(hipMalloc(&r.d_acc, bytes));
+    HIPCHK(hipMalloc(&r.d_boundary, words * sizeof(uint32_t)));
+    HIPCHK(hipMemsetAsync(r.d_acc, 0, bytes, c->stream));
+    HIPCHK(hipMemsetAsync(r.d_boundary, 0, words * sizeof(uint32_t), c->stream));
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(c->stream, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone) HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
-
-// the level kernel of a recorded sweep, on stream `s`, BEHIND the sweep's parameter update: the level is mu under the theta
-// that hml_get_theta returns inside the sweep's record callback
-static int launch_levels_record(hml_ctx* c, hipStream_t s, uint32_t hint) {
-    if (int r = ensure_level_buffers(c)) return r;
-    ProfScope ps(c, "levels");
-    hipLaunchKernelGGL(hml_k_levels_record, dim3(grid_for(hint, 256, 64, 16384)), dim3(256), 0, s, c->d_q, c->d_starts, c->d_mdl, c->d_levels, c->d_lev_boundary);
-    return 0;
-}
-
-// the breakpoint counts (hml_k_breaks.h): T + 1 words and (T + 32) / 32 words of bitmap, on first use; zeroed before this
-// returns, like the levels' accumulators
-static int ensure_break_buffers(hml_ctx* c) {
-    if (c->d_breaks) return 0;
-    const uint64_t words = (c->T + 32) / 32;
-    HIPCHK(hipMalloc(&c->d_breaks, (c->T + 1) * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&c->d_brk_boundary, words * sizeof(uint32_t)));
-    HIPCHK(hipMemsetAsync(c->d_breaks, 0, (c->T + 1) * sizeof(uint32_t), c->stream));
-    HIPCHK(hipMemsetAsync(c->d_brk_boundary, 0, words * sizeof(uint32_t), c->stream));
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(c->stream, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone) HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-// the breakpoint kernel of a recorded sweep, on stream `s` (it reads the sweep's states and block starts, not theta)
-static int launch_breaks_record(hml_ctx* c, hipStream_t s, uint32_t hint) {
-    if (int r = ensure_break_buffers(c)) return r;
-    ProfScope ps(c, "breaks");
-    hipLaunchKernelGGL(hml_k_breaks_record, dim3(grid_for(hint, 256, 64, 16384)), dim3(256), 0, s, c->d_q, c->d_starts, c->d_mdl, c->d_breaks, c->d_brk_boundary);
-    return 0;
-}
-
-
-// the level bands' accumulators (hml_k_bands.h): D (n_edges + 1) (T + 1) int32 and (T + 32) / 32 words of bitmap, on first
-// use; zeroed before this returns, like the levels' accumulators
-static int ensure_band_buffers(hml_ctx* c) {
-    if (c->d_bands) return 0;
-    const uint64_t ncol = (uint64_t)c->D * (uint64_t)(c->n_band_edges + 1);
-    if (c->n_band_edges < 1 || ncol > HML_CAP_K) return set_err(HML_ERR_ARG, "level bands: the data dimensions times (edges + 1) must be between 2 and 64 columns");
-    const uint64_t n = ncol * (c->T + 1);
-    const uint64_t words = (c->T + 32) / 32;
-    HIPCHK(hipMalloc(&c->d_bands, n * sizeof(int32_t)));
-    HIPCHK(hipMalloc(&c->d_band_boundary, words * sizeof(uint32_t)));
-    HIPCHK(hipMemsetAsync(c->d_bands, 0, n * sizeof(int32_t), c->stream));
-    HIPCHK(hipMemsetAsync(c->d_band_boundary, 0, words * sizeof(uint32_t), c->stream));
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(c->stream, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone) HIPCHK(hipStreamSynchronize(c->stream));
+// ... of every recording that is on
+static int ensure_recorders(hml_ctx* c) {
+    for (int kind = 0; kind < HML_REC_KINDS; ++kind)
+        if (c->rec[kind].on) { if (int r = ensure_recorder_buffers(c, kind)) return r; }
     return 0;
 }
 
@@ -312,11 +302,27 @@ static hml_band_edges band_edges_of(const hml_ctx* c) {
     return ed;
 }
 
-// the band kernel of a recorded sweep, on stream `s`, BEHIND the sweep's parameter update like the level kernel
-static int launch_bands_record(hml_ctx* c, hipStream_t s, uint32_t hint) {
-    if (int r = ensure_band_buffers(c)) return r;
-    ProfScope ps(c, "bands");
-    hipLaunchKernelGGL(hml_k_bands_record, dim3(grid_for(hint, 256, 64, 16384)), dim3(256), 0, s, c->d_q, c->d_starts, c->d_mdl, band_edges_of(c), c->d_bands, c->d_band_boundary);
+// the record kernel of one recording, on stream `s`
+static void launch_record_kernel(hml_ctx* c, int kind, hipStream_t s, dim3 grid) {
+    const hml_recorder& r = c->rec[kind];
+    if (kind == HML_REC_LEVELS)
+        hipLaunchKernelGGL(hml_k_levels_record, grid, dim3(256), 0, s, c->d_q, c->d_starts, c->d_mdl, r.acc<double>(), r.d_boundary);
+    else if (kind == HML_REC_BREAKS)
+        hipLaunchKernelGGL(hml_k_breaks_record, grid, dim3(256), 0, s, c->d_q, c->d_starts, c->d_mdl, r.acc<uint32_t>(), r.d_boundary);
+    else
+        hipLaunchKernelGGL(hml_k_bands_record, grid, dim3(256), 0, s, c->d_q, c->d_starts, c->d_mdl, band_edges_of(c), r.acc<int32_t>(), r.d_boundary);
+}
+
+// the record kernels of a recorded sweep, on stream `s`, BEHIND the sweep's parameter update: the level (and its band) is mu
+// under the theta that hml_get_theta returns inside the sweep's record callback; the breakpoint kernel reads the sweep's
+// states and block starts only
+static int launch_recorders(hml_ctx* c, hipStream_t s, uint32_t hint) {
+    for (int kind = 0; kind < HML_REC_KINDS; ++kind) {
+        if (!c->rec[kind].on) continue;
+        if (int r = ensure_recorder_buffers(c, kind)) return r;
+        ProfScope ps(c, hml_recorder_kinds[kind].family);
+        launch_record_kernel(c, kind, s, dim3(grid_for(hint, 256, 64, 16384)));
+    }
     return 0;
 }
 

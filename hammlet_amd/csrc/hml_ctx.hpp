@@ -29,6 +29,18 @@ struct hml_trace {
 
 struct ProfAcc { double ms = 0; uint64_t n = 0; uint32_t tick = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> pending; };
 
+// One per-position posterior summary that a recorded sweep accumulates beside the state marginals: emission levels, breakpoint
+// counts, level bands.  All three keep difference arrays touched only where a run starts and a boundary bitmap of their own;
+// what differs between them is in hml_recorder_kinds (hml_capi_shared.hpp).
+enum { HML_REC_LEVELS = 0, HML_REC_BREAKS = 1, HML_REC_BANDS = 2, HML_REC_KINDS = 3 };
+struct hml_recorder {
+    bool on = false;                  // recording now (hml_set_level_recording / hml_set_break_recording / hml_set_level_bands; HML_LEVELS / HML_BREAKS / HML_BANDS)
+    bool asked = false;               // ... was on at some time: the read-outs answer
+    void* d_acc = nullptr;            // [rows][T + 1] accumulators
+    uint32_t* d_boundary = nullptr;   // its own bitmap of the positions with a cell
+    template <class E> E* acc() const { return static_cast<E*>(d_acc); }
+};
+
 struct hml_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -112,23 +124,15 @@ struct hml_ctx {
     bool params_spread = false;    // single-chain sweeps: the parameter kernel's tree over 16 workgroups (hml_k_params.h; HML_PARAMS_SPREAD)
     int32_t* d_diff = nullptr;
     uint32_t* d_boundary = nullptr;
-    // emission levels per position (hml_k_levels.h), allocated by the first recorded sweep that wants them
-    bool rec_levels = false;        // hml_set_level_recording / HML_LEVELS
-    bool levels_asked = false;      // ... was on at some time: the read-outs answer (with nothing recorded: one segment, zero sums)
-    double* d_levels = nullptr;     // [2 D][T + 1]: row 2 d the level's difference array, row 2 d + 1 its square's
-    uint32_t* d_lev_boundary = nullptr;   // the levels' own bitmap of segment boundaries
-    // breakpoint counts per position (hml_k_breaks.h), allocated by the first recorded sweep that wants them
-    bool rec_breaks = false;        // hml_set_break_recording / HML_BREAKS
-    bool breaks_asked = false;      // ... was on at some time: the read-outs answer (with nothing recorded: an empty list)
-    uint32_t* d_breaks = nullptr;   // [T + 1]: recorded sweeps with a breakpoint at t
-    uint32_t* d_brk_boundary = nullptr;   // the breaks' own bitmap of the positions with a count
-    // level bands per position (hml_k_bands.h), allocated by the first recorded sweep that wants them
-    bool rec_bands = false;         // hml_set_level_bands / HML_BANDS
-    bool bands_asked = false;       // ... was on at some time: the read-outs answer (with nothing recorded: one segment of zeros)
-    int n_band_edges = 0;           // the edges last set (they stay when the recording is turned off)
+    // the per-position recordings beside the state marginals (hml_recorder above), allocated by the first recorded sweep that wants them:
+    //   HML_REC_LEVELS  double [2 D][T + 1]: row 2 d the level's difference array, row 2 d + 1 its square's (hml_k_levels.h);
+    //                   nothing recorded: one segment, zero sums
+    //   HML_REC_BREAKS  uint32 [T + 1]: recorded sweeps with a breakpoint at t (hml_k_breaks.h); nothing recorded: an empty list
+    //   HML_REC_BANDS   int32 [D (n_band_edges + 1)][T + 1]: difference arrays of the counts per band (hml_k_bands.h);
+    //                   nothing recorded: one segment of zeros
+    hml_recorder rec[HML_REC_KINDS];
+    int n_band_edges = 0;           // the bands' edges last set (they stay when the recording is turned off)
     float band_edges[31] = {};
-    int32_t* d_bands = nullptr;     // [D (n_band_edges + 1)][T + 1]: difference arrays of the counts per band
-    uint32_t* d_band_boundary = nullptr;   // the bands' own bitmap of segment boundaries
     hml_model* d_mdl = nullptr;
     uint32_t* h_B = nullptr;       // pinned + mapped, four words: [0] the block count of the latest enumeration (grid sizing hint),
                                     // [1] set by the fused block kernel when a bounded wait expired, [2] the chain is HALTED: the number of

@@ -7,7 +7,7 @@
 // difference arrays [columns][T + 1] and a boundary bitmap of the bands' own, touched only where the BAND VECTOR changes -
 // adjacent runs of different states in the same bands leave no cell and no bit.  Read-out never walks the T cells (but for the
 // dense form): hml_k_marg_count / _scatter / _gather compact the bitmap and gather the cells, hml_k_seg_partial and
-// hml_k_dense_chunkscan scan them, hml_k_seg_run_count / _run_scatter merge the calls into runs.
+// hml_k_scan_chunks scan them, hml_k_seg_run_count / _run_scatter merge the calls into runs.
 #ifndef HML_K_BANDS_H
 #define HML_K_BANDS_H
 
@@ -92,7 +92,7 @@ HML_KERNEL __launch_bounds__(256) void hml_k_bands_cumulate(int32_t* __restrict_
 
 // hml_bands_call: the band called for every band segment and dimension, from the count differences at the segment starts
 // g[M][columns] (hml_k_marg_gather) and the exclusive sums of their chunks of 256 segments (hml_k_seg_partial, then
-// hml_k_dense_chunkscan).  rank 0: the band with the largest count - first maximum, strict `>` from count 0, hml_k_seg_argmax's
+// hml_k_scan_chunks).  rank 0: the band with the largest count - first maximum, strict `>` from count 0, hml_k_seg_argmax's
 // rule; rank >= 1: the smallest band whose cumulative count over the bands up to it reaches `rank` (the last band if none does).
 // The D calls of a segment are packed into one key, sum over d of call_d nb^d - below 2^16 because D nb <= HML_CAP_K and
 // D <= HML_MAX_D - so that hml_k_seg_run_count / hml_k_seg_run_scatter merge equal neighbours; keys compare as bit patterns.
@@ -138,22 +138,6 @@ HML_KERNEL __launch_bounds__(256) void hml_k_bands_pick(const int32_t* __restric
         scale *= (uint32_t)nb;
     }
     if (i < M) seg_key[i] = (int16_t)(uint16_t)key;
-}
-
-// hml_bands_merge: the source's cells at the source's segment starts into the destination (same T, same columns), its
-// boundary bits, its count.  The starts are distinct: plain read-modify-writes.
-HML_KERNEL __launch_bounds__(256) void hml_k_bands_merge(const int32_t* __restrict__ src, const uint32_t* __restrict__ seg_start,
-                                                         uint32_t M, uint32_t T, int rows, const hml_model* __restrict__ src_mdl,
-                                                         int32_t* __restrict__ dst, uint32_t* __restrict__ dst_boundary,
-                                                         hml_model* __restrict__ dst_mdl) {
-    const uint64_t T1 = (uint64_t)T + 1u;
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < M; i += stride) {
-        const uint32_t t = seg_start[i];
-        for (int r = 0; r < rows; ++r) dst[(uint64_t)r * T1 + t] += src[(uint64_t)r * T1 + t];
-        atomicOr(&dst_boundary[t >> 5], 1u << (t & 31u));
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&dst_mdl->n_bands_recorded, src_mdl->n_bands_recorded);
 }
 
 #endif

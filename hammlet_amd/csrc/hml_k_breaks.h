@@ -5,7 +5,8 @@
 // everything here is an integer, so every read-out is exact.  Device form, like hml_k_levels_record: uint32 [T + 1], touched
 // only where a run of equal states starts, and a boundary bitmap of the breaks' own.  Read-out never walks the T cells: the
 // bitmap is compacted into the M break positions (hml_k_marg_count / hml_k_marg_scatter; entry 0 of that list is the
-// position 0 those kernels always emit and is dropped), the counts are gathered and scanned.
+// position 0 those kernels always emit and is dropped), the counts are gathered (hml_k_rec_gather, one row) and scanned
+// (hml_k_scan.h: 32-bit counts into exclusive 64-bit sums pre[i] = sum of v[j] over j < i, pre[M] = the total).
 #ifndef HML_K_BREAKS_H
 #define HML_K_BREAKS_H
 
@@ -29,90 +30,6 @@ HML_KERNEL __launch_bounds__(256) void hml_k_breaks_record(const int16_t* __rest
         atomicOr(&boundary[t >> 5], 1u << (t & 31u));
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&mdl->n_breaks_recorded, 1ull);
-}
-
-// cnt_out[i] = C[pos[i]] for the M listed positions
-HML_KERNEL __launch_bounds__(256) void hml_k_breaks_gather(const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ pos,
-                                                           uint32_t M, uint32_t* __restrict__ cnt_out) {
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < M; i += stride) cnt_out[i] = cnt[pos[i]];
-}
-
-// ---- exclusive prefix sums of M 32-bit counts in 64-bit integers: pre[i] = sum of v[j] over j < i, pre[M] = the total.
-// Chunks of HML_BRK_CHUNK entries, four consecutive entries per thread (integers: any order gives the same sums).
-#define HML_BRK_CHUNK 1024
-
-__device__ __forceinline__ void hml_breaks_chunk_scan(const uint32_t* __restrict__ v, uint32_t M, uint32_t chunk,
-                                                      unsigned long long* sh, unsigned long long out[4]) {
-    const uint32_t tid = threadIdx.x;
-    const uint64_t i0 = (uint64_t)chunk * HML_BRK_CHUNK + 4u * tid;
-    unsigned long long run = 0ull;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (i0 + k < M) run += v[i0 + k];
-        out[k] = run;
-    }
-    sh[tid] = run;
-    __syncthreads();
-    for (uint32_t d = 1; d < 256u; d <<= 1) {
-        const unsigned long long o = (tid >= d) ? sh[tid - d] : 0ull;
-        __syncthreads();
-        sh[tid] += o;
-        __syncthreads();
-    }
-    const unsigned long long before = (tid > 0) ? sh[tid - 1] : 0ull;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) out[k] += before;   // inclusive sums relative to the chunk's start
-}
-
-HML_KERNEL __launch_bounds__(256) void hml_k_breaks_scan_partial(const uint32_t* __restrict__ v, uint32_t M, uint32_t n_chunks,
-                                                                 unsigned long long* __restrict__ chunk_sum) {
-    __shared__ unsigned long long sh[256];
-    for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
-        unsigned long long o[4];
-        hml_breaks_chunk_scan(v, M, chunk, sh, o);
-        if (threadIdx.x == 255u) chunk_sum[chunk] = o[3];
-        __syncthreads();
-    }
-}
-
-// one workgroup: exclusive sums of the chunk totals, in place
-HML_KERNEL __launch_bounds__(1024) void hml_k_breaks_scan_chunks(unsigned long long* __restrict__ cs, uint32_t n_chunks) {
-    __shared__ unsigned long long part[1024];
-    const uint32_t tid = threadIdx.x;
-    const uint32_t per = (n_chunks + 1023u) / 1024u;
-    const uint32_t a = (uint64_t)tid * per < n_chunks ? tid * per : n_chunks;
-    const uint32_t b = (a + per < n_chunks) ? a + per : n_chunks;
-    unsigned long long sum = 0ull;
-    for (uint32_t i = a; i < b; ++i) sum += cs[i];
-    part[tid] = sum;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024u; d <<= 1) {
-        const unsigned long long o = (tid >= d) ? part[tid - d] : 0ull;
-        __syncthreads();
-        part[tid] += o;
-        __syncthreads();
-    }
-    unsigned long long run = part[tid] - sum;
-    for (uint32_t i = a; i < b; ++i) { const unsigned long long x = cs[i]; cs[i] = run; run += x; }
-}
-
-// pre[M + 1]: the exclusive sums and, in pre[M], the total
-HML_KERNEL __launch_bounds__(256) void hml_k_breaks_scan_final(const uint32_t* __restrict__ v, uint32_t M, uint32_t n_chunks,
-                                                               const unsigned long long* __restrict__ chunk_sum,
-                                                               unsigned long long* __restrict__ pre) {
-    __shared__ unsigned long long sh[256];
-    if (blockIdx.x == 0 && threadIdx.x == 0) pre[0] = 0ull;
-    for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
-        unsigned long long o[4];
-        hml_breaks_chunk_scan(v, M, chunk, sh, o);
-        const unsigned long long base = chunk_sum[chunk];
-        const uint64_t i0 = (uint64_t)chunk * HML_BRK_CHUNK + 4u * threadIdx.x;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (i0 + k < M) pre[i0 + k + 1] = base + o[k];
-        __syncthreads();
-    }
 }
 
 // the first i in [0, M] with pos[i] >= key (key may exceed every position: M)
@@ -182,20 +99,6 @@ HML_KERNEL __launch_bounds__(256) void hml_k_breaks_compact(const uint32_t* __re
         out_mass[k] = mass[i];
         out_peak[k] = cnt[i];
     }
-}
-
-// hml_breaks_merge: the source's counts at the source's break positions into the destination (same T), its boundary bits,
-// its count of recorded sweeps.  The positions are distinct: plain read-modify-writes.
-HML_KERNEL __launch_bounds__(256) void hml_k_breaks_merge(const uint32_t* __restrict__ src, const uint32_t* __restrict__ pos, uint32_t M,
-                                                          const hml_model* __restrict__ src_mdl, uint32_t* __restrict__ dst,
-                                                          uint32_t* __restrict__ dst_boundary, hml_model* __restrict__ dst_mdl) {
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < M; i += stride) {
-        const uint32_t t = pos[i];
-        dst[t] += src[t];
-        atomicOr(&dst_boundary[t >> 5], 1u << (t & 31u));
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&dst_mdl->n_breaks_recorded, src_mdl->n_breaks_recorded);
 }
 
 // ---- hml_levels_on_segments (the levels' accumulators, hml_k_levels.h, summed over caller-given segments) ----

@@ -4,7 +4,8 @@
 // add over sweeps and over chains without any relabelling.  Device form, like hml_b_record: a difference array touched
 // only where a run of equal states starts (rows 2 d = level, 2 d + 1 = level squared, T + 1 doubles each), and a boundary
 // bitmap of the levels' own.  Read-out never walks the T cells: the bitmap is compacted into segment starts
-// (hml_k_marg_count / hml_k_marg_scatter), the cells at the starts are gathered and scanned.
+// (hml_k_marg_count / hml_k_marg_scatter), the cells at the starts are gathered (hml_k_rec_gather) and scanned over the
+// fixed tree of hml_k_scan.h, in double.
 #ifndef HML_K_LEVELS_H
 #define HML_K_LEVELS_H
 
@@ -37,102 +38,6 @@ HML_KERNEL __launch_bounds__(256) void hml_k_levels_record(const int16_t* __rest
         }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&mdl->n_levels_recorded, 1ull);
-}
-
-// gather acc[r][seg_start[i]] for all 2 D rows: out[r * M + i]
-HML_KERNEL __launch_bounds__(256) void hml_k_levels_gather(const double* __restrict__ acc, uint32_t T, int rows,
-                                                           const uint32_t* __restrict__ seg_start, uint32_t M,
-                                                           double* __restrict__ out) {
-    const uint64_t T1 = (uint64_t)T + 1u;
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < M; i += stride) {
-        const uint32_t t = seg_start[i];
-        for (int r = 0; r < rows; ++r) out[(uint64_t)r * M + i] = acc[(uint64_t)r * T1 + t];
-    }
-}
-
-// ---- inclusive prefix sums over the M gathered entries of every row, in double, over a tree of FIXED shape: chunks of
-// HML_LEV_CHUNK entries; inside a chunk four consecutive entries per thread, then 8 doubling steps over the 256 threads'
-// sums; the chunk totals in pieces of ceil(chunks / 1024) with 10 doubling steps over the pieces.  Which additions happen,
-// and in which order, depends on M alone - not on the grid, which only decides which workgroup takes which chunk.
-#define HML_LEV_CHUNK 1024
-
-// inclusive sums of one chunk's entries, relative to the chunk's start (the calling workgroup's 256 threads; `sh`: 256 doubles)
-__device__ __forceinline__ void hml_levels_chunk_scan(const double* __restrict__ row, uint32_t M, uint32_t chunk, double* sh,
-                                                      double v[4]) {
-    const uint32_t tid = threadIdx.x;
-    const uint64_t i0 = (uint64_t)chunk * HML_LEV_CHUNK + 4u * tid;
-    double run = 0.0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (i0 + k < M) run += row[i0 + k];
-        v[k] = run;
-    }
-    sh[tid] = run;
-    __syncthreads();
-    for (uint32_t d = 1; d < 256u; d <<= 1) {
-        const double o = (tid >= d) ? sh[tid - d] : 0.0;
-        __syncthreads();
-        if (tid >= d) sh[tid] += o;
-        __syncthreads();
-    }
-    if (tid > 0) {
-        const double before = sh[tid - 1];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = before + v[k];
-    }
-}
-
-// grid (any x, rows): chunk totals
-HML_KERNEL __launch_bounds__(256) void hml_k_levels_scan_partial(const double* __restrict__ g, uint32_t M, uint32_t n_chunks,
-                                                                 double* __restrict__ chunk_sum) {
-    __shared__ double sh[256];
-    const double* row = g + (uint64_t)blockIdx.y * M;
-    for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
-        double v[4];
-        hml_levels_chunk_scan(row, M, chunk, sh, v);
-        if (threadIdx.x == 255u) chunk_sum[(uint64_t)blockIdx.y * n_chunks + chunk] = v[3];
-        __syncthreads();
-    }
-}
-
-// grid (rows): exclusive sums of the chunk totals, in place (hml_k_dense_chunkscan's shape, in double)
-HML_KERNEL __launch_bounds__(1024) void hml_k_levels_scan_chunks(double* __restrict__ chunk_sum, uint32_t n_chunks) {
-    __shared__ double part[1024];
-    double* cs = chunk_sum + (uint64_t)blockIdx.x * n_chunks;
-    const uint32_t tid = threadIdx.x;
-    const uint32_t per = (n_chunks + 1023u) / 1024u;
-    const uint32_t a = (uint64_t)tid * per < n_chunks ? tid * per : n_chunks;
-    const uint32_t b = (a + per < n_chunks) ? a + per : n_chunks;
-    double sum = 0.0;
-    for (uint32_t i = a; i < b; ++i) sum += cs[i];
-    part[tid] = sum;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024u; d <<= 1) {
-        const double o = (tid >= d) ? part[tid - d] : 0.0;
-        __syncthreads();
-        if (tid >= d) part[tid] += o;
-        __syncthreads();
-    }
-    double run = (tid > 0) ? part[tid - 1] : 0.0;
-    for (uint32_t i = a; i < b; ++i) { const double x = cs[i]; cs[i] = run; run += x; }
-}
-
-// grid (any x, rows): the entries become the inclusive sums, in place
-HML_KERNEL __launch_bounds__(256) void hml_k_levels_scan_final(double* __restrict__ g, uint32_t M, uint32_t n_chunks,
-                                                               const double* __restrict__ chunk_sum) {
-    __shared__ double sh[256];
-    double* row = g + (uint64_t)blockIdx.y * M;
-    for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
-        double v[4];
-        hml_levels_chunk_scan(row, M, chunk, sh, v);
-        const double base = chunk_sum[(uint64_t)blockIdx.y * n_chunks + chunk];
-        const uint64_t i0 = (uint64_t)chunk * HML_LEV_CHUNK + 4u * threadIdx.x;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (i0 + k < M) row[i0 + k] = base + v[k];
-        __syncthreads();
-    }
 }
 
 // mean and standard deviation of the level per segment, as floats: ms[(2 d) * M + i] = S1 / N, ms[(2 d + 1) * M + i] =
@@ -169,22 +74,6 @@ HML_KERNEL __launch_bounds__(256) void hml_k_levels_expand(const float* __restri
         }
         for (int r = 0; r < rows; ++r) out[(uint64_t)r * T + t] = ms[(uint64_t)r * M + lo];
     }
-}
-
-// hml_levels_merge: the source's cells at the source's segment starts into the destination (same T, same rows), its
-// boundary bits, its count.  The starts are distinct: plain read-modify-writes.
-HML_KERNEL __launch_bounds__(256) void hml_k_levels_merge(const double* __restrict__ src, const uint32_t* __restrict__ seg_start,
-                                                          uint32_t M, uint32_t T, int rows, const hml_model* __restrict__ src_mdl,
-                                                          double* __restrict__ dst, uint32_t* __restrict__ dst_boundary,
-                                                          hml_model* __restrict__ dst_mdl) {
-    const uint64_t T1 = (uint64_t)T + 1u;
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < M; i += stride) {
-        const uint32_t t = seg_start[i];
-        for (int r = 0; r < rows; ++r) dst[(uint64_t)r * T1 + t] += src[(uint64_t)r * T1 + t];
-        atomicOr(&dst_boundary[t >> 5], 1u << (t & 31u));
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&dst_mdl->n_levels_recorded, src_mdl->n_levels_recorded);
 }
 
 #endif

@@ -1,4 +1,6 @@
-// Finalisation of the state marginals: boundary compaction, per-segment gathers, dense expansion.
+// Finalisation of the state marginals: boundary compaction, per-segment gathers, dense expansion - and what the other
+// per-position recordings (levels, breaks, bands: hml_recorder, hml_ctx.hpp) share with them: the compaction of a boundary
+// bitmap, the gather of a recording's cells at the starts and the merge of one chain's recording into another's.
 #ifndef HML_K_MARGINALS_H
 #define HML_K_MARGINALS_H
 
@@ -71,8 +73,38 @@ HML_KERNEL __launch_bounds__(256) void hml_k_marg_gather(const int32_t* __restri
     }
 }
 
+// a recording's cells at the listed positions, row by row: out[r * M + i] = acc[r][pos[i]]
+template <typename E>
+__global__ __launch_bounds__(256) void hml_k_rec_gather(const E* __restrict__ acc, uint32_t T, int rows,
+                                                        const uint32_t* __restrict__ pos, uint32_t M, E* __restrict__ out) {
+    const uint64_t T1 = (uint64_t)T + 1u;
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < M; i += stride) {
+        const uint32_t t = pos[i];
+        for (int r = 0; r < rows; ++r) out[(uint64_t)r * M + i] = acc[(uint64_t)r * T1 + t];
+    }
+}
+
+// hml_levels_merge / hml_breaks_merge / hml_bands_merge: the source's cells at the source's M listed positions into the
+// destination (same T, same rows), its boundary bits, its count of recorded sweeps (src_n, dst_n: the two counters inside
+// the chains' hml_model).  The positions are distinct: plain read-modify-writes.
+template <typename E>
+__global__ __launch_bounds__(256) void hml_k_rec_merge(const E* __restrict__ src, const uint32_t* __restrict__ pos, uint32_t M,
+                                                       uint32_t T, int rows, const unsigned long long* __restrict__ src_n,
+                                                       E* __restrict__ dst, uint32_t* __restrict__ dst_boundary,
+                                                       unsigned long long* __restrict__ dst_n) {
+    const uint64_t T1 = (uint64_t)T + 1u;
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < M; i += stride) {
+        const uint32_t t = pos[i];
+        for (int r = 0; r < rows; ++r) dst[(uint64_t)r * T1 + t] += src[(uint64_t)r * T1 + t];
+        atomicOr(&dst_boundary[t >> 5], 1u << (t & 31u));
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(dst_n, *src_n);
+}
+
 // ---- dense expansion: counts[s][t] = prefix sum over t of diff[s][t]; row K = boundary indicator ----
-// three-phase scan over chunks of 4096 positions per state
+// three-phase scan over chunks of 4096 positions per state; the middle phase is hml_k_scan_chunks<int32_t> (hml_k_scan.h)
 HML_KERNEL __launch_bounds__(256) void hml_k_dense_partial(const int32_t* __restrict__ diff, uint32_t T, int K,
                                                            int32_t* __restrict__ chunk_sum, uint32_t n_chunks) {
     __shared__ int32_t red[4];
@@ -90,28 +122,6 @@ HML_KERNEL __launch_bounds__(256) void hml_k_dense_partial(const int32_t* __rest
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) chunk_sum[(uint64_t)s * n_chunks + chunk] = red[0] + red[1] + red[2] + red[3];
-}
-
-HML_KERNEL __launch_bounds__(1024) void hml_k_dense_chunkscan(int32_t* __restrict__ chunk_sum, uint32_t n_chunks) {
-    __shared__ int32_t part[1024];
-    const int s = blockIdx.x;
-    int32_t* cs = chunk_sum + (uint64_t)s * n_chunks;
-    const int tid = threadIdx.x;
-    const uint32_t per = (n_chunks + 1023u) / 1024u;
-    const uint32_t a = (uint32_t)tid * per < n_chunks ? (uint32_t)tid * per : n_chunks;
-    const uint32_t b = (a + per < n_chunks) ? a + per : n_chunks;
-    int32_t sum = 0;
-    for (uint32_t i = a; i < b; ++i) sum += cs[i];
-    part[tid] = sum;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const int32_t v = (tid >= d) ? part[tid - d] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    int32_t run = part[tid] - sum;
-    for (uint32_t i = a; i < b; ++i) { const int32_t v = cs[i]; cs[i] = run; run += v; }
 }
 
 HML_KERNEL __launch_bounds__(256) void hml_k_dense_final(const int32_t* __restrict__ diff, uint32_t T, int K,

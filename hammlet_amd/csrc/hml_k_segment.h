@@ -29,7 +29,7 @@ HML_KERNEL __launch_bounds__(256) void hml_k_seg_partial(const int32_t* __restri
         chunk_sum[(uint64_t)threadIdx.x * n_chunks + blockIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
-// phase 3 (phase 2 is hml_k_dense_chunkscan over the K rows of chunk_sum): running counts of every segment and
+// phase 3 (phase 2 is hml_k_scan_chunks over the K rows of chunk_sum): running counts of every segment and
 // their arg-max -> seg_state[i]
 // (KM: the most states the running counts are kept for - HML_MAX_K, or HML_CAP_K for the reference-compatible mode's larger models)
 template <int KM>

@@ -275,9 +275,7 @@ static int sweep_k(hml_ctx* c, char method, bool record) {
         if (c->params_spread) hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_params_spread<KK>), dim3(HML_PARAMS_TREE_WGS), dim3(1024), 0, s, c->d_mdl, c->d_partial);
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_params<KK>), dim3(1), dim3(1024), 0, s, c->d_mdl, c->d_partial, 0);
     }
-    if (record && c->rec_levels) { if (int r = launch_levels_record(c, s, hint)) return r; }   // (after the update: hml_k_levels.h)
-    if (record && c->rec_breaks) { if (int r = launch_breaks_record(c, s, hint)) return r; }
-    if (record && c->rec_bands) { if (int r = launch_bands_record(c, s, hint)) return r; }
+    if (record) { if (int r = launch_recorders(c, s, hint)) return r; }   // (after the update: hml_k_levels.h)
     KLAUNCH_CHECK();
     return 0;
 }
@@ -294,9 +292,7 @@ static int iterate_many_k(hml_ctx* const* cs, int n, uint64_t first, uint64_t it
     const bool records = thinning > 0 && thinning <= iterations;
     unsigned long long rec_mask = 0ull;
     for (int i = 0; i < n; ++i) {
-        if (records && cs[i]->rec_levels) { if (int r = ensure_level_buffers(cs[i])) return r; }
-        if (records && cs[i]->rec_breaks) { if (int r = ensure_break_buffers(cs[i])) return r; }
-        if (records && cs[i]->rec_bands) { if (int r = ensure_band_buffers(cs[i])) return r; }
+        if (records) { if (int r = ensure_recorders(cs[i])) return r; }
         if (records && cs[i]->rec_marginals) {
             if (cs[i]->pooled) return set_err(HML_ERR_ARG, "the marginals of a context are pooled (common labels, several chains): further sweeps cannot be recorded into them");
             if (int r = ensure_marginal_buffers(cs[i])) return r;
@@ -454,21 +450,9 @@ static int iterate_many_k(hml_ctx* const* cs, int n, uint64_t first, uint64_t it
                 if (record && (rec_mask >> k0)) hipLaunchKernelGGL(hml_m_record, dim3(gB, nyk), dim3(256), 0, s, ma, rec_mask >> k0);
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_m_params<KK>), dim3(HML_PARAMS_TREE_WGS, nyk), dim3(1024), 0, s, ma);
             }
-            // the chains that record their emission levels: one launch each behind the batch's parameter kernels (hml_k_levels.h)
-            if (record) for (int k = g0; k < g0 + gn; ++k) if (cs[k]->rec_levels) {
-                hml_ctx* c = cs[k];
-                hipLaunchKernelGGL(hml_k_levels_record, dim3(gB), dim3(256), 0, s, c->d_q, c->d_starts, c->d_mdl, c->d_levels, c->d_lev_boundary);
-            }
-            // ... and those that count their breakpoints (hml_k_breaks.h)
-            if (record) for (int k = g0; k < g0 + gn; ++k) if (cs[k]->rec_breaks) {
-                hml_ctx* c = cs[k];
-                hipLaunchKernelGGL(hml_k_breaks_record, dim3(gB), dim3(256), 0, s, c->d_q, c->d_starts, c->d_mdl, c->d_breaks, c->d_brk_boundary);
-            }
-            // ... and those that count their level bands (hml_k_bands.h; behind the parameter kernels, like the levels)
-            if (record) for (int k = g0; k < g0 + gn; ++k) if (cs[k]->rec_bands) {
-                hml_ctx* c = cs[k];
-                hipLaunchKernelGGL(hml_k_bands_record, dim3(gB), dim3(256), 0, s, c->d_q, c->d_starts, c->d_mdl, band_edges_of(c), c->d_bands, c->d_band_boundary);
-            }
+            // the chains' own recordings (levels, breaks, bands): one launch each behind the batch's parameter kernels
+            if (record) for (int kind = 0; kind < HML_REC_KINDS; ++kind)
+                for (int k = g0; k < g0 + gn; ++k) if (cs[k]->rec[kind].on) launch_record_kernel(cs[k], kind, s, dim3(gB));
         }
         KLAUNCH_CHECK();
         if (record) {

@@ -294,6 +294,31 @@ def test_levels_merge(hml):
     assert e.value.code == 1
 
 
+@pytest.mark.parametrize("name", list(lu.EXACT_CASES))
+def test_levels_double_sums_exactly(hml, name):
+    """levels_rle() and levels_on_segments() against the numpy restatement of the device's additions (tests/levels_util.py:
+    exact_cells, exact_merge, exact_scan, exact_on_segments), BIT FOR BIT: the order of the scan's additions is part of what
+    the library computes.  The cases put M into every regime of the scan's tree (lu.EXACT_CASES; the range is asserted)."""
+    kind, T, K, seed, chains, _ = lu.EXACT_CASES[name]
+    x = lu.exact_case_trace(name)
+    sweeps = [checker_sweeps(checker(K, seed, x, chain=ch), scheme) for ch, scheme in chains]
+    cells = lu.exact_case_cells(name, sweeps)
+    pos, want = lu.exact_rle(cells)
+    gs = [_levels_of(hml, x, K, seed, scheme, chain=ch)[0] for ch, scheme in chains]
+    for other in gs[1:]:
+        gs[0].merge_levels(other)
+    seg, n, s1, s2 = gs[0].levels_rle()
+    assert n == sum(len(s) for s in sweeps)
+    assert np.array_equal(seg.astype(np.int64), np.diff(np.append(pos, T))), name
+    cuts = lu.exact_case_cuts(name, cells)
+    o1, o2 = gs[0].levels_on_segments(cuts)
+    want_on = lu.exact_on_segments(cells, cuts)
+    got = [(s1[0], want[0]), (s2[0], want[1]), (o1[0], want_on[0]), (o2[0], want_on[1])]
+    differing = [int(np.sum(bits64(a) != bits64(b))) for a, b in got]
+    print("%s: M=%d, %d cuts; entries with other bits: sum %d, sum_sq %d, on segments %d / %d" % ((name, len(seg), len(cuts)) + tuple(differing)))
+    assert differing == [0, 0, 0, 0], (name, differing)
+
+
 def test_levels_are_label_invariant(hml):
     """the point of the feature: the same sweep with the states renamed - parameters, rows and columns of A and pi permuted
     alike, static blocks, one sweep with probes - against the checker fed the same permuted parameters"""

@@ -39,9 +39,9 @@ def test_levels_mean_sd_formula():
     assert np.all(np.isnan(mean)) and np.all(np.isnan(sd))
 
 
-def _chain(K, seed, x, mode, D=1, P=None):
+def _chain(K, seed, x, mode, D=1, P=None, chain=0):
     rng, math, red = (ol.RNG_CTR, ol.MATH_DEV, ol.REDUCE_DEV) if mode == "device" else (ol.RNG_MT, ol.MATH_LIBM, ol.REDUCE_REF)
-    o = ol.OracleChain(K=K, seed=seed, rng=rng, math=math, reduce=red)
+    o = ol.OracleChain(K=K, seed=seed, chain=chain, rng=rng, math=math, reduce=red)
     if D > 1:
         o.set_dimensions(D, P)
     o.load(x)
@@ -116,3 +116,38 @@ def test_helper_levels_by_hand():
     assert np.array_equal(S2[0], [1 + 16, 1 + 16, 1 + 16, 1 + 0.25, 4 + 0.25, 4 + 0.25])
     assert N == 2 and list(np.flatnonzero(boundary)) == [0, 3, 4]
     assert np.array_equal(lu.param_of_state(4, 2, 2), [[0, 0], [1, 0], [0, 1], [1, 1]])
+
+
+@pytest.mark.parametrize("M", [1, 3, 1023, 1024, 1025, 3038, (1 << 20) + 777])
+def test_exact_scan_is_a_prefix_sum(M):
+    """the restated tree on integers, where every order of additions gives the same sums, and on floats within rounding"""
+    rng = np.random.default_rng(M)
+    k = rng.integers(-9, 10, M).astype(np.float64)
+    assert np.array_equal(lu.exact_scan(k), np.cumsum(k))
+    x = rng.standard_normal(M)
+    assert np.max(np.abs(lu.exact_scan(x) - np.cumsum(x))) <= 2.0 ** -52 * M * np.sum(np.abs(x))
+
+
+@pytest.mark.parametrize("name", list(lu.EXACT_CASES))
+def test_exact_cases_land_in_their_ranges(name):
+    """the chains of test_levels_double_sums_exactly (tests/test_gpu_levels.py) on the checker: M lies in the regime of the
+    scan's tree that the case is there for (asserted by exact_case_cells), and the restated read-outs agree with plain dense
+    prefix sums within the levels' bounds"""
+    kind, T, K, seed, chains, _ = lu.EXACT_CASES[name]
+    x = lu.exact_case_trace(name)
+    sweeps = [step_checker(_chain(K, seed, x, "device", chain=ch), scheme) for ch, scheme in chains]
+    cells = lu.exact_case_cells(name, sweeps)
+    pos, v = lu.exact_rle(cells)
+    everything = [s for per_chain in sweeps for s in per_chain]
+    S1, S2, boundary, N = lu.accumulate(everything, T)
+    assert np.array_equal(np.flatnonzero(boundary), pos)
+    E1, E2 = lu.bounds(pos.size, N, lu.max_abs_mean(everything))
+    assert np.max(np.abs(v[0] - S1[0][pos])) <= E1 and np.max(np.abs(v[1] - S2[0][pos])) <= E2
+    cuts = lu.exact_case_cuts(name, cells)
+    assert cuts.size >= 8 and np.all(np.diff(cuts.astype(np.int64)) > 0)
+    out = lu.exact_on_segments(cells, cuts)
+    edges = np.concatenate(([0], cuts.astype(np.int64), [T]))
+    for r, S in enumerate((S1[0], S2[0])):
+        F = np.concatenate(([0.0], np.cumsum(S)))
+        # (every term of a segment's sum carries a segment-sum error of at most E; T terms at most)
+        assert np.max(np.abs(out[r] - (F[edges[1:]] - F[edges[:-1]]))) <= 4.0 * T * (E1, E2)[r] + 2.0 ** -50 * np.max(np.abs(F))
