@@ -1,5 +1,6 @@
-// Shared by the two kinds of translation unit of libhammlet_hip.so's chain code (hammlet_amd/build.py):
+// Shared by the three kinds of translation unit of libhammlet_hip.so's chain code (hammlet_amd/build.py):
 //   hml_capi.hip  - the C ABI (include/hml.h) and everything that does not depend on the number of states K: one object;
+//   hml_readout.hip - the C ABI's read-outs of what the recorded sweeps accumulated (marginals, levels, breaks, bands): one object;
 //   hml_sweep.hip - the sweep for K states: the kernels templated on K and the host code that launches them, behind a table
 //                   of function pointers (hml_ktab): fifteen objects, -DHML_TU_K=2 ... 16, compiled in parallel.
 // Every object carries its own code object, and the HIP runtime loads a code object when the first kernel of it is launched:
@@ -224,6 +225,10 @@ static inline void log_sweep(hml_ctx* c, char method, bool record) {
 }
 static inline int settle_if_limited(hml_ctx* c) { return cap_limited(c) ? hml_settle(c) : 0; }
 
+// how an entry point of the C ABI begins: a context with a model (with observations), its device current, no halted sweep left behind
+#define NEED_MODEL() if (!c || !c->model_set) return set_err(HML_ERR_ARG, "model not set"); if (int r_ = ctx_bind(c)) return r_; if (int r_ = settle_if_limited(c)) return r_
+#define NEED_LOADED() if (!c || !c->loaded) return set_err(HML_ERR_ARG, "no observations loaded"); if (int r_ = ctx_bind(c)) return r_; if (int r_ = settle_if_limited(c)) return r_
+
 static void refresh_hint(hml_ctx* c) {
     const uint32_t b = *(volatile uint32_t*)c->h_B;
     if (b) c->B_hint = b + b / 4 + 1024;
@@ -300,6 +305,9 @@ static hml_band_edges band_edges_of(const hml_ctx* c) {
     ed.n = c->n_band_edges;
     for (int j = 0; j < c->n_band_edges; ++j) ed.e[j] = c->band_edges[j];
     return ed;
+}
+static bool same_band_edges(const hml_ctx* a, int n, const float* edges) {
+    return a->n_band_edges == n && memcmp(a->band_edges, edges, (size_t)n * sizeof(float)) == 0;   // (bit for bit)
 }
 
 // the record kernel of one recording, on stream `s`

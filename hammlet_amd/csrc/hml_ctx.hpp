@@ -216,7 +216,8 @@ int hml_ctx_bind(hml_ctx* c);                         // hipSetDevice(ctx's devi
 int hml_ctx_fetch_model(hml_ctx* c, hml_model* out);  // synchronising copy of the device-resident model
 int hml_ctx_ensure_marginal_buffers(hml_ctx* c);
 int hml_settle(hml_ctx* c);                           // stream idle, no halted sweep left behind (block capacity, above)
-// marginal segments on the device: starts d_seg[M] and count differences at the starts d_g[M * K] (caller frees both)
-int hml_ctx_gather_marginal_segments(hml_ctx* c, uint64_t* M, uint32_t** d_seg, int32_t** d_g);
+// hml_readout.hip
+// marginal segments on the device: starts d_seg[M] and count differences at the starts d_g[M * K]
+int hml_ctx_gather_marginal_segments(hml_ctx* c, uint64_t* M, DevBuf& d_seg, DevBuf& d_g);
 
 #endif

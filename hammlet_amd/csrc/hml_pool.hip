@@ -282,7 +282,7 @@ int hml_pool_marginals(hml_pool* p, hml_ctx* c, int32_t* perm_out) {
     uint64_t M = 0, M_max = 0;
     DevBuf d_seg, d_g;
     if (!rc) rc = hml_ctx_ensure_marginal_buffers(c);
-    if (!rc) { uint32_t* sg = nullptr; int32_t* gg = nullptr; rc = hml_ctx_gather_marginal_segments(c, &M, &sg, &gg); d_seg.p = sg; d_g.p = gg; }
+    if (!rc) rc = hml_ctx_gather_marginal_segments(c, &M, d_seg, d_g);
     if (int r = handshake(p->comm, p->stream, p->d_handshake, rc, c, M, &M_max, p->form)) return r;
     const int K = c->K;
     const uint64_t n = payload_count(c);

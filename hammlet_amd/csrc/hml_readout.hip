@@ -1,0 +1,543 @@
+// libhammlet_hip.so - the read-outs of the C ABI (include/hml.h): what the recorded sweeps accumulated per position - state
+// marginals, emission levels, breakpoints, level bands - brought into the forms the callers ask for, and the merges of one
+// chain's recording into another's.  Nothing here runs inside a sweep; hml_capi.hip holds the chain itself.
+#include "hml_capi_shared.hpp"
+
+// The positions whose bit is set in a boundary bitmap over T positions (n_spans spans of HML_SPAN), ascending, on stream `s`:
+// d_seg[M + 1] is allocated here, position 0 is always the first entry.  Counts per span, their prefix sums on the host, scatter.
+static int compact_boundaries(hipStream_t s, const uint32_t* d_boundary, uint32_t T, uint32_t n_spans, uint64_t* M_out, DevBuf& d_seg) {
+    DevBuf d_cnt, d_off;
+    HIPCHK(hipMalloc(&d_cnt.p, n_spans * sizeof(uint32_t)));
+    HIPCHK(hipMalloc(&d_off.p, n_spans * sizeof(uint32_t)));
+    hipLaunchKernelGGL(hml_k_marg_count, dim3((n_spans + 3) / 4), dim3(256), 0, s, d_boundary, T, d_cnt.as<uint32_t>());
+    std::vector<uint32_t> h_cnt(n_spans), h_off(n_spans);
+    HIPCHK(hipMemcpyAsync(h_cnt.data(), d_cnt.p, n_spans * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    uint64_t M = 0;
+    for (uint32_t i = 0; i < n_spans; ++i) { h_off[i] = (uint32_t)M; M += h_cnt[i]; }
+    HIPCHK(hipMemcpyAsync(d_off.p, h_off.data(), n_spans * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMalloc(&d_seg.p, (M + 1) * sizeof(uint32_t)));
+    hipLaunchKernelGGL(hml_k_marg_scatter, dim3((n_spans + 3) / 4), dim3(256), 0, s, d_boundary, T, d_off.as<uint32_t>(), d_seg.as<uint32_t>());
+    KLAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(s));   // (d_cnt and d_off go with this frame)
+    *M_out = M;
+    return 0;
+}
+
+// The fixed-shape scan of hml_k_scan.h over `rows` rows of M entries on stream `s`: inclusive into d_out[rows][M] (d_out may
+// be d_in), or exclusive into d_out[rows][M + 1] with the totals last.
+template <typename In, typename Acc, bool Exclusive>
+static int scan_rows(hipStream_t s, const In* d_in, uint64_t M, int rows, Acc* d_out) {
+    DevBuf d_cs;
+    const uint32_t n_chunks = (uint32_t)((M + HML_SCAN_CHUNK - 1) / HML_SCAN_CHUNK);
+    HIPCHK(hipMalloc(&d_cs.p, ((uint64_t)n_chunks * rows + 1) * sizeof(Acc)));
+    const dim3 grid((unsigned)grid_for(n_chunks, 1, 1, 4096), (unsigned)rows);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_scan_partial<In, Acc>), grid, dim3(256), 0, s, d_in, (uint32_t)M, n_chunks, d_cs.as<Acc>());
+    hipLaunchKernelGGL(hml_k_scan_chunks<Acc>, dim3(rows), dim3(1024), 0, s, d_cs.as<Acc>(), n_chunks);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_scan_final<In, Acc, Exclusive>), grid, dim3(256), 0, s, d_in, (uint32_t)M, n_chunks, (const Acc*)d_cs.as<Acc>(), d_out);
+    KLAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(s));   // (d_cs goes with this frame)
+    return 0;
+}
+
+static int model_fault(const hml_model& m) {   // the device error a sweep left in the model, if any
+    if (!m.err_code) return 0;
+    char buf[256];
+    return set_err(HML_ERR_MODEL, deverr_text(m.err_code, m.err_value, buf, sizeof buf));
+}
+
+// M ascending starts (the first is position 0) and T into the M lengths
+static void lengths_of(const uint32_t* start, uint64_t M, uint32_t T, uint64_t* len) {
+    for (uint64_t i = 0; i < M; ++i) len[i] = (uint64_t)((i + 1 < M ? start[i + 1] : T) - start[i]);
+}
+
+// ---------------------------------------------------------------------------------------- count tables
+// What the state marginals and the level bands both are: int32 difference rows [ncol][T + 1], touched only where a run starts,
+// and the bitmap of those positions.  Read out as run-length segments (table_segments, table_rle), as a dense table
+// (table_dense) and as runs of a per-segment key (table_runs).
+struct hml_count_table {
+    const int32_t* d_diff;
+    const uint32_t* d_boundary;
+    int ncol;
+};
+static hml_count_table marginal_table(const hml_ctx* c) { return {c->d_diff, c->d_boundary, c->K}; }
+static hml_count_table band_table(const hml_ctx* c) {
+    const hml_recorder& rec = c->rec[HML_REC_BANDS];
+    return {rec.acc<int32_t>(), rec.d_boundary, recorder_rows(c, HML_REC_BANDS)};
+}
+
+// the table's segments on the device: starts d_seg[M] and the count differences at the starts d_g[M][ncol] (segment-major,
+// hml_k_marg_gather)
+static int table_segments(hml_ctx* c, const hml_count_table& tab, uint64_t* M_out, DevBuf& d_seg, DevBuf& d_g) {
+    const uint32_t T = (uint32_t)c->T;
+    uint64_t M = 0;
+    if (int r = compact_boundaries(c->stream, tab.d_boundary, T, c->n_spans, &M, d_seg)) return r;
+    HIPCHK(hipMalloc(&d_g.p, std::max<uint64_t>(M, 1) * tab.ncol * sizeof(int32_t)));
+    hipLaunchKernelGGL(hml_k_marg_gather, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, c->stream, tab.d_diff, T, tab.ncol, d_seg.as<uint32_t>(), (uint32_t)M, d_g.as<int32_t>());
+    KLAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *M_out = M;
+    return 0;
+}
+
+int hml_ctx_gather_marginal_segments(hml_ctx* c, uint64_t* M, DevBuf& d_seg, DevBuf& d_g) { return table_segments(c, marginal_table(c), M, d_seg, d_g); }
+
+// the segments on the host: their lengths and, in counts[M][ncol_out], the counts of the first ncol_out columns - the running
+// sums of the differences at all boundaries up to the segment
+static int table_rle(hml_ctx* c, const hml_count_table& tab, uint64_t M, const DevBuf& d_seg, const DevBuf& d_g, int ncol_out, uint64_t* seg_len, int32_t* counts) {
+    const int ncol = tab.ncol;
+    std::vector<uint32_t> h_seg(M);
+    std::vector<int32_t> h_g(M * ncol);
+    HIPCHK(hipMemcpyAsync(h_seg.data(), d_seg.p, M * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(h_g.data(), d_g.p, M * ncol * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    lengths_of(h_seg.data(), M, (uint32_t)c->T, seg_len);
+    if (!counts) return 0;
+    std::vector<int32_t> cur(ncol_out, 0);
+    for (uint64_t i = 0; i < M; ++i)
+        for (int s = 0; s < ncol_out; ++s) counts[i * ncol_out + s] = cur[s] += h_g[i * ncol + s];
+    return 0;
+}
+
+// the dense table out[ncol][T] on the device, enqueued on the context's stream: row j holds the prefix sums of difference row
+// d_perm[j] (row j without a permutation).  d_cs: the scan's work array, the caller's until the stream is idle.
+static int table_dense(hml_ctx* c, const hml_count_table& tab, const int32_t* d_perm, int32_t* out, DevBuf& d_cs) {
+    const uint32_t T = (uint32_t)c->T;
+    const uint32_t n_chunks = c->n_spans;
+    HIPCHK(hipMalloc(&d_cs.p, (uint64_t)tab.ncol * n_chunks * sizeof(int32_t)));
+    hipLaunchKernelGGL(hml_k_dense_partial, dim3(n_chunks, tab.ncol), dim3(256), 0, c->stream, tab.d_diff, T, tab.ncol, d_cs.as<int32_t>(), n_chunks);
+    hipLaunchKernelGGL(hml_k_scan_chunks<int32_t>, dim3(tab.ncol), dim3(1024), 0, c->stream, d_cs.as<int32_t>(), n_chunks);
+    hipLaunchKernelGGL(hml_k_dense_final, dim3(n_chunks, tab.ncol), dim3(256), 0, c->stream, tab.d_diff, T, tab.ncol, d_cs.as<int32_t>(), n_chunks, d_perm, out);
+    return 0;
+}
+
+// A 16-bit key per segment, adjacent segments with the same key merged into runs: *n_runs and, if run_len is given, the runs'
+// lengths and keys.  pick(d_g, M, d_cs, n_chunks, d_key) launches the kernel that writes the keys from the differences d_g[M][ncol]
+// and the exclusive sums d_cs[ncol][n_chunks] of their chunks of 256 segments (hml_k_segment.h).
+template <class Pick>
+static int table_runs(hml_ctx* c, const hml_count_table& tab, Pick pick, uint64_t* n_runs, uint64_t* run_len, std::vector<int16_t>& run_key) {
+    const int ncol = tab.ncol;
+    uint64_t M = 0;
+    DevBuf b_seg, b_g, b_cs, b_rc, b_key;
+    if (int r = table_segments(c, tab, &M, b_seg, b_g)) return r;
+    const uint32_t n_chunks = (uint32_t)((M + 255) / 256);
+    HIPCHK(hipMalloc(&b_cs.p, (uint64_t)ncol * n_chunks * sizeof(int32_t)));
+    HIPCHK(hipMalloc(&b_rc.p, ((uint64_t)n_chunks + 1) * sizeof(int32_t)));
+    HIPCHK(hipMalloc(&b_key.p, M * sizeof(int16_t)));
+    int32_t *const d_cs = b_cs.as<int32_t>(), *const d_rc = b_rc.as<int32_t>();
+    int16_t* const d_key = b_key.as<int16_t>();
+    HIPCHK(hipMemsetAsync(d_rc + n_chunks, 0, sizeof(int32_t), c->stream));
+    hipLaunchKernelGGL(hml_k_seg_partial, dim3(n_chunks), dim3(256), 0, c->stream, b_g.as<int32_t>(), (uint32_t)M, ncol, d_cs, n_chunks);
+    hipLaunchKernelGGL(hml_k_scan_chunks<int32_t>, dim3(ncol), dim3(1024), 0, c->stream, d_cs, n_chunks);
+    pick(b_g.as<int32_t>(), (uint32_t)M, d_cs, n_chunks, d_key);
+    hipLaunchKernelGGL(hml_k_seg_run_count, dim3(n_chunks), dim3(256), 0, c->stream, d_key, (uint32_t)M, d_rc);
+    hipLaunchKernelGGL(hml_k_scan_chunks<int32_t>, dim3(1), dim3(1024), 0, c->stream, d_rc, n_chunks + 1u);   // d_rc[n_chunks] = total
+    KLAUNCH_CHECK();
+    int32_t R = 0;
+    HIPCHK(hipMemcpyAsync(&R, d_rc + n_chunks, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *n_runs = (uint64_t)R;
+    if (!run_len) return 0;
+    DevBuf b_rs, b_rq;
+    HIPCHK(hipMalloc(&b_rs.p, (uint64_t)R * sizeof(uint32_t)));
+    HIPCHK(hipMalloc(&b_rq.p, (uint64_t)R * sizeof(int16_t)));
+    hipLaunchKernelGGL(hml_k_seg_run_scatter, dim3(n_chunks), dim3(256), 0, c->stream, d_key, b_seg.as<uint32_t>(), (uint32_t)M, d_rc, b_rs.as<uint32_t>(), b_rq.as<int16_t>());
+    KLAUNCH_CHECK();
+    std::vector<uint32_t> h_rs(R);
+    run_key.resize(R);
+    HIPCHK(hipMemcpyAsync(h_rs.data(), b_rs.p, (uint64_t)R * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(run_key.data(), b_rq.p, (uint64_t)R * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    lengths_of(h_rs.data(), (uint64_t)R, (uint32_t)c->T, run_len);
+    return 0;
+}
+
+extern "C" {
+
+// ---------------------------------------------------------------------------------------- state marginals
+int hml_marginals_rle(hml_ctx* c, uint64_t* n_segments, int* n_columns, uint64_t* seg_len, int32_t* counts) {
+    NEED_MODEL();
+    hml_model m; if (int r = fetch_model(c, &m)) return r;
+    if (int r = model_fault(m)) return r;
+    const int ncol = m.max_state_recorded + 1;
+    if (!c->d_diff || m.n_recorded == 0) {   // nothing recorded: one segment, no count columns
+        *n_segments = 1; *n_columns = 0;
+        if (seg_len) seg_len[0] = (uint32_t)c->T;
+        return 0;
+    }
+    uint64_t M = 0;
+    DevBuf b_seg, b_g;
+    if (int r = table_segments(c, marginal_table(c), &M, b_seg, b_g)) return r;
+    *n_segments = M; *n_columns = ncol;
+    if (!seg_len) return 0;
+    return table_rle(c, marginal_table(c), M, b_seg, b_g, ncol, seg_len, counts);
+}
+
+int hml_max_segmentation(hml_ctx* c, uint64_t* n_runs, uint64_t* run_len, int32_t* run_state) {
+    NEED_MODEL();
+    if (!n_runs) return set_err(HML_ERR_ARG, "null argument");
+    hml_model m; if (int r = fetch_model(c, &m)) return r;
+    if (int r = model_fault(m)) return r;
+    const int K = c->K;
+    if (!c->d_diff || m.n_recorded == 0) {   // nothing recorded: every count is zero, the arg-max is state 0
+        *n_runs = 1;
+        if (run_len) run_len[0] = (uint32_t)c->T;
+        if (run_state) run_state[0] = 0;
+        return 0;
+    }
+    std::vector<int16_t> state;
+    auto argmax = [&](const int32_t* d_g, uint32_t M, const int32_t* d_cs, uint32_t n_chunks, int16_t* d_st) {
+        if (K <= HML_MAX_K) hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_seg_argmax<HML_MAX_K>), dim3(n_chunks), dim3(256), 0, c->stream, d_g, M, K, d_cs, n_chunks, d_st);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_seg_argmax<HML_CAP_K>), dim3(n_chunks), dim3(256), 0, c->stream, d_g, M, K, d_cs, n_chunks, d_st);
+    };
+    if (int r = table_runs(c, marginal_table(c), argmax, n_runs, run_len, state)) return r;
+    if (run_len && run_state) std::copy(state.begin(), state.end(), run_state);
+    return 0;
+}
+
+int hml_marginals_dense_device(hml_ctx* c, void* out_dev, const int32_t* perm) {
+    NEED_MODEL();
+    const uint32_t T = (uint32_t)c->T;
+    const int K = c->K;
+    int32_t* out = (int32_t*)out_dev;
+    if (!c->d_diff) {
+        HIPCHK(hipMemsetAsync(out, 0, (uint64_t)(K + 1) * T * sizeof(int32_t), c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return 0;
+    }
+    DevBuf b_cs, b_perm;
+    if (perm) {
+        uint64_t seen = 0u;
+        for (int k = 0; k < K; ++k) {
+            if (perm[k] < 0 || perm[k] >= K || ((seen >> perm[k]) & 1u)) return set_err(HML_ERR_ARG, "perm is not a permutation of the K states");
+            seen |= (uint64_t)1 << perm[k];
+        }
+        HIPCHK(hipMalloc(&b_perm.p, K * sizeof(int32_t)));
+        HIPCHK(hipMemcpyAsync(b_perm.p, perm, K * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    }
+    if (int r = table_dense(c, marginal_table(c), b_perm.as<int32_t>(), out, b_cs)) return r;
+    hipLaunchKernelGGL(hml_k_dense_boundary, dim3(grid_for(T, 256, 1, 65536)), dim3(256), 0, c->stream, c->d_boundary, T,
+                       out + (uint64_t)K * T);
+    KLAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------- emission levels (hml_k_levels.h)
+
+// a recording's read-out may begin: it was asked for, its buffers exist (asked for, but no sweep was recorded yet: the empty
+// answer of its kind, hml_ctx.hpp), the model is fetched and carries no device error
+static int recorder_ready(hml_ctx* c, int kind, hml_model* m) {
+    if (!c->rec[kind].asked) return recorder_none(kind, "this");
+    if (int r = ensure_recorder_buffers(c, kind)) return r;
+    if (int r = fetch_model(c, m)) return r;
+    return model_fault(*m);
+}
+
+// hml_levels_merge / hml_breaks_merge / hml_bands_merge: the source's cells at the source's boundaries into the destination,
+// on the destination's stream
+static int recorder_merge(hml_ctx* dst, hml_ctx* src, int kind) {
+    const hml_recorder_kind& rk = hml_recorder_kinds[kind];
+    const bool per_dimension = kind != HML_REC_BREAKS;
+    if (!dst || !src || !dst->model_set || !src->model_set) return set_err(HML_ERR_ARG, "model not set");
+    if (dst == src) return set_err(HML_ERR_ARG, "a context cannot be merged into itself");
+    if (dst->device != src->device)
+        return set_err(HML_ERR_ARG, std::string("the ") + rk.noun + " of chains on different GPUs are not merged yet: run the chains of one " + rk.file + " file on one GPU");
+    if (dst->T != src->T || (per_dimension && dst->D != src->D))
+        return set_err(HML_ERR_ARG, std::string(rk.noun) + " can only be merged between chains over the same positions" + (per_dimension ? " and dimensions" : ""));
+    if (!src->rec[kind].asked) return recorder_none(kind, "the source");
+    if (kind == HML_REC_BANDS && !same_band_edges(dst, src->n_band_edges, src->band_edges)) {
+        // a destination that was never asked takes the source's edges; any other difference is refused
+        if (dst->rec[kind].asked || dst->rec[kind].d_acc) return set_err(HML_ERR_ARG, "level bands can only be merged between chains with the same edges, bit for bit");
+        dst->n_band_edges = src->n_band_edges;
+        memcpy(dst->band_edges, src->band_edges, sizeof dst->band_edges);
+    }
+    if (int r = ctx_bind(dst)) return r;
+    if (int r = hml_settle(src)) return r;   // (both streams idle: the merge reads the source's accumulators on the destination's stream)
+    if (int r = hml_settle(dst)) return r;
+    if (int r = ensure_recorder_buffers(src, kind)) return r;
+    if (int r = ensure_recorder_buffers(dst, kind)) return r;
+    dst->rec[kind].asked = true;
+    const hml_recorder &rs = src->rec[kind], &rd = dst->rec[kind];
+    const uint32_t T = (uint32_t)src->T;
+    const int rows = recorder_rows(src, kind);
+    uint64_t M = 0;
+    DevBuf b_seg;
+    if (int r = compact_boundaries(dst->stream, rs.d_boundary, T, src->n_spans, &M, b_seg)) return r;
+    const uint32_t* d_pos = b_seg.as<uint32_t>();
+    if (kind == HML_REC_BREAKS) { ++d_pos; --M; }   // (position 0 is never a breakpoint; M = 0 still adds the source's count of recorded sweeps)
+    const dim3 grid(grid_for(M, 256, 1, 16384));
+    unsigned long long *const src_n = recorder_counter(src, kind), *const dst_n = recorder_counter(dst, kind);
+    if (kind == HML_REC_LEVELS)
+        hipLaunchKernelGGL(hml_k_rec_merge<double>, grid, dim3(256), 0, dst->stream, rs.acc<double>(), d_pos, (uint32_t)M, T, rows, src_n, rd.acc<double>(), rd.d_boundary, dst_n);
+    else if (kind == HML_REC_BREAKS)
+        hipLaunchKernelGGL(hml_k_rec_merge<uint32_t>, grid, dim3(256), 0, dst->stream, rs.acc<uint32_t>(), d_pos, (uint32_t)M, T, rows, src_n, rd.acc<uint32_t>(), rd.d_boundary, dst_n);
+    else
+        hipLaunchKernelGGL(hml_k_rec_merge<int32_t>, grid, dim3(256), 0, dst->stream, rs.acc<int32_t>(), d_pos, (uint32_t)M, T, rows, src_n, rd.acc<int32_t>(), rd.d_boundary, dst_n);
+    KLAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(dst->stream));
+    return 0;
+}
+
+// the levels' segments on the device: starts d_seg[M] and, per row, the inclusive sums over the segments d_sum[2 D][M]
+static int gather_level_segments(hml_ctx* c, uint64_t* M_out, DevBuf& d_seg, DevBuf& d_sum) {
+    const uint32_t T = (uint32_t)c->T;
+    const int rows = 2 * c->D;
+    const hml_recorder& rec = c->rec[HML_REC_LEVELS];
+    uint64_t M = 0;
+    if (int r = compact_boundaries(c->stream, rec.d_boundary, T, c->n_spans, &M, d_seg)) return r;
+    HIPCHK(hipMalloc(&d_sum.p, M * rows * sizeof(double)));
+    hipLaunchKernelGGL(hml_k_rec_gather<double>, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, c->stream, rec.acc<double>(), T, rows, d_seg.as<uint32_t>(), (uint32_t)M, d_sum.as<double>());
+    if (int r = scan_rows<double, double, false>(c->stream, d_sum.as<double>(), M, rows, d_sum.as<double>())) return r;
+    *M_out = M;
+    return 0;
+}
+
+extern "C" {
+
+int hml_levels_rle(hml_ctx* c, uint64_t* n_segments, uint64_t* n_recorded, uint64_t* seg_len, double* sum, double* sum_sq) {
+    NEED_MODEL();
+    if (!n_segments) return set_err(HML_ERR_ARG, "null argument");
+    hml_model m; if (int r = recorder_ready(c, HML_REC_LEVELS, &m)) return r;
+    const uint32_t T = (uint32_t)c->T;
+    const int D = c->D;
+    uint64_t M = 0;
+    DevBuf b_seg, b_sum;
+    if (int r = gather_level_segments(c, &M, b_seg, b_sum)) return r;
+    *n_segments = M;
+    if (n_recorded) *n_recorded = m.n_levels_recorded;
+    if (!seg_len) return 0;
+    std::vector<uint32_t> h_seg(M);
+    std::vector<double> h_sum(M * 2 * D);
+    HIPCHK(hipMemcpyAsync(h_seg.data(), b_seg.p, M * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(h_sum.data(), b_sum.p, M * 2 * D * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    lengths_of(h_seg.data(), M, T, seg_len);
+    for (int d = 0; d < D; ++d) {
+        if (sum) memcpy(sum + (uint64_t)d * M, h_sum.data() + (uint64_t)(2 * d) * M, M * sizeof(double));
+        if (sum_sq) memcpy(sum_sq + (uint64_t)d * M, h_sum.data() + (uint64_t)(2 * d + 1) * M, M * sizeof(double));
+    }
+    return 0;
+}
+
+int hml_levels_dense_device(hml_ctx* c, void* out_dev) {
+    NEED_MODEL();
+    if (!out_dev) return set_err(HML_ERR_ARG, "null argument");
+    hml_model m; if (int r = recorder_ready(c, HML_REC_LEVELS, &m)) return r;
+    const uint32_t T = (uint32_t)c->T;
+    const int D = c->D;
+    uint64_t M = 0;
+    DevBuf b_seg, b_sum, b_ms;
+    if (int r = gather_level_segments(c, &M, b_seg, b_sum)) return r;
+    HIPCHK(hipMalloc(&b_ms.p, M * 2 * D * sizeof(float)));
+    hipLaunchKernelGGL(hml_k_levels_mean_sd, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, c->stream, b_sum.as<double>(), (uint32_t)M, D,
+                       m.n_levels_recorded, b_ms.as<float>());
+    hipLaunchKernelGGL(hml_k_levels_expand, dim3(grid_for(T, 256, 1, 65536)), dim3(256), 0, c->stream, b_ms.as<float>(), b_seg.as<uint32_t>(),
+                       (uint32_t)M, T, 2 * D, (float*)out_dev);
+    KLAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int hml_levels_merge(hml_ctx* dst, hml_ctx* src) { return recorder_merge(dst, src, HML_REC_LEVELS); }
+
+// ---------------------------------------------------------------------------------------- breakpoints (hml_k_breaks.h)
+}  // extern "C"
+
+// exclusive 64-bit prefix sums of M 32-bit values on `s`: d_pre[M + 1] (allocated here), d_pre[M] = the total
+static int breaks_scan(hipStream_t s, const uint32_t* d_v, uint64_t M, DevBuf& d_pre) {
+    HIPCHK(hipMalloc(&d_pre.p, (M + 1) * sizeof(unsigned long long)));
+    return scan_rows<uint32_t, unsigned long long, true>(s, d_v, M, 1, d_pre.as<unsigned long long>());
+}
+
+// the positions with a count, ascending, on the device: d_list[1 + M] - entry 0 is the position 0 that the compaction kernels
+// always emit (never a breakpoint), the M break positions follow
+static int compact_break_positions(hml_ctx* c, uint64_t* M_out, DevBuf& d_list) {
+    uint64_t n = 0;
+    if (int r = compact_boundaries(c->stream, c->rec[HML_REC_BREAKS].d_boundary, (uint32_t)c->T, c->n_spans, &n, d_list)) return r;
+    *M_out = n - 1;   // (position 0 always counts)
+    return 0;
+}
+
+// C[pos] for the M break positions of d_list into d_cnt[M] (allocated here with one spare entry)
+static int gather_break_counts(hml_ctx* c, const DevBuf& d_list, uint64_t M, DevBuf& d_cnt) {
+    HIPCHK(hipMalloc(&d_cnt.p, (M + 1) * sizeof(uint32_t)));
+    if (M) hipLaunchKernelGGL(hml_k_rec_gather<uint32_t>, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, c->stream, c->rec[HML_REC_BREAKS].acc<uint32_t>(), (uint32_t)c->T, 1,
+                              d_list.as<uint32_t>() + 1, (uint32_t)M, d_cnt.as<uint32_t>());
+    KLAUNCH_CHECK();
+    return 0;
+}
+
+// break positions d_list[1 + M] (see above), their counts d_cnt[M] and the exclusive sums of the counts d_pre[M + 1]
+static int gather_breaks(hml_ctx* c, uint64_t* M_out, DevBuf& d_list, DevBuf& d_cnt, DevBuf& d_pre) {
+    uint64_t M = 0;
+    if (int r = compact_break_positions(c, &M, d_list)) return r;
+    if (int r = gather_break_counts(c, d_list, M, d_cnt)) return r;
+    if (int r = breaks_scan(c->stream, d_cnt.as<uint32_t>(), M, d_pre)) return r;
+    *M_out = M;
+    return 0;
+}
+
+extern "C" {
+
+int hml_breaks_list(hml_ctx* c, uint64_t* n_breaks, uint64_t* n_recorded, uint32_t* pos, uint32_t* count) {
+    NEED_MODEL();
+    if (!n_breaks) return set_err(HML_ERR_ARG, "null argument");
+    hml_model m; if (int r = recorder_ready(c, HML_REC_BREAKS, &m)) return r;
+    uint64_t M = 0;
+    DevBuf b_list, b_cnt;
+    if (int r = compact_break_positions(c, &M, b_list)) return r;
+    *n_breaks = M;
+    if (n_recorded) *n_recorded = m.n_breaks_recorded;
+    if (!pos || M == 0) return 0;
+    HIPCHK(hipMemcpyAsync(pos, b_list.as<uint32_t>() + 1, M * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (count) {
+        if (int r = gather_break_counts(c, b_list, M, b_cnt)) return r;
+        HIPCHK(hipMemcpyAsync(count, b_cnt.p, M * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int hml_breaks_dense_device(hml_ctx* c, void* out_dev, uint32_t window) {
+    NEED_MODEL();
+    if (!out_dev) return set_err(HML_ERR_ARG, "null argument");
+    hml_model m; if (int r = recorder_ready(c, HML_REC_BREAKS, &m)) return r;
+    uint64_t M = 0;
+    DevBuf b_list, b_cnt, b_pre;
+    if (int r = gather_breaks(c, &M, b_list, b_cnt, b_pre)) return r;
+    const uint32_t T = (uint32_t)c->T;
+    hipLaunchKernelGGL(hml_k_breaks_dense, dim3(grid_for(T, 256, 1, 65536)), dim3(256), 0, c->stream, b_list.as<uint32_t>() + 1, b_pre.as<unsigned long long>(),
+                       (uint32_t)M, T, window, m.n_breaks_recorded, (float*)out_dev);
+    KLAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int hml_breaks_consensus(hml_ctx* c, uint32_t window, uint64_t min_count, uint64_t* n_selected, uint32_t* pos, uint64_t* mass, uint32_t* peak) {
+    NEED_MODEL();
+    if (!n_selected) return set_err(HML_ERR_ARG, "null argument");
+    hml_model m; if (int r = recorder_ready(c, HML_REC_BREAKS, &m)) return r;
+    uint64_t M = 0;
+    DevBuf b_list, b_cnt, b_pre, b_mass, b_sel, b_where, b_opos, b_omass, b_opeak;
+    if (int r = gather_breaks(c, &M, b_list, b_cnt, b_pre)) return r;
+    *n_selected = 0;
+    if (M == 0) return 0;
+    HIPCHK(hipMalloc(&b_mass.p, M * sizeof(unsigned long long)));
+    HIPCHK(hipMalloc(&b_sel.p, M * sizeof(uint32_t)));
+    const uint32_t* d_pos = b_list.as<uint32_t>() + 1;
+    hipLaunchKernelGGL(hml_k_breaks_select, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, c->stream, d_pos, b_cnt.as<uint32_t>(), b_pre.as<unsigned long long>(),
+                       (uint32_t)M, window, (unsigned long long)(min_count > 1 ? min_count : 1), b_mass.as<unsigned long long>(), b_sel.as<uint32_t>());
+    KLAUNCH_CHECK();
+    if (int r = breaks_scan(c->stream, b_sel.as<uint32_t>(), M, b_where)) return r;
+    unsigned long long S = 0;
+    HIPCHK(hipMemcpyAsync(&S, b_where.as<unsigned long long>() + M, sizeof S, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *n_selected = S;
+    if (!pos || S == 0) return 0;
+    HIPCHK(hipMalloc(&b_opos.p, S * sizeof(uint32_t)));
+    HIPCHK(hipMalloc(&b_omass.p, S * sizeof(unsigned long long)));
+    HIPCHK(hipMalloc(&b_opeak.p, S * sizeof(uint32_t)));
+    hipLaunchKernelGGL(hml_k_breaks_compact, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, c->stream, d_pos, b_cnt.as<uint32_t>(), b_mass.as<unsigned long long>(),
+                       b_sel.as<uint32_t>(), b_where.as<unsigned long long>(), (uint32_t)M, b_opos.as<uint32_t>(), b_omass.as<unsigned long long>(), b_opeak.as<uint32_t>());
+    KLAUNCH_CHECK();
+    HIPCHK(hipMemcpyAsync(pos, b_opos.p, S * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (mass) HIPCHK(hipMemcpyAsync(mass, b_omass.p, S * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (peak) HIPCHK(hipMemcpyAsync(peak, b_opeak.p, S * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int hml_breaks_merge(hml_ctx* dst, hml_ctx* src) { return recorder_merge(dst, src, HML_REC_BREAKS); }
+
+int hml_levels_on_segments(hml_ctx* c, uint64_t n_cuts, const uint32_t* cuts, double* sum, double* sum_sq) {
+    NEED_MODEL();
+    if (n_cuts && !cuts) return set_err(HML_ERR_ARG, "null argument");
+    const uint32_t T = (uint32_t)c->T;
+    if (n_cuts >= T) return set_err(HML_ERR_ARG, "more cuts than positions");
+    for (uint64_t i = 0; i < n_cuts; ++i) {
+        if (cuts[i] == 0 || cuts[i] >= T) return set_err(HML_ERR_ARG, "a cut must lie inside (0, T)");
+        if (i > 0 && cuts[i] <= cuts[i - 1]) return set_err(HML_ERR_ARG, "the cuts must be strictly ascending");
+    }
+    hml_model m; if (int r = recorder_ready(c, HML_REC_LEVELS, &m)) return r;
+    const int D = c->D, rows = 2 * D;
+    uint64_t M = 0;
+    DevBuf b_seg, b_val, b_w, b_cuts, b_out;
+    if (int r = gather_level_segments(c, &M, b_seg, b_val)) return r;
+    const uint64_t n_seg = n_cuts + 1;
+    HIPCHK(hipMalloc(&b_w.p, M * rows * sizeof(double)));
+    HIPCHK(hipMalloc(&b_cuts.p, (n_cuts + 1) * sizeof(uint32_t)));
+    HIPCHK(hipMalloc(&b_out.p, n_seg * rows * sizeof(double)));
+    if (n_cuts) HIPCHK(hipMemcpyAsync(b_cuts.p, cuts, n_cuts * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(hml_k_levels_weigh, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, c->stream, b_val.as<double>(), b_seg.as<uint32_t>(), (uint32_t)M, T, rows, b_w.as<double>());
+    // the fixed-shape scan of the levels' read-out, now over len_i * value_i
+    if (int r = scan_rows<double, double, false>(c->stream, b_w.as<double>(), M, rows, b_w.as<double>())) return r;
+    hipLaunchKernelGGL(hml_k_levels_on_segments, dim3(grid_for(n_seg, 256, 1, 16384)), dim3(256), 0, c->stream, b_val.as<double>(), b_w.as<double>(), b_seg.as<uint32_t>(),
+                       (uint32_t)M, T, rows, b_cuts.as<uint32_t>(), (uint32_t)n_cuts, b_out.as<double>());
+    KLAUNCH_CHECK();
+    std::vector<double> h_out(n_seg * rows);
+    HIPCHK(hipMemcpyAsync(h_out.data(), b_out.p, n_seg * rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int d = 0; d < D; ++d) {
+        if (sum) memcpy(sum + (uint64_t)d * n_seg, h_out.data() + (uint64_t)(2 * d) * n_seg, n_seg * sizeof(double));
+        if (sum_sq) memcpy(sum_sq + (uint64_t)d * n_seg, h_out.data() + (uint64_t)(2 * d + 1) * n_seg, n_seg * sizeof(double));
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------- level bands (hml_k_bands.h)
+int hml_bands_rle(hml_ctx* c, uint64_t* n_segments, int* n_columns, uint64_t* n_recorded, uint64_t* seg_len, int32_t* counts) {
+    NEED_MODEL();
+    if (!n_segments) return set_err(HML_ERR_ARG, "null argument");
+    hml_model m; if (int r = recorder_ready(c, HML_REC_BANDS, &m)) return r;
+    const hml_count_table tab = band_table(c);
+    uint64_t M = 0;
+    DevBuf b_seg, b_g;
+    if (int r = table_segments(c, tab, &M, b_seg, b_g)) return r;
+    *n_segments = M;
+    if (n_columns) *n_columns = tab.ncol;
+    if (n_recorded) *n_recorded = m.n_bands_recorded;
+    if (!seg_len) return 0;
+    return table_rle(c, tab, M, b_seg, b_g, tab.ncol, seg_len, counts);
+}
+
+int hml_bands_dense_device(hml_ctx* c, void* out_dev, int cumulative) {
+    NEED_MODEL();
+    if (!out_dev) return set_err(HML_ERR_ARG, "null argument");
+    hml_model m; if (int r = recorder_ready(c, HML_REC_BANDS, &m)) return r;
+    const uint32_t T = (uint32_t)c->T;
+    int32_t* out = (int32_t*)out_dev;
+    DevBuf b_cs;
+    if (int r = table_dense(c, band_table(c), nullptr, out, b_cs)) return r;
+    if (cumulative) hipLaunchKernelGGL(hml_k_bands_cumulate, dim3(grid_for(T, 256, 1, 65536)), dim3(256), 0, c->stream, out, T, c->D, c->n_band_edges + 1);
+    KLAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int hml_bands_call(hml_ctx* c, uint64_t rank, uint64_t* n_runs, uint64_t* run_len, int32_t* run_band) {
+    NEED_MODEL();
+    if (!n_runs) return set_err(HML_ERR_ARG, "null argument");
+    hml_model m; if (int r = recorder_ready(c, HML_REC_BANDS, &m)) return r;
+    if (rank > m.n_bands_recorded) return set_err(HML_ERR_ARG, "hml_bands_call: the rank must be 0 (the most probable band) or between 1 and the number of recorded sweeps");
+    const int D = c->D, nb = c->n_band_edges + 1;
+    std::vector<int16_t> keys;
+    auto pick = [&](const int32_t* d_g, uint32_t M, const int32_t* d_cs, uint32_t n_chunks, int16_t* d_key) {
+        hipLaunchKernelGGL(hml_k_bands_pick, dim3(n_chunks), dim3(256), 0, c->stream, d_g, M, D, nb, d_cs, n_chunks, (unsigned long long)rank, d_key);
+    };
+    if (int r = table_runs(c, band_table(c), pick, n_runs, run_len, keys)) return r;
+    if (!run_len || !run_band) return 0;
+    const uint64_t R = keys.size();
+    for (uint64_t r = 0; r < R; ++r) {
+        uint32_t key = (uint16_t)keys[r];   // (hml_k_bands_pick: the D calls as digits to the base of the bands per dimension)
+        for (int d = 0; d < D; ++d) { run_band[(uint64_t)d * R + r] = (int32_t)(key % (uint32_t)nb); key /= (uint32_t)nb; }
+    }
+    return 0;
+}
+
+int hml_bands_merge(hml_ctx* dst, hml_ctx* src) { return recorder_merge(dst, src, HML_REC_BANDS); }
+
+}  // extern "C"
+

@@ -29,8 +29,8 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_library_holds_the_sweep_of_every_number_of_states():
-    """hammlet_amd/build.py links sixteen objects: the C ABI and, per number of states 2 ... 16, the sweep behind its table of
-    function pointers (csrc/hml_capi.hip once, csrc/hml_sweep.hip with -DHML_TU_K=k) - one table per K must be there, and the objects of the
+    """hammlet_amd/build.py links the C ABI (csrc/hml_capi.hip and csrc/hml_readout.hip, once each) and, per number of states
+    2 ... 16, the sweep behind its table of function pointers (csrc/hml_sweep.hip with -DHML_TU_K=k) - one table per K must be there, and the objects of the
     build must be the ones the layout names (a stale single-object build would define the C ABI twice or not at all)."""
     from hammlet_amd import build
     build.build_library()
