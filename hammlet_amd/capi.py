@@ -89,6 +89,9 @@ SIGNATURES = {
     "hml_levels_dense_device": (C.c_int, [_P, _P]),
     "hml_levels_merge": (C.c_int, [_P, _P]),
     "hml_levels_on_segments": (C.c_int, [_P, C.c_uint64, _P, _P, _P]),
+    "hml_levels_agreement_rle": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _P, _P, _P, _P]),
+    "hml_levels_agreement_dense_device": (C.c_int, [_P, C.c_int, _P]),
+    "hml_levels_agreement_summary": (C.c_int, [_P, C.c_int, C.c_double, _P, _P, _P]),
     "hml_set_break_recording": (C.c_int, [_P, C.c_int]),
     "hml_breaks_list": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _P, _P]),
     "hml_breaks_dense_device": (C.c_int, [_P, _P, C.c_uint32]),
@@ -684,6 +687,73 @@ def iterate_many(chains, method, iterations, thinning=0):
     lib = load_library()
     arr = (_P * len(chains))(*[c.h for c in chains])
     _check(lib.hml_iterate_many(C.cast(arr, _P), len(chains), method.encode(), iterations, thinning))
+
+
+def _handles(chains):
+    return C.cast((_P * len(chains))(*[c.h for c in chains]), _P)
+
+
+def levels_agreement_rle(chains):
+    """(seg_len[U], n_recorded, within[D, U], between[D, U], rhat[D, U]): the Gelman-Rubin R-hat of the emission level over
+    the chains, per segment of the union of their level boundaries (hml_levels_agreement_rle); the chains are only read"""
+    lib = load_library()
+    arr = _handles(chains)
+    u, n = C.c_uint64(), C.c_uint64()
+    _check(lib.hml_levels_agreement_rle(arr, len(chains), C.byref(u), C.byref(n), None, None, None, None))
+    D = chains[0].D
+    seg = np.empty(u.value, np.uint64)
+    within = np.empty((D, u.value), np.float64)
+    between = np.empty((D, u.value), np.float64)
+    rhat = np.empty((D, u.value), np.float64)
+    _check(lib.hml_levels_agreement_rle(arr, len(chains), C.byref(u), C.byref(n), seg.ctypes.data, within.ctypes.data,
+                                        between.ctypes.data, rhat.ctypes.data))
+    return seg, n.value, within, between, rhat
+
+
+def levels_agreement_dense_device(chains, out_ptr):
+    """R-hat per position into a device buffer float32 [D][T] (hml_levels_agreement_dense_device)"""
+    _check(load_library().hml_levels_agreement_dense_device(_handles(chains), len(chains), out_ptr))
+
+
+def levels_agreement_summary(chains, threshold):
+    """(n_above[D], max_finite[D], n_infinite[D]): the positions with R-hat above `threshold` (+inf included), the largest
+    finite R-hat (0 if none) and the positions with R-hat == +inf, per dimension (hml_levels_agreement_summary)"""
+    D = chains[0].D
+    above = np.zeros(D, np.uint64)
+    largest = np.zeros(D, np.float64)
+    infinite = np.zeros(D, np.uint64)
+    _check(load_library().hml_levels_agreement_summary(_handles(chains), len(chains), float(threshold), above.ctypes.data,
+                                                       largest.ctypes.data, infinite.ctypes.data))
+    return above, largest, infinite
+
+
+def levels_rhat(n_recorded, s1, s2):
+    """(within, between, rhat), float64 of shape s1.shape[1:]: the formula of hml_levels_agreement_rle (include/hml.h) in
+    numpy, in the same order of operations.  s1, s2: [n][D][U], the chains' S1 and S2 per union segment; n_recorded = N >= 2."""
+    s1 = np.asarray(s1, np.float64)
+    s2 = np.asarray(s2, np.float64)
+    n = s1.shape[0]
+    N = np.float64(n_recorded)
+    sq = np.zeros(s1.shape[1:], np.float64)
+    sm = np.zeros(s1.shape[1:], np.float64)
+    means = []
+    for c in range(n):   # (from chain 0 upward, starting at 0.0)
+        m = s1[c] / N
+        q = s2[c] / N - m * m
+        q = np.where(q > 0.0, q, 0.0)
+        sq = sq + q
+        sm = sm + m
+        means.append(m)
+    w0 = sq / np.float64(n)
+    mbar = sm / np.float64(n)
+    sb = np.zeros(s1.shape[1:], np.float64)
+    for m in means:
+        sb = sb + (m - mbar) * (m - mbar)
+    between = sb / (np.float64(n) - 1.0)
+    within = w0 * (N / (N - 1.0))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rhat = np.where(within > 0.0, np.sqrt((w0 + between) / within), np.where(between == 0.0, 1.0, np.inf))
+    return within, between, rhat
 
 
 def levels_mean_sd(n, s1, s2):

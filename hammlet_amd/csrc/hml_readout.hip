@@ -2,6 +2,7 @@
 // marginals, emission levels, breakpoints, level bands - brought into the forms the callers ask for, and the merges of one
 // chain's recording into another's.  Nothing here runs inside a sweep; hml_capi.hip holds the chain itself.
 #include "hml_capi_shared.hpp"
+#include "hml_k_agree.h"   // (launched from this object alone)
 
 // The positions whose bit is set in a boundary bitmap over T positions (n_spans spans of HML_SPAN), ascending, on stream `s`:
 // d_seg[M + 1] is allocated here, position 0 is always the first entry.  Counts per span, their prefix sums on the host, scatter.
@@ -342,6 +343,173 @@ int hml_levels_dense_device(hml_ctx* c, void* out_dev) {
 }
 
 int hml_levels_merge(hml_ctx* dst, hml_ctx* src) { return recorder_merge(dst, src, HML_REC_LEVELS); }
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------- agreement of chains (hml_k_agree.h)
+
+// how the three agreement calls begin: the arguments hold n distinct contexts of one device over the same positions and
+// dimensions that recorded the same N >= 2 levels; every context settled, the device bound.  The work runs on ctxs[0]'s stream.
+static int agreement_ready(hml_ctx* const* ctxs, int n, uint64_t* N_out) {
+    if (!ctxs) return set_err(HML_ERR_ARG, "null argument");
+    if (n < 2 || n > HML_AGREE_MAX_CHAINS) return set_err(HML_ERR_ARG, "the agreement of the emission levels is taken over 2 to 64 chains");
+    for (int i = 0; i < n; ++i) {
+        if (!ctxs[i]) return set_err(HML_ERR_ARG, "null argument");
+        if (!ctxs[i]->model_set) return set_err(HML_ERR_ARG, "model not set");
+        for (int j = 0; j < i; ++j)
+            if (ctxs[j] == ctxs[i]) return set_err(HML_ERR_ARG, "a context was given twice: the agreement of a chain with itself says nothing");
+    }
+    const hml_ctx* a = ctxs[0];
+    for (int i = 1; i < n; ++i) {
+        if (ctxs[i]->device != a->device)
+            return set_err(HML_ERR_ARG, "the agreement of the emission levels of chains on different GPUs is not computed yet: run the chains of one rhat file on one GPU");
+        if (ctxs[i]->T != a->T || ctxs[i]->D != a->D)
+            return set_err(HML_ERR_ARG, "the agreement of the emission levels can only be computed between chains over the same positions and dimensions");
+    }
+    for (int i = 0; i < n; ++i)
+        if (!ctxs[i]->rec[HML_REC_LEVELS].asked) return recorder_none(HML_REC_LEVELS, i == 0 ? "the first" : "a");
+    if (int r = ctx_bind(ctxs[0])) return r;
+    for (int i = 0; i < n; ++i) { if (int r = hml_settle(ctxs[i])) return r; }
+    uint64_t N = 0;
+    for (int i = 0; i < n; ++i) {
+        hml_ctx* c = ctxs[i];
+        if (int r = check_device_error(c)) return r;
+        unsigned long long Ni = 0;   // (a context that was asked but has no buffers yet recorded nothing)
+        if (c->rec[HML_REC_LEVELS].d_acc) {
+            HIPCHK(hipMemcpyAsync(&Ni, recorder_counter(c, HML_REC_LEVELS), sizeof Ni, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+        }
+        if (Ni < 2) return set_err(HML_ERR_ARG, "the agreement of the emission levels needs at least two recorded sweeps in every chain");
+        if (i > 0 && Ni != N) return set_err(HML_ERR_ARG, "the agreement of the emission levels needs the same number of recorded sweeps in every chain");
+        N = Ni;
+    }
+    *N_out = N;
+    return 0;
+}
+
+// the union of the chains' level boundaries on the device: starts d_useg[U], and the chains' bitmaps in `ch`
+static int agreement_union(hml_ctx* const* ctxs, int n, hml_agree_chains& ch, uint64_t* U_out, DevBuf& d_useg) {
+    hml_ctx* a = ctxs[0];
+    const uint32_t T = (uint32_t)a->T;
+    const uint32_t words = (uint32_t)((a->T + 32) / 32);   // (what ensure_recorder_buffers allocates)
+    memset(&ch, 0, sizeof ch);
+    for (int i = 0; i < n; ++i) ch.boundary[i] = ctxs[i]->rec[HML_REC_LEVELS].d_boundary;
+    DevBuf d_or;
+    HIPCHK(hipMalloc(&d_or.p, (uint64_t)words * sizeof(uint32_t)));
+    hipLaunchKernelGGL(hml_k_agree_or, dim3(grid_for(words, 256, 1, 16384)), dim3(256), 0, a->stream, ch, n, words, d_or.as<uint32_t>());
+    KLAUNCH_CHECK();
+    return compact_boundaries(a->stream, d_or.as<uint32_t>(), T, a->n_spans, U_out, d_useg);   // (synchronises: d_or may go)
+}
+
+// within, between and rhat per union segment and dimension, [D][U] each, and rhat as floats, on the device
+struct hml_agreement {
+    uint64_t U = 0, N = 0;
+    DevBuf useg, within, between, rhat, rhat_f;
+};
+static int agreement_segments(hml_ctx* const* ctxs, int n, hml_agreement& ag) {
+    hml_ctx* a = ctxs[0];
+    const int D = a->D;
+    hml_agree_chains ch;
+    if (int r = agreement_union(ctxs, n, ch, &ag.U, ag.useg)) return r;
+    const uint64_t U = ag.U;
+    // each chain's own segments: the sums hml_levels_rle returns (on the chain's stream, idle again when the call returns)
+    std::vector<DevBuf> b_seg(n), b_sum(n);
+    for (int i = 0; i < n; ++i) {
+        uint64_t M = 0;
+        if (int r = gather_level_segments(ctxs[i], &M, b_seg[i], b_sum[i])) return r;
+        hipFree(b_seg[i].p); b_seg[i].p = nullptr;   // (the rank takes the place of the starts)
+        ch.sum[i] = b_sum[i].as<double>();
+        ch.M[i] = (uint32_t)M;
+    }
+    // the chains' segments under the union's, by rank: flags, then the fixed scan over each chain's row
+    DevBuf b_flag, b_rank;
+    HIPCHK(hipMalloc(&b_flag.p, (uint64_t)n * U * sizeof(uint8_t)));
+    HIPCHK(hipMalloc(&b_rank.p, (uint64_t)n * U * sizeof(uint32_t)));
+    const dim3 grid(grid_for(U, 256, 1, 16384));
+    hipLaunchKernelGGL(hml_k_agree_flags, grid, dim3(256), 0, a->stream, ch, n, ag.useg.as<uint32_t>(), (uint32_t)U, b_flag.as<uint8_t>());
+    KLAUNCH_CHECK();
+    if (int r = scan_rows<uint8_t, uint32_t, false>(a->stream, b_flag.as<uint8_t>(), U, n, b_rank.as<uint32_t>())) return r;
+    HIPCHK(hipMalloc(&ag.within.p, (uint64_t)D * U * sizeof(double)));
+    HIPCHK(hipMalloc(&ag.between.p, (uint64_t)D * U * sizeof(double)));
+    HIPCHK(hipMalloc(&ag.rhat.p, (uint64_t)D * U * sizeof(double)));
+    HIPCHK(hipMalloc(&ag.rhat_f.p, (uint64_t)D * U * sizeof(float)));
+    hipLaunchKernelGGL(hml_k_agree_eval, grid, dim3(256), 0, a->stream, ch, n, D, b_rank.as<uint32_t>(), (uint32_t)U, (unsigned long long)ag.N,
+                       ag.within.as<double>(), ag.between.as<double>(), ag.rhat.as<double>(), ag.rhat_f.as<float>());
+    KLAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(a->stream));   // (the chains' sums, the flags and the ranks go with this frame)
+    return 0;
+}
+
+extern "C" {
+
+int hml_levels_agreement_rle(hml_ctx* const* ctxs, int n, uint64_t* n_segments, uint64_t* n_recorded, uint64_t* seg_len, double* within,
+                             double* between, double* rhat) {
+    if (!n_segments) return set_err(HML_ERR_ARG, "null argument");
+    hml_agreement ag;
+    if (int r = agreement_ready(ctxs, n, &ag.N)) return r;
+    if (n_recorded) *n_recorded = ag.N;
+    if (!seg_len) {   // the sizes: the union alone
+        hml_agree_chains ch;
+        return agreement_union(ctxs, n, ch, n_segments, ag.useg);
+    }
+    if (int r = agreement_segments(ctxs, n, ag)) return r;
+    hml_ctx* a = ctxs[0];
+    const uint64_t U = ag.U, bytes = (uint64_t)a->D * U * sizeof(double);
+    *n_segments = U;
+    std::vector<uint32_t> h_seg(U);
+    HIPCHK(hipMemcpyAsync(h_seg.data(), ag.useg.p, U * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
+    if (within) HIPCHK(hipMemcpyAsync(within, ag.within.p, bytes, hipMemcpyDeviceToHost, a->stream));
+    if (between) HIPCHK(hipMemcpyAsync(between, ag.between.p, bytes, hipMemcpyDeviceToHost, a->stream));
+    if (rhat) HIPCHK(hipMemcpyAsync(rhat, ag.rhat.p, bytes, hipMemcpyDeviceToHost, a->stream));
+    HIPCHK(hipStreamSynchronize(a->stream));
+    lengths_of(h_seg.data(), U, (uint32_t)a->T, seg_len);
+    return 0;
+}
+
+int hml_levels_agreement_dense_device(hml_ctx* const* ctxs, int n, void* out_dev) {
+    if (!out_dev) return set_err(HML_ERR_ARG, "null argument");
+    hml_agreement ag;
+    if (int r = agreement_ready(ctxs, n, &ag.N)) return r;
+    if (int r = agreement_segments(ctxs, n, ag)) return r;
+    hml_ctx* a = ctxs[0];
+    const uint32_t T = (uint32_t)a->T;
+    hipLaunchKernelGGL(hml_k_levels_expand, dim3(grid_for(T, 256, 1, 65536)), dim3(256), 0, a->stream, ag.rhat_f.as<float>(), ag.useg.as<uint32_t>(),
+                       (uint32_t)ag.U, T, a->D, (float*)out_dev);
+    KLAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(a->stream));
+    return 0;
+}
+
+int hml_levels_agreement_summary(hml_ctx* const* ctxs, int n, double threshold, uint64_t* n_above, double* max_finite, uint64_t* n_infinite) {
+    if (!n_above || !max_finite || !n_infinite) return set_err(HML_ERR_ARG, "null argument");
+    hml_agreement ag;
+    if (int r = agreement_ready(ctxs, n, &ag.N)) return r;
+    if (int r = agreement_segments(ctxs, n, ag)) return r;
+    hml_ctx* a = ctxs[0];
+    const int D = a->D;
+    const int blocks = grid_for(ag.U, 1024, 1, 256);
+    DevBuf b_cnt, b_max;
+    HIPCHK(hipMalloc(&b_cnt.p, (uint64_t)blocks * D * 2 * sizeof(unsigned long long)));
+    HIPCHK(hipMalloc(&b_max.p, (uint64_t)blocks * D * sizeof(double)));
+    hipLaunchKernelGGL(hml_k_agree_summary, dim3(blocks), dim3(256), 0, a->stream, ag.rhat.as<double>(), ag.useg.as<uint32_t>(), (uint32_t)ag.U, (uint32_t)a->T,
+                       D, threshold, b_cnt.as<unsigned long long>(), b_max.as<double>());
+    KLAUNCH_CHECK();
+    std::vector<unsigned long long> h_cnt((size_t)blocks * D * 2);
+    std::vector<double> h_max((size_t)blocks * D);
+    HIPCHK(hipMemcpyAsync(h_cnt.data(), b_cnt.p, h_cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, a->stream));
+    HIPCHK(hipMemcpyAsync(h_max.data(), b_max.p, h_max.size() * sizeof(double), hipMemcpyDeviceToHost, a->stream));
+    HIPCHK(hipStreamSynchronize(a->stream));
+    // the second stage: integers and a maximum - the same answer in any order
+    for (int d = 0; d < D; ++d) {
+        n_above[d] = 0; n_infinite[d] = 0; max_finite[d] = 0.0;
+        for (int b = 0; b < blocks; ++b) {
+            n_above[d] += h_cnt[((size_t)b * D + d) * 2];
+            n_infinite[d] += h_cnt[((size_t)b * D + d) * 2 + 1];
+            max_finite[d] = std::max(max_finite[d], h_max[(size_t)b * D + d]);
+        }
+    }
+    return 0;
+}
 
 // ---------------------------------------------------------------------------------------- breakpoints (hml_k_breaks.h)
 }  // extern "C"

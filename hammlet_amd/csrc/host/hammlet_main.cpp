@@ -12,7 +12,9 @@
 // `-bands E0 [E1 ...]` gives ascending edges of the emission level, and `-O LB` (bands) writes PREFIXbandsSUFFIX, per band segment
 // its length and per data dimension and band the number of recorded sweeps whose level lay in it - marginals that need no
 // labels - and `-O LC` (bandcalls) writes PREFIXbandcallsSUFFIX, the band called per run under `-bandcall P` (hml_bands_rle,
-// hml_bands_call);
+// hml_bands_call); `-O R` (rhat) with -chains N writes PREFIXrhatSUFFIX, the agreement of the N chains on the emission level before
+// they are merged: per segment of the union of their level boundaries its length and per data dimension the Gelman-Rubin R-hat
+// (hml_levels_agreement_rle);
 // -raw FILE reads float32 values instead of text; -device N selects
 // the GPU; -chain N selects the Philox sub-key of an independent chain; -chains N runs N independent chains (sub-keys
 // chain .. chain+N-1), chain k on GPU (device + k) mod #GPUs in its own host thread, and pools their recorded marginals
@@ -62,6 +64,10 @@ static const char* kHelp =
     "                                 whose emission level lay in the band, one line per band segment (extension)\n"
     "                    LC           bandcalls: start, length, then the band called per data dimension, one line per run\n"
     "                                 of equal calls (extension; see -bandcall)\n"
+    "                    R            rhat: length, then per data dimension the Gelman-Rubin R-hat of the emission level over\n"
+    "                                 the chains of -chains N (N >= 2, one GPU), one line per segment of the union of the chains'\n"
+    "                                 level boundaries, taken before the chains are merged: near 1 the chains agree there, well\n"
+    "                                 above 1 they sit in different modes; turns the recording of the levels on (extension)\n"
     "  -w, -overwrite                 allow overwriting output files\n"
     "  -s, -states K | C P D          number of states (default 3), or P parameters shared by P^D states over D dimensions\n"
     "  -e, -emissions normal VAR P    automatic prior: P(variance < VAR) = P (default normal 0.2 0.9)\n"
@@ -197,6 +203,44 @@ static void writeLevels(const Job& job, hml_ctx* ctx) {
         fputc('\n', out);
     }
     if (fclose(out) != 0) throw std::runtime_error("Cannot write to file " + fn + "!");
+}
+
+static const char* kRhatDevicesMessage =
+    "The agreement of the emission levels of chains on different GPUs is not computed yet: run -O rhat with -chains N on one GPU!";
+static const char* kRhatChainsMessage =
+    "The output rhat (R) compares the chains of one run: give -chains N with N between 2 and 64!";
+
+static string rhatFileName(const Job& job) { return job.opref + "rhat" + job.osuff; }
+
+// PREFIXrhatSUFFIX from the chains' recorded levels, BEFORE they are merged: "length rhat_0 [rhat_1 ...]" per segment of the
+// union of the chains' level boundaries, %.9g of the double.  verbose: the positions with R-hat above 1.1 and the largest finite value.
+static void writeRhat(const Job& job, const vector<hml_ctx*>& ctxs, bool verbose) {
+    const int n = (int)ctxs.size();
+    uint64_t U = 0, N = 0;
+    hml_check(hml_levels_agreement_rle(ctxs.data(), n, &U, &N, nullptr, nullptr, nullptr, nullptr));
+    const size_t D = job.nrDataDim;
+    vector<uint64_t> len(U);
+    vector<double> rhat(U * D);
+    hml_check(hml_levels_agreement_rle(ctxs.data(), n, &U, &N, len.data(), nullptr, nullptr, rhat.data()));
+    const string fn = rhatFileName(job);
+    FILE* out = fopen(fn.c_str(), "w");
+    if (!out) throw std::runtime_error("Cannot write to file " + fn + "!");
+    for (uint64_t i = 0; i < U; ++i) {
+        fprintf(out, "%llu", (unsigned long long)len[i]);
+        for (size_t d = 0; d < D; ++d) fprintf(out, " %.9g", rhat[d * U + i]);
+        fputc('\n', out);
+    }
+    if (fclose(out) != 0) throw std::runtime_error("Cannot write to file " + fn + "!");
+    if (verbose) {
+        vector<uint64_t> above(D), infinite(D);
+        vector<double> largest(D);
+        hml_check(hml_levels_agreement_summary(ctxs.data(), n, 1.1, above.data(), largest.data(), infinite.data()));
+        cout << "Positions with R-hat above 1.1 over " << n << " chains:";
+        for (size_t d = 0; d < D; ++d) cout << " " << above[d];
+        cout << "; largest finite R-hat:";
+        for (size_t d = 0; d < D; ++d) cout << " " << largest[d];
+        cout << endl << flush;
+    }
 }
 
 static const char* kBreaksDevicesMessage =
@@ -585,6 +629,7 @@ int main(int argc, const char* argv[]) {
         outputArgs.registerFlags({"CS", "consensus"});        // extension
         outputArgs.registerFlags({"LB", "bands"});            // extension
         outputArgs.registerFlags({"LC", "bandcalls"});        // extension
+        outputArgs.registerFlags({"R", "rhat"});              // extension
         outputArgs.parseArgs();
 
         // ---- input
@@ -657,13 +702,15 @@ int main(int argc, const char* argv[]) {
         job.weightMultiplier = weightMultiplier; job.useSelfTrans = useSelfTrans;
         job.thetaParams = thetaParams; job.trans = trans; job.selfTrans = selfTrans; job.initialAlpha = initialAlpha;
         job.scheme = scheme;
-        for (const char* o : {"sequences", "parameters", "blocks", "compression", "marginals", "segments", "maxsegmentation", "levels", "breakpoints", "consensus", "bands", "bandcalls"})
+        for (const char* o : {"sequences", "parameters", "blocks", "compression", "marginals", "segments", "maxsegmentation", "levels", "breakpoints", "consensus", "bands", "bandcalls", "rhat"})
             job.outputs[o] = outputArgs.isSet(o);
         auto refuseExisting = [&](const string& fn) {
             if (!overwrite) { std::ifstream probe(fn); if (probe.good()) throw std::runtime_error("File " + fn + " already exists! Use -w to allow overwrite!"); }
         };
         const bool wantsBreaks = job.outputs.at("breakpoints") || job.outputs.at("consensus");
-        const bool wantsLevels = job.outputs.at("levels") || job.outputs.at("consensus");   // (a consensus segment carries its level)
+        const bool wantsRhat = job.outputs.at("rhat");
+        if (wantsRhat && (nrChains < 2 || nrChains > 64)) throw std::runtime_error(kRhatChainsMessage);   // (before anything runs)
+        const bool wantsLevels = job.outputs.at("levels") || job.outputs.at("consensus") || wantsRhat;   // (a consensus segment carries its level)
         if (wantsLevels) setenv("HML_LEVELS", "1", 1);   // every context of this process accumulates the emission levels of its recorded sweeps (include/hml.h)
         if (wantsBreaks) setenv("HML_BREAKS", "1", 1);   // ... and counts their breakpoints
         const bool wantsBands = job.outputs.at("bands") || job.outputs.at("bandcalls");
@@ -695,6 +742,7 @@ int main(int argc, const char* argv[]) {
         if (job.outputs.at("bands")) refuseExisting(bandsFileName(job));
         if (job.outputs.at("bandcalls")) refuseExisting(bandCallsFileName(job));
         if (job.outputs.at("levels")) refuseExisting(levelsFileName(job));
+        if (wantsRhat) refuseExisting(rhatFileName(job));
         if (job.outputs.at("breakpoints")) refuseExisting(breaksFileName(job));
         if (job.outputs.at("consensus")) {
             refuseExisting(consensusFileName(job));
@@ -714,6 +762,7 @@ int main(int argc, const char* argv[]) {
             int nDev = 1;
             hml_check(hml_device_count(&nDev));
             if (job.outputs.at("levels") && nDev > 1) throw std::runtime_error(kLevelsDevicesMessage);   // (before anything runs)
+            if (wantsRhat && nDev > 1) throw std::runtime_error(kRhatDevicesMessage);
             if (wantsBreaks && nDev > 1) throw std::runtime_error(kBreaksDevicesMessage);
             if (wantsBands && nDev > 1) throw std::runtime_error(kBandsDevicesMessage);
             Rendezvous rv(nrChains);
@@ -765,6 +814,7 @@ int main(int argc, const char* argv[]) {
                 // the chains share the GPU: their levels, breakpoint counts and band counts add up in the first chain's context, which the
                 // files are written from
                 try {
+                    if (wantsRhat) writeRhat(job, ctxs, verbose);   // (the chains one by one: the merge below changes the first)
                     for (int k = 1; k < nrChains; ++k) {
                         if (wantsLevels) hml_check(hml_levels_merge(ctxs[0], ctxs[k]));
                         if (wantsBreaks) hml_check(hml_breaks_merge(ctxs[0], ctxs[k]));

@@ -274,6 +274,45 @@ int hml_levels_merge(hml_ctx* dst, hml_ctx* src);
 int hml_levels_on_segments(hml_ctx* ctx, uint64_t n_cuts, const uint32_t* cuts /*n_cuts, ascending, in (0, T)*/,
                            double* sum /*D*(n_cuts+1), dimension-major*/, double* sum_sq /*D*(n_cuts+1)*/);
 
+/* ---- agreement of chains on the emission level: R-hat per position (an addition to ABI 5).  No counterpart in the reference. ----
+ * Do the chains that hml_levels_merge is about to add up tell the same story?  A chain's S1 and S2 at a position are the
+ * sufficient statistics of the Gelman-Rubin potential scale reduction of the level there, and like the level the diagnostic
+ * does not depend on what a state is called: twin states and switched labels neither fake disagreement nor hide it.
+ * INPUT: n contexts, 2 <= n <= 64, distinct, on one device, with the same T and D, each with recorded levels and the same
+ * N >= 2.  The contexts are only read: accumulators, bitmaps, counters and later recording are untouched.  Every context is
+ * settled, the device is bound, the work runs on ctxs[0]'s stream.
+ * SEGMENTS: the union of the chains' level boundaries, U of them.  On a union segment every chain's (S1, S2) is constant: the
+ * values of the chain's own hml_levels_rle segment that contains it, the same bits.
+ * ARITHMETIC per union segment and dimension, all in double, in this order, without contraction; the sums over the chains run
+ * from chain 0 upward, starting at 0.0:
+ *     m_c  = S1_c / N
+ *     q_c  = S2_c / N - m_c * m_c ;  if !(q_c > 0) q_c = 0           (a chain's population variance)
+ *     w0   = (sum_c q_c) / n
+ *     mbar = (sum_c m_c) / n
+ *     between = (sum_c (m_c - mbar) * (m_c - mbar)) / (n - 1)        (the variance of the chain means, B / N)
+ *     within  = w0 * (N / (N - 1))                                    (W)
+ *     rhat    = sqrt((w0 + between) / within)   if within > 0
+ *             = 1                               if within == 0 and between == 0
+ *             = +infinity                       if within == 0 and between > 0
+ * MEANING: identical chains give between == 0 and rhat = sqrt((N - 1) / N) < 1; values near 1: the chains tell the same story
+ * at that position; values well above 1: they sit in different modes there.
+ * CANCELLATION: q_c is a difference of nearly equal numbers when a chain's level hardly moved; its absolute error is bounded
+ * by E2 / N + 2 |m| E1 / N with the bounds E1, E2 of the segment sums (2^-52 M N (N + 1) max|mu| and the same with max mu^2: at
+ * most N rounded additions into a cell, M in the scan).  A chain whose level never moved can therefore show a tiny positive
+ * q_c, and a segment on which no chain's level moved a finite rhat instead of 1 or +infinity.
+ * HML_ERR_ARG, each with a message of its own: a null argument, n outside 2 .. 64, a context given twice, chains on different
+ * GPUs, different T or D, a context that never recorded levels, N < 2, unequal N.
+ * hml_levels_agreement_rle: within, between and rhat per union segment, [d * n_segments + i]; each of the three may be NULL.
+ * Call with seg_len == NULL for n_segments and n_recorded. */
+int hml_levels_agreement_rle(hml_ctx* const* ctxs, int n, uint64_t* n_segments, uint64_t* n_recorded, uint64_t* seg_len /*n_segments*/,
+                             double* within /*D*n_segments, dimension-major*/, double* between /*D*n_segments*/, double* rhat /*D*n_segments*/);
+/* Dense form on the DEVICE: float [D][T], rhat computed in double and rounded once. */
+int hml_levels_agreement_dense_device(hml_ctx* const* ctxs, int n, void* out_dev /* float [D][T] */);
+/* Per dimension: the positions with rhat > threshold (+infinity included), the largest finite rhat (0 if there is none) and
+ * the positions with rhat == +infinity.  Positions are counted in 64-bit integers over the union segments' lengths: exact. */
+int hml_levels_agreement_summary(hml_ctx* const* ctxs, int n, double threshold, uint64_t* n_above /*D*/, double* max_finite /*D*/,
+                                 uint64_t* n_infinite /*D*/);
+
 /* ---- breakpoint posteriors per position and the consensus segmentation (ABI 5).  No counterpart in the reference. ----
  * A recorded sweep has a BREAKPOINT at position t (0 < t < T) iff a block starts at t whose state differs from the state of
  * the block before it; position 0 is never one.  The context counts, per position, the recorded sweeps with a breakpoint
