@@ -103,6 +103,10 @@ SIGNATURES = {
     "hml_bands_dense_device": (C.c_int, [_P, _P, C.c_int]),
     "hml_bands_call": (C.c_int, [_P, C.c_uint64, C.POINTER(C.c_uint64), _P, _P]),
     "hml_bands_merge": (C.c_int, [_P, _P]),
+    "hml_recording_payload_size": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64)]),
+    "hml_recording_export": (C.c_int, [_P, C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "hml_recording_merge_payload": (C.c_int, [_P, C.c_int, _P, C.c_uint64]),
+    "hml_recording_merge_across": (C.c_int, [_P, _P, C.c_int]),
     "hml_categorical_draw": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_uint32)]),
     "hml_relabel_permutation": (C.c_int, [_P, _P]),
     "hml_pool_payload_size": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
@@ -128,6 +132,9 @@ SIGNATURES = {
 
 
 ABI_VERSION = 5   # hml_abi_version() of include/hml.h this mirror was written against
+
+# the kinds of recording of the sparse payloads (HML_RECORDING_* of include/hml.h)
+RECORDING_LEVELS, RECORDING_BREAKS, RECORDING_BANDS = 0, 1, 2
 
 
 def load_library(path=None):
@@ -229,6 +236,7 @@ class Chain:
         h = _P()
         _check(self.lib.hml_create(C.byref(h), device, seed, chain_id, stream))
         self.h = h
+        self.device = device
         self.K = None
         self.T = None
         self.D = 1          # data dimensions / emission parameters ("-s C P D"); P = None: P = K
@@ -550,6 +558,29 @@ class Chain:
     def merge_bands(self, other):
         """add `other`'s band counts into this chain's (same GPU, positions, dimensions and edges); no relabelling involved"""
         _check(self.lib.hml_bands_merge(self.h, other.h))
+
+    # ---- sparse payloads of the levels, breakpoints and bands (across GPUs) -------------------
+    def recording_payload_size(self, kind):
+        """bytes of the payload hml_recording_export would write now for RECORDING_LEVELS / _BREAKS / _BANDS"""
+        n = C.c_uint64()
+        _check(self.lib.hml_recording_payload_size(self.h, kind, C.byref(n)))
+        return n.value
+
+    def recording_export(self, kind, payload_ptr, capacity_bytes):
+        """the recording's positions and raw cells into a device buffer of this chain's GPU (layout: include/hml.h); returns
+        the bytes written"""
+        n = C.c_uint64()
+        _check(self.lib.hml_recording_export(self.h, kind, payload_ptr, capacity_bytes, C.byref(n)))
+        return n.value
+
+    def recording_merge_payload(self, kind, payload_ptr, n_bytes):
+        """add a payload that lies on this chain's GPU into its recording, as merge_levels / breaks_merge / merge_bands add the
+        exporting chain; checked before anything is written"""
+        _check(self.lib.hml_recording_merge_payload(self.h, kind, payload_ptr, n_bytes))
+
+    def recording_merge_across(self, other, kind):
+        """add `other`'s recording into this chain's through the payload: `other` may live on another GPU"""
+        _check(self.lib.hml_recording_merge_across(self.h, other.h, kind))
 
     # ---- chain-parallel pooling ---------------------------------------------------------
     def relabel_permutation(self):

@@ -7,6 +7,11 @@ launcher glue around it - how the ranks of a torch.distributed job obtain the RC
 payload algebra (`payload_from_dense`, `pool_payload`, `payload_to_rle`) that works on any backend, which is how the
 world-size-2 gloo test on CPU covers the N > 1 semantics (relabel, sum, cut at the union of the boundaries).
 
+The label-free recordings - emission levels, breakpoint counts, level bands - cross GPUs as SPARSE PAYLOADS (include/hml.h,
+hml_recording_export / hml_recording_merge_payload): `recording_payload`, `parse_recording_payload` and
+`merge_recording_payloads` are the numpy mirror of that layout and of the merge, `gather_recording_payloads` the all-gather
+of payloads of unequal length on any backend, `pooled_recording` the product path of one process per GPU.
+
 The reference has nothing distributed (one process, one thread, src/main.cpp:108).  Pooling needs (1) a common
 labelling of the states - every chain relabels its states by ascending emission mean, the idea of the reference's
 bin/sortStates:1-6 - and (2) one all-reduce over the int32 payload [K+1][T+1] (+ K+1 words): K relabelled difference
@@ -157,3 +162,123 @@ def pooled_marginals(chain, pool):
     perm = pool.marginals(chain)
     seg, cnt = chain.marginals_rle()
     return seg, cnt, perm
+
+
+# ---- sparse payloads of the levels, breakpoints and bands (include/hml.h; csrc/hml_k_rec_payload.h) ----
+RECORDING_MAGIC = 0x00314345524C4D48           # the bytes "HMLREC1\0"
+RECORDING_LEVELS, RECORDING_BREAKS, RECORDING_BANDS = 0, 1, 2
+RECORDING_CELL = {RECORDING_LEVELS: np.dtype("<f8"), RECORDING_BREAKS: np.dtype("<u4"), RECORDING_BANDS: np.dtype("<i4")}
+_REC_FIXED = 192                               # 8 uint64 of header, 32 floats of edges
+
+
+def recording_payload_size(M, rows, cell_bytes):
+    """192 + 8 ceil(M / 2) + rows M (bytes per cell)"""
+    return _REC_FIXED + 8 * ((int(M) + 1) // 2) + int(rows) * int(M) * int(cell_bytes)
+
+
+def recording_payload(kind, T, positions, cells, n_recorded, edges=None):
+    """The payload hml_recording_export writes, as a uint8 array: `positions` [M] ascending, `cells` [rows][M] the raw cells of
+    the recorder there (float64 for levels, uint32 for breaks, int32 for bands), `edges` the bands' edges.  Nothing is checked
+    here - the library checks what it is given - so that faulty payloads can be built as well."""
+    cell = RECORDING_CELL[kind]
+    pos = np.ascontiguousarray(positions, "<u4").reshape(-1)
+    M = pos.size
+    cells = np.ascontiguousarray(cells, cell)
+    cells = cells.reshape(-1, M) if M else cells.reshape(cells.shape[0] if cells.ndim == 2 else 0, 0)
+    rows = cells.shape[0]
+    e = np.zeros(32, "<f4")
+    n_edges = 0
+    if edges is not None:
+        edges = np.ascontiguousarray(edges, "<f4").reshape(-1)
+        n_edges = edges.size
+        e[:n_edges] = edges
+    head = np.array([RECORDING_MAGIC, kind, T, rows, M, n_recorded, cell.itemsize, n_edges], "<u8")
+    padded = np.zeros(2 * ((M + 1) // 2), "<u4")
+    padded[:M] = pos
+    out = np.concatenate([head.view(np.uint8), e.view(np.uint8), padded.view(np.uint8), cells.reshape(-1).view(np.uint8)])
+    assert out.size == recording_payload_size(M, rows, cell.itemsize)
+    return out
+
+
+def parse_recording_payload(buf):
+    """dict(kind, T, rows, M, n_recorded, cell_bytes, n_edges, edges[n_edges], edge_slots[32], positions[M], cells[rows][M]) of a
+    payload given as bytes, a uint8 array or a uint8 tensor on the host; raises ValueError on a buffer that is not one"""
+    buf = np.frombuffer(bytes(buf), np.uint8) if isinstance(buf, (bytes, bytearray, memoryview)) else np.ascontiguousarray(np.asarray(buf), np.uint8).reshape(-1)
+    if buf.size < _REC_FIXED:
+        raise ValueError("shorter than the header of a recording's payload")
+    head = buf[:64].view("<u8")
+    if int(head[0]) != RECORDING_MAGIC:
+        raise ValueError("not a recording's payload: wrong magic number")
+    kind, T, rows, M, N, cell_bytes, n_edges = (int(v) for v in head[1:8])
+    if kind not in RECORDING_CELL or RECORDING_CELL[kind].itemsize != cell_bytes:
+        raise ValueError("unknown kind or cell size")
+    if buf.size != recording_payload_size(M, rows, cell_bytes):
+        raise ValueError("the size is not the one the header implies")
+    slots = buf[64:_REC_FIXED].view("<f4").copy()
+    off = _REC_FIXED
+    pos = buf[off:off + 4 * M].view("<u4").copy()
+    off += 8 * ((M + 1) // 2)
+    cells = buf[off:].view(RECORDING_CELL[kind]).reshape(rows, M).copy()
+    return {"kind": kind, "T": T, "rows": rows, "M": M, "n_recorded": N, "cell_bytes": cell_bytes, "n_edges": n_edges,
+            "edges": slots[:n_edges].copy(), "edge_slots": slots, "positions": pos, "cells": cells}
+
+
+def merge_recording_payloads(payloads):
+    """What a recorder holds after the payloads were merged into a fresh one, in list order, as a payload again: the union of
+    the positions, the cells added in list order starting from zero (the order matters for the levels' doubles), the counts of
+    recorded sweeps summed.  The payloads must agree in kind, T, rows and edges."""
+    parts = [p if isinstance(p, dict) else parse_recording_payload(p) for p in payloads]
+    a = parts[0]
+    for p in parts[1:]:
+        if (p["kind"], p["T"], p["rows"]) != (a["kind"], a["T"], a["rows"]) or p["edge_slots"].tobytes() != a["edge_slots"].tobytes():
+            raise ValueError("payloads of different kinds, positions, rows or edges")
+    union = np.unique(np.concatenate([p["positions"] for p in parts])) if parts else np.zeros(0, np.uint32)
+    cells = np.zeros((a["rows"], union.size), RECORDING_CELL[a["kind"]])
+    for p in parts:
+        idx = np.searchsorted(union, p["positions"])
+        cells[:, idx] = cells[:, idx] + p["cells"]
+    return recording_payload(a["kind"], a["T"], union, cells, sum(p["n_recorded"] for p in parts), a["edges"] if a["n_edges"] else None)
+
+
+def gather_recording_payloads(tensor, group=None):
+    """All-gather of the ranks' payloads (1-D uint8 tensors of unequal length): first the sizes, then the payloads padded with
+    zeros to the longest; returns every rank's payload, unpadded, in rank order - on every rank.  Any backend: "gloo" with
+    host tensors, "nccl" (= RCCL on ROCm) with tensors of the rank's GPU.  Without a process group: [tensor]."""
+    import torch
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1):
+        return [tensor]
+    world = dist.get_world_size(group)
+    size = torch.tensor([tensor.numel()], dtype=torch.int64, device=tensor.device)
+    sizes = [torch.zeros(1, dtype=torch.int64, device=tensor.device) for _ in range(world)]
+    dist.all_gather(sizes, size, group=group)
+    sizes = [int(s.item()) for s in sizes]
+    slot = max(sizes)
+    mine = torch.zeros(slot, dtype=torch.uint8, device=tensor.device)
+    mine[: tensor.numel()] = tensor
+    out = [torch.zeros(slot, dtype=torch.uint8, device=tensor.device) for _ in range(world)]
+    dist.all_gather(out, mine, group=group)
+    return [o[:n] for o, n in zip(out, sizes)]
+
+
+def pooled_recording(chain, kind, group=None, root=0):
+    """One process per GPU: every rank exports its chain's recording of `kind`, the payloads are gathered over the group
+    (device tensors: the group's backend must move them, i.e. "nccl"), and rank `root` merges the other ranks' payloads into
+    its chain in ascending rank order (hml_recording_merge_payload); the other ranks' chains are left as they were.  Returns the
+    gathered payloads in rank order."""
+    import torch
+    import torch.distributed as dist
+    dev = torch.device("cuda", chain.device)
+    n = chain.recording_payload_size(kind)
+    buf = torch.zeros(n, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize(dev)              # (the chain writes on its own stream)
+    chain.recording_export(kind, buf.data_ptr(), n)
+    parts = gather_recording_payloads(buf, group)
+    torch.cuda.synchronize(dev)
+    rank = dist.get_rank(group) if dist.is_available() and dist.is_initialized() else 0
+    if rank == root:
+        for r, part in enumerate(parts):
+            if r != rank:
+                part = part.contiguous()
+                chain.recording_merge_payload(kind, part.data_ptr(), part.numel())
+    return parts

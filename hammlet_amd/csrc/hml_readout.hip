@@ -1,8 +1,10 @@
 // libhammlet_hip.so - the read-outs of the C ABI (include/hml.h): what the recorded sweeps accumulated per position - state
 // marginals, emission levels, breakpoints, level bands - brought into the forms the callers ask for, and the merges of one
-// chain's recording into another's.  Nothing here runs inside a sweep; hml_capi.hip holds the chain itself.
+// chain's recording into another's: on one device from recorder to recorder, across devices through the sparse payload of
+// hml_k_rec_payload.h.  Nothing here runs inside a sweep; hml_capi.hip holds the chain itself.
 #include "hml_capi_shared.hpp"
 #include "hml_k_agree.h"   // (launched from this object alone)
+#include "hml_k_rec_payload.h"
 
 // The positions whose bit is set in a boundary bitmap over T positions (n_spans spans of HML_SPAN), ascending, on stream `s`:
 // d_seg[M + 1] is allocated here, position 0 is always the first entry.  Counts per span, their prefix sums on the host, scatter.
@@ -709,3 +711,207 @@ int hml_bands_merge(hml_ctx* dst, hml_ctx* src) { return recorder_merge(dst, src
 
 }  // extern "C"
 
+
+// ---------------------------------------------------------------------------------------- sparse payloads (hml_k_rec_payload.h)
+static_assert(HML_RECORDING_LEVELS == HML_REC_LEVELS && HML_RECORDING_BREAKS == HML_REC_BREAKS && HML_RECORDING_BANDS == HML_REC_BANDS,
+              "the public kinds carry the values of the internal ones");
+
+static uint64_t payload_bytes(uint64_t M, uint64_t rows, uint64_t cell) { return HML_RECPAY_FIXED_BYTES + 8u * ((M + 1u) / 2u) + rows * M * cell; }
+static int payload_kind(int kind) {
+    return kind >= 0 && kind < HML_REC_KINDS ? 0 : set_err(HML_ERR_ARG, "the kind of a recording is HML_RECORDING_LEVELS, HML_RECORDING_BREAKS or HML_RECORDING_BANDS");
+}
+
+// What an export of the context's recording holds: the chain settled, its M positions on the device (d_seg owns them, *d_pos
+// points at the first) - compact_boundaries' list, for breaks without the position 0 it always emits; no position at all
+// from a recorder that has recorded no sweep.
+static int payload_positions(hml_ctx* c, int kind, uint64_t* M_out, DevBuf& d_seg, const uint32_t** d_pos) {
+    if (!c->rec[kind].asked) return recorder_none(kind, "this");
+    if (int r = hml_settle(c)) return r;
+    if (int r = check_device_error(c)) return r;
+    if (int r = ensure_recorder_buffers(c, kind)) return r;
+    unsigned long long N = 0;
+    HIPCHK(hipMemcpyAsync(&N, recorder_counter(c, kind), sizeof N, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *M_out = 0; *d_pos = nullptr;
+    if (N == 0) return 0;
+    uint64_t M = 0;
+    if (int r = compact_boundaries(c->stream, c->rec[kind].d_boundary, (uint32_t)c->T, c->n_spans, &M, d_seg)) return r;
+    *d_pos = d_seg.as<uint32_t>();
+    if (kind == HML_REC_BREAKS) { ++*d_pos; --M; }
+    *M_out = M;
+    return 0;
+}
+
+// ... and the export itself; *n_bytes is set also when the capacity is too small (nothing is written then)
+static int payload_export(hml_ctx* c, int kind, void* payload_dev, uint64_t capacity, uint64_t* n_bytes) {
+    uint64_t M = 0;
+    DevBuf b_seg;
+    const uint32_t* d_pos = nullptr;
+    if (int r = payload_positions(c, kind, &M, b_seg, &d_pos)) return r;
+    const uint64_t rows = (uint64_t)recorder_rows(c, kind), cell = hml_recorder_kinds[kind].elem;
+    const uint64_t bytes = payload_bytes(M, rows, cell);
+    if (n_bytes) *n_bytes = bytes;
+    if (!payload_dev) return set_err(HML_ERR_ARG, "null argument");
+    if (capacity < bytes) return set_err(HML_ERR_ARG, "hml_recording_export: the buffer is smaller than hml_recording_payload_size says");
+    if ((uintptr_t)payload_dev % 8u) return set_err(HML_ERR_ARG, "a recording's payload must be aligned to 8 bytes");
+    const uint32_t T = (uint32_t)c->T;
+    hml_band_edges ed;
+    memset(&ed, 0, sizeof ed);
+    if (kind == HML_REC_BANDS) ed = band_edges_of(c);
+    char* const out = (char*)payload_dev;
+    hipLaunchKernelGGL(hml_k_recpay_header, dim3(1), dim3(64), 0, c->stream, (unsigned long long*)out, (unsigned long long)kind, (unsigned long long)T,
+                       (unsigned long long)rows, (unsigned long long)M, (const unsigned long long*)recorder_counter(c, kind), (unsigned long long)cell, ed);
+    KLAUNCH_CHECK();
+    if (M) {
+        HIPCHK(hipMemcpyAsync(out + HML_RECPAY_FIXED_BYTES, d_pos, M * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+        char* const cells = out + HML_RECPAY_FIXED_BYTES + 8u * ((M + 1u) / 2u);
+        const dim3 grid(grid_for(M, 256, 1, 16384));
+        const hml_recorder& rec = c->rec[kind];
+        if (kind == HML_REC_LEVELS)
+            hipLaunchKernelGGL(hml_k_rec_gather<double>, grid, dim3(256), 0, c->stream, rec.acc<double>(), T, (int)rows, d_pos, (uint32_t)M, (double*)cells);
+        else if (kind == HML_REC_BREAKS)
+            hipLaunchKernelGGL(hml_k_rec_gather<uint32_t>, grid, dim3(256), 0, c->stream, rec.acc<uint32_t>(), T, (int)rows, d_pos, (uint32_t)M, (uint32_t*)cells);
+        else
+            hipLaunchKernelGGL(hml_k_rec_gather<int32_t>, grid, dim3(256), 0, c->stream, rec.acc<int32_t>(), T, (int)rows, d_pos, (uint32_t)M, (int32_t*)cells);
+        KLAUNCH_CHECK();
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));   // (the positions go with this frame)
+    return 0;
+}
+
+// hml_recording_merge_payload.  Everything is checked before anything is written: the header on the host, the positions by
+// hml_k_recpay_check on the device.
+static int payload_merge(hml_ctx* dst, int kind, const void* payload_dev, uint64_t n_bytes) {
+    if (!dst || !dst->model_set) return set_err(HML_ERR_ARG, "model not set");
+    if (int r = payload_kind(kind)) return r;
+    if (!payload_dev) return set_err(HML_ERR_ARG, "null argument");
+    if ((uintptr_t)payload_dev % 8u) return set_err(HML_ERR_ARG, "a recording's payload must be aligned to 8 bytes");
+    if (n_bytes < HML_RECPAY_FIXED_BYTES) return set_err(HML_ERR_ARG, "the payload is shorter than its header");
+    if (int r = ctx_bind(dst)) return r;
+    if (int r = hml_settle(dst)) return r;
+    struct { uint64_t h[HML_RECPAY_HEADER_WORDS]; float edges[HML_RECPAY_EDGE_SLOTS]; } head;
+    static_assert(sizeof head == HML_RECPAY_FIXED_BYTES, "header and edges are 192 bytes");
+    HIPCHK(hipMemcpyAsync(&head, payload_dev, sizeof head, hipMemcpyDeviceToHost, dst->stream));
+    HIPCHK(hipStreamSynchronize(dst->stream));
+    const hml_recorder_kind& rk = hml_recorder_kinds[kind];
+    const uint64_t T = head.h[2], rows = head.h[3], M = head.h[4], N = head.h[5], n_edges = head.h[7];
+    if (head.h[0] != HML_RECPAY_MAGIC) return set_err(HML_ERR_ARG, "the payload does not begin with the magic number of a recording (HMLREC1)");
+    if (head.h[1] != (uint64_t)kind) return set_err(HML_ERR_ARG, std::string("the payload holds another kind of recording, not ") + rk.noun);
+    if (T != dst->T) return set_err(HML_ERR_ARG, std::string("the payload's ") + rk.noun + " were recorded over another number of positions than the destination's");
+    if (kind == HML_REC_BANDS && (n_edges < 1 || n_edges > HML_MAX_BAND_EDGES)) return set_err(HML_ERR_ARG, "the payload's number of band edges must be between 1 and 31");
+    if (kind != HML_REC_BANDS && n_edges != 0) return set_err(HML_ERR_ARG, "the payload carries band edges but is not a bands payload");
+    const uint64_t want_rows = kind == HML_REC_LEVELS ? 2u * (uint64_t)dst->D : kind == HML_REC_BREAKS ? 1u : (uint64_t)dst->D * (n_edges + 1u);
+    if (rows != want_rows || rows > (kind == HML_REC_LEVELS ? 2u * HML_MAX_D : (uint64_t)HML_CAP_K))
+        return set_err(HML_ERR_ARG, std::string("the payload's rows do not match the destination's dimensions") + (kind == HML_REC_BANDS ? " and the payload's edges" : ""));
+    if (head.h[6] != rk.elem) return set_err(HML_ERR_ARG, std::string("the payload's cell size is not the one of ") + rk.noun);
+    if (M > T) return set_err(HML_ERR_ARG, "the payload lists more positions than there are");
+    if (n_bytes != payload_bytes(M, rows, rk.elem)) return set_err(HML_ERR_ARG, "the payload's size in bytes is not the one its header implies");
+    bool take_edges = false;
+    if (kind == HML_REC_BANDS) {
+        for (uint64_t j = 0; j < HML_RECPAY_EDGE_SLOTS; ++j) {
+            uint32_t bits; memcpy(&bits, &head.edges[j], 4);
+            if (j >= n_edges ? bits != 0u : !std::isfinite(head.edges[j]) || (j > 0 && !(head.edges[j - 1] < head.edges[j])))
+                return set_err(HML_ERR_ARG, "the payload's band edges must be finite and strictly ascending, followed by zeros");
+        }
+        if (!same_band_edges(dst, (int)n_edges, head.edges)) {
+            // a destination that was never asked takes the payload's edges; any other difference is refused
+            if (dst->rec[kind].asked || dst->rec[kind].d_acc) return set_err(HML_ERR_ARG, "level bands can only be merged between chains with the same edges, bit for bit");
+            take_edges = true;
+        }
+    }
+    const char* const base = (const char*)payload_dev;
+    const uint32_t* const d_pos = (const uint32_t*)(base + HML_RECPAY_FIXED_BYTES);
+    const char* const cells = base + HML_RECPAY_FIXED_BYTES + 8u * ((M + 1u) / 2u);
+    if (M) {
+        DevBuf b_flag;
+        HIPCHK(hipMalloc(&b_flag.p, sizeof(uint32_t)));
+        HIPCHK(hipMemsetAsync(b_flag.p, 0, sizeof(uint32_t), dst->stream));
+        hipLaunchKernelGGL(hml_k_recpay_check, dim3(grid_for(M, 256, 1, 1024)), dim3(256), 0, dst->stream, d_pos, (uint32_t)M, (uint32_t)T, kind == HML_REC_BREAKS ? 1u : 0u,
+                           b_flag.as<uint32_t>());
+        KLAUNCH_CHECK();
+        uint32_t bad = 0;
+        HIPCHK(hipMemcpyAsync(&bad, b_flag.p, sizeof bad, hipMemcpyDeviceToHost, dst->stream));
+        HIPCHK(hipStreamSynchronize(dst->stream));
+        if (bad & HML_RECPAY_BAD_RANGE) return set_err(HML_ERR_ARG, "the payload lists a position beyond the last one");
+        if (bad & HML_RECPAY_BAD_ZERO) return set_err(HML_ERR_ARG, "a breaks payload lists position 0, which is never a breakpoint");
+        if (bad & HML_RECPAY_BAD_ORDER) return set_err(HML_ERR_ARG, "the payload's positions are not strictly ascending");
+    }
+    // valid: from here on the destination changes
+    if (take_edges) {
+        dst->n_band_edges = (int)n_edges;
+        memset(dst->band_edges, 0, sizeof dst->band_edges);
+        memcpy(dst->band_edges, head.edges, (size_t)n_edges * sizeof(float));
+    }
+    if (int r = ensure_recorder_buffers(dst, kind)) return r;
+    dst->rec[kind].asked = true;
+    const hml_recorder& rd = dst->rec[kind];
+    const dim3 grid(grid_for(M, 256, 1, 16384));
+    unsigned long long* const dst_n = recorder_counter(dst, kind);
+    if (kind == HML_REC_LEVELS)
+        hipLaunchKernelGGL(hml_k_rec_merge_list<double>, grid, dim3(256), 0, dst->stream, d_pos, (const double*)cells, (uint32_t)M, (uint32_t)T, (int)rows, (unsigned long long)N, rd.acc<double>(), rd.d_boundary, dst_n);
+    else if (kind == HML_REC_BREAKS)
+        hipLaunchKernelGGL(hml_k_rec_merge_list<uint32_t>, grid, dim3(256), 0, dst->stream, d_pos, (const uint32_t*)cells, (uint32_t)M, (uint32_t)T, (int)rows, (unsigned long long)N, rd.acc<uint32_t>(), rd.d_boundary, dst_n);
+    else
+        hipLaunchKernelGGL(hml_k_rec_merge_list<int32_t>, grid, dim3(256), 0, dst->stream, d_pos, (const int32_t*)cells, (uint32_t)M, (uint32_t)T, (int)rows, (unsigned long long)N, rd.acc<int32_t>(), rd.d_boundary, dst_n);
+    KLAUNCH_CHECK();
+    HIPCHK(hipStreamSynchronize(dst->stream));
+    return 0;
+}
+
+extern "C" {
+
+int hml_recording_payload_size(hml_ctx* c, int kind, uint64_t* n_bytes) {
+    NEED_MODEL();
+    if (!n_bytes) return set_err(HML_ERR_ARG, "null argument");
+    if (int r = payload_kind(kind)) return r;
+    uint64_t M = 0;
+    DevBuf b_seg;
+    const uint32_t* d_pos = nullptr;
+    if (int r = payload_positions(c, kind, &M, b_seg, &d_pos)) return r;
+    *n_bytes = payload_bytes(M, (uint64_t)recorder_rows(c, kind), hml_recorder_kinds[kind].elem);
+    return 0;
+}
+
+int hml_recording_export(hml_ctx* c, int kind, void* payload_dev, uint64_t capacity_bytes, uint64_t* n_bytes) {
+    NEED_MODEL();
+    if (int r = payload_kind(kind)) return r;
+    return payload_export(c, kind, payload_dev, capacity_bytes, n_bytes);
+}
+
+int hml_recording_merge_payload(hml_ctx* dst, int kind, const void* payload_dev, uint64_t n_bytes) { return payload_merge(dst, kind, payload_dev, n_bytes); }
+
+int hml_recording_merge_across(hml_ctx* dst, hml_ctx* src, int kind) {
+    if (!dst || !src || !dst->model_set || !src->model_set) return set_err(HML_ERR_ARG, "model not set");
+    if (int r = payload_kind(kind)) return r;
+    const hml_recorder_kind& rk = hml_recorder_kinds[kind];
+    const bool per_dimension = kind != HML_REC_BREAKS;
+    if (dst == src) return set_err(HML_ERR_ARG, "a context cannot be merged into itself");
+    if (dst->T != src->T || (per_dimension && dst->D != src->D))
+        return set_err(HML_ERR_ARG, std::string(rk.noun) + " can only be merged between chains over the same positions" + (per_dimension ? " and dimensions" : ""));
+    if (!src->rec[kind].asked) return recorder_none(kind, "the source");
+    // the export, on the source's device
+    if (int r = ctx_bind(src)) return r;
+    if (int r = settle_if_limited(src)) return r;
+    uint64_t bytes = 0;
+    DevBuf b_src, b_dst;
+    {
+        uint64_t M = 0;
+        DevBuf b_seg;
+        const uint32_t* d_pos = nullptr;
+        if (int r = payload_positions(src, kind, &M, b_seg, &d_pos)) return r;
+        bytes = payload_bytes(M, (uint64_t)recorder_rows(src, kind), rk.elem);
+    }
+    HIPCHK(hipMalloc(&b_src.p, bytes));
+    uint64_t written = 0;
+    if (int r = payload_export(src, kind, b_src.p, bytes, &written)) return r;
+    if (written != bytes) return set_err(HML_ERR_HIP, "internal error: a recording changed between its sizing and its export");
+    if (dst->device == src->device) return payload_merge(dst, kind, b_src.p, bytes);
+    // ... its bytes to the destination's device (no peer access needed), and the merge there
+    if (int r = ctx_bind(dst)) return r;
+    HIPCHK(hipMalloc(&b_dst.p, bytes));
+    HIPCHK(hipMemcpyPeer(b_dst.p, dst->device, b_src.p, src->device, bytes));
+    HIPCHK(hipDeviceSynchronize());
+    return payload_merge(dst, kind, b_dst.p, bytes);
+}
+
+}  // extern "C"

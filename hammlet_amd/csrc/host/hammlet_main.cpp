@@ -14,7 +14,9 @@
 // labels - and `-O LC` (bandcalls) writes PREFIXbandcallsSUFFIX, the band called per run under `-bandcall P` (hml_bands_rle,
 // hml_bands_call); `-O R` (rhat) with -chains N writes PREFIXrhatSUFFIX, the agreement of the N chains on the emission level before
 // they are merged: per segment of the union of their level boundaries its length and per data dimension the Gelman-Rubin R-hat
-// (hml_levels_agreement_rle);
+// (hml_levels_agreement_rle); `-merge-gpus` with -chains N lets the levels, breakpoints, consensus, bands, bandcalls and rhat outputs cross
+// GPUs: the chains' recordings reach the first chain's GPU as sparse payloads (hml_recording_merge_across), R-hat is taken over
+// the first chain and shadow contexts on its GPU;
 // -raw FILE reads float32 values instead of text; -device N selects
 // the GPU; -chain N selects the Philox sub-key of an independent chain; -chains N runs N independent chains (sub-keys
 // chain .. chain+N-1), chain k on GPU (device + k) mod #GPUs in its own host thread, and pools their recorded marginals
@@ -96,6 +98,10 @@ static const char* kHelp =
     "                                 The pooled marginals / maxsegmentation files use common labels (states by\n"
     "                                 ascending mean); PREFIX[chainK.]relabelSUFFIX lists each chain's own label of\n"
     "                                 pooled state 0, 1, ... (its parameters / sequences files keep its own labels)\n"
+    "  -merge-gpus                    with -chains N on several GPUs: allow -O L, R, BP, CS, LB and LC - the chains' levels,\n"
+    "                                 breakpoint counts and band counts are sent to the first chain's GPU as lists of the\n"
+    "                                 positions with a change of state and added there in chain order; R-hat is taken there\n"
+    "                                 as well.  On one GPU: the same files as without the flag (extension)\n"
     "  -v, -verbose   -g, -arguments   -h, -help\n";
 
 // one entry of the sampling scheme (-i)
@@ -242,6 +248,34 @@ static void writeRhat(const Job& job, const vector<hml_ctx*>& ctxs, bool verbose
         cout << endl << flush;
     }
 }
+
+// -merge-gpus: the chains of other GPUs as the agreement calls need them - on the first chain's GPU.  A SHADOW of chain k is a
+// context attached to the first chain's observations, with a model of the run's shape and no sweep of its own, that chain k's
+// levels payload was merged into: it reads out like chain k, bit for bit (include/hml.h).  Released with this object.
+class ShadowContexts {
+    vector<hml_ctx*> mOwned;
+
+public:
+    ShadowContexts() = default;
+    ShadowContexts(const ShadowContexts&) = delete;
+    ShadowContexts& operator=(const ShadowContexts&) = delete;
+    ~ShadowContexts() { for (hml_ctx* c : mOwned) hml_destroy(c); }
+    // chain 0 and the shadows of chains 1 .. N-1, in chain order
+    vector<hml_ctx*> of(const Job& job, const vector<hml_ctx*>& ctxs, int device, uint32_t chain) {
+        vector<hml_ctx*> out{ctxs[0]};
+        const float nig[4] = {1.0f, 1.0f, 0.0f, 1.0f};   // (any valid prior: a shadow never sweeps)
+        for (size_t k = 1; k < ctxs.size(); ++k) {
+            hml_ctx* sh = nullptr;
+            hml_check(hml_create(&sh, device, job.seed, chain + (uint32_t)k, nullptr));
+            mOwned.push_back(sh);
+            hml_check(hml_attach_observations(sh, ctxs[0]));
+            hml_check(hml_set_model(sh, (int)job.nrStates, nig, job.trans, job.selfTrans, job.initialAlpha, job.useSelfTrans ? 1 : 0));
+            hml_check(hml_recording_merge_across(sh, ctxs[k], HML_RECORDING_LEVELS));
+            out.push_back(sh);
+        }
+        return out;
+    }
+};
 
 static const char* kBreaksDevicesMessage =
     "The breakpoints of chains on different GPUs are not merged yet: run -O breakpoints / -O consensus with -chains N on one GPU!";
@@ -544,6 +578,7 @@ int main(int argc, const char* argv[]) {
         args.registerFlags({"-consensus"}, "16 0.5");
         args.registerFlags({"-bands"});
         args.registerFlags({"-bandcall"}, "0");
+        args.registerFlags({"-merge-gpus"});
         args.parseArgs();
 
         if (args.isSet("-g")) args.print();
@@ -761,10 +796,12 @@ int main(int argc, const char* argv[]) {
             // nothing is exchanged while sampling; the recorded marginals are pooled by one all-reduce (RCCL) at the end
             int nDev = 1;
             hml_check(hml_device_count(&nDev));
-            if (job.outputs.at("levels") && nDev > 1) throw std::runtime_error(kLevelsDevicesMessage);   // (before anything runs)
-            if (wantsRhat && nDev > 1) throw std::runtime_error(kRhatDevicesMessage);
-            if (wantsBreaks && nDev > 1) throw std::runtime_error(kBreaksDevicesMessage);
-            if (wantsBands && nDev > 1) throw std::runtime_error(kBandsDevicesMessage);
+            // -merge-gpus: the recordings cross GPUs as sparse payloads (below); without it they stay on one
+            const bool mergeGpus = args.isSet("-merge-gpus");
+            if (job.outputs.at("levels") && nDev > 1 && !mergeGpus) throw std::runtime_error(kLevelsDevicesMessage);   // (before anything runs)
+            if (wantsRhat && nDev > 1 && !mergeGpus) throw std::runtime_error(kRhatDevicesMessage);
+            if (wantsBreaks && nDev > 1 && !mergeGpus) throw std::runtime_error(kBreaksDevicesMessage);
+            if (wantsBands && nDev > 1 && !mergeGpus) throw std::runtime_error(kBandsDevicesMessage);
             Rendezvous rv(nrChains);
             // chain k lives on GPU (device + k) mod #GPUs; the chains of one GPU are driven by ONE host thread in lockstep and
             // share the construction of the observations
@@ -814,11 +851,25 @@ int main(int argc, const char* argv[]) {
                 // the chains share the GPU: their levels, breakpoint counts and band counts add up in the first chain's context, which the
                 // files are written from
                 try {
-                    if (wantsRhat) writeRhat(job, ctxs, verbose);   // (the chains one by one: the merge below changes the first)
-                    for (int k = 1; k < nrChains; ++k) {
-                        if (wantsLevels) hml_check(hml_levels_merge(ctxs[0], ctxs[k]));
-                        if (wantsBreaks) hml_check(hml_breaks_merge(ctxs[0], ctxs[k]));
-                        if (wantsBands) hml_check(hml_bands_merge(ctxs[0], ctxs[k]));
+                    if (mergeGpus) {
+                        // ... or they do not: the recordings of chains 1 .. N-1 reach the first chain's GPU as sparse payloads
+                        // (hml_recording_merge_across), in ascending chain index - on one GPU the same additions in the same order
+                        if (wantsRhat) {
+                            ShadowContexts shadows;
+                            writeRhat(job, shadows.of(job, ctxs, device % nDev, chain), verbose);
+                        }
+                        for (int k = 1; k < nrChains; ++k) {
+                            if (wantsLevels) hml_check(hml_recording_merge_across(ctxs[0], ctxs[k], HML_RECORDING_LEVELS));
+                            if (wantsBreaks) hml_check(hml_recording_merge_across(ctxs[0], ctxs[k], HML_RECORDING_BREAKS));
+                            if (wantsBands) hml_check(hml_recording_merge_across(ctxs[0], ctxs[k], HML_RECORDING_BANDS));
+                        }
+                    } else {
+                        if (wantsRhat) writeRhat(job, ctxs, verbose);   // (the chains one by one: the merge below changes the first)
+                        for (int k = 1; k < nrChains; ++k) {
+                            if (wantsLevels) hml_check(hml_levels_merge(ctxs[0], ctxs[k]));
+                            if (wantsBreaks) hml_check(hml_breaks_merge(ctxs[0], ctxs[k]));
+                            if (wantsBands) hml_check(hml_bands_merge(ctxs[0], ctxs[k]));
+                        }
                     }
                     writeContextFiles(job, ctxs[0]);
                 } catch (...) { poolError = std::current_exception(); }

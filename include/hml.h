@@ -259,7 +259,7 @@ int hml_levels_rle(hml_ctx* ctx, uint64_t* n_segments, uint64_t* n_recorded, uin
  * (both computed in double, then rounded once; not-a-number when nothing was recorded). */
 int hml_levels_dense_device(hml_ctx* ctx, void* out_dev /* float [2D][T] */);
 /* Adds `src`'s accumulators, boundary bits and count of recorded sweeps into `dst`; `src` is unchanged and `dst` may go on
- * recording.  Same device, T and D, otherwise HML_ERR_ARG (chains on different GPUs are not merged yet).  Unlike the pooled
+ * recording.  Same device, T and D, otherwise HML_ERR_ARG (chains on different GPUs: hml_recording_merge_across, below).  Unlike the pooled
  * marginals (hml_pool_*, below) this needs NO common labels: the marginals count states, and two chains - or two halves of
  * one - may call the same level "state 1" and "state 3", so pooling them relies on hml_relabel_permutation's ordering by
  * the last sampled means; the level itself is the same number whatever the state is called, so sums over sweeps and
@@ -301,7 +301,8 @@ int hml_levels_on_segments(hml_ctx* ctx, uint64_t n_cuts, const uint32_t* cuts /
  * most N rounded additions into a cell, M in the scan).  A chain whose level never moved can therefore show a tiny positive
  * q_c, and a segment on which no chain's level moved a finite rhat instead of 1 or +infinity.
  * HML_ERR_ARG, each with a message of its own: a null argument, n outside 2 .. 64, a context given twice, chains on different
- * GPUs, different T or D, a context that never recorded levels, N < 2, unequal N.
+ * GPUs (merge their levels payloads into contexts of one device first: hml_recording_merge_payload), different T or D, a context
+ * that never recorded levels, N < 2, unequal N.
  * hml_levels_agreement_rle: within, between and rhat per union segment, [d * n_segments + i]; each of the three may be NULL.
  * Call with seg_len == NULL for n_segments and n_recorded. */
 int hml_levels_agreement_rle(hml_ctx* const* ctxs, int n, uint64_t* n_segments, uint64_t* n_recorded, uint64_t* seg_len /*n_segments*/,
@@ -332,7 +333,7 @@ int hml_breaks_list(hml_ctx* ctx, uint64_t* n_breaks, uint64_t* n_recorded, uint
  * is taken in double and rounded once to float; not-a-number when N = 0. */
 int hml_breaks_dense_device(hml_ctx* ctx, void* out_dev /* float [T] */, uint32_t window);
 /* Adds `src`'s counts, positions and N into `dst`; `src` is unchanged and `dst` may go on recording.  Same device and T,
- * otherwise HML_ERR_ARG (chains on different GPUs are not merged yet).  No common labels are needed. */
+ * otherwise HML_ERR_ARG (chains on different GPUs: hml_recording_merge_across, below).  No common labels are needed. */
 int hml_breaks_merge(hml_ctx* dst, hml_ctx* src);
 /* Consensus breakpoints.  The candidates are the listed positions t_i with counts C_i; mass_i = the sum of C_j over
  * |t_j - t_i| <= window.  Candidate i is SELECTED iff mass_i >= max(min_count, 1) and no other candidate j within the
@@ -375,8 +376,47 @@ int hml_bands_dense_device(hml_ctx* ctx, void* out_dev /* int32 [n_columns][T] *
  * obtain n_runs. */
 int hml_bands_call(hml_ctx* ctx, uint64_t rank, uint64_t* n_runs, uint64_t* run_len /*n_runs*/, int32_t* run_band /*D*n_runs, dimension-major*/);
 /* Adds `src`'s cells, boundary bits and N into `dst`; `src` is unchanged and `dst` may go on recording.  Same device, T, D and
- * bit-identical edges, otherwise HML_ERR_ARG; a `dst` that was never given edges takes `src`'s. */
+ * bit-identical edges, otherwise HML_ERR_ARG (chains on different GPUs: hml_recording_merge_across, below); a `dst` that was never
+ * given edges takes `src`'s. */
 int hml_bands_merge(hml_ctx* dst, hml_ctx* src);
+
+/* ---- sparse payloads: levels, breakpoints and bands across GPUs.  No counterpart in the reference. ----
+ * The three recordings above keep a cell and a boundary bit per change of state, so what another GPU needs of one is a list:
+ * the M positions with a cell and the cells there.  The PAYLOAD is one contiguous buffer in device memory, little endian,
+ * aligned to 8 bytes, of the same form for the three kinds:
+ *     uint64 header[8]  [0] the magic number 0x00314345524C4D48 (the bytes "HMLREC1\0"), [1] the kind, [2] T,
+ *                       [3] rows: 2 D for levels, 1 for breaks, D (n_edges + 1) for bands, [4] M, [5] N, the recorder's count
+ *                       of recorded sweeps, [6] bytes per cell (8, 4, 4), [7] n_band_edges (0 unless bands)
+ *     float  edges[32]  the bands' edges followed by zeros; all zero for levels and breaks
+ *     uint32 pos[M]     strictly ascending, all < T: for levels and bands the positions whose boundary bit is set and the
+ *                       position 0, for breaks the positions with a count (never 0); zero bytes up to a multiple of 8 bytes
+ *     cells[rows][M]    cells[r * M + i] = the recorder's RAW cell of row r at pos[i] - the difference the recorded sweeps
+ *                       accumulated there, not the run-length read-outs' sums: double for levels, uint32 for breaks, int32 for bands
+ * Size: 192 + 8 ceil(M / 2) + rows M (bytes per cell).  A recorder that was asked for but has recorded no sweep exports
+ * M = 0 and N = 0; one that was never asked for is HML_ERR_ARG, with the message of the kind's read-outs.
+ * hml_recording_payload_size / hml_recording_export: the chain is settled, its boundary bitmap compacted, the cells gathered
+ * and the payload written on the context's stream, which is synchronised.  capacity_bytes below the size: HML_ERR_ARG, nothing
+ * is written (n_bytes, if given, still receives the size).
+ * hml_recording_merge_payload: `payload_dev` lies on `dst`'s device.  dst[r][pos[i]] += cells[r * M + i], the boundary bits
+ * are set and N is added - the additions of hml_levels_merge / hml_breaks_merge / hml_bands_merge, in their order, so `dst`
+ * ends in the bits it would hold after that call with the exporting chain as `src`; `dst` may go on recording.  A bands
+ * destination that was never given edges takes the payload's; edges that differ in any bit are refused.  Everything is checked
+ * BEFORE anything is written - magic number, kind, T, rows against `dst`'s D (and the payload's edges), cell size, n_bytes
+ * against the size formula, the edges, and on the device that the positions are strictly ascending, below T and, for breaks,
+ * above 0: each failure is HML_ERR_ARG with a message of its own and leaves `dst` as it was.
+ * hml_recording_merge_across: export on `src`'s device, the bytes to `dst`'s device (hipMemcpyPeer; none when they share
+ * one), merge.  Same T (and D) as for the merges above, otherwise HML_ERR_ARG.
+ * R-HAT ACROSS GPUS needs no call of its own: a context attached to a chain of the target device (hml_attach_observations),
+ * with its model set and no recorded sweep, that a levels payload was merged into reads out exactly like the exporting chain
+ * - the same bits from hml_levels_rle (a cell is never -0.0, so 0.0 + cell is the cell), the same N - and is accepted by
+ * hml_levels_agreement_* beside the chains of that device. */
+#define HML_RECORDING_LEVELS 0
+#define HML_RECORDING_BREAKS 1
+#define HML_RECORDING_BANDS 2
+int hml_recording_payload_size(hml_ctx* ctx, int kind, uint64_t* n_bytes);
+int hml_recording_export(hml_ctx* ctx, int kind, void* payload_dev, uint64_t capacity_bytes, uint64_t* n_bytes);
+int hml_recording_merge_payload(hml_ctx* dst, int kind, const void* payload_dev, uint64_t n_bytes);
+int hml_recording_merge_across(hml_ctx* dst, hml_ctx* src, int kind);
 
 /* Trellis::sample(t) (src/Trellis.hpp:61-66): one draw of std::discrete_distribution over K weights - p_i = w_i / sum in
  * double, first i whose cumulative probability reaches u - with u from the chain's Philox key (sub-stream HOST,
