@@ -862,6 +862,8 @@ int hml_set_model(hml_ctx* c, int K, const float nig4[4], float a_off, float a_d
     m.fwd_burnin_sweeps = c->fwd_burnin_sweeps;
     m.fwd_quiet_need = c->fwd_quiet_need;
     m.n_spans = c->n_spans;
+    // the parameter kernel stamps its stages only when they will be printed (hml_sync): the flag travels with the model
+    m.dbg_t[HML_PARAMS_DBG_FLAG] = getenv("HML_PARAMS_DEBUG") ? 1ull : 0ull;
     // keep the block count of an earlier enumeration (autoprior) out of the model: B = 0
     HIPCHK(hipMemcpyAsync(c->d_mdl, &m, sizeof m, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1423,7 +1425,10 @@ int hml_sync(hml_ctx* c) {
     }
     if (c->model_set && getenv("HML_PARAMS_DEBUG")) {
         hml_model m;
-        if (fetch_model(c, &m) == 0) {
+        // (the kernel stamps only when the model carries the flag, which hml_set_model takes from the same variable)
+        if (fetch_model(c, &m) == 0 && m.dbg_t[HML_PARAMS_DBG_FLAG] == 0ull) {
+            fprintf(stderr, "[params dbg] no stamps: HML_PARAMS_DEBUG was not set when the model was set up\n");
+        } else if (fetch_model(c, &m) == 0) {
             fprintf(stderr, "[params dbg] us since the kernel's start: accumulators read %.2f | tree %.2f | theta drawn %.2f | A gammas %.2f | barrier %.2f | end %.2f\n",
                     (m.dbg_t[1] - m.dbg_t[0]) * 0.01, (m.dbg_t[2] - m.dbg_t[0]) * 0.01, (m.dbg_t[3] - m.dbg_t[0]) * 0.01, (m.dbg_t[4] - m.dbg_t[0]) * 0.01,
                     (m.dbg_t[5] - m.dbg_t[0]) * 0.01, (m.dbg_t[6] - m.dbg_t[0]) * 0.01);

@@ -34,4 +34,25 @@ HML_HD double hml_u2d(uint64_t u) { return __builtin_bit_cast(double, u); }
 
 #define HML_INF_F (hml_u2f(0x7f800000u))
 
+#if defined(__HIPCC__)
+// hml_pin(x): forces the wave-uniform value x into scalar registers AT THIS POINT.  The compiler sinks every load to its
+// first use, and a wait in front of one scalar value waits for every scalar load issued so far: a kernel that reads its
+// model values where it needs them starts with two to four cold memory round trips in a row.  Written as
+//     a = mdl->a; b = mdl->b; ...; hml_pin(a); hml_pin(b); ...
+// every load above the first pin is issued back to back and all of them are waited for ONCE.  The value does not change.
+// Only for values that are uniform by construction - loads through a kernel-argument pointer: a value that differed
+// between lanes would be replaced by its first active lane's.
+// (32-bit values take one scalar register, 64-bit values - an epoch, a double - a pair)
+template <typename T>
+__device__ __forceinline__ void hml_pin(T& x) {
+    static_assert(sizeof(T) == 4 || sizeof(T) == 8, "a 32-bit or a 64-bit value");
+    asm volatile("" : "+s"(x));
+}
+template <typename T, int N>
+__device__ __forceinline__ void hml_pin(T (&x)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) hml_pin(x[i]);
+}
+#endif
+
 #endif

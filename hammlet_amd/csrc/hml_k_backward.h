@@ -141,13 +141,17 @@ struct hml_bwd_ctx {
     hml_amat<K> A;   // registers up to 7 states, the workgroup's LDS copy beyond (hml_k_forward.h)
     float logA[K];
     bool self;
+    int32_t self_word;   // the model's self_trans as loaded
+    // behind the loads of a kernel's head (hml_pin, hml_common.h): A (where it lives in registers), logA, self_trans
+    __device__ __forceinline__ void pin() { A.pin(); hml_pin(logA); hml_pin(self_word); self = self_word != 0; }
 };
 template <int K>
 __device__ __forceinline__ void hml_bwd_ctx_load(hml_bwd_ctx<K>& bx, const hml_model* __restrict__ mdl_ro, const float* lds_A) {
     bx.A.attach(mdl_ro, lds_A);
 #pragma unroll
     for (int i = 0; i < K; ++i) bx.logA[i] = mdl_ro->logA[i];
-    bx.self = mdl_ro->self_trans != 0;
+    bx.self_word = mdl_ro->self_trans;
+    bx.self = bx.self_word != 0;
 }
 
 template <int K>
@@ -206,6 +210,9 @@ __device__ __forceinline__ void hml_bwd_chunk_maps(const float (&r)[K], hml_mode
     if (lane == 0) cmap[c] = map;
 }
 
+// threads per workgroup of the backward-map kernels: the kernels and their launch sites (hml_sweep.hip) share the
+// constant, so the kernels need not fetch blockDim.x from the dispatch packet (a vector load with a wait of its own)
+#define HML_BWD_MAPS_THREADS 256
 // One wavefront per backward chunk.  It first verifies the forward chunks whose rows it is about to read
 // (start vector == predecessor's end vector, bit for bit; see hml_k_forward): after a failed check the chunk
 // goes on the list of the repair step (fail_list, counted by mdl->fwd_mismatch), which also computes its maps.
@@ -217,18 +224,21 @@ __device__ __forceinline__ void hml_b_backward_maps(const float* __restrict__ ro
                                                            uint32_t* __restrict__ fail_list, int L,
                                                            const uint32_t* __restrict__ starts,
                                                            const hml_model* __restrict__ mdl_ro) {
-    const uint32_t B = mdl_ro->B;
-    const uint32_t nchunks = (B + HML_BWD_CHUNK - 1u) / HML_BWD_CHUNK;
-    const int lane = threadIdx.x & 63;
-    const uint32_t wave_global = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
-    const unsigned long long epoch = mdl_ro->epoch;
-    const hml_key key = mdl_ro->key;
-    const int W = (int)mdl_ro->fwd_W;
+    // the head: every model value the kernel needs is requested here, in one group, and waited for once (hml_pin)
+    uint32_t B = mdl_ro->B;
+    unsigned long long epoch = mdl_ro->epoch;
+    hml_key key = mdl_ro->key;
+    uint32_t fwd_W = mdl_ro->fwd_W;
     __shared__ float sm_A[hml_amat<K>::LDS_FLOATS];
-    hml_amat_fill<K>(sm_A, mdl_ro, (int)threadIdx.x, (int)blockDim.x);
     hml_bwd_ctx<K> bx;
     hml_bwd_ctx_load<K>(bx, mdl_ro, sm_A);
+    hml_amat_fill<K>(sm_A, mdl_ro, (int)threadIdx.x, HML_BWD_MAPS_THREADS);
+    hml_pin(B); hml_pin(epoch); hml_pin(key.k0); hml_pin(key.k1); hml_pin(fwd_W); bx.pin();
+    const int W = (int)fwd_W;
+    const uint32_t nchunks = (B + HML_BWD_CHUNK - 1u) / HML_BWD_CHUNK;
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave_global = (blockIdx.x * HML_BWD_MAPS_THREADS + threadIdx.x) >> 6;
+    const uint32_t nwaves = (gridDim.x * HML_BWD_MAPS_THREADS) >> 6;
     const uint32_t C = (B + (uint32_t)L - 1u) / (uint32_t)L;
     for (uint32_t c = wave_global; c < nchunks; c += nwaves) {
         float r[K];
@@ -255,7 +265,7 @@ __device__ __forceinline__ void hml_b_backward_maps(const float* __restrict__ ro
 }
 // the kernel: hml_b_backward_maps over one chain (hml_k_many.h runs it over several chains in one launch)
 template <int K>
-HML_KERNEL __launch_bounds__(256) void hml_k_backward_maps(const float* __restrict__ rows, hml_model* __restrict__ mdl,
+HML_KERNEL __launch_bounds__(HML_BWD_MAPS_THREADS) void hml_k_backward_maps(const float* __restrict__ rows, hml_model* __restrict__ mdl,
                                                            unsigned long long* __restrict__ smap,
                                                            unsigned long long* __restrict__ cmap, const hml_layout lay,
                                                            const float* __restrict__ entry, const float* __restrict__ exitv,
@@ -318,19 +328,22 @@ __device__ __forceinline__ void hml_b_backward_maps2(const float* __restrict__ r
                                                             uint32_t* __restrict__ fail_list, int L,
                                                             const uint32_t* __restrict__ starts,
                                                             const hml_model* __restrict__ mdl_ro) {
-    const uint32_t B = mdl_ro->B;
+    // the head: every model value the kernel needs is requested here, in one group, and waited for once (hml_pin)
+    uint32_t B = mdl_ro->B;
+    unsigned long long epoch = mdl_ro->epoch;
+    hml_key key = mdl_ro->key;
+    uint32_t fwd_W = mdl_ro->fwd_W;
+    __shared__ float sm_A[hml_amat<K>::LDS_FLOATS];
+    hml_bwd_ctx<K> bx;
+    hml_bwd_ctx_load<K>(bx, mdl_ro, sm_A);
+    hml_amat_fill<K>(sm_A, mdl_ro, (int)threadIdx.x, HML_BWD_MAPS_THREADS);
+    hml_pin(B); hml_pin(epoch); hml_pin(key.k0); hml_pin(key.k1); hml_pin(fwd_W); bx.pin();
+    const int W = (int)fwd_W;
     const uint32_t nchunks = (B + HML_BWD_CHUNK - 1u) / HML_BWD_CHUNK;
     const uint32_t npairs = (nchunks + 1u) / 2u;
     const int lane = threadIdx.x & 63, li = lane & 31, half = lane >> 5;
-    const uint32_t wave_global = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
-    const unsigned long long epoch = mdl_ro->epoch;
-    const hml_key key = mdl_ro->key;
-    const int W = (int)mdl_ro->fwd_W;
-    __shared__ float sm_A[hml_amat<K>::LDS_FLOATS];
-    hml_amat_fill<K>(sm_A, mdl_ro, (int)threadIdx.x, (int)blockDim.x);
-    hml_bwd_ctx<K> bx;
-    hml_bwd_ctx_load<K>(bx, mdl_ro, sm_A);
+    const uint32_t wave_global = (blockIdx.x * HML_BWD_MAPS_THREADS + threadIdx.x) >> 6;
+    const uint32_t nwaves = (gridDim.x * HML_BWD_MAPS_THREADS) >> 6;
     const uint32_t C = (B + (uint32_t)L - 1u) / (uint32_t)L;
     for (uint32_t pw = wave_global; pw < npairs; pw += nwaves) {
         const uint32_t c = 2u * pw + (uint32_t)half;                          // this lane's backward chunk

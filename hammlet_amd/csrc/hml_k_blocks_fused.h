@@ -51,7 +51,8 @@ __device__ __forceinline__ unsigned long long hml_group_word(uint32_t gen, uint3
 }
 // the generation of a launch: the chain's epoch (one fused launch per sweep, the parameter kernel advances the epoch at
 // a kernel boundary), so every workgroup of a launch derives the same value whenever it starts
-__device__ __forceinline__ uint32_t hml_fused_generation(const hml_model* mdl) { return ((uint32_t)mdl->epoch + 1u) & HML_FUSED_GEN_MASK; }
+__device__ __forceinline__ uint32_t hml_fused_generation(unsigned long long epoch) { return ((uint32_t)epoch + 1u) & HML_FUSED_GEN_MASK; }
+__device__ __forceinline__ uint32_t hml_fused_generation(const hml_model* mdl) { return hml_fused_generation(mdl->epoch); }
 
 // The word tile `tile` publishes, computed by ONE thread from the summary and the weights (the bounded wait's fallback).
 __device__ __forceinline__ unsigned long long hml_fused_tile_word(const uint8_t* __restrict__ summary, const float* __restrict__ w, uint32_t T,
@@ -93,6 +94,10 @@ HML_KERNEL __launch_bounds__(HML_FUSED_WAVES * 64, 6) void hml_k_blocks_fused(co
     // mdl_ro: the same model through a read-only pointer - the parameters this kernel only reads (threshold, epoch, theta,
     // log-terms; written by the parameter kernel of the sweep before) then come through the scalar unit into scalar
     // registers instead of occupying 4 K + 3 vector registers per lane (the kernel is held to 80 VGPRs for residency)
+    // (T and n_sub lie in the first and the third cache line of the argument segment, the model's pointer in the second:
+    // wanted here, the three lines are in flight together, and the argument batches that follow find them in the scalar
+    // cache - read as the code came to need them, the line of `summary` was a second cold trip in front of the first load)
+    { uint32_t a0 = T, a1 = n_sub; hml_pin(a0); hml_pin(a1); }
     if (dbg && threadIdx.x == 0) dbg[blockIdx.x * 4 + 0] = wall_clock64();
     static_assert(HML_FUSED_MAX_SUB * HML_FUSED_SUB_POSITIONS == (1 << HML_FUSED_POS_BITS), "tile geometry (bit fields of hml_group_word)");
     static_assert(HML_FUSED_MAX_SUB * HML_FUSED_WAVE_BATCH <= 65536, "16-bit offsets into a wavefront's eighth");
@@ -104,10 +109,8 @@ HML_KERNEL __launch_bounds__(HML_FUSED_WAVES * 64, 6) void hml_k_blocks_fused(co
     __shared__ uint32_t wave_total[NW], wave_last[NW];         // block starts per wavefront; 1 + tile-relative position of the last
     __shared__ unsigned long long red_sum[NW], red_near[NW];
     __shared__ uint64_t sm_exp_tab[32];   // hml_expf's table: phase B looks it up at the end of the launch's critical path
-    if (threadIdx.x < 32u) sm_exp_tab[threadIdx.x] = HML_EXP2F_TAB[threadIdx.x];   // (visible behind the barriers of phase A)
     constexpr bool LOOPED = K > 6;        // many states: emission parameters from LDS, states walked in a loop (hml_emit_block_looped)
     __shared__ hml_emit_lds<LOOPED ? K : 1> sm_emit;
-    if (LOOPED) hml_emit_lds_fill<LOOPED ? K : 1>(sm_emit, mdl_ro, (int)threadIdx.x);
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t g = blockIdx.x;
@@ -115,11 +118,31 @@ HML_KERNEL __launch_bounds__(HML_FUSED_WAVES * 64, 6) void hml_k_blocks_fused(co
     const uint32_t eighth = n_sub * (uint32_t)HML_FUSED_WAVE_BATCH;                   // positions per wavefront
     const uint32_t tile_positions = eighth * (uint32_t)NW;
     const uint64_t wave_base = ((uint64_t)g * NW + (uint32_t)wave) * eighth;          // first position of this wavefront's eighth
-    const uint32_t gen = hml_fused_generation(mdl_ro);
+    // The head.  The first batch's summary words - their addresses depend on kernel arguments and indices only - are
+    // requested before anything of the model is waited for; then the model values of phase A and of the hand-off in ONE
+    // group with one wait (hml_pin, hml_common.h); hml_expf's table is requested here too and written to LDS behind
+    // phase A, so wavefront 0 does not stall on it at entry.
+    auto load_batch = [&](uint32_t j, uint32_t (&gw)[HML_SUM_SPANS]) {
+        const uint32_t span0 = (uint32_t)(wave_base / HML_SPAN) + j * HML_SUM_SPANS;
+#pragma unroll
+        for (int s = 0; s < HML_SUM_SPANS; ++s)
+            gw[s] = (j < n_sub && span0 + s < n_spans)
+                        ? __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(summary) + (uint64_t)(span0 + s) * 64u + lane)
+                        : 0u;
+    };
+    uint32_t gw[HML_SUM_SPANS];
+    load_batch(0u, gw);
+    float thr = mdl_ro->thr;
+    unsigned long long epoch = mdl_ro->epoch;
+    uint32_t cap = mdl_ro->cap;
+    int32_t self_word = mdl_ro->self_trans;
+    uint64_t exp_tab_word = 0ull;
+    if (threadIdx.x < 32u) exp_tab_word = HML_EXP2F_TAB[threadIdx.x];
+    if (LOOPED) hml_emit_lds_fill<LOOPED ? K : 1>(sm_emit, mdl_ro, (int)threadIdx.x);
+    hml_pin(thr); hml_pin(epoch); hml_pin(cap); hml_pin(self_word);
+    const uint32_t gen = hml_fused_generation(epoch);
     uint16_t* listed = listed_all[wave];
     uint16_t* masks = mask_all[wave];
-    const float thr = mdl_ro->thr;
-    const uint32_t cap = mdl_ro->cap;
 
     // ---------------- phase A
     uint32_t total = 0u, last1 = 0u;
@@ -166,16 +189,6 @@ HML_KERNEL __launch_bounds__(HML_FUSED_WAVES * 64, 6) void hml_k_blocks_fused(co
         // NaN threshold: !(w < thr) holds everywhere, every position starts a block; key 0 opens every group
         const uint32_t kthr = (thr != thr) ? 0u : hml_weight_key(thr, base);
         const hml_swar_ge sw_ge = hml_swar_ge_make(kthr);
-        auto load_batch = [&](uint32_t j, uint32_t (&gw)[HML_SUM_SPANS]) {
-            const uint32_t span0 = (uint32_t)(wave_base / HML_SPAN) + j * HML_SUM_SPANS;
-#pragma unroll
-            for (int s = 0; s < HML_SUM_SPANS; ++s)
-                gw[s] = (j < n_sub && span0 + s < n_spans)
-                            ? __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(summary) + (uint64_t)(span0 + s) * 64u + lane)
-                            : 0u;
-        };
-        uint32_t gw[HML_SUM_SPANS];
-        load_batch(0u, gw);
         for (uint32_t j = 0; j < n_sub; ++j) {   // wave-uniform
             const uint32_t span0 = (uint32_t)(wave_base / HML_SPAN) + j * HML_SUM_SPANS;
             if (span0 >= n_spans) break;
@@ -217,6 +230,7 @@ HML_KERNEL __launch_bounds__(HML_FUSED_WAVES * 64, 6) void hml_k_blocks_fused(co
         for (int m = 1; m < 64; m <<= 1) { const uint32_t o = __shfl_xor(last1, m); last1 = o > last1 ? o : last1; }
     }
     if (lane == 0) { wave_total[wave] = total; wave_last[wave] = last1; }
+    if (threadIdx.x < 32u) sm_exp_tab[threadIdx.x] = exp_tab_word;   // (requested at the head; visible behind the barriers below)
     __syncthreads();
     if (dbg && threadIdx.x == 0) dbg[blockIdx.x * 4 + 1] = wall_clock64();
     uint32_t wg_total = 0u, wg_last1 = 0u;
@@ -315,7 +329,7 @@ HML_KERNEL __launch_bounds__(HML_FUSED_WAVES * 64, 6) void hml_k_blocks_fused(co
     // ---------------- phase B: emission terms and the writes
     hml_emit_params<LOOPED ? 1 : K> p;
     if (!LOOPED) hml_emit_load<LOOPED ? 1 : K>(p, mdl_ro, mixture);
-    const bool self_trans = mdl_ro->self_trans != 0;
+    const bool self_trans = self_word != 0;
     {
         uint32_t t = first_t, n = first_n;
         float sx = first_sx, sq = first_sq;

@@ -409,6 +409,7 @@ struct hml_amat<K, true> {
         for (int i = 0; i < K * K; ++i) v[i] = mdl->A[i];
     }
     __device__ __forceinline__ float operator[](int i) const { return v[i]; }
+    __device__ __forceinline__ void pin() { hml_pin(v); }   // (hml_common.h: behind the loads of a kernel's head)
 };
 template <int K>
 struct hml_amat<K, false> {
@@ -416,6 +417,7 @@ struct hml_amat<K, false> {
     const float* p;
     __device__ __forceinline__ void attach(const hml_model*, const float* lds) { p = lds; }
     __device__ __forceinline__ float operator[](int i) const { return p[i]; }
+    __device__ __forceinline__ void pin() {}
 };
 template <int K>
 __device__ __forceinline__ void hml_amat_fill(float* lds, const hml_model* mdl, int tid, int nthreads) {
@@ -430,6 +432,7 @@ struct hml_fwd_ctx {
     hml_amat<K> A;
     float invK;
     bool self;
+    int32_t self_word;   // the model's self_trans as loaded (a kernel's head pins it before `self` is derived)
     uint32_t B;
 };
 
@@ -438,7 +441,8 @@ template <int K>
 __device__ __forceinline__ void hml_fwd_ctx_load(hml_fwd_ctx<K>& cx, const hml_model* mdl, const float* lds_A) {
     cx.A.attach(mdl, lds_A);
     cx.invK = (float)(1.0 / (double)(float)K);
-    cx.self = mdl->self_trans != 0;
+    cx.self_word = mdl->self_trans;
+    cx.self = cx.self_word != 0;
     cx.B = mdl->B;
 }
 
@@ -531,6 +535,9 @@ __device__ __forceinline__ void hml_fwd_run(const hml_fwd_ctx<K>& cx, float (&al
     }
 }
 
+// threads per workgroup of the forward kernel: the kernel and its launch sites (hml_sweep.hip) share the constant, so the
+// kernel need not fetch blockDim.x from the dispatch packet (a vector load with a wait of its own in the kernel's head)
+#define HML_FWD_THREADS 256
 // The speculative pass: every chunk warms up over the W blocks before it, stores the vector it then starts from
 // (entry) and the one it ends in (exit).  Verification (entry[c] == exit[c-1], bit for bit) happens in the
 // backward-map kernel, which reads the rows anyway; repairs in hml_fwd_repair.
@@ -541,14 +548,27 @@ __device__ __forceinline__ void hml_b_forward(const float* __restrict__ em, cons
                                                      float* __restrict__ exitv, uint32_t* __restrict__ fb_count, int L,
                                                      const hml_layout lay) {
     __shared__ float sm_A[hml_amat<K>::LDS_FLOATS];
-    hml_amat_fill<K>(sm_A, mdl, (int)threadIdx.x, (int)blockDim.x);
+    // the head: every model value the kernel needs is requested here, in one group, and waited for once (hml_pin)
     hml_fwd_ctx<K> cx;
     hml_fwd_ctx_load<K>(cx, mdl, sm_A);
+    uint32_t fwd_W = mdl->fwd_W;   // adaptive, device-resident
+    // (pi too while A lives in registers; with more states it is read where a chunk starts from it, as before: held in
+    // registers across the loop it cost the K = 10 kernel 130 spilled vector registers)
+    constexpr bool PI_HEAD = K <= HML_A_REGISTERS_MAX_K;
+    float pi[PI_HEAD ? K : 1];
+    if constexpr (PI_HEAD) {
+#pragma unroll
+        for (int s = 0; s < K; ++s) pi[s] = mdl->pi[s];
+    }
+    hml_amat_fill<K>(sm_A, mdl, (int)threadIdx.x, HML_FWD_THREADS);
+    cx.A.pin(); hml_pin(cx.B); hml_pin(cx.self_word); hml_pin(fwd_W);
+    if constexpr (PI_HEAD) hml_pin(pi);
+    cx.self = cx.self_word != 0;
     const uint32_t B = cx.B;
-    const int W = (int)mdl->fwd_W;   // adaptive, device-resident
+    const int W = (int)fwd_W;
     const uint32_t C = (B + (uint32_t)L - 1u) / (uint32_t)L;
-    const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t nthreads = gridDim.x * blockDim.x;
+    const uint32_t gid = blockIdx.x * HML_FWD_THREADS + threadIdx.x;
+    const uint32_t nthreads = gridDim.x * HML_FWD_THREADS;
     if (gid < (uint32_t)K && aprobe) aprobe[gid] = mdl->pi[gid];
     // grid-stride over chunks: correctness never depends on the launch size (B is only known on the device)
     for (uint32_t c = gid; c < C; c += nthreads) {
@@ -559,7 +579,7 @@ __device__ __forceinline__ void hml_b_forward(const float* __restrict__ em, cons
         float alpha[K];
         uint32_t nfb = 0;
 #pragma unroll
-        for (int s = 0; s < K; ++s) alpha[s] = exact ? mdl->pi[s] : cx.invK;
+        for (int s = 0; s < K; ++s) alpha[s] = exact ? (PI_HEAD ? pi[PI_HEAD ? s : 0] : mdl->pi[s]) : cx.invK;
         hml_fwd_run<K, false>(cx, alpha, em, gsc, rows, aprobe, ws, first, nfb, lay);   // warm-up, nothing stored
 #pragma unroll
         for (int s = 0; s < K; ++s) entry[(uint64_t)c * K + s] = alpha[s];
@@ -574,7 +594,7 @@ __device__ __forceinline__ void hml_b_forward(const float* __restrict__ em, cons
 }
 // the kernel: hml_b_forward over one chain (hml_k_many.h runs it over several chains in one launch)
 template <int K>
-HML_KERNEL __launch_bounds__(256) void hml_k_forward(const float* __restrict__ em, const float* __restrict__ gsc,
+HML_KERNEL __launch_bounds__(HML_FWD_THREADS) void hml_k_forward(const float* __restrict__ em, const float* __restrict__ gsc,
                                                      hml_model* __restrict__ mdl, float* __restrict__ rows,
                                                      float* __restrict__ aprobe, float* __restrict__ entry,
                                                      float* __restrict__ exitv, uint32_t* __restrict__ fb_count, int L,

@@ -59,12 +59,12 @@ HML_KERNEL __launch_bounds__(256) void hml_m_stats_emission(const hml_chain_dev*
     hml_b_stats_emission<K>(c.ia, c.starts, c.mdl, c.bstat, c.em, with_gsc ? c.gsc : nullptr, nullptr, 0, c.lay);
 }
 template <int K>
-HML_KERNEL __launch_bounds__(256) void hml_m_forward(const hml_many_args a, int with_gsc, int L) {
+HML_KERNEL __launch_bounds__(HML_FWD_THREADS) void hml_m_forward(const hml_many_args a, int with_gsc, int L) {
     const hml_chain_dev& c = a.c[blockIdx.y];
     hml_b_forward<K>(c.em, with_gsc ? c.gsc : nullptr, c.mdl, c.rows, nullptr, c.entry, c.exitv, c.fb, L, c.lay);
 }
 template <int K>
-HML_KERNEL __launch_bounds__(256) void hml_m_backward_maps(const hml_many_args a, int with_gsc, int L) {
+HML_KERNEL __launch_bounds__(HML_BWD_MAPS_THREADS) void hml_m_backward_maps(const hml_many_args a, int with_gsc, int L) {
     const hml_chain_dev& c = a.c[blockIdx.y];
     hml_b_backward_maps2<K>(c.rows, c.mdl, c.smap, c.cmap, c.lay, c.entry, c.exitv, c.redo, L, with_gsc ? nullptr : c.starts, c.mdl);   // (two rows per lane)
 }

@@ -8,6 +8,43 @@
 #include "hml_k_backward.h"
 #include "hml_state.h"
 
+// The fields of the model that the warm-up adaptation at the end of the parameter kernel reads and writes, and the sweep
+// counters it advances: loaded in the kernel's head with everything else (scalar loads, one wait), kept in scalar registers,
+// and written back by the one lane that runs the rule.  Read where the rule uses them they were loads through the cache
+// behind the kernel's last barrier, several in a row, on the lane whose last store ends the launch.
+struct hml_warmup_state {
+    uint32_t fwd_W, fwd_W0, fwd_quiet, fwd_W_burnin, fwd_burnin_sweeps, fwd_quiet_need;
+    uint32_t tre_fused, tre_hi_shift, tre_lo_shift, tre_W_floor, tre_floor_age;
+    uint32_t wl_W_need, wl_need_age;
+    uint32_t B;
+    unsigned long long forward_refits, forward_serial, fwd_refits_seen, fwd_serial_seen, sweeps, block_updates;
+    __device__ __forceinline__ void load(const hml_model* mdl) {
+        fwd_W = mdl->fwd_W; fwd_W0 = mdl->fwd_W0; fwd_quiet = mdl->fwd_quiet; fwd_W_burnin = mdl->fwd_W_burnin;
+        fwd_burnin_sweeps = mdl->fwd_burnin_sweeps; fwd_quiet_need = mdl->fwd_quiet_need;
+        tre_fused = mdl->tre_fused; tre_hi_shift = mdl->tre_hi_shift; tre_lo_shift = mdl->tre_lo_shift;
+        tre_W_floor = mdl->tre_W_floor; tre_floor_age = mdl->tre_floor_age;
+        wl_W_need = mdl->wl_W_need; wl_need_age = mdl->wl_need_age;
+        B = mdl->B;
+        forward_refits = mdl->forward_refits; forward_serial = mdl->forward_serial;
+        fwd_refits_seen = mdl->fwd_refits_seen; fwd_serial_seen = mdl->fwd_serial_seen;
+        sweeps = mdl->sweeps; block_updates = mdl->block_updates;
+    }
+    __device__ __forceinline__ void pin() {
+        hml_pin(fwd_W); hml_pin(fwd_W0); hml_pin(fwd_quiet); hml_pin(fwd_W_burnin); hml_pin(fwd_burnin_sweeps); hml_pin(fwd_quiet_need);
+        hml_pin(tre_fused); hml_pin(tre_hi_shift); hml_pin(tre_lo_shift); hml_pin(tre_W_floor); hml_pin(tre_floor_age);
+        hml_pin(wl_W_need); hml_pin(wl_need_age); hml_pin(B);
+        hml_pin(forward_refits); hml_pin(forward_serial); hml_pin(fwd_refits_seen); hml_pin(fwd_serial_seen);
+        hml_pin(sweeps); hml_pin(block_updates);
+    }
+    // what the adaptation may have changed
+    __device__ __forceinline__ void store_adapted(hml_model* mdl) const {
+        mdl->fwd_W = fwd_W; mdl->fwd_quiet = fwd_quiet;
+        mdl->tre_W_floor = tre_W_floor; mdl->tre_floor_age = tre_floor_age;
+        mdl->wl_W_need = wl_W_need; mdl->wl_need_age = wl_need_age;
+        mdl->fwd_refits_seen = fwd_refits_seen; mdl->fwd_serial_seen = fwd_serial_seen;
+    }
+};
+
 struct hml_dev_src {
     hml_stream s;
     __device__ __forceinline__ uint32_t next() { return hml_stream_next(&s); }
@@ -85,41 +122,68 @@ __device__ __forceinline__ void hml_b_params(hml_model* __restrict__ mdl, typena
     __shared__ unsigned long long s_trans[K * K];
     __shared__ unsigned long long s_occ[K];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // a halted chain (the sweep's enumeration found more blocks than its buffers hold, hml_state.h): the sweep did not happen
-    if (mode == 0 && mdl->halted != 0u) return;   // workgroup-uniform, before any barrier
-    if (tid == 0) mdl->dbg_t[0] = wall_clock64();
     __shared__ float s_var[K], s_logN[K];
-    const int P = mdl->P, D = mdl->D;
-    const unsigned long long epoch = mdl->epoch;
-    const hml_key key = mdl->key;
+    // ---- The head: every value of the model that the kernel needs - what decides whether it runs at all, the keys of the
+    // draws, the priors it resets the posteriors to, the state of the warm-up adaptation at the kernel's end - is requested
+    // HERE, in one group with the hyperparameters and the count accumulators, and waited for once (hml_pin, hml_common.h).
+    // Read where they are used they were three cold round trips in a row at the start, and loads through the cache
+    // behind the last barrier, one after the other on the lane that ends the kernel.  Nothing is stored before the halted
+    // chain's early return.  The vector loads are bounded by the compile-time K (nig_post, dirA and dirPi have HML_CAP_K
+    // rows); `lane < P` applies where a value is used.
     // hyperparameters of this thread's variate, requested before the reductions below need the memory pipeline
     float hyp0 = 0.0f, hyp1 = 0.0f, hyp2 = 0.0f, hyp3 = 0.0f;
-    if (wave == 0 && lane < P) { hyp0 = mdl->nig_post[lane][0]; hyp1 = mdl->nig_post[lane][1]; hyp2 = mdl->nig_post[lane][2]; hyp3 = mdl->nig_post[lane][3]; }
+    if (wave == 0 && lane < K) { hyp0 = mdl->nig_post[lane][0]; hyp1 = mdl->nig_post[lane][1]; hyp2 = mdl->nig_post[lane][2]; hyp3 = mdl->nig_post[lane][3]; }
     if (wave == 1 && lane < K) hyp0 = mdl->dirPi[lane];
     if (tid >= 128 && tid < 128 + K * K) hyp0 = mdl->dirA[tid - 128];
-    // gather the split integer accumulators (SPREAD: every workgroup reads them, the one that goes on resets them - below, once it
+    // the split integer accumulators (SPREAD: every workgroup reads them, the one that goes on resets them - below, once it
     // knows it is the one; each workgroup has read them before it takes its ticket)
+    // (ONE group of loads for both kinds of counter - a thread holds a transition count or an occupancy, never both: two
+    // groups into one register array were serialised by the compiler, two arrays cost 32 more vector registers)
+    unsigned long long cnt_v[HML_CNT_SPLIT];
+#pragma unroll
+    for (int sp = 0; sp < HML_CNT_SPLIT; ++sp) cnt_v[sp] = 0ull;
+    const bool has_trans = tid >= 128 && tid < 128 + K * K, has_occ = tid >= 512 && tid < 512 + K;
+    if (has_trans || has_occ) {
+        const unsigned long long* const src = has_trans ? &mdl->trans[0][tid - 128] : &mdl->occ[0][tid - 512];
+        const int pitch = has_trans ? HML_MAX_K * HML_MAX_K : HML_MAX_K;   // counters per split
+#pragma unroll
+        for (int sp = 0; sp < HML_CNT_SPLIT; ++sp) cnt_v[sp] = src[sp * pitch];   // all loads in flight together
+    }
+    uint32_t halted = mdl->halted;
+    int32_t P = mdl->P, D = mdl->D;
+    unsigned long long epoch = mdl->epoch;
+    hml_key key = mdl->key;
+    unsigned long long dbg_word = mdl->dbg_t[HML_PARAMS_DBG_FLAG];
+    uint32_t m_T = mdl->T;
+    int32_t m_dynamic = mdl->dynamic;
+    float nig_prior[4] = {mdl->nig_prior[0], mdl->nig_prior[1], mdl->nig_prior[2], mdl->nig_prior[3]};
+    float a_off = mdl->a_off, a_diag = mdl->a_diag, pi_alpha = mdl->pi_alpha;
+    hml_warmup_state ws;
+    ws.load(mdl);
+    hml_pin(halted); hml_pin(P); hml_pin(D); hml_pin(epoch); hml_pin(key.k0); hml_pin(key.k1); hml_pin(dbg_word);
+    hml_pin(m_T); hml_pin(m_dynamic); hml_pin(nig_prior); hml_pin(a_off); hml_pin(a_diag); hml_pin(pi_alpha);
+    ws.pin();
+    // a halted chain (the sweep's enumeration found more blocks than its buffers hold, hml_state.h): the sweep did not happen
+    if (mode == 0 && halted != 0u) return;   // workgroup-uniform, before any barrier and before any store
+    // stage stamps (printed by hml_sync with HML_PARAMS_DEBUG, which sets the flag when the model is set up): without the
+    // flag the kernel reads no clock
+    const bool dbg = dbg_word != 0ull;
+    if (dbg && tid == 0) mdl->dbg_t[0] = wall_clock64();
     unsigned long long acc_total = 0ull;
     if (tid >= 128 && tid < 128 + K * K) {
         const int e = tid - 128;
-        unsigned long long v[HML_CNT_SPLIT];
-#pragma unroll
-        for (int sp = 0; sp < HML_CNT_SPLIT; ++sp) v[sp] = mdl->trans[sp][e];   // all loads in flight together
         unsigned long long t = 0ull;
 #pragma unroll
-        for (int sp = 0; sp < HML_CNT_SPLIT; ++sp) { t += v[sp]; if (!SPREAD) mdl->trans[sp][e] = 0ull; }
+        for (int sp = 0; sp < HML_CNT_SPLIT; ++sp) { t += cnt_v[sp]; if (!SPREAD) mdl->trans[sp][e] = 0ull; }
         s_trans[e] = t;
         if (!SPREAD) mdl->last_trans[e] = t;
         acc_total = t;
     }
     if (tid >= 512 && tid < 512 + K) {
         const int k = tid - 512;
-        unsigned long long v[HML_CNT_SPLIT];
-#pragma unroll
-        for (int sp = 0; sp < HML_CNT_SPLIT; ++sp) v[sp] = mdl->occ[sp][k];
         unsigned long long t = 0ull;
 #pragma unroll
-        for (int sp = 0; sp < HML_CNT_SPLIT; ++sp) { t += v[sp]; if (!SPREAD) mdl->occ[sp][k] = 0ull; }
+        for (int sp = 0; sp < HML_CNT_SPLIT; ++sp) { t += cnt_v[sp]; if (!SPREAD) mdl->occ[sp][k] = 0ull; }
         s_occ[k] = t;
         if (!SPREAD) mdl->last_occ[k] = t;
         acc_total = t;
@@ -153,7 +217,7 @@ __device__ __forceinline__ void hml_b_params(hml_model* __restrict__ mdl, typena
     // a barrier that waits for LDS traffic only (__syncthreads would also wait for every outstanding global load)
     if (SPREAD) __syncthreads();   // (this workgroup's first-level sums are on their way before its ticket is taken)
     else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    if (tid == 0) mdl->dbg_t[1] = wall_clock64();
+    if (dbg && tid == 0) mdl->dbg_t[1] = wall_clock64();
     if constexpr (SPREAD) {
         // the ticket, by the last wavefront (it draws nothing) while the others draw
         static_assert(NDRAW <= 8, "wavefronts 8 (occupancies) and 15 (ticket) draw nothing");
@@ -197,7 +261,7 @@ __device__ __forceinline__ void hml_b_params(hml_model* __restrict__ mdl, typena
         th_gcore = hml_gamma_core_f32<hml_devmath>(src, th_alpha);
         hml_normal_f32<hml_devmath> nd;
         th_z = nd.draw_std(src);
-        if (tid == 0) mdl->dbg_t[7] = wall_clock64();
+        if (dbg && tid == 0) mdl->dbg_t[7] = wall_clock64();
     }
     if (mode != 2) {
         if (wave == 1 && lane < K) {
@@ -215,7 +279,7 @@ __device__ __forceinline__ void hml_b_params(hml_model* __restrict__ mdl, typena
             graw[e] = hml_gamma_f32<hml_devmath>(src, al, 1.0f);
         }
     }
-    if (tid == 128) mdl->dbg_t[4] = wall_clock64();
+    if (dbg && tid == 128) mdl->dbg_t[4] = wall_clock64();
 
     if constexpr (SPREAD) {
         __syncthreads();   // the ticket's outcome and, in the workgroup that goes on, the first-level sums
@@ -249,7 +313,7 @@ __device__ __forceinline__ void hml_b_params(hml_model* __restrict__ mdl, typena
                 if (lane == 0) { wp[mirror][s][0] = a; wp[mirror][s][1] = d; }
             }
         }
-        if (tid == 1023) mdl->dbg_t[8] = wall_clock64();
+        if (dbg && tid == 1023) mdl->dbg_t[8] = wall_clock64();
         __syncthreads();
         // ... then a pairwise tree over the 16 wavefront sums
         if (tid < 2 * K) {
@@ -264,7 +328,7 @@ __device__ __forceinline__ void hml_b_params(hml_model* __restrict__ mdl, typena
             fin[s][c] = (float)v[0];
         }
         __syncthreads();
-        if (tid == 0) mdl->dbg_t[2] = wall_clock64();
+        if (dbg && tid == 0) mdl->dbg_t[2] = wall_clock64();
     }
 
     if (wave == 0 && lane < P) {
@@ -309,11 +373,11 @@ __device__ __forceinline__ void hml_b_params(hml_model* __restrict__ mdl, typena
             s_var[k] = v;
         }
 #pragma unroll
-        for (int i = 0; i < 4; ++i) mdl->nig_post[k][i] = mdl->nig_prior[i];
-        if (tid == 0) mdl->dbg_t[3] = wall_clock64();
+        for (int i = 0; i < 4; ++i) mdl->nig_post[k][i] = nig_prior[i];
+        if (dbg && tid == 0) mdl->dbg_t[3] = wall_clock64();
     }
     __syncthreads();
-    if (tid == 0) mdl->dbg_t[5] = wall_clock64();
+    if (dbg && tid == 0) mdl->dbg_t[5] = wall_clock64();
     if (mode != 2) {
         // dirichlet_sample's normalisation (Distribution.hpp:116-139): float sum in index order
         if (tid < K) {
@@ -334,11 +398,11 @@ __device__ __forceinline__ void hml_b_params(hml_model* __restrict__ mdl, typena
             float mv = HML_INF_F;
 #pragma unroll
             for (int k = 0; k < P; ++k) { const float v = s_var[k]; mv = (v < mv) ? v : mv; }   // std::min(result, var)
-            const float l = hml_logf((float)mdl->T);
+            const float l = hml_logf((float)m_T);
             const float arg = 2 * l * mv;
             const float t = HML_SQRTF(arg);
             mdl->thr_theta = t;
-            if (mdl->dynamic) mdl->thr = t;
+            if (m_dynamic) mdl->thr = t;
         }
         if (tid == 64) {
             float sum = 0.0f;
@@ -350,11 +414,11 @@ __device__ __forceinline__ void hml_b_params(hml_model* __restrict__ mdl, typena
         // reset Dirichlet posteriors and the sweep's accumulators
         if (tid >= 128 && tid < 128 + K * K) {
             const int e = tid - 128;
-            mdl->dirA[e] = (e / K == e % K) ? mdl->a_diag : mdl->a_off;
+            mdl->dirA[e] = (e / K == e % K) ? a_diag : a_off;
         }
         if (tid >= 512 && tid < 512 + K) {
             const int k = tid - 512;
-            mdl->dirPi[k] = mdl->pi_alpha;
+            mdl->dirPi[k] = pi_alpha;
         }
     }
     if (mode != 0) {
@@ -363,23 +427,25 @@ __device__ __forceinline__ void hml_b_params(hml_model* __restrict__ mdl, typena
         hml_derive<K>(mdl, tid);
     }
     if (tid == 1023) {
+        // (`ws`: the model's fields of this rule as the kernel's head read them - nothing in this launch writes them before
+        // this point - under their own names; what the rule changes goes back to the model at its end, hml_warmup_state)
         // adapt the forward warm-up (speed only - the rows are bit-exact for every W): double it when the repair step
         // had real work - its serial pass ran, or it recomputed more than a handful of chunks - and shrink it slowly
         // after fwd_quiet_need (16) sweeps without a single refit (shrinking while a few chunks still fail was measured: the failure
         // count has a cliff, sweeps with 10^5 refits follow)
         if (mode == 0) {
-            uint32_t W = mdl->fwd_W;
-            const unsigned long long refits = mdl->forward_refits - mdl->fwd_refits_seen;
-            const unsigned long long serial = mdl->forward_serial - mdl->fwd_serial_seen;
+            uint32_t W = ws.fwd_W;
+            const unsigned long long refits = ws.forward_refits - ws.fwd_refits_seen;
+            const unsigned long long serial = ws.forward_serial - ws.fwd_serial_seen;
             // a handful: none while a sweep has fewer than 2^22 blocks (a repair is then a visible share of the sweep),
             // one chunk in some thousands beyond
-            const unsigned long long handful = (mdl->B >> 22) ? (((unsigned long long)(mdl->B >> 16) > 16ull) ? (unsigned long long)(mdl->B >> 16) : 16ull) : 0ull;
-            if (mdl->tre_fused && (mdl->B >> 22)) {
+            const unsigned long long handful = (ws.B >> 22) ? (((unsigned long long)(ws.B >> 16) > 16ull) ? (unsigned long long)(ws.B >> 16) : 16ull) : 0ull;
+            if (ws.tre_fused && (ws.B >> 22)) {
                 // fused trellis path: a stale chunk costs one wavefront ~0.1 ms, in parallel with all the others, while
                 // every block pays for the warm-up - so the warm-up follows the refit count down to a few per
                 // ten thousand chunks instead of insisting on none: +8 above B / 2^17 refits (or a sequential finish),
                 // -8 below B / 2^20
-                const unsigned long long hi = (unsigned long long)(mdl->B >> mdl->tre_hi_shift) + 16ull, lo = (unsigned long long)(mdl->B >> mdl->tre_lo_shift) + 2ull;
+                const unsigned long long hi = (unsigned long long)(ws.B >> ws.tre_hi_shift) + 16ull, lo = (unsigned long long)(ws.B >> ws.tre_lo_shift) + 2ull;
                 // The number of stale chunks is a cliff in W (a factor 10-100 per 8 rows below some length that depends on the
                 // parameters), so the band between `lo` and `hi` may hold no W at all: the rule would then step down into the
                 // cliff and back up every other sweep (K = 6 on 5e7 blocks: 61 000 refits per sweep on average, 1.0 ms of a
@@ -387,11 +453,11 @@ __device__ __forceinline__ void hml_b_params(hml_model* __restrict__ mdl, typena
                 // one step above it - and forgotten one step every 256 sweeps (the parameters move).
                 if (serial != 0ull || refits > hi) {
                     W = (W + 8u < (uint32_t)HML_TRE_HALO_MAX) ? W + 8u : (uint32_t)HML_TRE_HALO_MAX;
-                    mdl->tre_W_floor = W;
-                    mdl->tre_floor_age = 0u;
+                    ws.tre_W_floor = W;
+                    ws.tre_floor_age = 0u;
                 } else {
-                    if (++mdl->tre_floor_age >= 256u) { mdl->tre_floor_age = 0u; mdl->tre_W_floor = (mdl->tre_W_floor > 8u) ? mdl->tre_W_floor - 8u : 0u; }
-                    const uint32_t lowest = (mdl->tre_W_floor > 8u) ? mdl->tre_W_floor : 8u;
+                    if (++ws.tre_floor_age >= 256u) { ws.tre_floor_age = 0u; ws.tre_W_floor = (ws.tre_W_floor > 8u) ? ws.tre_W_floor - 8u : 0u; }
+                    const uint32_t lowest = (ws.tre_W_floor > 8u) ? ws.tre_W_floor : 8u;
                     if (refits < lo && W >= lowest + 8u) W -= 8u;
                 }
                 if (W > (uint32_t)HML_TRE_HALO_MAX) W = (uint32_t)HML_TRE_HALO_MAX;
@@ -401,35 +467,36 @@ __device__ __forceinline__ void hml_b_params(hml_model* __restrict__ mdl, typena
             // rows) above it: a sweep with stale chunks costs a repair by ONE workgroup - with 8 states on config 3's trace (3 10^5
             // blocks) the warm-up went 48 -> 36 -> 24 -> some two hundred stale chunks -> 48 every 33 sweeps, and the repairs were 137 us
             // of the 169 us average sweep.  (wl_W_need / wl_need_age: the fields of hml_k_wide_lanes.h's rule; a context has one path.)
-            if (mdl->wl_W_need != 0u && ++mdl->wl_need_age > 128u) mdl->wl_W_need = 0u;
+            if (ws.wl_W_need != 0u && ++ws.wl_need_age > 128u) ws.wl_W_need = 0u;
             if (serial != 0ull || refits > handful) {
                 // (a failure of a few chunks is cheap and a short warm-up worth more: the headline's chain walks down to 12 rows and repairs 1-5
                 // chunks every twenty-odd sweeps - held at 20-24 rows for 512 sweeps it lost 3 %; remembered from 16 stale chunks on, or a serial
                 // pass, and for 128 sweeps; not for chains batched by hml_iterate_many (MANY), whose launches are bound by throughput: eight
                 // chains lost 6 % with it)
-                if (mdl->sweeps >= (unsigned long long)mdl->fwd_burnin_sweeps && (serial != 0ull || refits >= 16ull) && !MANY) { mdl->wl_W_need = W; mdl->wl_need_age = 0u; }
-                W = (2u * W < 1024u) ? 2u * W : 1024u; mdl->fwd_quiet = 0u;
+                if (ws.sweeps >= (unsigned long long)ws.fwd_burnin_sweeps && (serial != 0ull || refits >= 16ull) && !MANY) { ws.wl_W_need = W; ws.wl_need_age = 0u; }
+                W = (2u * W < 1024u) ? 2u * W : 1024u; ws.fwd_quiet = 0u;
             } else if (refits == 0ull) {
-                uint32_t floorW = (mdl->sweeps < (unsigned long long)mdl->fwd_burnin_sweeps) ? mdl->fwd_W_burnin : mdl->fwd_W0;
-                if (mdl->wl_W_need != 0u) { const uint32_t keep = ((mdl->wl_W_need + 8u) & ~7u) < 1024u ? ((mdl->wl_W_need + 8u) & ~7u) : 1024u; floorW = keep > floorW ? keep : floorW; }
-                if (++mdl->fwd_quiet >= mdl->fwd_quiet_need) {
+                uint32_t floorW = (ws.sweeps < (unsigned long long)ws.fwd_burnin_sweeps) ? ws.fwd_W_burnin : ws.fwd_W0;
+                if (ws.wl_W_need != 0u) { const uint32_t keep = ((ws.wl_W_need + 8u) & ~7u) < 1024u ? ((ws.wl_W_need + 8u) & ~7u) : 1024u; floorW = keep > floorW ? keep : floorW; }
+                if (++ws.fwd_quiet >= ws.fwd_quiet_need) {
                     const uint32_t w2 = W - W / 4u;
                     const uint32_t lower = (w2 > floorW) ? ((w2 & ~7u) > floorW ? (w2 & ~7u) : floorW) : floorW;
                     W = lower < W ? lower : W;   // (the floor may lie above the warm-up: the walk down never raises it)
-                    mdl->fwd_quiet = 0u;
+                    ws.fwd_quiet = 0u;
                 }
-            } else mdl->fwd_quiet = 0u;
+            } else ws.fwd_quiet = 0u;
             }
-            mdl->fwd_W = W;
-            mdl->fwd_refits_seen = mdl->forward_refits;
-            mdl->fwd_serial_seen = mdl->forward_serial;
+            ws.fwd_W = W;
+            ws.fwd_refits_seen = ws.forward_refits;
+            ws.fwd_serial_seen = ws.forward_serial;
             mdl->fwd_serial_ran = 0u;
+            ws.store_adapted(mdl);
         }
-        mdl->dbg_t[6] = wall_clock64();
+        if (dbg) mdl->dbg_t[6] = wall_clock64();
         mdl->fwd_mismatch = 0u;
         mdl->fwd_mismatch2 = 0u;
         mdl->epoch = epoch + 1ull;
-        if (mode == 0) { mdl->sweeps += 1ull; mdl->block_updates += (unsigned long long)mdl->B; }
+        if (mode == 0) { mdl->sweeps = ws.sweeps + 1ull; mdl->block_updates = ws.block_updates + (unsigned long long)ws.B; }
     }
 }
 // the kernel: hml_b_params over one chain (hml_k_many.h runs it over several chains in one launch)

@@ -120,7 +120,10 @@ struct hml_model {
     uint32_t tre_W_floor, tre_floor_age;   // ... and does not shrink below the length that last let the refits explode (forgotten slowly)
     unsigned long long fwd_refits_seen, fwd_serial_seen;
     uint32_t params_ticket;      // arrivals of the parameter kernel's workgroups (hml_k_params.h: the last of every 16 goes on)
-    unsigned long long dbg_t[12];   // wall_clock64 stamps of the parameter kernel's stages (printed by hml_sync with HML_PARAMS_DEBUG)
+    // wall_clock64 stamps of the parameter kernel's stages (printed by hml_sync with HML_PARAMS_DEBUG); the last word is the
+    // flag that asks for them (hml_set_model sets it from HML_PARAMS_DEBUG): without it the kernel reads no clock
+#define HML_PARAMS_DBG_FLAG 11
+    unsigned long long dbg_t[12];
     // more than 16 states, a chunk a lane (hml_k_wide_lanes.h): this sweep's chunk length (log2) and the chunk-transposed arrays' stride
     uint32_t wl_lshift, wl_cstride;
     // ... the warm-up of its backward draws' chunks, adapted on its own (chains of draws from different states coalesce within a few

@@ -197,10 +197,10 @@ static int sweep_k(hml_ctx* c, char method, bool record) {
         }
     } else if (!mix) {
         const uint64_t chunks = ((uint64_t)hint + L - 1) / L;
-        const int gF = grid_for(chunks, 256, 16, 1 << 20);
+        const int gF = grid_for(chunks, HML_FWD_THREADS, 16, 1 << 20);
         {
             ProfScope ps(c, "forward");
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_forward<KK>), dim3(gF), dim3(256), 0, s, c->d_em, gsc_plane, c->d_mdl, c->d_rows,
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_forward<KK>), dim3(gF), dim3(HML_FWD_THREADS), 0, s, c->d_em, gsc_plane, c->d_mdl, c->d_rows,
                                c->probes ? c->d_aprobe : nullptr, c->d_entry, c->d_exitA, c->d_fb, L, lay);
         }
         {
@@ -209,7 +209,7 @@ static int sweep_k(hml_ctx* c, char method, bool record) {
             const uint64_t bch = ((uint64_t)hint + HML_BWD_CHUNK - 1) / HML_BWD_CHUNK;
             {
                 ProfScope ps(c, "backward_maps");
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_backward_maps<KK>), dim3(grid_for(bch * 64, 256, 16, 1 << 18)), dim3(256), 0,
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_backward_maps<KK>), dim3(grid_for(bch * 64, HML_BWD_MAPS_THREADS, 16, 1 << 18)), dim3(HML_BWD_MAPS_THREADS), 0,
                                    s, c->d_rows, c->d_mdl, c->d_smap, c->d_cmap, lay, c->d_entry, c->d_exitA, c->d_redo, L, starts_for_maps, c->d_mdl);
             }
             ProfScope ps(c, "backward_chain");
@@ -443,8 +443,8 @@ static int iterate_many_k(hml_ctx* const* cs, int n, uint64_t first, uint64_t it
                 memset(&ma, 0, sizeof ma);
                 for (int k = 0; k < nk; ++k) ma.c[k] = h[k0 + k];
                 const unsigned nyk = (unsigned)nk;
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_m_forward<KK>), dim3((unsigned)grid_for(chunks, 256, 16, 1 << 20), nyk), dim3(256), 0, s, ma, with_gsc, L);
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_m_backward_maps<KK>), dim3((unsigned)grid_for((bch + 1) / 2 * 64, 256, 16, 1 << 18), nyk), dim3(256), 0, s, ma, with_gsc, L);   // (a wavefront per two chunks)
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_m_forward<KK>), dim3((unsigned)grid_for(chunks, HML_FWD_THREADS, 16, 1 << 20), nyk), dim3(HML_FWD_THREADS), 0, s, ma, with_gsc, L);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_m_backward_maps<KK>), dim3((unsigned)grid_for((bch + 1) / 2 * 64, HML_BWD_MAPS_THREADS, 16, 1 << 18), nyk), dim3(HML_BWD_MAPS_THREADS), 0, s, ma, with_gsc, L);   // (a wavefront per two chunks)
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_m_backward_chain<KK>), dim3(1, nyk), dim3(1024), 0, s, ma, with_gsc, L);
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_m_counts<KK>), dim3(HML_REDUCE_GROUPS, nyk), dim3(256), 0, s, ma);
                 if (record && (rec_mask >> k0)) hipLaunchKernelGGL(hml_m_record, dim3(gB, nyk), dim3(256), 0, s, ma, rec_mask >> k0);
