@@ -103,6 +103,11 @@ SIGNATURES = {
     "hml_bands_dense_device": (C.c_int, [_P, _P, C.c_int]),
     "hml_bands_call": (C.c_int, [_P, C.c_uint64, C.POINTER(C.c_uint64), _P, _P]),
     "hml_bands_merge": (C.c_int, [_P, _P]),
+    "hml_set_regions": (C.c_int, [_P, C.c_uint64, _P, _P, C.c_int, _P]),
+    "hml_get_regions": (C.c_int, [_P, C.POINTER(C.c_uint64), _P, _P, C.POINTER(C.c_int), _P]),
+    "hml_regions_read": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_uint64), _P, _P, _P, _P, _P, _P]),
+    "hml_regions_add": (C.c_int, [_P, C.c_uint64, _P, _P, _P, _P, _P, _P]),
+    "hml_regions_merge": (C.c_int, [_P, _P]),
     "hml_recording_payload_size": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64)]),
     "hml_recording_export": (C.c_int, [_P, C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "hml_recording_merge_payload": (C.c_int, [_P, C.c_int, _P, C.c_uint64]),
@@ -559,6 +564,48 @@ class Chain:
         """add `other`'s band counts into this chain's (same GPU, positions, dimensions and edges); no relabelling involved"""
         _check(self.lib.hml_bands_merge(self.h, other.h))
 
+    # ---- joint posteriors over caller-given regions ---------------------------------------------
+    def set_regions(self, start, end, edges=()):
+        """accumulate, per region [start[r], end[r]) and recorded sweep, whether the region is one segment, its number of
+        breakpoints, its mean level and - with `edges` - whether all of it lies in one band (hml_set_regions); no regions
+        turn the recording off and keep the regions and the sums"""
+        start, end = _region_positions(start, "start"), _region_positions(end, "end")
+        if start.shape != end.shape:
+            raise ValueError("start and end: two one-dimensional arrays of one length")
+        edges = np.ascontiguousarray(edges, np.float32)
+        _check(self.lib.hml_set_regions(self.h, start.size, start.ctypes.data if start.size else None, end.ctypes.data if end.size else None,
+                                        edges.size, edges.ctypes.data if edges.size else None))
+
+    def get_regions(self):
+        """(start, end, edges) last set"""
+        n, ne = C.c_uint64(), C.c_int()
+        _check(self.lib.hml_get_regions(self.h, C.byref(n), None, None, C.byref(ne), None))
+        start, end, edges = np.empty(n.value, np.uint32), np.empty(n.value, np.uint32), np.zeros(31, np.float32)
+        _check(self.lib.hml_get_regions(self.h, C.byref(n), start.ctypes.data, end.ctypes.data, C.byref(ne), edges.ctypes.data))
+        return start, end, edges[:ne.value].copy()
+
+    def regions(self):
+        """the raw sums of hml_regions_read: dict(N, whole[n], breaks_sum[n], breaks_sq[n] (uint64), level_sum[D, n],
+        level_sq[D, n] (float64), inband[n, D * (n_edges + 1)] (uint64; no columns without edges)); regions_summary() derives
+        the probabilities, means and spreads"""
+        n, ncol, N = C.c_uint64(), C.c_int(), C.c_uint64()
+        _check(self.lib.hml_regions_read(self.h, C.byref(n), C.byref(ncol), C.byref(N), None, None, None, None, None, None))
+        out = dict(whole=np.empty(n.value, np.uint64), breaks_sum=np.empty(n.value, np.uint64), breaks_sq=np.empty(n.value, np.uint64),
+                   level_sum=np.empty((self.D, n.value), np.float64), level_sq=np.empty((self.D, n.value), np.float64),
+                   inband=np.empty((n.value, ncol.value), np.uint64))
+        _check(self.lib.hml_regions_read(self.h, C.byref(n), C.byref(ncol), C.byref(N), *[out[k].ctypes.data for k in REGION_SUMS]))
+        out["N"] = N.value
+        return out
+
+    def regions_add(self, sums):
+        """add raw sums of the same regions (a dict like regions()'s, from any chain, GPU or process) into this chain's"""
+        arr = [np.ascontiguousarray(sums[k], np.float64 if k.startswith("level") else np.uint64) for k in REGION_SUMS]
+        _check(self.lib.hml_regions_add(self.h, int(sums["N"]), *[a.ctypes.data if a.size else None for a in arr]))
+
+    def regions_merge(self, other):
+        """add `other`'s region sums into this chain's (same positions, dimensions, regions and edges; any two GPUs)"""
+        _check(self.lib.hml_regions_merge(self.h, other.h))
+
     # ---- sparse payloads of the levels, breakpoints and bands (across GPUs) -------------------
     def recording_payload_size(self, kind):
         """bytes of the payload hml_recording_export would write now for RECORDING_LEVELS / _BREAKS / _BANDS"""
@@ -798,6 +845,48 @@ def levels_mean_sd(n, s1, s2):
     mean = s1 / np.float64(n)
     var = s2 / np.float64(n) - mean * mean
     return mean.astype(np.float32), np.sqrt(np.maximum(var, 0.0)).astype(np.float32)
+
+
+def _region_positions(values, name):
+    """positions as uint32, refused - not wrapped - when they are negative, not whole or beyond 2^32 - 1"""
+    a = np.asarray(values)
+    if a.ndim != 1:
+        raise ValueError("%s: a one-dimensional array of positions" % name)
+    if a.size == 0:
+        return np.zeros(0, np.uint32)
+    if a.dtype.kind not in "iu":
+        if a.dtype.kind != "f" or not np.all(np.isfinite(a)) or np.any(a != np.floor(a)):
+            raise ValueError("%s: positions are whole numbers" % name)
+    if np.any(a < 0) or np.any(a > 2 ** 32 - 1):
+        raise ValueError("%s: positions lie in [0, 2^32 - 1]" % name)
+    return np.ascontiguousarray(a.astype(np.uint64), np.uint32)
+
+
+REGION_SUMS = ("whole", "breaks_sum", "breaks_sq", "level_sum", "level_sq", "inband")   # the arrays of hml_regions_read, in its order
+U64_MAX = 2 ** 64 - 1
+
+
+def regions_summary(sums):
+    """What a caller wants of Chain.regions()'s raw sums, in double: p_whole[n] = whole / N; breaks_mean[n] and breaks_sd[n] of the
+    number of breakpoints inside the region (sd: not a number where breaks_sq is saturated at 2^64 - 1); level_mean[D, n] and
+    level_sd[D, n] of the region's mean level; p_inband[n, columns] = inband / N.  sd = sqrt(max(0, S2 / N - (S1 / N)^2)).
+    N = 0: everything not a number."""
+    N = int(sums["N"])
+    whole, bsum, bsq = (np.asarray(sums[k], np.uint64) for k in REGION_SUMS[:3])
+    lsum, lsq = np.asarray(sums["level_sum"], np.float64), np.asarray(sums["level_sq"], np.float64)
+    inband = np.asarray(sums["inband"], np.uint64)
+    if N == 0:
+        nan = lambda a: np.full(a.shape, np.nan, np.float64)
+        return dict(N=0, p_whole=nan(whole), breaks_mean=nan(bsum), breaks_sd=nan(bsq), level_mean=nan(lsum), level_sd=nan(lsq), p_inband=nan(inband))
+    n = np.float64(N)
+    bmean = bsum.astype(np.float64) / n
+    bsd = np.sqrt(np.maximum(bsq.astype(np.float64) / n - bmean * bmean, 0.0))
+    bsd[bsq == np.uint64(U64_MAX)] = np.nan
+    lmean = lsum / n
+    with np.errstate(invalid="ignore"):
+        lsd = np.sqrt(np.maximum(lsq / n - lmean * lmean, 0.0))
+    return dict(N=N, p_whole=whole.astype(np.float64) / n, breaks_mean=bmean, breaks_sd=bsd, level_mean=lmean, level_sd=lsd,
+                p_inband=inband.astype(np.float64) / n)
 
 
 def bands_exceedance(counts, n_edges, D):

@@ -256,6 +256,7 @@ static void free_all(hml_ctx* c) {
                     c->d_diff, c->d_boundary, c->d_mdl, c->d_many};
     for (void* p : ptrs) if (p) hipFree(p);
     for (hml_recorder& r : c->rec) { if (r.d_acc) hipFree(r.d_acc); if (r.d_boundary) hipFree(r.d_boundary); }
+    free_region_buffers(c);
     if (c->h_B) hipHostFree(c->h_B);
     c->h_B = nullptr;
 }
@@ -1007,6 +1008,57 @@ int hml_get_level_bands(hml_ctx* c, int* n_edges, float* edges) {
     if (!c || !n_edges) return set_err(HML_ERR_ARG, "null argument");
     *n_edges = c->n_band_edges;
     if (edges) memcpy(edges, c->band_edges, (size_t)c->n_band_edges * sizeof(float));
+    return 0;
+}
+
+// The regions of the joint posteriors (hml_k_regions.h).  What can be told without the trace is refused here, the rest -
+// a region beyond the trace that is loaded later - by the first recorded sweep (regions_fault).
+int hml_set_regions(hml_ctx* c, uint64_t n, const uint32_t* start, const uint32_t* end, int n_edges, const float* edges) {
+    if (!c) return set_err(HML_ERR_ARG, "null context");
+    // (as in hml_set_level_recording: a graph captured under the other setting goes)
+    if (c->graph_exec) { if (int r = ctx_bind(c)) return r; hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
+    if (n == 0) { c->rg.on = false; return 0; }   // (what was accumulated stays, and so do the regions and their edges)
+    if (!start || !end || (n_edges > 0 && !edges)) return set_err(HML_ERR_ARG, "null argument");
+    if (n > (1ull << 22)) return set_err(HML_ERR_ARG, "regions: 1 to 2^22 regions");
+    if (n_edges < 0) return set_err(HML_ERR_ARG, "level bands take 1 to 31 edges");
+    if (n_edges > 0) { if (const char* why = band_edges_fault(n_edges, edges)) return set_err(HML_ERR_ARG, why); }
+    if (c->model_set && (uint64_t)c->D * (uint64_t)(n_edges + 1) > HML_CAP_K)
+        return set_err(HML_ERR_ARG, "regions: the data dimensions times (edges + 1) exceed 64 columns");
+    for (uint64_t r = 0; r < n; ++r)
+        if (!(start[r] < end[r]) || (c->loaded && (uint64_t)end[r] > c->T)) {
+            char buf[200];
+            if (c->loaded) snprintf(buf, sizeof buf, "regions: region %llu, [%u, %u), does not lie inside the %llu positions of the trace", (unsigned long long)r, start[r], end[r], (unsigned long long)c->T);
+            else snprintf(buf, sizeof buf, "regions: region %llu, [%u, %u), is empty", (unsigned long long)r, start[r], end[r]);
+            return set_err(HML_ERR_ARG, buf);
+        }
+    if (!same_regions(c, n, start, end, n_edges, edges)) {
+        if (c->rg.d_acc) {
+            // buffers of other regions or edges: they go if they hold nothing
+            if (int r = ctx_bind(c)) return r;
+            if (int r = hml_settle(c)) return r;
+            unsigned long long N = 0;
+            HIPCHK(hipMemcpy(&N, &c->d_mdl->n_regions_recorded, sizeof N, hipMemcpyDeviceToHost));
+            if (N != 0ull) return set_err(HML_ERR_ARG, "regions were already recorded under other regions or edges: they cannot be changed any more");
+            free_region_buffers(c);
+        }
+        c->rg.start.assign(start, start + n);
+        c->rg.end.assign(end, end + n);
+        c->rg.n_edges = n_edges;
+        memset(c->rg.edges, 0, sizeof c->rg.edges);
+        if (n_edges > 0) memcpy(c->rg.edges, edges, (size_t)n_edges * sizeof(float));
+        c->rg.checked = c->loaded && c->model_set;
+    }
+    c->rg.on = c->rg.asked = true;
+    return 0;
+}
+
+int hml_get_regions(hml_ctx* c, uint64_t* n, uint32_t* start, uint32_t* end, int* n_edges, float* edges) {
+    if (!c || !n) return set_err(HML_ERR_ARG, "null argument");
+    *n = c->rg.start.size();
+    if (start) memcpy(start, c->rg.start.data(), c->rg.start.size() * sizeof(uint32_t));
+    if (end) memcpy(end, c->rg.end.data(), c->rg.end.size() * sizeof(uint32_t));
+    if (n_edges) *n_edges = c->rg.n_edges;
+    if (edges) memcpy(edges, c->rg.edges, (size_t)c->rg.n_edges * sizeof(float));
     return 0;
 }
 

@@ -1,6 +1,6 @@
 // Shared by the three kinds of translation unit of libhammlet_hip.so's chain code (hammlet_amd/build.py):
 //   hml_capi.hip  - the C ABI (include/hml.h) and everything that does not depend on the number of states K: one object;
-//   hml_readout.hip - the C ABI's read-outs of what the recorded sweeps accumulated (marginals, levels, breaks, bands): one object;
+//   hml_readout.hip - the C ABI's read-outs of what the recorded sweeps accumulated (marginals, levels, breaks, bands, regions): one object;
 //   hml_sweep.hip - the sweep for K states: the kernels templated on K and the host code that launches them, behind a table
 //                   of function pointers (hml_ktab): fifteen objects, -DHML_TU_K=2 ... 16, compiled in parallel.
 // Every object carries its own code object, and the HIP runtime loads a code object when the first kernel of it is launched:
@@ -35,6 +35,7 @@
 #include "hml_k_levels.h"
 #include "hml_k_breaks.h"
 #include "hml_k_bands.h"
+#include "hml_k_regions.h"
 #include "hml_k_segment.h"
 #include "hml_k_trellis.h"
 #include "hml_k_trellis_rows.h"
@@ -292,10 +293,12 @@ static int ensure_recorder_buffers(hml_ctx* c, int kind) {
     if (hipStreamIsCapturing(c->stream, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone) HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
+static int ensure_region_buffers(hml_ctx* c);   // (below)
 // ... of every recording that is on
 static int ensure_recorders(hml_ctx* c) {
     for (int kind = 0; kind < HML_REC_KINDS; ++kind)
         if (c->rec[kind].on) { if (int r = ensure_recorder_buffers(c, kind)) return r; }
+    if (c->rg.on) { if (int r = ensure_region_buffers(c)) return r; }
     return 0;
 }
 
@@ -321,6 +324,71 @@ static void launch_record_kernel(hml_ctx* c, int kind, hipStream_t s, dim3 grid)
         hipLaunchKernelGGL(hml_k_bands_record, grid, dim3(256), 0, s, c->d_q, c->d_starts, c->d_mdl, band_edges_of(c), r.acc<int32_t>(), r.d_boundary);
 }
 
+// ---- the joint posteriors over caller-given regions (hml_regions, hml_ctx.hpp; hml_k_regions.h) ----
+static const char* const hml_regions_none = "no regions were recorded by %s context: give them with hml_set_regions before the recorded sweeps";
+static int regions_none(const char* whose) {
+    char buf[256];
+    snprintf(buf, sizeof buf, hml_regions_none, whose);
+    return set_err(HML_ERR_ARG, buf);
+}
+static int regions_columns(const hml_ctx* c) { return c->rg.n_edges > 0 ? c->D * (c->rg.n_edges + 1) : 0; }
+static hml_band_edges region_edges_of(const hml_ctx* c) {
+    hml_band_edges ed;
+    memset(&ed, 0, sizeof ed);
+    ed.n = c->rg.n_edges;
+    for (int j = 0; j < c->rg.n_edges; ++j) ed.e[j] = c->rg.edges[j];
+    return ed;
+}
+static bool same_regions(const hml_ctx* c, uint64_t n, const uint32_t* start, const uint32_t* end, int n_edges, const float* edges) {
+    const hml_regions& g = c->rg;
+    return g.start.size() == n && g.n_edges == n_edges && memcmp(g.start.data(), start, n * sizeof(uint32_t)) == 0 &&
+           memcmp(g.end.data(), end, n * sizeof(uint32_t)) == 0 && (n_edges == 0 || memcmp(g.edges, edges, (size_t)n_edges * sizeof(float)) == 0);   // (bit for bit)
+}
+// words of 8 bytes per region: whole, breaks_sum, breaks_sq, D level sums, D sums of squares, the band columns
+static uint64_t regions_acc_words(const hml_ctx* c) { return 3u + 2u * (uint64_t)c->D + (uint64_t)regions_columns(c); }
+static hml_regions_acc regions_acc_views(const hml_ctx* c) {
+    const uint64_t n = c->rg.start.size();
+    hml_regions_acc a;
+    unsigned long long* w = (unsigned long long*)c->rg.d_acc;
+    a.whole = w; a.breaks_sum = w + n; a.breaks_sq = w + 2 * n;
+    a.level_sum = (double*)(w + 3 * n);
+    a.level_sq = a.level_sum + (uint64_t)c->D * n;
+    a.inband = w + (3u + 2u * (uint64_t)c->D) * n;
+    return a;
+}
+// (one entry per chunk of HML_RG_CHUNK blocks; at most T blocks, whatever the block capacity)
+static uint32_t regions_chunk_stride(const hml_ctx* c) { return (uint32_t)((c->T + HML_RG_CHUNK - 1u) / HML_RG_CHUNK); }
+static hml_regions_chunks regions_chunk_views(const hml_ctx* c) {
+    hml_regions_chunks ch;
+    ch.stride = regions_chunk_stride(c);
+    ch.lev = (double*)c->rg.d_chunks;
+    ch.cnt = (uint32_t*)(ch.lev + (uint64_t)c->D * ch.stride);
+    return ch;
+}
+static int regions_fault(const hml_ctx* c) {   // what only the loaded trace and the model can tell
+    const hml_regions& g = c->rg;
+    for (size_t r = 0; r < g.start.size(); ++r)
+        if (!(g.start[r] < g.end[r] && (uint64_t)g.end[r] <= c->T)) {
+            char buf[200];
+            snprintf(buf, sizeof buf, "regions: region %llu, [%u, %u), does not lie inside the %llu positions of the trace", (unsigned long long)r, g.start[r], g.end[r],
+                     (unsigned long long)c->T);
+            return set_err(HML_ERR_ARG, buf);
+        }
+    if ((uint64_t)c->D * (uint64_t)(g.n_edges + 1) > HML_CAP_K) return set_err(HML_ERR_ARG, "regions: the data dimensions times (edges + 1) exceed 64 columns");
+    return 0;
+}
+static void free_region_buffers(hml_ctx* c) {
+    void** ptrs[] = {(void**)&c->rg.d_start, (void**)&c->rg.d_end, (void**)&c->rg.d_acc, (void**)&c->rg.d_chunks};
+    for (void** p : ptrs) if (*p) { hipFree(*p); *p = nullptr; }
+}
+// hml_readout.hip: the regions' buffers on first use, and the three launches of a recorded sweep's regions.  Defined in ONE
+// object, so that the code objects of the sweeps and of the core hold the kernels they held before.
+// (internal to the library: not part of the C ABI, not exported)
+__attribute__((visibility("hidden"))) int hml_regions_ensure(hml_ctx* c);
+__attribute__((visibility("hidden"))) void hml_regions_launch(hml_ctx* c, hipStream_t s, uint32_t hint, bool bracket);
+static int ensure_region_buffers(hml_ctx* c) { return hml_regions_ensure(c); }
+static void launch_region_kernels(hml_ctx* c, hipStream_t s, uint32_t hint, bool bracket) { hml_regions_launch(c, s, hint, bracket); }
+
 // the record kernels of a recorded sweep, on stream `s`, BEHIND the sweep's parameter update: the level (and its band) is mu
 // under the theta that hml_get_theta returns inside the sweep's record callback; the breakpoint kernel reads the sweep's
 // states and block starts only
@@ -330,6 +398,11 @@ static int launch_recorders(hml_ctx* c, hipStream_t s, uint32_t hint) {
         if (int r = ensure_recorder_buffers(c, kind)) return r;
         ProfScope ps(c, hml_recorder_kinds[kind].family);
         launch_record_kernel(c, kind, s, dim3(grid_for(hint, 256, 64, 16384)));
+    }
+    if (c->rg.on) {
+        if (int r = ensure_region_buffers(c)) return r;
+        ProfScope ps(c, "regions");
+        launch_region_kernels(c, s, hint, /*bracket*/ true);
     }
     return 0;
 }

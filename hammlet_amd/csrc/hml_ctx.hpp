@@ -41,6 +41,20 @@ struct hml_recorder {
     template <class E> E* acc() const { return static_cast<E*>(d_acc); }
 };
 
+// The joint posteriors over caller-given regions (hml_set_regions; hml_k_regions.h).  Not a fourth hml_recorder: no cells per
+// position and no bitmap, a few words per region instead.
+struct hml_regions {
+    bool on = false;                  // recording now
+    bool asked = false;               // ... was on at some time: the read-out answers
+    bool checked = false;             // the regions were compared with T (at hml_set_regions, or at the first recorded sweep)
+    std::vector<uint32_t> start, end; // the regions last set, [start, end) each (they stay when the recording is turned off)
+    int n_edges = 0;                  // the regions' own band edges (0: no band columns)
+    float edges[31] = {};
+    uint32_t *d_start = nullptr, *d_end = nullptr;
+    void* d_acc = nullptr;            // the accumulators of hml_regions_acc, one allocation
+    void* d_chunks = nullptr;         // chunk totals of a recorded sweep, sized by T (hml_regions_chunks)
+};
+
 struct hml_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -131,6 +145,7 @@ struct hml_ctx {
     //   HML_REC_BANDS   int32 [D (n_band_edges + 1)][T + 1]: difference arrays of the counts per band (hml_k_bands.h);
     //                   nothing recorded: one segment of zeros
     hml_recorder rec[HML_REC_KINDS];
+    hml_regions rg;
     int n_band_edges = 0;           // the bands' edges last set (they stay when the recording is turned off)
     float band_edges[31] = {};
     hml_model* d_mdl = nullptr;

@@ -2,6 +2,7 @@
 // marginals, emission levels, breakpoints, level bands - brought into the forms the callers ask for, and the merges of one
 // chain's recording into another's: on one device from recorder to recorder, across devices through the sparse payload of
 // hml_k_rec_payload.h.  Nothing here runs inside a sweep; hml_capi.hip holds the chain itself.
+#define HML_REGIONS_KERNELS   // (hml_k_regions.h: this object holds the regions' kernels)
 #include "hml_capi_shared.hpp"
 #include "hml_k_agree.h"   // (launched from this object alone)
 #include "hml_k_rec_payload.h"
@@ -708,6 +709,144 @@ int hml_bands_call(hml_ctx* c, uint64_t rank, uint64_t* n_runs, uint64_t* run_le
 }
 
 int hml_bands_merge(hml_ctx* dst, hml_ctx* src) { return recorder_merge(dst, src, HML_REC_BANDS); }
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------- regions (hml_k_regions.h)
+// The accumulators are a few words per region: the read-out copies them, and sums from elsewhere - another chain, another
+// GPU, another process - are added on the host, one addition per number, and written back.
+
+// the regions, their accumulators and the chunk scratch on first use.  Ready before this returns: chains batched by
+// hml_iterate_many run on their group's stream, not on their own.
+int hml_regions_ensure(hml_ctx* c) {
+    hml_regions& g = c->rg;
+    if (g.d_acc) return 0;
+    if (g.start.empty()) return set_err(HML_ERR_ARG, "regions: none were given");
+    if (!g.checked) { if (int r = regions_fault(c)) return r; g.checked = true; }
+    const uint64_t n = g.start.size();
+    const uint64_t acc_bytes = regions_acc_words(c) * n * 8u;
+    const uint64_t chunk_bytes = (uint64_t)regions_chunk_stride(c) * ((uint64_t)c->D * sizeof(double) + (1u + (uint64_t)c->D) * sizeof(uint32_t));
+    HIPCHK(hipMalloc(&g.d_start, n * sizeof(uint32_t)));
+    HIPCHK(hipMalloc(&g.d_end, n * sizeof(uint32_t)));
+    HIPCHK(hipMalloc(&g.d_chunks, chunk_bytes));
+    HIPCHK(hipMalloc(&g.d_acc, acc_bytes));
+    HIPCHK(hipMemcpyAsync(g.d_start, g.start.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(g.d_end, g.end.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(g.d_chunks, 0, chunk_bytes, c->stream));
+    HIPCHK(hipMemsetAsync(g.d_acc, 0, acc_bytes, c->stream));
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(c->stream, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone) HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// the three launches of a recorded sweep's regions, on stream `s`, behind the sweep's parameter update like the recorders
+// above: chunk totals, their exclusive sums, a wavefront per region (the buffers exist: ensure_region_buffers)
+void hml_regions_launch(hml_ctx* c, hipStream_t s, uint32_t hint, bool bracket) {
+    const hml_band_edges ed = region_edges_of(c);
+    const hml_regions_chunks ch = regions_chunk_views(c);
+    const uint32_t n = (uint32_t)c->rg.start.size();
+    // (bracket: `s` is the context's own stream - launch_recorders - and the three kernels get profile families of their own
+    // inside the family "regions"; the batches of hml_iterate_many run on their group's stream and are never profiled)
+    const int level = bracket ? 2 : 1 << 30;
+    {
+        ProfScope ps(c, "regions_chunks", level);
+        hipLaunchKernelGGL(hml_k_regions_chunks, dim3(grid_for(hint, HML_RG_CHUNK, 1, 16384)), dim3(HML_RG_CHUNK), 0, s, c->d_q, c->d_starts, c->d_mdl, ed, ch);
+    }
+    {
+        ProfScope ps(c, "regions_scan", level);
+        hipLaunchKernelGGL(hml_k_regions_scan, dim3(1 + (ed.n > 0 ? 2 : 1) * c->D), dim3(1024), 0, s, c->d_mdl, ch);
+    }
+    {
+        ProfScope ps(c, "regions_accumulate", level);
+        hipLaunchKernelGGL(hml_k_regions_accumulate, dim3(grid_for(n, 4, 1, 16384)), dim3(256), 0, s, c->d_q, c->d_starts, c->d_mdl, ed, ch, c->rg.d_start, c->rg.d_end, n,
+                           regions_acc_views(c));
+    }
+}
+
+
+struct hml_regions_host {
+    uint64_t n = 0, N = 0;
+    int D = 1, ncol = 0;
+    std::vector<unsigned long long> words;   // the device layout (hml_regions_acc)
+    unsigned long long* whole() { return words.data(); }
+    unsigned long long* breaks_sum() { return words.data() + n; }
+    unsigned long long* breaks_sq() { return words.data() + 2 * n; }
+    double* level_sum() { return reinterpret_cast<double*>(words.data() + 3 * n); }
+    double* level_sq() { return level_sum() + (uint64_t)D * n; }
+    unsigned long long* inband() { return words.data() + (3u + 2u * (uint64_t)D) * n; }
+};
+
+static int regions_fetch(hml_ctx* c, const char* whose, hml_regions_host& h) {
+    if (!c || !c->model_set) return set_err(HML_ERR_ARG, "model not set");
+    if (!c->rg.asked) return regions_none(whose);
+    if (int r = ctx_bind(c)) return r;
+    if (int r = hml_settle(c)) return r;
+    if (int r = ensure_region_buffers(c)) return r;
+    hml_model m;
+    if (int r = fetch_model(c, &m)) return r;
+    if (int r = model_fault(m)) return r;
+    h.n = c->rg.start.size(); h.N = m.n_regions_recorded; h.D = c->D; h.ncol = regions_columns(c);
+    h.words.resize(regions_acc_words(c) * h.n);
+    HIPCHK(hipMemcpy(h.words.data(), c->rg.d_acc, h.words.size() * 8u, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// raw sums into the context's accumulators: integers add (breaks_sq saturates and stays there), a double gets one addition
+static int regions_add_host(hml_ctx* c, uint64_t N, const uint64_t* whole, const uint64_t* breaks_sum, const uint64_t* breaks_sq, const double* level_sum,
+                            const double* level_sq, const uint64_t* inband) {
+    hml_regions_host h;
+    if (int r = regions_fetch(c, "this", h)) return r;
+    if (!whole || !breaks_sum || !breaks_sq || !level_sum || !level_sq || (h.ncol > 0 && !inband)) return set_err(HML_ERR_ARG, "null argument");
+    for (uint64_t r = 0; r < h.n; ++r) {
+        h.whole()[r] += whole[r];
+        h.breaks_sum()[r] += breaks_sum[r];
+        h.breaks_sq()[r] = hml_sat_add_u64(h.breaks_sq()[r], breaks_sq[r]);
+    }
+    for (uint64_t i = 0; i < (uint64_t)h.D * h.n; ++i) { h.level_sum()[i] += level_sum[i]; h.level_sq()[i] += level_sq[i]; }
+    for (uint64_t i = 0; i < h.n * (uint64_t)h.ncol; ++i) h.inband()[i] += inband[i];
+    const unsigned long long total = h.N + N;
+    HIPCHK(hipMemcpy(c->rg.d_acc, h.words.data(), h.words.size() * 8u, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(&c->d_mdl->n_regions_recorded, &total, sizeof total, hipMemcpyHostToDevice));
+    return 0;
+}
+
+extern "C" {
+
+int hml_regions_read(hml_ctx* c, uint64_t* n, int* n_columns, uint64_t* n_recorded, uint64_t* whole, uint64_t* breaks_sum, uint64_t* breaks_sq, double* level_sum,
+                     double* level_sq, uint64_t* inband) {
+    if (!n) return set_err(HML_ERR_ARG, "null argument");
+    hml_regions_host h;
+    if (int r = regions_fetch(c, "this", h)) return r;
+    *n = h.n;
+    if (n_columns) *n_columns = h.ncol;
+    if (n_recorded) *n_recorded = h.N;
+    if (whole) memcpy(whole, h.whole(), h.n * 8u);
+    if (breaks_sum) memcpy(breaks_sum, h.breaks_sum(), h.n * 8u);
+    if (breaks_sq) memcpy(breaks_sq, h.breaks_sq(), h.n * 8u);
+    if (level_sum) memcpy(level_sum, h.level_sum(), (uint64_t)h.D * h.n * 8u);
+    if (level_sq) memcpy(level_sq, h.level_sq(), (uint64_t)h.D * h.n * 8u);
+    if (inband && h.ncol > 0) memcpy(inband, h.inband(), h.n * (uint64_t)h.ncol * 8u);
+    return 0;
+}
+
+int hml_regions_add(hml_ctx* c, uint64_t n_recorded, const uint64_t* whole, const uint64_t* breaks_sum, const uint64_t* breaks_sq, const double* level_sum,
+                    const double* level_sq, const uint64_t* inband) {
+    return regions_add_host(c, n_recorded, whole, breaks_sum, breaks_sq, level_sum, level_sq, inband);
+}
+
+int hml_regions_merge(hml_ctx* dst, hml_ctx* src) {
+    if (!dst || !src || !dst->model_set || !src->model_set) return set_err(HML_ERR_ARG, "model not set");
+    if (dst == src) return set_err(HML_ERR_ARG, "a context cannot be merged into itself");
+    if (dst->T != src->T || dst->D != src->D) return set_err(HML_ERR_ARG, "regions can only be merged between chains over the same positions and dimensions");
+    if (!src->rg.asked) return regions_none("the source");
+    if (!dst->rg.asked) return regions_none("the destination");
+    if (!same_regions(dst, src->rg.start.size(), src->rg.start.data(), src->rg.end.data(), src->rg.n_edges, src->rg.edges))
+        return set_err(HML_ERR_ARG, "regions can only be merged between chains with the same regions and edges, bit for bit");
+    hml_regions_host h;
+    if (int r = regions_fetch(src, "the source", h)) return r;   // (the two contexts may lie on different GPUs: the sums travel through the host)
+    return regions_add_host(dst, h.N, (const uint64_t*)h.whole(), (const uint64_t*)h.breaks_sum(), (const uint64_t*)h.breaks_sq(), h.level_sum(), h.level_sq(),
+                            (const uint64_t*)h.inband());
+}
 
 }  // extern "C"
 

@@ -134,6 +134,7 @@ struct hml_model {
     unsigned long long n_levels_recorded;   // sweeps whose emission levels were accumulated (hml_k_levels.h), merged chains included
     unsigned long long n_breaks_recorded;   // sweeps whose breakpoints were counted (hml_k_breaks.h), merged chains included
     unsigned long long n_bands_recorded;    // sweeps whose level bands were counted (hml_k_bands.h), merged chains included
+    unsigned long long n_regions_recorded;  // sweeps whose regions were accumulated (hml_k_regions.h), added and merged sums included
 };
 
 #if defined(__HIPCC__)

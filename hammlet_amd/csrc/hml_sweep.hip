@@ -453,6 +453,7 @@ static int iterate_many_k(hml_ctx* const* cs, int n, uint64_t first, uint64_t it
             // the chains' own recordings (levels, breaks, bands): one launch each behind the batch's parameter kernels
             if (record) for (int kind = 0; kind < HML_REC_KINDS; ++kind)
                 for (int k = g0; k < g0 + gn; ++k) if (cs[k]->rec[kind].on) launch_record_kernel(cs[k], kind, s, dim3(gB));
+            if (record) for (int k = g0; k < g0 + gn; ++k) if (cs[k]->rg.on) launch_region_kernels(cs[k], s, hint, /*bracket*/ false);   // (and their regions: hml_k_regions.h)
         }
         KLAUNCH_CHECK();
         if (record) {

@@ -16,7 +16,11 @@
 // they are merged: per segment of the union of their level boundaries its length and per data dimension the Gelman-Rubin R-hat
 // (hml_levels_agreement_rle); `-merge-gpus` with -chains N lets the levels, breakpoints, consensus, bands, bandcalls and rhat outputs cross
 // GPUs: the chains' recordings reach the first chain's GPU as sparse payloads (hml_recording_merge_across), R-hat is taken over
-// the first chain and shadow contexts on its GPU;
+// the first chain and shadow contexts on its GPU; `-regions FILE` names regions of positions ("start end [label]" per line, 0-based,
+// half-open) and `-O RG` (regions) writes PREFIXregionsSUFFIX, per region the joint posterior that no per-position file holds: the
+// number of recorded sweeps N, those in which the whole region was one segment, mean and standard deviation of the number of
+// breakpoints inside it and of its mean level, and - with -bands - the sweeps in which all of it lay in one band
+// (hml_set_regions, hml_regions_read); with -chains N the chains' sums are added into the first chain's, on any GPUs;
 // -raw FILE reads float32 values instead of text; -device N selects
 // the GPU; -chain N selects the Philox sub-key of an independent chain; -chains N runs N independent chains (sub-keys
 // chain .. chain+N-1), chain k on GPU (device + k) mod #GPUs in its own host thread, and pools their recorded marginals
@@ -70,6 +74,12 @@ static const char* kHelp =
     "                                 the chains of -chains N (N >= 2, one GPU), one line per segment of the union of the chains'\n"
     "                                 level boundaries, taken before the chains are merged: near 1 the chains agree there, well\n"
     "                                 above 1 they sit in different modes; turns the recording of the levels on (extension)\n"
+    "                    RG           regions: per region of -regions, tab-separated: start, end, the recorded sweeps N, those\n"
+    "                                 in which the whole region was one segment, mean and standard deviation of the number\n"
+    "                                 of breakpoints inside it, per data dimension mean and standard deviation of the\n"
+    "                                 region's mean level, with -bands per data dimension and band the sweeps in which the\n"
+    "                                 whole region lay in that band, then the label; one line per region, in file order.\n"
+    "                                 With -chains N the chains are added up, on one GPU or several (extension)\n"
     "  -w, -overwrite                 allow overwriting output files\n"
     "  -s, -states K | C P D          number of states (default 3), or P parameters shared by P^D states over D dimensions\n"
     "  -e, -emissions normal VAR P    automatic prior: P(variance < VAR) = P (default normal 0.2 0.9)\n"
@@ -93,6 +103,9 @@ static const char* kHelp =
     "                                 sweeps, whatever the states are called (-O LB, -O LC) (extension)\n"
     "  -bandcall P                    the call of -O LC: 0 (default) the most probable band, 0 < P <= 1 the band of the\n"
     "                                 P-quantile of the recorded levels (0.5: the median) (extension)\n"
+    "  -regions FILE                  the regions of -O RG, one per line: start end [label ...], positions counted from 0, the\n"
+    "                                 end not included; lines that begin with # and blank lines are skipped.  Regions may\n"
+    "                                 overlap, nest and repeat (extension)\n"
     "  -chains N                      N independent chains, one per GPU, marginals pooled over RCCL (extension);\n"
     "                                 chains beyond the number of GPUs share a GPU and the construction it holds.\n"
     "                                 The pooled marginals / maxsegmentation files use common labels (states by\n"
@@ -124,6 +137,9 @@ struct Job {
     double consensusShare = 0.5;
     size_t nrBandEdges = 0;          // -bands
     double bandCall = 0;             // -bandcall P
+    vector<uint32_t> regionStart, regionEnd;   // -regions FILE (recorded when -O RG asks for them)
+    vector<string> regionLabel;
+    vector<float> regionEdges;       // ... and their edges: those of -bands
 };
 
 // Meeting point of the chain threads of `-chains N` and the main thread: a chain arrives with its context once its
@@ -391,6 +407,80 @@ static void writeBandCalls(const Job& job, hml_ctx* ctx) {
     if (fclose(out) != 0) throw std::runtime_error("Cannot write to file " + fn + "!");
 }
 
+static string regionsFileName(const Job& job) { return job.opref + "regions" + job.osuff; }
+
+// -regions FILE: "start end [label ...]" per line, 0-based and half-open; lines that begin with # and blank lines are skipped
+static void readRegions(const string& fname, size_t T, Job& job) {
+    std::ifstream fin(fname);
+    if (!fin) throw std::runtime_error("Cannot read from regions file " + fname + "!");
+    string line;
+    size_t lineNo = 0;
+    while (std::getline(fin, line)) {
+        ++lineNo;
+        const string where = "Regions file " + fname + ", line " + std::to_string(lineNo) + ": ";
+        size_t i = line.find_first_not_of(" \t\r");
+        if (i == string::npos || line[i] == '#') continue;
+        unsigned long long v[2];
+        for (int k = 0; k < 2; ++k) {
+            const size_t j = line.find_first_of(" \t\r", i);
+            const string tok = line.substr(i, j == string::npos ? string::npos : j - i);
+            char* end = nullptr;
+            if (tok.empty() || tok[0] < '0' || tok[0] > '9') throw std::runtime_error(where + "expected \"start end [label]\", two whole numbers, found \"" + tok + "\"!");
+            v[k] = strtoull(tok.c_str(), &end, 10);
+            if (*end || tok.size() > 18) throw std::runtime_error(where + "expected \"start end [label]\", two whole numbers, found \"" + tok + "\"!");
+            i = j == string::npos ? string::npos : line.find_first_not_of(" \t\r", j);
+            if (k == 0 && i == string::npos) throw std::runtime_error(where + "expected \"start end [label]\", found one number only!");
+        }
+        if (v[1] <= v[0]) throw std::runtime_error(where + "the end (" + std::to_string(v[1]) + ") must lie beyond the start (" + std::to_string(v[0]) + ")!");
+        if (v[1] > T) throw std::runtime_error(where + "the end (" + std::to_string(v[1]) + ") lies beyond the " + std::to_string(T) + " positions of the input!");
+        string label = i == string::npos ? "" : line.substr(i);
+        while (!label.empty() && (label.back() == ' ' || label.back() == '\t' || label.back() == '\r')) label.pop_back();
+        if (job.regionStart.size() >= (size_t(1) << 22)) throw std::runtime_error("Regions file " + fname + " holds more than 4194304 regions!");
+        job.regionStart.push_back((uint32_t)v[0]);
+        job.regionEnd.push_back((uint32_t)v[1]);
+        job.regionLabel.push_back(label);
+    }
+    if (job.regionStart.empty()) throw std::runtime_error("Regions file " + fname + " holds no regions!");
+}
+
+// PREFIXregionsSUFFIX from the context's region sums, one line per region in the order of the regions file, tab-separated:
+// start end N whole breaks_mean breaks_sd [level_mean_d level_sd_d per dimension] [inband per dimension and band] label.
+// Means and standard deviations as the levels file prints them: double arithmetic, one rounding to float, %.9g; nothing
+// recorded: nan; the spread of the breakpoint count is nan once its sum of squares has saturated.
+static void writeRegions(const Job& job, hml_ctx* ctx) {
+    uint64_t n = 0, N = 0;
+    int ncol = 0;
+    hml_check(hml_regions_read(ctx, &n, &ncol, &N, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+    const size_t D = job.nrDataDim;
+    vector<uint64_t> whole(n), bsum(n), bsq(n), inband(n * (size_t)ncol);
+    vector<double> lsum(n * D), lsq(n * D);
+    hml_check(hml_regions_read(ctx, &n, &ncol, &N, whole.data(), bsum.data(), bsq.data(), lsum.data(), lsq.data(), inband.data()));
+    const string fn = regionsFileName(job);
+    FILE* out = fopen(fn.c_str(), "w");
+    if (!out) throw std::runtime_error("Cannot write to file " + fn + "!");
+    auto meanSd = [&](double s1, double s2, bool known, float* mean, float* sd) {
+        *mean = NAN; *sd = NAN;
+        if (N == 0) return;
+        const double m = s1 / (double)N;
+        const double var = s2 / (double)N - m * m;
+        *mean = (float)m;
+        if (known) *sd = (float)std::sqrt(var > 0.0 ? var : 0.0);   // (a variance that is not a number stays one)
+        if (known && var != var) *sd = NAN;
+    };
+    for (uint64_t r = 0; r < n; ++r) {
+        float mean, sd;
+        meanSd((double)bsum[r], (double)bsq[r], bsq[r] != ~0ull, &mean, &sd);
+        fprintf(out, "%u\t%u\t%llu\t%llu\t%.9g\t%.9g", job.regionStart[r], job.regionEnd[r], (unsigned long long)N, (unsigned long long)whole[r], (double)mean, (double)sd);
+        for (size_t d = 0; d < D; ++d) {
+            meanSd(lsum[d * n + r], lsq[d * n + r], true, &mean, &sd);
+            fprintf(out, "\t%.9g\t%.9g", (double)mean, (double)sd);
+        }
+        for (int j = 0; j < ncol; ++j) fprintf(out, "\t%llu", (unsigned long long)inband[r * (size_t)ncol + j]);
+        fprintf(out, "\t%s\n", job.regionLabel[r].c_str());
+    }
+    if (fclose(out) != 0) throw std::runtime_error("Cannot write to file " + fn + "!");
+}
+
 // the files written from a finished context (one chain, or the first of several after the others were merged into it)
 static void writeContextFiles(const Job& job, hml_ctx* ctx) {
     if (job.outputs.at("levels")) writeLevels(job, ctx);
@@ -398,6 +488,7 @@ static void writeContextFiles(const Job& job, hml_ctx* ctx) {
     if (job.outputs.at("consensus")) writeConsensus(job, ctx);
     if (job.outputs.at("bands")) writeBands(job, ctx);
     if (job.outputs.at("bandcalls")) writeBandCalls(job, ctx);
+    if (job.outputs.at("regions")) writeRegions(job, ctx);
 }
 
 // One chain from its device context to its output files.  `index` > 0 (chains of `-chains N` beyond the first): the
@@ -458,6 +549,9 @@ struct ChainRun {
         for (auto& p : thetaParams) p = thetaParams[0];
         tau_theta.reset(new ThetaHyperParam<NormalInverseGammaParam>(thetaParams));
         theta.reset(new Theta<NormalInverseGamma>(*tau_theta, tau_A, tau_pi, job.useSelfTrans, RNG));
+        if (job.outputs.at("regions"))   // the joint posteriors over the regions of -regions, under the edges of -bands (include/hml.h)
+            hml_check(hml_set_regions(RNG.ctx(), job.regionStart.size(), job.regionStart.data(), job.regionEnd.data(), (int)job.regionEdges.size(),
+                                      job.regionEdges.empty() ? nullptr : job.regionEdges.data()));
         if (verbose) cout << "Setting block structure to dynamic" << endl << flush;
     }
     // a token of the scheme up to (not including) the sweeps of "F" / "M" (reference main.cpp:383-452): a pending prior draw
@@ -579,6 +673,7 @@ int main(int argc, const char* argv[]) {
         args.registerFlags({"-bands"});
         args.registerFlags({"-bandcall"}, "0");
         args.registerFlags({"-merge-gpus"});
+        args.registerFlags({"-regions"});
         args.parseArgs();
 
         if (args.isSet("-g")) args.print();
@@ -665,6 +760,7 @@ int main(int argc, const char* argv[]) {
         outputArgs.registerFlags({"LB", "bands"});            // extension
         outputArgs.registerFlags({"LC", "bandcalls"});        // extension
         outputArgs.registerFlags({"R", "rhat"});              // extension
+        outputArgs.registerFlags({"RG", "regions"});          // extension
         outputArgs.parseArgs();
 
         // ---- input
@@ -737,7 +833,7 @@ int main(int argc, const char* argv[]) {
         job.weightMultiplier = weightMultiplier; job.useSelfTrans = useSelfTrans;
         job.thetaParams = thetaParams; job.trans = trans; job.selfTrans = selfTrans; job.initialAlpha = initialAlpha;
         job.scheme = scheme;
-        for (const char* o : {"sequences", "parameters", "blocks", "compression", "marginals", "segments", "maxsegmentation", "levels", "breakpoints", "consensus", "bands", "bandcalls", "rhat"})
+        for (const char* o : {"sequences", "parameters", "blocks", "compression", "marginals", "segments", "maxsegmentation", "levels", "breakpoints", "consensus", "bands", "bandcalls", "rhat", "regions"})
             job.outputs[o] = outputArgs.isSet(o);
         auto refuseExisting = [&](const string& fn) {
             if (!overwrite) { std::ifstream probe(fn); if (probe.good()) throw std::runtime_error("File " + fn + " already exists! Use -w to allow overwrite!"); }
@@ -764,6 +860,7 @@ int main(int argc, const char* argv[]) {
                 if (!std::isfinite(e)) throw std::runtime_error("The edges of -bands must be finite!");
                 if (j > 0 && !(prev < e)) throw std::runtime_error("The edges of -bands must be strictly ascending!");
                 prev = e;
+                job.regionEdges.push_back(e);
                 char buf[32];
                 snprintf(buf, sizeof buf, "%.9g", (double)e);   // (nine digits give the float back)
                 env += (j ? "," : "") + string(buf);
@@ -774,6 +871,14 @@ int main(int argc, const char* argv[]) {
             if (!(job.bandCall >= 0 && job.bandCall <= 1)) throw std::runtime_error("The quantile of -bandcall must lie in [0, 1]!");
             if (wantsBands) setenv("HML_BANDS", env.c_str(), 1);
         }
+        // -regions FILE: read and checked against the input before anything runs and before any output file exists
+        const bool wantsRegions = job.outputs.at("regions");
+        if (wantsRegions && !args.isSet("-regions")) throw std::runtime_error("The output regions (RG) needs the regions: give them with -regions FILE!");
+        if (args.isSet("-regions")) {
+            if (args.nrTokens("-regions") != 1) throw std::runtime_error("Not enough arguments for flag -regions!");
+            readRegions(args.parse<string>("-regions"), T, job);
+        }
+        if (wantsRegions) refuseExisting(regionsFileName(job));
         if (job.outputs.at("bands")) refuseExisting(bandsFileName(job));
         if (job.outputs.at("bandcalls")) refuseExisting(bandCallsFileName(job));
         if (job.outputs.at("levels")) refuseExisting(levelsFileName(job));
@@ -847,7 +952,7 @@ int main(int argc, const char* argv[]) {
                     }
                 } catch (...) { poolError = std::current_exception(); }
             }
-            if ((int)ctxs.size() == nrChains && (wantsLevels || wantsBreaks || wantsBands) && !poolError) {
+            if ((int)ctxs.size() == nrChains && (wantsLevels || wantsBreaks || wantsBands || wantsRegions) && !poolError) {
                 // the chains share the GPU: their levels, breakpoint counts and band counts add up in the first chain's context, which the
                 // files are written from
                 try {
@@ -871,6 +976,8 @@ int main(int argc, const char* argv[]) {
                             if (wantsBands) hml_check(hml_bands_merge(ctxs[0], ctxs[k]));
                         }
                     }
+                    // (the regions' sums are a few words per region: they travel through the host, whichever GPUs the chains are on)
+                    if (wantsRegions) for (int k = 1; k < nrChains; ++k) hml_check(hml_regions_merge(ctxs[0], ctxs[k]));
                     writeContextFiles(job, ctxs[0]);
                 } catch (...) { poolError = std::current_exception(); }
             }

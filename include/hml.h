@@ -380,6 +380,48 @@ int hml_bands_call(hml_ctx* ctx, uint64_t rank, uint64_t* n_runs, uint64_t* run_
  * given edges takes `src`'s. */
 int hml_bands_merge(hml_ctx* dst, hml_ctx* src);
 
+/* ---- joint posteriors over caller-given regions.  No counterpart in the reference. ----
+ * A region is a half-open range of positions [start, end), 0 <= start < end <= T: a gene, an exon, a consensus segment.  The
+ * recordings above are per position, and the positions of a region are strongly correlated within a sweep: whether the WHOLE
+ * region is one segment, whether ALL of it lies in one band, how far its mean level spreads - none of these follows from
+ * them.  So every recorded sweep (its blocks, its states, and theta after its parameter update: the pairing of the levels)
+ * gives, per region, with blk(p) the block that holds position p, ba = blk(start), be = blk(end - 1):
+ *   nb     the breakpoints strictly inside: the blocks b in (ba, be] whose state differs from that of block b - 1;
+ *   same_d per data dimension d, with edges only: every block of [ba, be] has its level of dimension d in one band j_d - the
+ *          bands of hml_set_level_bands (band = the number of edges <= the level, as floats; not a number: band 0), over the
+ *          REGIONS' OWN edges, which have nothing to do with the edges of the per-position bands;
+ *   m_d    the region's mean level, (1 / (end - start)) sum over b of (positions of block b inside the region) x level, in double.
+ * and accumulates, per region,
+ *   whole += (nb == 0), breaks_sum += nb, breaks_sq += nb^2 (saturating at 2^64 - 1, and staying there),
+ *   level_sum[d] += m_d, level_sq[d] += m_d^2, inband[d (n_edges + 1) + j_d] += 1 when same_d.
+ * N counts the sweeps recorded while the regions were on.  Everything is label-free: the sums add over sweeps, chains and GPUs.
+ * The integers are exact; the double sums are the same bits on every run and depend on the sweep's blocks, states, theta and
+ * the region alone (not on launch geometry, block capacity, sweep path or hml_iterate_many); their error bound is in
+ * DESIGN.md 3c''''''.  A level that is not a number counts as band 0 and makes double sums not a number: those of
+ * every region that holds a block of that level, and - the blocks between a region's ends are summed through running sums over
+ * the sweep's blocks - those of every region that reaches beyond the chunk of 256 blocks with such a block.
+ *
+ * hml_set_regions gives up to 2^22 regions - in any order, overlapping, nested or repeated, each with accumulators of its own -
+ * and 0 to 31 edges (the rules of hml_set_level_bands; D (n_edges + 1) <= 64), and turns the recording on.  n = 0 turns it off
+ * and keeps the regions and what was accumulated; the same regions and edges, bit for bit, turn it on again.  Other regions or
+ * edges replace the buffers while N = 0 and are refused afterwards.  Regions given before the observations are loaded are
+ * compared with T by the first recorded sweep, which fails with a message.  hml_get_regions: what was last set (any pointer
+ * but n may be NULL). */
+int hml_set_regions(hml_ctx* ctx, uint64_t n, const uint32_t* start /*n*/, const uint32_t* end /*n*/, int n_edges, const float* edges /*n_edges*/);
+int hml_get_regions(hml_ctx* ctx, uint64_t* n, uint32_t* start /*n*/, uint32_t* end /*n*/, int* n_edges, float* edges /*31*/);
+/* The raw sums (after hml_settle).  n_columns = D (n_edges + 1), 0 without edges.  NULL arrays: the sizes only.  A context
+ * that was given regions but recorded nothing answers zeros with N = 0; HML_ERR_ARG on one that was never given regions. */
+int hml_regions_read(hml_ctx* ctx, uint64_t* n, int* n_columns, uint64_t* n_recorded, uint64_t* whole /*n*/, uint64_t* breaks_sum /*n*/,
+                     uint64_t* breaks_sq /*n*/, double* level_sum /*D*n, dimension-major*/, double* level_sq /*D*n*/,
+                     uint64_t* inband /*n*n_columns, region-major*/);
+/* Adds raw sums of the same regions from anywhere - another process included - and n_recorded to N: the integers add
+ * (breaks_sq with its saturation), every double gets ONE addition, ctx's value + the given one. */
+int hml_regions_add(hml_ctx* ctx, uint64_t n_recorded, const uint64_t* whole, const uint64_t* breaks_sum, const uint64_t* breaks_sq,
+                    const double* level_sum, const double* level_sq, const uint64_t* inband /*NULL without edges*/);
+/* hml_regions_read of `src` into hml_regions_add of `dst`: same T, D, regions and edges, bit for bit, otherwise HML_ERR_ARG; the
+ * two contexts may lie on any two devices.  `src` is unchanged and `dst` may go on recording. */
+int hml_regions_merge(hml_ctx* dst, hml_ctx* src);
+
 /* ---- sparse payloads: levels, breakpoints and bands across GPUs.  No counterpart in the reference. ----
  * The three recordings above keep a cell and a boundary bit per change of state, so what another GPU needs of one is a list:
  * the M positions with a cell and the cells there.  The PAYLOAD is one contiguous buffer in device memory, little endian,
@@ -489,7 +531,7 @@ int hml_get_stats(hml_ctx* ctx, hml_stats* out);
 
 /* HIP-event timing of one named kernel family accumulated since the last reset (milliseconds and
  * launches); name is one of "blocks_compact", "blocks_scatter", "block_stats", "stats_emission", "emission", "forward",
- * "backward_maps", "backward_chain", "mixture", "counts", "params", "marginals", "levels", "breaks", "bands", "event_null".  level 0 = off, 1 = only the dominant kernel
+ * "backward_maps", "backward_chain", "mixture", "counts", "params", "marginals", "levels", "breaks", "bands", "regions" (and inside it "regions_chunks", "regions_scan", "regions_accumulate"), "event_null".  level 0 = off, 1 = only the dominant kernel
  * ("blocks_compact", two events per sweep), 2 = every family. */
 int hml_profile_enable(hml_ctx* ctx, int level);
 int hml_profile_get(hml_ctx* ctx, const char* name, double* total_ms, uint64_t* launches);
