@@ -131,6 +131,8 @@ SIGNATURES = {
     "hml_profile_enable": (C.c_int, [_P, C.c_int]),
     "hml_profile_get": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "hml_debug_eval": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, C.c_uint64, C.c_uint64]),
+    "hml_device_memory_live": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "hml_debug_fail_allocation": (C.c_int, [C.c_int64]),
     "hml_synth_depth": (C.c_int, [_P, _P, C.c_uint64, C.c_double, C.c_double, C.c_uint64, C.c_int]),
     "hml_synth_gauss": (C.c_int, [_P, _P, C.c_uint64, C.c_int, _P, C.c_float, C.c_double, C.c_uint64, C.c_int]),
 }
@@ -230,6 +232,19 @@ def debug_eval(fn, a, b=None, seed=0, device=0):
         b = np.ascontiguousarray(b, np.float32)
     _check(lib.hml_debug_eval(device, fn, a.ctypes.data, b.ctypes.data if b is not None else None, out.ctypes.data, a.size, seed))
     return out
+
+
+def device_memory_live():
+    """(bytes, allocations) of device memory that the library's contexts and read-outs hold now, over the whole process"""
+    b, n = C.c_uint64(), C.c_uint64()
+    _check(load_library().hml_device_memory_live(C.byref(b), C.byref(n)))
+    return b.value, n.value
+
+
+def debug_fail_allocation(nth):
+    """Test hook: the nth device allocation from now (1: the next) fails once, as if out of memory; 0 turns it off.
+    Returns the number of allocations made since the hook was last set."""
+    return load_library().hml_debug_fail_allocation(nth)
 
 
 class Chain:

@@ -151,18 +151,25 @@ int hml_device_count(int* n) {
     return 0;
 }
 
-static void free_all(hml_ctx* c);
+// the context goes, and with it every buffer it owns; its own stream last
+static void delete_ctx(hml_ctx* c) {
+    const hipStream_t own = c->own_stream ? c->stream : nullptr;
+    delete c;
+    if (own) hipStreamDestroy(own);
+}
 
-// allocations of a fresh context; on failure the caller releases whatever was created
+// allocations of a fresh context; on failure the caller deletes it
 static int create_inner(hml_ctx* c, void* stream) {
     HIPCHK(hipSetDevice(c->device));
     if (stream) { c->stream = (hipStream_t)stream; c->own_stream = false; }
     else { HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); c->own_stream = true; }
-    HIPCHK(hipMalloc(&c->d_mdl, sizeof(hml_model)));
+    HIPCHK(c->d_mdl.alloc(1));
     HIPCHK(hipMemsetAsync(c->d_mdl, 0, sizeof(hml_model), c->stream));
     HIPCHK(hipHostMalloc(&c->h_B, 4 * sizeof(uint32_t), hipHostMallocMapped));
     c->h_B[0] = 0; c->h_B[1] = 0; c->h_B[2] = 0; c->h_B[3] = 0;
-    HIPCHK(hipHostGetDevicePointer((void**)&c->d_hB, c->h_B, 0));
+    void* d_hB = nullptr;
+    HIPCHK(hipHostGetDevicePointer(&d_hB, c->h_B, 0));
+    c->d_hB = static_cast<uint32_t*>(d_hB);
     return 0;
 }
 
@@ -174,12 +181,7 @@ int hml_create(hml_ctx** out, int device, uint64_t seed, uint32_t chain_id, void
     if (device < 0 || device >= n) return set_err(HML_ERR_ARG, "device index out of range");
     hml_ctx* c = new hml_ctx();
     c->device = device; c->seed = seed; c->chain = chain_id;
-    if (int r = create_inner(c, stream)) {
-        free_all(c);
-        if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
-        delete c;
-        return r;
-    }
+    if (int r = create_inner(c, stream)) { delete_ctx(c); return r; }
     if (const char* e = getenv("HML_FWD_CHUNK")) { int l = std::max(1, atoi(e)); int sh = 0; while ((1 << (sh + 1)) <= l && sh < 10) ++sh; c->fwdL = 1 << sh; }
     if (const char* e = getenv("HML_FWD_WARMUP")) c->fwdW = c->fwdW_init = std::max(0, atoi(e));
     if (const char* e = getenv("HML_FWD_BURNIN_SWEEPS")) c->fwd_burnin_sweeps = (uint32_t)std::max(0, atoi(e));
@@ -221,46 +223,15 @@ int hml_create(hml_ctx** out, int device, uint64_t seed, uint32_t chain_id, void
     return 0;
 }
 
-// the shared construction: the last context that holds it frees it
-static void trace_release(hml_ctx* c) {
-    if (c->trace) {
-        if (c->trace->refs.fetch_sub(1) == 1) {
-            void* ptrs[] = {c->trace->d_w, c->trace->d_summary, c->trace->d_coeff, c->trace->d_ia};
-            for (void* p : ptrs) if (p) hipFree(p);
-            delete c->trace;
-        }
-        c->trace = nullptr;
-    } else {
-        // (a load that failed before the trace object existed)
-        void* ptrs[] = {c->d_w, c->d_summary, c->d_coeff, c->d_ia};
-        for (void* p : ptrs) if (p) hipFree(p);
-    }
-    c->d_w = nullptr; c->d_summary = nullptr; c->d_coeff = nullptr; c->d_ia = nullptr;
+// the shared construction this context reads (none: nullptr), and the context's views of it; the last context that holds a
+// construction frees it
+static void set_trace(hml_ctx* c, std::shared_ptr<hml_trace> tr) {
+    c->trace = std::move(tr);
+    const hml_trace* t = c->trace.get();
+    c->d_w = t ? t->d_w.get() : nullptr; c->d_summary = t ? t->d_summary.get() : nullptr;
+    c->d_coeff = t ? t->d_coeff.get() : nullptr; c->d_ia = t ? t->d_ia.get() : nullptr;
 }
-static bool trace_shared(const hml_ctx* c) { return c->trace && c->trace->refs.load() > 1; }
-
-// the buffers hml_set_model allocates (keep_engine: growing the buffers of a running chain - the reference-compatible
-// mode's mt19937 state lives on)
-static void free_sweep_buffers(hml_ctx* c, bool keep_engine = false) {
-    void** ptrs[] = {(void**)&c->d_em, (void**)&c->d_gsc, (void**)&c->d_rows, (void**)&c->d_entry, (void**)&c->d_exitA, (void**)&c->d_redo, (void**)&c->d_touched,
-                     (void**)&c->d_fb, (void**)&c->d_smap, (void**)&c->d_cmap, (void**)&c->d_scmap, (void**)&c->d_super, (void**)&c->d_bentry2, (void**)&c->d_bentry,
-                     (void**)&c->d_q, (void**)&c->d_partial, (void**)&c->d_redo2, (void**)&c->d_tre_bitmap, (void**)&c->d_tre_ckpt, (void**)&c->d_crows, (void**)&c->d_cchunk, (void**)&c->d_cdraws, (void**)&c->d_clists, (void**)&c->d_wacc, (void**)&c->d_wA};
-    for (void** p : ptrs) if (*p) { hipFree(*p); *p = nullptr; }
-    if (!keep_engine && c->d_mt) { hipFree(c->d_mt); c->d_mt = nullptr; }
-}
-
-static void free_all(hml_ctx* c) {
-    trace_release(c);
-    free_sweep_buffers(c);
-    void* ptrs[] = {c->d_group_word, c->d_wave_total, c->d_stage, c->d_span_count, c->d_starts, c->d_bstat, c->d_eprobe, c->d_aprobe, c->d_coarse1,
-                    c->d_diff, c->d_boundary, c->d_mdl, c->d_many};
-    for (void* p : ptrs) if (p) hipFree(p);
-    for (hml_recorder& r : c->rec) { if (r.d_acc) hipFree(r.d_acc); if (r.d_boundary) hipFree(r.d_boundary); }
-    free_region_buffers(c);
-    if (c->h_B) hipHostFree(c->h_B);
-    c->h_B = nullptr;
-}
-
+static bool trace_shared(const hml_ctx* c) { return c->trace.use_count() > 1; }
 
 void hml_destroy(hml_ctx* c) {
     if (!c) return;
@@ -269,10 +240,8 @@ void hml_destroy(hml_ctx* c) {
     hipStreamSynchronize(c->stream);
     for (auto& kv : c->prof) for (auto& p : kv.second.pending) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
     for (auto e : c->ev_pool) hipEventDestroy(e);
-    if (c->graph_exec) hipGraphExecDestroy(c->graph_exec);
-    free_all(c);
-    if (c->own_stream) hipStreamDestroy(c->stream);
-    delete c;
+    drop_graph(c);
+    delete_ctx(c);
 }
 
 // ---------------------------------------------------------------------------------------- load
@@ -283,7 +252,8 @@ static int build_keys(hml_ctx* c) {
     if (!c->d_summary) {
         // one byte per 16-position group, padded with zeros to whole spans
         const uint64_t n_spans = (T + HML_SPAN - 1) / HML_SPAN;
-        HIPCHK(hipMalloc(&c->d_summary, n_spans * (HML_SPAN / 16) + 16));
+        HIPCHK(c->trace->d_summary.alloc(n_spans * (HML_SPAN / 16) + 16));
+        c->d_summary = c->trace->d_summary;
         HIPCHK(hipMemsetAsync(c->d_summary, 0, n_spans * (HML_SPAN / 16) + 16, c->stream));
     }
     const float thr0 = (float)(std::sqrt(2 * std::log((double)std::max<uint64_t>(T, 2))) * c->sigma * c->key_scale);
@@ -300,22 +270,24 @@ HML_KERNEL void hml_k_max_inplace(float* __restrict__ a, const float* __restrict
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) { const float x = a[i], y = b[i]; a[i] = (x < y) ? y : x; }   // std::max(x, y)
 }
 
+enum { CAPBUF_BLOCKS = 1, CAPBUF_PROBES = 2, CAPBUF_SWEEP = 4 };
+static int alloc_capacity_buffers(hml_ctx* c, int what);   // (below)
+
 // the per-chain block-structure buffers (every context has its own; the construction above them may be shared)
 static int alloc_block_buffers(hml_ctx* c) {
     const uint64_t T = c->T;
     c->n_spans = (uint32_t)((T + HML_SPAN - 1) / HML_SPAN);
-    HIPCHK(hipMalloc(&c->d_stage, (uint64_t)c->n_spans * HML_SPAN * sizeof(uint16_t)));
-    HIPCHK(hipMalloc(&c->d_span_count, c->n_spans * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&c->d_starts, (c->cap + 1) * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&c->d_coarse1, ((c->n_spans + HML_GROUP_SPANS - 1) / HML_GROUP_SPANS + 1u) * sizeof(uint32_t)));
+    HIPCHK(c->d_stage.alloc((uint64_t)c->n_spans * HML_SPAN));
+    HIPCHK(c->d_span_count.alloc(c->n_spans));
+    HIPCHK(c->d_coarse1.alloc((c->n_spans + HML_GROUP_SPANS - 1) / HML_GROUP_SPANS + 1u));
     {
         const uint64_t n_tiles = (T + HML_FUSED_SUB_POSITIONS - 1) / HML_FUSED_SUB_POSITIONS;   // (tiles of one batch: the most there can be)
-        HIPCHK(hipMalloc(&c->d_group_word, (n_tiles + 1) * sizeof(unsigned long long)));
+        HIPCHK(c->d_group_word.alloc(n_tiles + 1));
         HIPCHK(hipMemsetAsync(c->d_group_word, 0, (n_tiles + 1) * sizeof(unsigned long long), c->stream));
-        HIPCHK(hipMalloc(&c->d_wave_total, (n_tiles + 1) * (HML_FUSED_WAVES + 2) * sizeof(uint32_t)));   // (+ tile_before, tile_prev)
-        if (getenv("HML_FUSED_DEBUG")) { HIPCHK(hipMalloc(&c->d_dbg, 4096 * 8 * 8)); HIPCHK(hipMemset(c->d_dbg, 0, 4096 * 8 * 8)); }
+        HIPCHK(c->d_wave_total.alloc((n_tiles + 1) * (HML_FUSED_WAVES + 2)));   // (+ tile_before, tile_prev)
+        if (getenv("HML_FUSED_DEBUG")) { HIPCHK(c->d_dbg.alloc(4096 * 8)); HIPCHK(hipMemset(c->d_dbg, 0, 4096 * 8 * 8)); }
     }
-    HIPCHK(hipMalloc(&c->d_bstat, c->cap * (uint64_t)c->D * sizeof(float2)));   // (D > 1: cap = T, the planes lie T apart)
+    if (int r = alloc_capacity_buffers(c, CAPBUF_BLOCKS)) return r;
     // the capacity the enumeration kernels respect (they run before there is a model: auto prior, explicit thresholds)
     const uint32_t cap32 = (uint32_t)c->cap;
     HIPCHK(hipMemcpyAsync(&c->d_mdl->cap, &cap32, sizeof cap32, hipMemcpyHostToDevice, c->stream));
@@ -339,11 +311,7 @@ static void choose_capacity(hml_ctx* c, bool attached) {
 static int build_from_device_x(hml_ctx* c, const float* const* d_x, const float* const* h_x) {
     const uint64_t T = c->T;
     const int D = c->D;
-    {   // what an earlier load that failed half-way may have left behind
-        trace_release(c);
-        void** stale[] = {(void**)&c->d_stage, (void**)&c->d_span_count, (void**)&c->d_starts, (void**)&c->d_coarse1, (void**)&c->d_group_word, (void**)&c->d_wave_total, (void**)&c->d_bstat};
-        for (void** q : stale) if (*q) { hipFree(*q); *q = nullptr; }
-    }
+    set_trace(c, std::make_shared<hml_trace>());   // (an earlier load that failed half-way: its construction goes first)
     // noise estimate (src/main.cpp:303-311): f64 accumulation, in index order, of the finest-level
     // maxlet coefficients c[t] = max over the dimensions of sqrt2half * |x[t-1] - x[t]| at odd t
     // (wavelet.hpp:139-158, level 1)
@@ -365,9 +333,10 @@ static int build_from_device_x(hml_ctx* c, const float* const* d_x, const float*
         acc /= 0.797884560802865355879892119868763736951717262329869315331;
         c->sigma = acc;
     }
-    HIPCHK(hipMalloc(&c->d_w, T * sizeof(float)));
-    HIPCHK(hipMalloc(&c->d_coeff, T * sizeof(float)));
-    HIPCHK(hipMalloc(&c->d_ia, (T + 1) * (uint64_t)D * sizeof(float2)));
+    HIPCHK(c->trace->d_w.alloc(T));
+    HIPCHK(c->trace->d_coeff.alloc(T));
+    HIPCHK(c->trace->d_ia.alloc((T + 1) * (uint64_t)D));
+    set_trace(c, c->trace);
     // K1: levels 10 at a time, one dimension after the other; the coefficient is the maximum over the dimensions
     {
         float h_norm[64];
@@ -376,15 +345,15 @@ static int build_from_device_x(hml_ctx* c, const float* const* d_x, const float*
         h_norm[0] = 1.0f;
         float nrm = sqrt2half;
         for (int l = 1; l < 64; ++l) { h_norm[l] = nrm; nrm *= sqrt2half; }
-        DevScratch s_norm, s_a, s_b, s_other;   // freed on every path out of this scope
-        HIPCHK(hipMalloc(&s_norm.p, sizeof h_norm));
-        float* d_norm = s_norm.as<float>();
+        DevArr<float> s_norm, s_a, s_b, s_other;   // freed on every path out of this scope
+        HIPCHK(s_norm.alloc(64));
+        float* d_norm = s_norm;
         HIPCHK(hipMemcpyAsync(d_norm, h_norm, sizeof h_norm, hipMemcpyHostToDevice, c->stream));
         const uint64_t n1 = T >> HML_MAXLET_LOG_TILE;
-        HIPCHK(hipMalloc(&s_a.p, std::max<uint64_t>(n1, 1) * sizeof(float)));
-        HIPCHK(hipMalloc(&s_b.p, std::max<uint64_t>(n1 >> HML_MAXLET_LOG_TILE, 1) * sizeof(float)));
-        if (D > 1) HIPCHK(hipMalloc(&s_other.p, T * sizeof(float)));
-        float *bufA = s_a.as<float>(), *bufB = s_b.as<float>(), *d_other = s_other.as<float>();
+        HIPCHK(s_a.alloc(std::max<uint64_t>(n1, 1)));
+        HIPCHK(s_b.alloc(std::max<uint64_t>(n1 >> HML_MAXLET_LOG_TILE, 1)));
+        if (D > 1) HIPCHK(s_other.alloc(T));
+        float *bufA = s_a, *bufB = s_b, *d_other = s_other;
         for (int d = 0; d < D; ++d) {
             float* coeff_out = d == 0 ? c->d_coeff : d_other;
             uint64_t n = T;
@@ -421,8 +390,6 @@ static int build_from_device_x(hml_ctx* c, const float* const* d_x, const float*
     choose_capacity(c, false);
     if (int r = alloc_block_buffers(c)) return r;
     HIPCHK(hipStreamSynchronize(c->stream));
-    c->trace = new hml_trace();
-    c->trace->d_w = c->d_w; c->trace->d_summary = c->d_summary; c->trace->d_coeff = c->d_coeff; c->trace->d_ia = c->d_ia;
     c->loaded = true;
     return 0;
 }
@@ -455,9 +422,9 @@ int hml_load_observations(hml_ctx* c, const float* x, uint64_t n_values) {
     if (c->loaded) return set_err(HML_ERR_ARG, "observations already loaded");
     if (int r = ctx_bind(c)) return r;
     c->T = T;
-    DevScratch s_x;
-    HIPCHK(hipMalloc(&s_x.p, n_values * sizeof(float)));
-    float* d_x = s_x.as<float>();
+    DevArr<float> s_x;
+    HIPCHK(s_x.alloc(n_values));
+    float* d_x = s_x;
     std::vector<float> planes;             // dimension-major copy when D > 1
     const float* h_dim[HML_MAX_D];
     const float* d_dim[HML_MAX_D];
@@ -499,19 +466,12 @@ int hml_attach_observations(hml_ctx* c, hml_ctx* src) {
     if (c->use_keys != src->use_keys) return set_err(HML_ERR_ARG, "option weight_keys differs from the source context's");
     if (int r = ctx_bind(c)) return r;
     HIPCHK(hipStreamSynchronize(src->stream));   // (a weight multiplier still on its way)
-    trace_release(c);
-    {
-        void** stale[] = {(void**)&c->d_stage, (void**)&c->d_span_count, (void**)&c->d_starts, (void**)&c->d_coarse1, (void**)&c->d_group_word, (void**)&c->d_wave_total, (void**)&c->d_bstat};
-        for (void** q : stale) if (*q) { hipFree(*q); *q = nullptr; }
-    }
     c->T = src->T; c->D = src->D;
     if (c->P == 0 || c->D > 1) c->P = src->P;
     c->sigma = src->sigma; c->key_base = src->key_base; c->key_scale = src->key_scale;
-    c->trace = src->trace;
-    c->trace->refs.fetch_add(1);
-    c->d_w = src->d_w; c->d_summary = src->d_summary; c->d_coeff = src->d_coeff; c->d_ia = src->d_ia;
+    set_trace(c, src->trace);
     choose_capacity(c, true);
-    if (int r = alloc_block_buffers(c)) { trace_release(c); return r; }
+    if (int r = alloc_block_buffers(c)) { set_trace(c, nullptr); return r; }
     HIPCHK(hipStreamSynchronize(c->stream));
     c->loaded = true;
     return 0;
@@ -552,8 +512,6 @@ int hml_set_weights(hml_ctx* c, const float* w, uint64_t T) {
 
 }  // extern "C"
 
-extern "C" {
-}  // extern "C"
 static int grow_capacity(hml_ctx* c, uint64_t needed);
 // an enumeration at an explicit threshold (with block statistics), waited for; a context with a reduced block capacity
 // grows until the blocks fit (hml_state.h)
@@ -643,17 +601,17 @@ static int alloc_sweep_buffers(hml_ctx* c) {
     const int K = c->K;
     const uint64_t cap = c->cap;
     if (c->compat) {   // the reference-compatible mode (hml_k_compat.h): plain emission terms [b][s], a plain (B + 1) x K trellis, the states
-        HIPCHK(hipMalloc(&c->d_em, cap * K * sizeof(float)));
-        HIPCHK(hipMalloc(&c->d_gsc, cap * K * sizeof(float)));
-        HIPCHK(hipMalloc(&c->d_crows, (cap + 1) * K * sizeof(float)));
+        HIPCHK(c->d_em.alloc(cap * K));
+        HIPCHK(c->d_gsc.alloc(cap * K));
+        HIPCHK(c->d_crows.alloc((cap + 1) * K));
         // chunks of the filter and of the backward draws (hml_compat_chunks), the engine's outputs of a sweep (two per block)
-        HIPCHK(hipMalloc(&c->d_cchunk, (uint64_t)HML_COMPAT_MAX_CHUNKS * (2 * K * sizeof(float) + 4 * sizeof(uint32_t)) + 64));
-        HIPCHK(hipMalloc(&c->d_cdraws, 2 * cap * sizeof(uint32_t)));
+        HIPCHK(c->d_cchunk.alloc((uint64_t)HML_COMPAT_MAX_CHUNKS * (2 * K * sizeof(float) + 4 * sizeof(uint32_t)) + 64));
+        HIPCHK(c->d_cdraws.alloc(2 * cap));
         // the count pass's lists by state (hml_compat_lists): statistics, sizes, per-tile counts, flags
         // (three arrays of cap + 4 K entries, each 16-byte aligned: a state's list starts at a multiple of four entries)
-        HIPCHK(hipMalloc(&c->d_clists, 3 * compat_list_entries(c) * sizeof(uint32_t) + (uint64_t)HML_CAP_K * HML_CAP_K * sizeof(unsigned long long) +
+        HIPCHK(c->d_clists.alloc(3 * compat_list_entries(c) * sizeof(uint32_t) + (uint64_t)HML_CAP_K * HML_CAP_K * sizeof(unsigned long long) +
                                         ((cap + HML_COMPAT_PART_TILE - 1) / HML_COMPAT_PART_TILE) * K * sizeof(uint32_t) + 2 * (HML_CAP_K + 1) * sizeof(uint32_t) + 64));
-        HIPCHK(hipMalloc(&c->d_q, cap * sizeof(int16_t)));
+        HIPCHK(c->d_q.alloc(cap));
         return 0;
     }
     if (c->wide) {   // more than 16 states (hml_k_wide.h, hml_k_wide_lanes.h): [b][s] arrays or chunk-transposed ones, the default path's count tree
@@ -663,23 +621,23 @@ static int alloc_sweep_buffers(hml_ctx* c) {
         if (c->wide_lshift >= 0) Lmax = std::max<uint64_t>(Lmax, 1ull << c->wide_lshift);
         while ((cap + Lmax - 1) / Lmax > (uint64_t)wide_max_chunks_of(c)) Lmax *= 2;   // (the longest chunks hml_k_wl_prepare can choose: B <= cap)
         const uint64_t plane = (cap + 1 + 64 * Lmax) * K;
-        HIPCHK(hipMalloc(&c->d_em, plane * sizeof(float)));
-        HIPCHK(hipMalloc(&c->d_gsc, plane * sizeof(float)));
-        HIPCHK(hipMalloc(&c->d_crows, plane * sizeof(float)));
+        HIPCHK(c->d_em.alloc(plane));
+        HIPCHK(c->d_gsc.alloc(plane));
+        HIPCHK(c->d_crows.alloc(plane));
         // (per-chunk arrays: as many chunks as the shortest chunk length makes of the capacity - at least what the lane-per-state form may ask for)
         const uint64_t Lmin = c->wide_lshift >= 0 ? (1ull << c->wide_lshift) : (1ull << HML_WL_MIN_LSHIFT);
         c->wide_chunks_cap = std::max<uint64_t>(HML_COMPAT_MAX_CHUNKS, std::min<uint64_t>(HML_WL_MAX_CHUNKS, (cap + Lmin - 1) / Lmin + 64));
         const uint64_t chunk_bytes = c->wide_chunks_cap * (2 * K * sizeof(float) + 4 * sizeof(uint32_t));
-        HIPCHK(hipMalloc(&c->d_cchunk, chunk_bytes + HML_WL_TOT_WORDS * sizeof(unsigned long long)));
-        HIPCHK(hipMemsetAsync((char*)c->d_cchunk + chunk_bytes, 0, HML_WL_TOT_WORDS * sizeof(unsigned long long), c->stream));   // (counters and bit maps of wrong chunks)
-        HIPCHK(hipMalloc(&c->d_wA, ((uint64_t)HML_WL_PITCH * HML_WL_PITCH + (uint64_t)HML_CAP_K * HML_WL_GTAB) * sizeof(float)));   // (... and the table of rescale factors behind it)
-        HIPCHK(hipMalloc(&c->d_cdraws, 2 * (cap + 1) * sizeof(uint32_t)));
-        HIPCHK(hipMalloc(&c->d_q, cap * sizeof(int16_t)));
+        HIPCHK(c->d_cchunk.alloc(chunk_bytes + HML_WL_TOT_WORDS * sizeof(unsigned long long)));
+        HIPCHK(hipMemsetAsync(c->d_cchunk.as<char>() + chunk_bytes, 0, HML_WL_TOT_WORDS * sizeof(unsigned long long), c->stream));   // (counters and bit maps of wrong chunks)
+        HIPCHK(c->d_wA.alloc((uint64_t)HML_WL_PITCH * HML_WL_PITCH + (uint64_t)HML_CAP_K * HML_WL_GTAB));   // (... and the table of rescale factors behind it)
+        HIPCHK(c->d_cdraws.alloc(2 * (cap + 1)));
+        HIPCHK(c->d_q.alloc(cap));
         const uint64_t n_partial = (uint64_t)HML_REDUCE_GROUPS * K * 2;
-        HIPCHK(hipMalloc(&c->d_partial, n_partial * sizeof(double)));
+        HIPCHK(c->d_partial.alloc(n_partial));
         HIPCHK(hipMemsetAsync(c->d_partial, 0, n_partial * sizeof(double), c->stream));
-        HIPCHK(hipMalloc(&c->d_wacc, sizeof(hml_wide_acc)));
-        HIPCHK(hipMemsetAsync(c->d_wacc, 0, sizeof(hml_wide_acc), c->stream));
+        HIPCHK(c->d_wacc.alloc(sizeof(hml_wide_acc)));
+        HIPCHK(hipMemsetAsync(c->d_wacc.get(), 0, sizeof(hml_wide_acc), c->stream));
         return 0;
     }
     const int minL = std::min(std::min(std::min(c->fwdL, c->fwdL_dense), c->fwdL_many), c->fwdL_mid);
@@ -695,59 +653,65 @@ static int alloc_sweep_buffers(hml_ctx* c) {
     layout(c->fwdL_dense, c->lay_dense);
     layout(c->fwdL_mid, c->lay_mid);
     layout(c->fwdL_many, c->lay_many);
-    HIPCHK(hipMalloc(&c->d_em, plane * sizeof(float)));
-    HIPCHK(hipMalloc(&c->d_gsc, plane * sizeof(float)));
-    HIPCHK(hipMalloc(&c->d_rows, plane * sizeof(float)));
-    HIPCHK(hipMalloc(&c->d_entry, maxChunks * K * sizeof(float)));
-    HIPCHK(hipMalloc(&c->d_exitA, maxChunks * K * sizeof(float)));
-    HIPCHK(hipMalloc(&c->d_fb, maxChunks * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&c->d_smap, (cap + 2) * sizeof(unsigned long long)));
+    HIPCHK(c->d_em.alloc(plane));
+    HIPCHK(c->d_gsc.alloc(plane));
+    HIPCHK(c->d_rows.alloc(plane));
+    HIPCHK(c->d_entry.alloc(maxChunks * K));
+    HIPCHK(c->d_exitA.alloc(maxChunks * K));
+    HIPCHK(c->d_fb.alloc(maxChunks));
+    HIPCHK(c->d_smap.alloc(cap + 2));
     // per-chunk arrays serve the backward chunks of 64 rows and the fused trellis path's forward chunks of 16 or 32
     const uint64_t bchunks = (cap + 15) / 16 + 1;
-    HIPCHK(hipMalloc(&c->d_cmap, bchunks * sizeof(unsigned long long)));
-    HIPCHK(hipMalloc(&c->d_bentry, bchunks));
-    HIPCHK(hipMalloc(&c->d_scmap, bchunks * sizeof(unsigned long long)));
-    HIPCHK(hipMalloc(&c->d_super, (bchunks / 64 + 2) * sizeof(unsigned long long)));
-    HIPCHK(hipMalloc(&c->d_bentry2, bchunks / 64 + 2));
-    HIPCHK(hipMalloc(&c->d_redo, bchunks * sizeof(uint32_t)));
+    HIPCHK(c->d_cmap.alloc(bchunks));
+    HIPCHK(c->d_bentry.alloc(bchunks));
+    HIPCHK(c->d_scmap.alloc(bchunks));
+    HIPCHK(c->d_super.alloc(bchunks / 64 + 2));
+    HIPCHK(c->d_bentry2.alloc(bchunks / 64 + 2));
+    HIPCHK(c->d_redo.alloc(bchunks));
     HIPCHK(hipMemsetAsync(c->d_redo, 0, bchunks * sizeof(uint32_t), c->stream));
-    HIPCHK(hipMalloc(&c->d_touched, bchunks * sizeof(uint32_t)));
+    HIPCHK(c->d_touched.alloc(bchunks));
     HIPCHK(hipMemsetAsync(c->d_touched, 0, bchunks * sizeof(uint32_t), c->stream));
-    HIPCHK(hipMalloc(&c->d_redo2, bchunks * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&c->d_tre_bitmap, (bchunks / 32 + 2) * sizeof(uint32_t)));
+    HIPCHK(c->d_redo2.alloc(bchunks));
+    HIPCHK(c->d_tre_bitmap.alloc(bchunks / 32 + 2));
     // (checkpoints of the fused trellis path: (L / 64 - 1) x ceil(B / L) <= B / 64 + 16 vectors of K + 1 words)
-    HIPCHK(hipMalloc(&c->d_tre_ckpt, (cap / HML_TRE_CKPT_ROWS + 64) * (uint64_t)(K + 1) * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&c->d_q, cap * sizeof(int16_t)));
+    HIPCHK(c->d_tre_ckpt.alloc((cap / HML_TRE_CKPT_ROWS + 64) * (uint64_t)(K + 1)));
+    HIPCHK(c->d_q.alloc(cap));
     // (the count pass's group partials [2 K][1024] and, behind them, the first level of their tree [16][2 K]: hml_k_params.h)
     const uint64_t n_partial = ((uint64_t)HML_REDUCE_GROUPS + HML_PARAMS_TREE_WGS) * K * 2;
-    HIPCHK(hipMalloc(&c->d_partial, n_partial * sizeof(double)));
+    HIPCHK(c->d_partial.alloc(n_partial));
     HIPCHK(hipMemsetAsync(c->d_partial, 0, n_partial * sizeof(double), c->stream));
     return 0;
 }
 
-// More room for blocks: the per-block buffers are released and allocated again for at least `needed` blocks (half as many
-// again, at least twice the old capacity, at most T).  Nothing in them outlives a sweep except a static block structure, which
-// the next sweep enumerates again.  The stream is idle.
-static int grow_capacity(hml_ctx* c, uint64_t needed) {
-    const uint64_t cap = std::min<uint64_t>(c->T, std::max<uint64_t>(needed + needed / 2 + 1024, 2 * c->cap));
-    if (c->graph_exec) { hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
-    void** blocks[] = {(void**)&c->d_starts, (void**)&c->d_bstat};
-    for (void** q : blocks) if (*q) { hipFree(*q); *q = nullptr; }
-    free_sweep_buffers(c, /*keep_engine*/ true);
-    if (c->d_eprobe) { hipFree(c->d_eprobe); c->d_eprobe = nullptr; }
-    if (c->d_aprobe) { hipFree(c->d_aprobe); c->d_aprobe = nullptr; }
-    c->cap = cap;
-    HIPCHK(hipMalloc(&c->d_starts, (cap + 1) * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&c->d_bstat, cap * (uint64_t)c->D * sizeof(float2)));
-    if (c->model_set) {
-        if (int r = alloc_sweep_buffers(c)) return r;
-        if (c->probes) {
-            HIPCHK(hipMalloc(&c->d_eprobe, c->cap * c->K * sizeof(float)));
-            HIPCHK(hipMalloc(&c->d_aprobe, (c->cap + 1) * c->K * sizeof(float)));
-        }
+// Everything that is sized by the block capacity, in ONE place: block starts and statistics (from the load on), the probes
+// (hml_enable_probes) and the sweep buffers (from the model on).  Allocating a buffer replaces what it held, so a call that
+// failed half-way is simply made again.
+static int alloc_capacity_buffers(hml_ctx* c, int what) {
+    if (what & CAPBUF_BLOCKS) {
+        HIPCHK(c->d_starts.alloc(c->cap + 1));
+        HIPCHK(c->d_bstat.alloc(c->cap * (uint64_t)c->D));   // (D > 1: cap = T, the planes lie T apart)
     }
-    const uint32_t words[2] = {(uint32_t)cap, 0u};   // hml_model: cap, halted (adjacent)
+    if (what & CAPBUF_PROBES) {
+        HIPCHK(c->d_eprobe.alloc(c->cap * c->K));
+        HIPCHK(c->d_aprobe.alloc((c->cap + 1) * c->K));
+    }
+    return (what & CAPBUF_SWEEP) ? alloc_sweep_buffers(c) : 0;
+}
+
+// More room for blocks: the per-block buffers are allocated again for at least `needed` blocks (half as many again, at least
+// twice the old capacity, at most T).  Nothing in them outlives a sweep except a static block structure, which the next sweep
+// enumerates again; the reference-compatible mode's engine (d_mt) is not among them and lives on.  Buffer by buffer: every
+// new one is at least as large as the one it replaces, so the device never holds more than the new total.  The stream is idle.
+// A failure leaves the capacity as it was and the chain halted: the next entry point comes here again (hml_settle) before
+// anything is launched.
+static int grow_capacity(hml_ctx* c, uint64_t needed) {
+    const uint64_t old_cap = c->cap;
+    drop_graph(c);
+    c->cap = std::min<uint64_t>(c->T, std::max<uint64_t>(needed + needed / 2 + 1024, 2 * old_cap));
+    const uint32_t words[2] = {(uint32_t)c->cap, 0u};   // hml_model: cap, halted (adjacent)
     static_assert(offsetof(hml_model, halted) == offsetof(hml_model, cap) + sizeof(uint32_t), "cap and halted are written together");
+    if (!c->probes) { c->d_eprobe.free(); c->d_aprobe.free(); }   // (switched off: hml_enable_probes allocates them again, at the capacity of its day)
+    if (int r = alloc_capacity_buffers(c, CAPBUF_BLOCKS | (c->model_set ? CAPBUF_SWEEP | (c->probes ? CAPBUF_PROBES : 0) : 0))) { c->cap = old_cap; return r; }
     HIPCHK(hipMemcpyAsync(&c->d_mdl->cap, words, sizeof words, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     c->h_B[2] = 0u;
@@ -770,17 +734,19 @@ int hml_settle(hml_ctx* c) {
         const uint64_t needed = c->h_B[2];
         if (c->cap >= c->T) return set_err(HML_ERR_HIP, "internal error: a chain with full block capacity halted");
         std::vector<uint8_t> pending;
+        unsigned long long base = c->log_base;
         if (c->model_set) {
             hml_model m;
             if (int r = fetch_model(c, &m)) return r;
             // (the log starts at log_base sweeps; what the counter says beyond that ran, the rest did not)
             const uint64_t ran = m.sweeps >= c->log_base ? m.sweeps - c->log_base : 0;
             if (ran < c->sweep_log.size()) pending.assign(c->sweep_log.begin() + ran, c->sweep_log.end());
-            c->log_base = m.sweeps;
+            base = m.sweeps;
         }
-        if (int r = grow_capacity(c, needed)) return r;
+        if (int r = grow_capacity(c, needed)) return r;   // (log and base as they were: the call can be made again)
         // the log now holds exactly the sweeps that have to run (again): the model's counter tells how far they got
         c->sweep_log = pending;
+        c->log_base = base;
         bool halted_again = false;
         for (size_t i = 0; i < pending.size() && !halted_again; ++i) {
             const char method = (pending[i] & 1) ? HML_METHOD_MIXTURE : HML_METHOD_FB;
@@ -826,13 +792,12 @@ int hml_set_model(hml_ctx* c, int K, const float nig4[4], float a_off, float a_d
     c->wide = !c->compat && (K > HML_MAX_K || (getenv("HML_WIDE") && atoi(getenv("HML_WIDE")) != 0));
     if (!c->compat && !c->wide) { kt = ktab(K); if (!kt) return set_err(HML_ERR_ARG, "number of states must be in [2,16]"); }
     if (int r = ctx_bind(c)) return r;
-    free_sweep_buffers(c);   // (what an earlier call that failed half-way left behind)
     c->K = K;
     // the parameter kernel's tree over 16 workgroups (hml_k_params.h) from 8 states: it reads 2 K x 8 KB of group partials -
     // config 4's sweep (10 states) 0.0938 -> 0.0869 ms, config 3's (5 states) unchanged either way
     if (!getenv("HML_PARAMS_SPREAD")) c->params_spread = K >= 8;
     const uint64_t T = c->T;
-    if (int r = alloc_sweep_buffers(c)) return r;
+    if (int r = alloc_capacity_buffers(c, CAPBUF_SWEEP)) return r;
 
     hml_model m;
     memset(&m, 0, sizeof m);
@@ -878,15 +843,15 @@ int hml_set_model(hml_ctx* c, int K, const float nig4[4], float a_off, float a_d
         // marginals.
         hml_mt_state h;
         hml_mt_seed(&h, c->seed + (uint64_t)c->chain);
-        HIPCHK(hipMalloc(&c->d_mt, sizeof(hml_mt_state)));
-        HIPCHK(hipMemcpyAsync(c->d_mt, &h, sizeof h, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c->d_mt.alloc(sizeof(hml_mt_state)));
+        HIPCHK(hipMemcpyAsync(c->d_mt.get(), &h, sizeof h, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
-        hipLaunchKernelGGL(hml_k_compat_draw, dim3(1), dim3(64), 0, c->stream, c->d_mdl, (hml_mt_state*)c->d_mt, 2);
+        hipLaunchKernelGGL(hml_k_compat_draw, dim3(1), dim3(64), 0, c->stream, c->d_mdl, c->d_mt.as<hml_mt_state>(), 2);
         KLAUNCH_CHECK();
         c->model_set = true;
         return 0;
     }
-    if (c->wide) hipLaunchKernelGGL(hml_k_wide_params, dim3(1), dim3(1024), 0, c->stream, c->d_mdl, c->d_partial, (hml_wide_acc*)c->d_wacc, 2);
+    if (c->wide) hipLaunchKernelGGL(hml_k_wide_params, dim3(1), dim3(1024), 0, c->stream, c->d_mdl, c->d_partial, c->d_wacc.as<hml_wide_acc>(), 2);
     else kt->params(c, 2);
     KLAUNCH_CHECK();
     c->model_set = true;
@@ -898,9 +863,9 @@ int hml_sample_prior(hml_ctx* c) {
     if (int r = ctx_bind(c)) return r;
     if (int r = settle_if_limited(c)) return r;
     if (c->compat) {
-        hipLaunchKernelGGL(hml_k_compat_draw, dim3(1), dim3(64), 0, c->stream, c->d_mdl, (hml_mt_state*)c->d_mt, 1);
+        hipLaunchKernelGGL(hml_k_compat_draw, dim3(1), dim3(64), 0, c->stream, c->d_mdl, c->d_mt.as<hml_mt_state>(), 1);
     } else if (c->wide) {
-        hipLaunchKernelGGL(hml_k_wide_params, dim3(1), dim3(1024), 0, c->stream, c->d_mdl, c->d_partial, (hml_wide_acc*)c->d_wacc, 1);
+        hipLaunchKernelGGL(hml_k_wide_params, dim3(1), dim3(1024), 0, c->stream, c->d_mdl, c->d_partial, c->d_wacc.as<hml_wide_acc>(), 1);
     } else { HML_KTAB(c->K, kt); kt->params(c, 1); }
     KLAUNCH_CHECK();
     if (c->dynamic) c->blocks_valid = false;
@@ -918,7 +883,7 @@ int hml_set_self_transitions(hml_ctx* c, int on) {
     if (int r = settle_if_limited(c)) return r;
     hipLaunchKernelGGL(hml_k_set_self_trans, dim3(1), dim3(64), 0, c->stream, c->d_mdl, on ? 1 : 0);
     KLAUNCH_CHECK();
-    if (c->graph_exec) { hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
+    drop_graph(c);
     return 0;
 }
 
@@ -973,7 +938,7 @@ static int set_recorder(hml_ctx* c, int kind, int on) {
     c->rec[kind].on = on != 0;
     if (on) c->rec[kind].asked = true;
     // (recorded sweeps are never replayed from a captured graph - hml_iterate - but a graph captured under the other setting goes anyway)
-    if (c->graph_exec) { if (int r = ctx_bind(c)) return r; hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
+    if (c->graph_exec) { if (int r = ctx_bind(c)) return r; drop_graph(c); }
     return 0;
 }
 int hml_set_level_recording(hml_ctx* c, int on) { return set_recorder(c, HML_REC_LEVELS, on); }
@@ -982,7 +947,7 @@ int hml_set_break_recording(hml_ctx* c, int on) { return set_recorder(c, HML_REC
 int hml_set_level_bands(hml_ctx* c, int n_edges, const float* edges) {
     if (!c) return set_err(HML_ERR_ARG, "null context");
     // (as in hml_set_level_recording: a graph captured under the other setting goes)
-    if (c->graph_exec) { if (int r = ctx_bind(c)) return r; hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
+    if (c->graph_exec) { if (int r = ctx_bind(c)) return r; drop_graph(c); }
     if (n_edges == 0) { c->rec[HML_REC_BANDS].on = false; return 0; }   // (what was accumulated stays, and so do its edges)
     if (!edges) return set_err(HML_ERR_ARG, "null argument");
     if (const char* why = band_edges_fault(n_edges, edges)) return set_err(HML_ERR_ARG, why);
@@ -995,8 +960,8 @@ int hml_set_level_bands(hml_ctx* c, int n_edges, const float* edges) {
         hml_model m; if (int r = fetch_model(c, &m)) return r;
         if (m.n_bands_recorded != 0ull) return set_err(HML_ERR_ARG, "level bands were already recorded under other edges: they cannot be changed any more");
         hml_recorder& rec = c->rec[HML_REC_BANDS];
-        HIPCHK(hipFree(rec.d_acc)); rec.d_acc = nullptr;
-        HIPCHK(hipFree(rec.d_boundary)); rec.d_boundary = nullptr;
+        rec.d_acc.free();
+        rec.d_boundary.free();
     }
     c->n_band_edges = n_edges;
     memcpy(c->band_edges, edges, (size_t)n_edges * sizeof(float));
@@ -1016,7 +981,7 @@ int hml_get_level_bands(hml_ctx* c, int* n_edges, float* edges) {
 int hml_set_regions(hml_ctx* c, uint64_t n, const uint32_t* start, const uint32_t* end, int n_edges, const float* edges) {
     if (!c) return set_err(HML_ERR_ARG, "null context");
     // (as in hml_set_level_recording: a graph captured under the other setting goes)
-    if (c->graph_exec) { if (int r = ctx_bind(c)) return r; hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
+    if (c->graph_exec) { if (int r = ctx_bind(c)) return r; drop_graph(c); }
     if (n == 0) { c->rg.on = false; return 0; }   // (what was accumulated stays, and so do the regions and their edges)
     if (!start || !end || (n_edges > 0 && !edges)) return set_err(HML_ERR_ARG, "null argument");
     if (n > (1ull << 22)) return set_err(HML_ERR_ARG, "regions: 1 to 2^22 regions");
@@ -1039,7 +1004,7 @@ int hml_set_regions(hml_ctx* c, uint64_t n, const uint32_t* start, const uint32_
             unsigned long long N = 0;
             HIPCHK(hipMemcpy(&N, &c->d_mdl->n_regions_recorded, sizeof N, hipMemcpyDeviceToHost));
             if (N != 0ull) return set_err(HML_ERR_ARG, "regions were already recorded under other regions or edges: they cannot be changed any more");
-            free_region_buffers(c);
+            c->rg.d_start.free(); c->rg.d_end.free(); c->rg.d_chunks.free(); c->rg.d_acc.free();
         }
         c->rg.start.assign(start, start + n);
         c->rg.end.assign(end, end + n);
@@ -1066,10 +1031,7 @@ int hml_enable_probes(hml_ctx* c, int on) {
     if (!c || !c->model_set) return set_err(HML_ERR_ARG, "model not set");
     if (int r = ctx_bind(c)) return r;
     if (int r = settle_if_limited(c)) return r;
-    if (on && !c->d_eprobe) {
-        HIPCHK(hipMalloc(&c->d_eprobe, c->cap * c->K * sizeof(float)));
-        HIPCHK(hipMalloc(&c->d_aprobe, (c->cap + 1) * c->K * sizeof(float)));
-    }
+    if (on && !c->d_aprobe) { if (int r = alloc_capacity_buffers(c, CAPBUF_PROBES)) return r; }   // (the second of the pair: both are there)
     c->probes = on != 0;
     return 0;
 }
@@ -1084,7 +1046,7 @@ int hml_ctx_ensure_marginal_buffers(hml_ctx* c) { return ensure_marginal_buffers
 // marginals by hml_k_record.
 static hml_compat_chunks chunk_views(const hml_ctx* c) {   // the arrays of d_cchunk (alloc_sweep_buffers)
     hml_compat_chunks ch;
-    char* base = (char*)c->d_cchunk;
+    char* base = c->d_cchunk.as<char>();
     const uint64_t n = c->wide ? c->wide_chunks_cap : (uint64_t)HML_COMPAT_MAX_CHUNKS;
     ch.entry = (float*)base; base += n * c->K * sizeof(float);
     ch.exitv = (float*)base; base += n * c->K * sizeof(float);
@@ -1124,7 +1086,7 @@ static int sweep_compat(hml_ctx* c, char method, bool record) {
     refresh_hint(c);
     const uint32_t hint = c->B_hint ? c->B_hint : (uint32_t)std::min<uint64_t>(c->T, 1u << 20);
     const int mix = method == HML_METHOD_MIXTURE ? 1 : 0;
-    hml_mt_state* const mt = (hml_mt_state*)c->d_mt;
+    hml_mt_state* const mt = c->d_mt.as<hml_mt_state>();
     hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_compat_emission<hml_glibc_exp>), dim3(grid_for(hint, 256, 64, 16384)), dim3(256), 0, s, c->d_mdl, c->d_starts, c->d_bstat, c->d_em, c->d_gsc, mix,
                        c->probes ? c->d_eprobe : nullptr);
     if (mix) hipLaunchKernelGGL(hml_k_compat_mixture, dim3(1), dim3(64), 0, s, c->d_mdl, mt, c->d_em, c->d_q);
@@ -1154,7 +1116,7 @@ static int sweep_compat(hml_ctx* c, char method, bool record) {
     hml_compat_lists pl;
     {
         const uint64_t tiles = (c->cap + HML_COMPAT_PART_TILE - 1) / HML_COMPAT_PART_TILE;
-        char* base = (char*)c->d_clists;
+        char* base = c->d_clists.as<char>();
         pl.sx = (float*)base; base += compat_list_entries(c) * sizeof(float);
         pl.sq = (float*)base; base += compat_list_entries(c) * sizeof(float);
         pl.n = (uint32_t*)base; base += compat_list_entries(c) * sizeof(uint32_t);
@@ -1258,7 +1220,7 @@ static int sweep_wide(hml_ctx* c, char method, bool record) {
     }
     {
         ProfScope ps(c, "counts");
-        hipLaunchKernelGGL(hml_k_wide_counts, dim3(HML_REDUCE_GROUPS), dim3(256), 0, s, c->d_q, c->d_starts, c->d_bstat, c->d_mdl, c->d_partial, (hml_wide_acc*)c->d_wacc);
+        hipLaunchKernelGGL(hml_k_wide_counts, dim3(HML_REDUCE_GROUPS), dim3(256), 0, s, c->d_q, c->d_starts, c->d_bstat, c->d_mdl, c->d_partial, c->d_wacc.as<hml_wide_acc>());
     }
     if (record && c->rec_marginals) {
         if (c->pooled) return set_err(HML_ERR_ARG, "the marginals of this context are pooled (common labels, several chains): further sweeps cannot be recorded into them");
@@ -1267,7 +1229,7 @@ static int sweep_wide(hml_ctx* c, char method, bool record) {
     }
     {
         ProfScope ps(c, "params");
-        hipLaunchKernelGGL(hml_k_wide_params, dim3(1), dim3(1024), 0, s, c->d_mdl, c->d_partial, (hml_wide_acc*)c->d_wacc, 0);
+        hipLaunchKernelGGL(hml_k_wide_params, dim3(1), dim3(1024), 0, s, c->d_mdl, c->d_partial, c->d_wacc.as<hml_wide_acc>(), 0);
     }
     if (record) { if (int r = launch_recorders(c, s, hint)) return r; }   // (after the update: hml_k_levels.h)
     KLAUNCH_CHECK();
@@ -1310,7 +1272,7 @@ int hml_iterate(hml_ctx* c, char method, uint64_t iterations, uint64_t thinning)
                                c->graph_dense != (hint >= c->dense_min_blocks) || c->graph_mid != (hint >= c->mid_min_blocks) ||
                                (tre_path && c->graph_tre_L != tre_pick_L(c, hint, true, &unused));
             if (stale && hint) {
-                if (c->graph_exec) { hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
+                drop_graph(c);
                 hipGraph_t g = nullptr;
                 HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
                 // whatever happens below, the stream must leave capture mode (a failure in between would otherwise
@@ -1367,7 +1329,7 @@ extern "C" int hml_iterate_many(hml_ctx* const* cs, int n, char method, uint64_t
             if (c->hint_stale) { launch_compact_pair(c, 0, 0.0f); KLAUNCH_CHECK(); }
             HIPCHK(hipStreamSynchronize(c->stream));
             c->hint_stale = false;
-            if (c->graph_exec) { hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
+            drop_graph(c);
         }
         int r = 0;
         uint64_t reached = done;
@@ -1431,7 +1393,7 @@ int hml_set_option(hml_ctx* c, const char* name, int value) {
     if (std::string(name) == "fused_blocks") {
         c->fused_blocks = value != 0;
         c->fused_keep = value == 2;
-        if (c->graph_exec) { hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
+        drop_graph(c);
         return 0;
     }
     if (std::string(name) == "compat") {   // the reference-compatible mode (hml_k_compat.h): before hml_set_model
@@ -1695,15 +1657,26 @@ int hml_profile_get(hml_ctx* c, const char* name, double* total_ms, uint64_t* la
 
 int hml_debug_eval(int device, int fn, const float* a, const float* b, float* out, uint64_t n, uint64_t seed) {
     HIPCHK(hipSetDevice(device));
-    float *d_a = nullptr, *d_b = nullptr, *d_o = nullptr;
-    HIPCHK(hipMalloc(&d_a, n * 4)); HIPCHK(hipMalloc(&d_o, n * 4));
+    DevArr<float> d_a, d_b, d_o;
+    HIPCHK(d_a.alloc(n)); HIPCHK(d_o.alloc(n));
     HIPCHK(hipMemcpy(d_a, a, n * 4, hipMemcpyHostToDevice));
-    if (b) { HIPCHK(hipMalloc(&d_b, n * 4)); HIPCHK(hipMemcpy(d_b, b, n * 4, hipMemcpyHostToDevice)); }
+    if (b) { HIPCHK(d_b.alloc(n)); HIPCHK(hipMemcpy(d_b, b, n * 4, hipMemcpyHostToDevice)); }
     hipLaunchKernelGGL(hml_k_debug_eval, dim3(1024), dim3(256), 0, 0, fn, d_a, d_b, d_o, n, seed);
     KLAUNCH_CHECK();
     HIPCHK(hipMemcpy(out, d_o, n * 4, hipMemcpyDeviceToHost));
-    hipFree(d_a); hipFree(d_o); if (d_b) hipFree(d_b);
     return 0;
+}
+
+int hml_device_memory_live(uint64_t* bytes, uint64_t* allocations) {
+    if (!bytes || !allocations) return set_err(HML_ERR_ARG, "null argument");
+    *bytes = hml_dev_live_bytes.load(); *allocations = hml_dev_live_allocations.load();
+    return 0;
+}
+
+int hml_debug_fail_allocation(int64_t nth) {
+    const int64_t made = hml_dev_alloc_seen.exchange(0);
+    hml_dev_alloc_fail_at = nth > 0 ? nth : 0;
+    return (int)made;
 }
 
 int hml_synth_gauss(float* x, int16_t* states, uint64_t T, int K, const float* mu, float sigma, double mean_dwell,

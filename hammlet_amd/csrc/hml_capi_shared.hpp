@@ -112,12 +112,10 @@ struct ProfScope {
     }
 };
 
-// device scratch that is released on every path out of a function
-struct DevScratch {
-    void* p = nullptr;
-    ~DevScratch() { if (p) hipFree(p); }
-    template <typename T> T* as() const { return static_cast<T*>(p); }
-};
+// a captured sweep that no longer matches the context's settings or buffers goes (the context's device is current)
+static void drop_graph(hml_ctx* c) {
+    if (c->graph_exec) { hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
+}
 
 static int grid_for(uint64_t items, int per_block, int lo, int hi) {
     uint64_t g = (items + per_block - 1) / per_block;
@@ -183,7 +181,7 @@ static void launch_compact_pair(hml_ctx* c, int mode, float thr) {
                                (uint32_t)c->T, c->d_mdl, thr, mode, c->key_base, c->d_stage, c->d_span_count, c->d_coarse1);
         } else if (bits) {
             hipLaunchKernelGGL(hml_k_compact_scan_bits, dim3((c->n_spans + 3) / 4), dim3(256), 0, c->stream, c->d_w, (uint32_t)c->T,
-                               c->d_mdl, thr, mode, (unsigned long long*)c->d_stage, c->d_span_count);
+                               c->d_mdl, thr, mode, c->d_stage.as<unsigned long long>(), c->d_span_count);
         } else {
             hipLaunchKernelGGL(hml_k_compact_scan, dim3((c->n_spans + 3) / 4), dim3(256), 0, c->stream, c->d_w, (uint32_t)c->T,
                                c->d_mdl, thr, mode, c->d_stage, c->d_span_count);
@@ -195,7 +193,7 @@ static void launch_compact_pair(hml_ctx* c, int mode, float thr) {
             hipLaunchKernelGGL(hml_k_group_totals, dim3((n_groups + 255) / 256), dim3(256), 0, c->stream, c->d_span_count,
                                c->n_spans, c->d_coarse1);
         if (bits)
-            hipLaunchKernelGGL(hml_k_compact_scatter_bits, dim3(n_groups), dim3(256), 0, c->stream, (const unsigned long long*)c->d_stage,
+            hipLaunchKernelGGL(hml_k_compact_scatter_bits, dim3(n_groups), dim3(256), 0, c->stream, c->d_stage.as<const unsigned long long>(),
                                c->d_span_count, c->d_coarse1, c->n_spans, (uint32_t)c->T, c->d_mdl, c->d_starts, c->d_hB);
         else
         hipLaunchKernelGGL(hml_k_compact_scatter, dim3(n_groups), dim3(256), 0, c->stream, c->d_stage, c->d_span_count,
@@ -239,10 +237,10 @@ static void refresh_hint(hml_ctx* c) {
 static int ensure_marginal_buffers(hml_ctx* c) {
     if (c->d_diff) return 0;
     const uint64_t n = (uint64_t)c->K * (c->T + 1);
-    HIPCHK(hipMalloc(&c->d_diff, n * sizeof(int32_t)));
-    HIPCHK(hipMemsetAsync(c->d_diff, 0, n * sizeof(int32_t), c->stream));
     const uint64_t words = (c->T + 1 + 31) / 32 + 1;
-    HIPCHK(hipMalloc(&c->d_boundary, words * sizeof(uint32_t)));
+    HIPCHK(c->d_boundary.alloc(words));
+    HIPCHK(c->d_diff.alloc(n));   // (last: it is what tells that both are there)
+    HIPCHK(hipMemsetAsync(c->d_diff, 0, n * sizeof(int32_t), c->stream));
     HIPCHK(hipMemsetAsync(c->d_boundary, 0, words * sizeof(uint32_t), c->stream));
     return 0;
 }
@@ -268,7 +266,7 @@ static int recorder_rows(const hml_ctx* c, int kind) {
     return kind == HML_REC_LEVELS ? 2 * c->D : kind == HML_REC_BREAKS ? 1 : c->D * (c->n_band_edges + 1);
 }
 static unsigned long long* recorder_counter(const hml_ctx* c, int kind) {
-    return (unsigned long long*)((char*)c->d_mdl + hml_recorder_kinds[kind].counter);
+    return (unsigned long long*)(c->d_mdl.as<char>() + hml_recorder_kinds[kind].counter);
 }
 static int recorder_none(int kind, const char* whose) {
     char buf[256];
@@ -285,9 +283,9 @@ static int ensure_recorder_buffers(hml_ctx* c, int kind) {
         return set_err(HML_ERR_ARG, "level bands: the data dimensions times (edges + 1) must be between 2 and 64 columns");
     const uint64_t bytes = (uint64_t)recorder_rows(c, kind) * (c->T + 1) * hml_recorder_kinds[kind].elem;
     const uint64_t words = (c->T + 32) / 32;
-    HIPCHK(hipMalloc(&r.d_acc, bytes));
-    HIPCHK(hipMalloc(&r.d_boundary, words * sizeof(uint32_t)));
-    HIPCHK(hipMemsetAsync(r.d_acc, 0, bytes, c->stream));
+    HIPCHK(r.d_boundary.alloc(words));
+    HIPCHK(r.d_acc.alloc(bytes));   // (last: it is what tells that both are there)
+    HIPCHK(hipMemsetAsync(r.d_acc.get(), 0, bytes, c->stream));
     HIPCHK(hipMemsetAsync(r.d_boundary, 0, words * sizeof(uint32_t), c->stream));
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(c->stream, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone) HIPCHK(hipStreamSynchronize(c->stream));
@@ -349,7 +347,7 @@ static uint64_t regions_acc_words(const hml_ctx* c) { return 3u + 2u * (uint64_t
 static hml_regions_acc regions_acc_views(const hml_ctx* c) {
     const uint64_t n = c->rg.start.size();
     hml_regions_acc a;
-    unsigned long long* w = (unsigned long long*)c->rg.d_acc;
+    unsigned long long* w = c->rg.d_acc.as<unsigned long long>();
     a.whole = w; a.breaks_sum = w + n; a.breaks_sq = w + 2 * n;
     a.level_sum = (double*)(w + 3 * n);
     a.level_sq = a.level_sum + (uint64_t)c->D * n;
@@ -361,7 +359,7 @@ static uint32_t regions_chunk_stride(const hml_ctx* c) { return (uint32_t)((c->T
 static hml_regions_chunks regions_chunk_views(const hml_ctx* c) {
     hml_regions_chunks ch;
     ch.stride = regions_chunk_stride(c);
-    ch.lev = (double*)c->rg.d_chunks;
+    ch.lev = c->rg.d_chunks.as<double>();
     ch.cnt = (uint32_t*)(ch.lev + (uint64_t)c->D * ch.stride);
     return ch;
 }
@@ -376,10 +374,6 @@ static int regions_fault(const hml_ctx* c) {   // what only the loaded trace and
         }
     if ((uint64_t)c->D * (uint64_t)(g.n_edges + 1) > HML_CAP_K) return set_err(HML_ERR_ARG, "regions: the data dimensions times (edges + 1) exceed 64 columns");
     return 0;
-}
-static void free_region_buffers(hml_ctx* c) {
-    void** ptrs[] = {(void**)&c->rg.d_start, (void**)&c->rg.d_end, (void**)&c->rg.d_acc, (void**)&c->rg.d_chunks};
-    for (void** p : ptrs) if (*p) { hipFree(*p); *p = nullptr; }
 }
 // hml_readout.hip: the regions' buffers on first use, and the three launches of a recorded sweep's regions.  Defined in ONE
 // object, so that the code objects of the sweeps and of the core hold the kernels they held before.

@@ -7,6 +7,7 @@
 
 #include <atomic>
 #include <map>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
@@ -18,13 +19,12 @@
 // The read-only construction of one observation trace on one device - breakpoint weights, their group summary, maxlet
 // coefficients, integral array(s) - shared by every chain that was attached to it (hml_attach_observations): the chains of a
 // run read the same trace, their block sets are nested by threshold, and private copies (0.8 GB of integral array per chain at
-// 10^8 positions) only defeat the caches.  Freed with the last context that holds it.
+// 10^8 positions) only defeat the caches.  Freed with the last context that holds it (hml_ctx::trace).
 struct hml_trace {
-    std::atomic<int> refs{1};
-    float* d_w = nullptr;
-    uint8_t* d_summary = nullptr;
-    float* d_coeff = nullptr;
-    float2* d_ia = nullptr;
+    DevArr<float> d_w;
+    DevArr<uint8_t> d_summary;
+    DevArr<float> d_coeff;
+    DevArr<float2> d_ia;
 };
 
 struct ProfAcc { double ms = 0; uint64_t n = 0; uint32_t tick = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> pending; };
@@ -36,9 +36,9 @@ enum { HML_REC_LEVELS = 0, HML_REC_BREAKS = 1, HML_REC_BANDS = 2, HML_REC_KINDS 
 struct hml_recorder {
     bool on = false;                  // recording now (hml_set_level_recording / hml_set_break_recording / hml_set_level_bands; HML_LEVELS / HML_BREAKS / HML_BANDS)
     bool asked = false;               // ... was on at some time: the read-outs answer
-    void* d_acc = nullptr;            // [rows][T + 1] accumulators
-    uint32_t* d_boundary = nullptr;   // its own bitmap of the positions with a cell
-    template <class E> E* acc() const { return static_cast<E*>(d_acc); }
+    DevBuf d_acc;                     // [rows][T + 1] accumulators
+    DevArr<uint32_t> d_boundary;      // its own bitmap of the positions with a cell
+    template <class E> E* acc() const { return d_acc.as<E>(); }
 };
 
 // The joint posteriors over caller-given regions (hml_set_regions; hml_k_regions.h).  Not a fourth hml_recorder: no cells per
@@ -50,9 +50,9 @@ struct hml_regions {
     std::vector<uint32_t> start, end; // the regions last set, [start, end) each (they stay when the recording is turned off)
     int n_edges = 0;                  // the regions' own band edges (0: no band columns)
     float edges[31] = {};
-    uint32_t *d_start = nullptr, *d_end = nullptr;
-    void* d_acc = nullptr;            // the accumulators of hml_regions_acc, one allocation
-    void* d_chunks = nullptr;         // chunk totals of a recorded sweep, sized by T (hml_regions_chunks)
+    DevArr<uint32_t> d_start, d_end;
+    DevBuf d_acc;                     // the accumulators of hml_regions_acc, one allocation
+    DevBuf d_chunks;                  // chunk totals of a recorded sweep, sized by T (hml_regions_chunks)
 };
 
 struct hml_ctx {
@@ -68,8 +68,8 @@ struct hml_ctx {
     bool dynamic = true;
     bool blocks_valid = false;     // starts/bstat describe the current threshold
     double sigma = 0;
-    // construction (owned by `trace`; the pointers below are this context's view of it)
-    hml_trace* trace = nullptr;
+    // construction (owned by `trace`, which the contexts attached to it share; the pointers below are this context's view of it)
+    std::shared_ptr<hml_trace> trace;
     float* d_w = nullptr;
     uint8_t* d_summary = nullptr;  // largest key of every 16-position group (what the scan streams)
     int32_t key_base = 0;
@@ -81,17 +81,17 @@ struct hml_ctx {
     float* d_coeff = nullptr;
     float2* d_ia = nullptr;
     // block structure
-    uint16_t* d_stage = nullptr;
-    uint32_t *d_span_count = nullptr, *d_starts = nullptr;
-    float2* d_bstat = nullptr;
+    DevArr<uint16_t> d_stage;
+    DevArr<uint32_t> d_span_count, d_starts;
+    DevArr<float2> d_bstat;
     uint32_t n_spans = 0;
-    uint32_t* d_coarse1 = nullptr;   // block count per group of HML_GROUP_SPANS spans
-    unsigned long long* d_group_word = nullptr;   // fused block kernel: {generation, starts, last start} per tile
-    uint32_t* d_wave_total = nullptr;             // split many-chain block kernels: starts per wavefront of a tile (hml_k_blocks_split_many.h)
+    DevArr<uint32_t> d_coarse1;      // block count per group of HML_GROUP_SPANS spans
+    DevArr<unsigned long long> d_group_word;      // fused block kernel: {generation, starts, last start} per tile
+    DevArr<uint32_t> d_wave_total;                // split many-chain block kernels: starts per wavefront of a tile (hml_k_blocks_split_many.h)
     int fused_slots = 0;                          // workgroups of it that are resident at once (occupancy x compute units; 0: not asked yet)
     uint32_t fused_spin_limit = 4096;             // polls of a tile word before the waiting thread computes the word itself
     bool fused_keep = false;                      // option fused_blocks = 2 (tests): keep the kernel after it reported trouble
-    unsigned long long* d_dbg = nullptr;
+    DevArr<unsigned long long> d_dbg;             // HML_FUSED_DEBUG: the block kernels' time stamps (hml_sync prints them)
     // hipGraph replay of a non-recording sweep (launch-bound inner loop); re-captured when the grid hint moves
     bool use_graph = false;
     hipGraphExec_t graph_exec = nullptr;
@@ -100,12 +100,12 @@ struct hml_ctx {
     bool graph_dynamic = false, graph_valid_blocks = false;
     bool graph_fused = false;       // the captured sweep was free to take the fused block kernel
     // sweep buffers (allocated by set_model)
-    float *d_em = nullptr, *d_gsc = nullptr, *d_rows = nullptr, *d_eprobe = nullptr, *d_aprobe = nullptr;
-    float *d_entry = nullptr, *d_exitA = nullptr;
-    uint32_t* d_redo = nullptr;    // backward chunks that failed the forward verification (list for the repair step)
-    uint32_t* d_redo2 = nullptr;   // second list of stale chunks and the bitmap of the sequential finisher (fused trellis path)
-    uint32_t* d_tre_bitmap = nullptr;
-    uint32_t* d_tre_ckpt = nullptr;      // the first pass's forward vectors every 64 rows of a chunk (hml_k_trellis_rows.h): where a refit may stop
+    DevArr<float> d_em, d_gsc, d_rows, d_eprobe, d_aprobe;
+    DevArr<float> d_entry, d_exitA;
+    DevArr<uint32_t> d_redo;       // backward chunks that failed the forward verification (list for the repair step)
+    DevArr<uint32_t> d_redo2;      // second list of stale chunks and the bitmap of the sequential finisher (fused trellis path)
+    DevArr<uint32_t> d_tre_bitmap;
+    DevArr<uint32_t> d_tre_ckpt;         // the first pass's forward vectors every 64 rows of a chunk (hml_k_trellis_rows.h): where a refit may stop
     bool late_rescale = true;      // strongly compressed univariate sweeps: no plane of rescale factors (HML_LATE_RESCALE=0: keep it)
     uint32_t tre_L = 0;            // its chunk length (0: chosen from the number of blocks, then by measurement; HML_TRELLIS_L, option "trellis_L")
     // The best chunk length depends on how the wavefronts of hml_k_trellis_tile (64 chunks each, resident for the whole
@@ -128,16 +128,16 @@ struct hml_ctx {
     bool tre_ckpt = true;          // refits stop where they meet the first pass's checkpoint again (HML_TRELLIS_CKPT=0: always the whole chunk)
     bool tre_rows = true;          // its first pass is hml_k_trellis_rows (round 3); HML_TRELLIS_ROWS=0: hml_k_trellis_tile (round 2)
     bool tre_fused = true;         // weakly compressed FB sweeps take the fused trellis kernels (HML_TRELLIS_FUSED=0: the separate ones)
-    uint32_t* d_touched = nullptr; // backward chunks whose rows the repair recomputed, tagged with the sweep
-    uint32_t* d_fb = nullptr;
-    unsigned long long *d_smap = nullptr, *d_cmap = nullptr;
-    unsigned long long *d_scmap = nullptr, *d_super = nullptr;   // two-level chain (weakly compressed sweeps)
-    uint8_t *d_bentry = nullptr, *d_bentry2 = nullptr;
-    int16_t* d_q = nullptr;
-    double* d_partial = nullptr;
+    DevArr<uint32_t> d_touched;    // backward chunks whose rows the repair recomputed, tagged with the sweep
+    DevArr<uint32_t> d_fb;
+    DevArr<unsigned long long> d_smap, d_cmap;
+    DevArr<unsigned long long> d_scmap, d_super;   // two-level chain (weakly compressed sweeps)
+    DevArr<uint8_t> d_bentry, d_bentry2;
+    DevArr<int16_t> d_q;
+    DevArr<double> d_partial;
     bool params_spread = false;    // single-chain sweeps: the parameter kernel's tree over 16 workgroups (hml_k_params.h; HML_PARAMS_SPREAD)
-    int32_t* d_diff = nullptr;
-    uint32_t* d_boundary = nullptr;
+    DevArr<int32_t> d_diff;
+    DevArr<uint32_t> d_boundary;
     // the per-position recordings beside the state marginals (hml_recorder above), allocated by the first recorded sweep that wants them:
     //   HML_REC_LEVELS  double [2 D][T + 1]: row 2 d the level's difference array, row 2 d + 1 its square's (hml_k_levels.h);
     //                   nothing recorded: one segment, zero sums
@@ -148,7 +148,7 @@ struct hml_ctx {
     hml_regions rg;
     int n_band_edges = 0;           // the bands' edges last set (they stay when the recording is turned off)
     float band_edges[31] = {};
-    hml_model* d_mdl = nullptr;
+    DevArr<hml_model> d_mdl;
     uint32_t* h_B = nullptr;       // pinned + mapped, four words: [0] the block count of the latest enumeration (grid sizing hint),
                                     // [1] set by the fused block kernel when a bounded wait expired, [2] the chain is HALTED: the number of
                                     // blocks an enumeration found beyond the capacity of the per-block buffers (hml_state.h)
@@ -164,7 +164,7 @@ struct hml_ctx {
     unsigned long long call_base = 0;  // `requested` when the current hml_iterate / hml_iterate_many call began: a sweep's index in
                                        // its call (what the recording callback is told) = its ordinal - call_base
     uint64_t grown = 0;             // times the buffers were grown (hml_stats)
-    uint32_t* d_hB = nullptr;       // device view of h_B
+    uint32_t* d_hB = nullptr;       // device view of h_B (not an allocation of its own)
     uint32_t B_hint = 0;
     bool hint_stale = true;         // the hint predates the current parameters (new model, prior draw, mode switch)
     // forward geometry
@@ -200,19 +200,19 @@ struct hml_ctx {
     hml_record_cb cb = nullptr;
     void* cb_user = nullptr;
     int fm_slots = 0;              // workgroups of the many-chain block kernel that are resident at once (0: not asked yet)
-    void* d_many = nullptr;        // hml_iterate_many: the chains' pointers (hml_chain_dev), kept by the first chain of a batch
+    DevBuf d_many;                 // hml_iterate_many: the chains' pointers (hml_chain_dev), kept by the first chain of a batch
     int many_cap = 0;
     bool compat = false;           // option "compat": sweeps exactly as the reference computes them (hml_k_compat.h)
-    void* d_mt = nullptr;          // its engine (hml_mt_state)
-    float* d_crows = nullptr;      // its trellis, (T + 1) x K
-    void* d_cchunk = nullptr;      // chunks of its filter / backward draws (hml_compat_chunks, hml_k_compat.h)
-    uint32_t* d_cdraws = nullptr;  // the engine's outputs of a sweep's categorical draws
-    void* d_clists = nullptr;      // its count pass's lists by state (hml_compat_lists)
+    DevBuf d_mt;                   // its engine (hml_mt_state)
+    DevArr<float> d_crows;         // its trellis, (T + 1) x K
+    DevBuf d_cchunk;               // chunks of its filter / backward draws (hml_compat_chunks, hml_k_compat.h)
+    DevArr<uint32_t> d_cdraws;     // the engine's outputs of a sweep's categorical draws
+    DevBuf d_clists;               // its count pass's lists by state (hml_compat_lists)
     int compat_chunks = 0;         // 0: chosen from the block count; 1: the sequential form (HML_COMPAT_CHUNKS)
     int compat_warmup = 0;         // blocks a chunk runs ahead of its first; 0: 64 (128 beyond 16 states) (HML_COMPAT_WARMUP)
     bool wide = false;             // more than 16 states on the default path: the number of states is a run-time value, a state a lane (hml_k_wide.h)
-    void* d_wacc = nullptr;        // its integer counts of a sweep (hml_wide_acc)
-    float* d_wA = nullptr;         // ... the transition matrix padded to 64 x 64 (hml_k_wide_lanes.h)
+    DevBuf d_wacc;                 // its integer counts of a sweep (hml_wide_acc)
+    DevArr<float> d_wA;            // ... the transition matrix padded to 64 x 64 (hml_k_wide_lanes.h)
     int wide_lanes = 1;            // ... filter and backward draws with a chunk a lane (0: a state a lane, hml_k_compat.h's kernels) (HML_WIDE_LANES)
     int wide_w0 = 32;              // ... the floor of its chunks' adaptive warm-up, blocks (HML_WIDE_W0)
     uint32_t wide_max_chunks = 0;  // ... the most chunks a sweep is cut into (HML_WIDE_MAX_CHUNKS; 0: HML_WL_MAX_CHUNKS)
@@ -224,6 +224,9 @@ struct hml_ctx {
     uint32_t prof_tick = 0;
     std::map<std::string, ProfAcc> prof;
     std::vector<hipEvent_t> ev_pool;
+    // Every d_* above that is not a plain pointer owns its buffer (DevBuf / DevArr, hml_host_common.hpp): deleting the context
+    // frees them, whatever a call that failed half-way left allocated, and allocating one again replaces what it held.
+    ~hml_ctx() { if (h_B) (void)hipHostFree(h_B); }
 };
 
 // hml_capi.hip

@@ -4,6 +4,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
+#include <cstdint>
 #include <string>
 
 #include "../../include/hml.h"
@@ -20,15 +22,53 @@ int hml_set_err(int code, const std::string& msg);
 
 #define KLAUNCH_CHECK() HIPCHK(hipGetLastError())
 
-// device memory that is released on every path out of a function (HIPCHK returns early)
-struct DevBuf {
-    void* p = nullptr;
+// The one owner of device memory of the chain code: a buffer is freed when its owner goes (a context's member with the
+// context, scratch on every path out of a function - HIPCHK returns early), and nothing else calls hipMalloc / hipFree.
+// What the owners hold is counted (hml_device_memory_live), and a test can make the n-th allocation from now fail
+// (hml_debug_fail_allocation): the failure paths are otherwise unreachable.
+inline std::atomic<uint64_t> hml_dev_live_bytes{0}, hml_dev_live_allocations{0};
+inline std::atomic<int64_t> hml_dev_alloc_seen{0}, hml_dev_alloc_fail_at{0};   // allocations since the hook was armed; the one that fails (0: none)
+
+class DevBuf {
+    void* p_ = nullptr;
+    uint64_t bytes_ = 0;
+public:
     DevBuf() = default;
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-    template <class T> T* release() { T* q = static_cast<T*>(p); p = nullptr; return q; }
+    ~DevBuf() { free(); }
+    // frees what it held, then allocates anew (a failure leaves it empty)
+    hipError_t alloc(uint64_t bytes) {
+        free();
+        if (++hml_dev_alloc_seen == hml_dev_alloc_fail_at.load()) { hml_dev_alloc_fail_at = 0; return hipErrorOutOfMemory; }
+        const hipError_t e = hipMalloc(&p_, bytes);
+        if (e != hipSuccess) { p_ = nullptr; return e; }
+        if (p_) { bytes_ = bytes; hml_dev_live_bytes += bytes; hml_dev_live_allocations++; }
+        return hipSuccess;
+    }
+    void free() {
+        if (!p_) return;
+        (void)hipFree(p_);
+        hml_dev_live_bytes -= bytes_; hml_dev_live_allocations--;
+        p_ = nullptr; bytes_ = 0;
+    }
+    explicit operator bool() const { return p_ != nullptr; }
+    void* get() const { return p_; }
+    template <class T> T* as() const { return static_cast<T*>(p_); }
+    template <class T> T* release() {   // the caller owns it from here (and frees it with hipFree)
+        T* q = static_cast<T*>(p_);
+        if (p_) { hml_dev_live_bytes -= bytes_; hml_dev_live_allocations--; }
+        p_ = nullptr; bytes_ = 0;
+        return q;
+    }
+};
+
+// ... of n elements of T: reads as the T* it holds
+template <class T> struct DevArr : DevBuf {
+    hipError_t alloc(uint64_t n) { return DevBuf::alloc(n * sizeof(T)); }
+    T* get() const { return as<T>(); }
+    operator T*() const { return get(); }
+    T* operator->() const { return get(); }
 };
 
 #endif

@@ -114,8 +114,8 @@ int export_payload(hml_ctx* c, int32_t* payload, int32_t* perm_out) {
     if (int r = hml_relabel_permutation(c, perm.data())) return r;
     if (perm_out) memcpy(perm_out, perm.data(), sizeof(int32_t) * c->K);
     DevBuf d_perm;
-    HIPCHK(hipMalloc(&d_perm.p, sizeof(int32_t) * c->K));
-    HIPCHK(hipMemcpyAsync(d_perm.p, perm.data(), sizeof(int32_t) * c->K, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(d_perm.alloc(sizeof(int32_t) * c->K));
+    HIPCHK(hipMemcpyAsync(d_perm.get(), perm.data(), sizeof(int32_t) * c->K, hipMemcpyHostToDevice, c->stream));
     const uint64_t n = payload_count(c);
     HIPCHK(hipMemsetAsync(payload + (n - 1u - (uint64_t)c->K), 0, sizeof(int32_t) * (1u + (uint64_t)c->K), c->stream));
     hipLaunchKernelGGL(hml_k_pool_export, dim3(grid_for(n, 256, 1 << 16)), dim3(256), 0, c->stream, c->d_diff, c->d_boundary, c->d_mdl,
@@ -317,10 +317,10 @@ int hml_pool_marginals(hml_pool* p, hml_ctx* c, int32_t* perm_out) {
     if (!rc) rc = hml_relabel_permutation(c, perm.data());
     if (!rc) {
         if (perm_out) memcpy(perm_out, perm.data(), sizeof(int32_t) * K);
-        if (hipMalloc(&d_perm.p, sizeof(int32_t) * K) != hipSuccess) { (void)hipGetLastError(); rc = set_err(HML_ERR_HIP, "out of device memory"); }
+        if (d_perm.alloc(sizeof(int32_t) * K) != hipSuccess) { (void)hipGetLastError(); rc = set_err(HML_ERR_HIP, "out of device memory"); }
     }
     if (!rc) {
-        bool ok = hipMemcpyAsync(d_perm.p, perm.data(), sizeof(int32_t) * K, hipMemcpyHostToDevice, c->stream) == hipSuccess &&
+        bool ok = hipMemcpyAsync(d_perm.get(), perm.data(), sizeof(int32_t) * K, hipMemcpyHostToDevice, c->stream) == hipSuccess &&
                   hipMemsetAsync(mine, 0, hml_pool_list_header(K) * sizeof(int32_t), c->stream) == hipSuccess;
         if (ok) {
             hipLaunchKernelGGL(hml_k_pool_list_pack, dim3(grid_for(std::max<uint64_t>(M, 1), 256, 1 << 14)), dim3(256), 0, c->stream, d_seg.as<uint32_t>(),

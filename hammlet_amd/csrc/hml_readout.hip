@@ -11,16 +11,16 @@
 // d_seg[M + 1] is allocated here, position 0 is always the first entry.  Counts per span, their prefix sums on the host, scatter.
 static int compact_boundaries(hipStream_t s, const uint32_t* d_boundary, uint32_t T, uint32_t n_spans, uint64_t* M_out, DevBuf& d_seg) {
     DevBuf d_cnt, d_off;
-    HIPCHK(hipMalloc(&d_cnt.p, n_spans * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&d_off.p, n_spans * sizeof(uint32_t)));
+    HIPCHK(d_cnt.alloc(n_spans * sizeof(uint32_t)));
+    HIPCHK(d_off.alloc(n_spans * sizeof(uint32_t)));
     hipLaunchKernelGGL(hml_k_marg_count, dim3((n_spans + 3) / 4), dim3(256), 0, s, d_boundary, T, d_cnt.as<uint32_t>());
     std::vector<uint32_t> h_cnt(n_spans), h_off(n_spans);
-    HIPCHK(hipMemcpyAsync(h_cnt.data(), d_cnt.p, n_spans * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h_cnt.data(), d_cnt.get(), n_spans * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     uint64_t M = 0;
     for (uint32_t i = 0; i < n_spans; ++i) { h_off[i] = (uint32_t)M; M += h_cnt[i]; }
-    HIPCHK(hipMemcpyAsync(d_off.p, h_off.data(), n_spans * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMalloc(&d_seg.p, (M + 1) * sizeof(uint32_t)));
+    HIPCHK(hipMemcpyAsync(d_off.get(), h_off.data(), n_spans * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(d_seg.alloc((M + 1) * sizeof(uint32_t)));
     hipLaunchKernelGGL(hml_k_marg_scatter, dim3((n_spans + 3) / 4), dim3(256), 0, s, d_boundary, T, d_off.as<uint32_t>(), d_seg.as<uint32_t>());
     KLAUNCH_CHECK();
     HIPCHK(hipStreamSynchronize(s));   // (d_cnt and d_off go with this frame)
@@ -34,7 +34,7 @@ template <typename In, typename Acc, bool Exclusive>
 static int scan_rows(hipStream_t s, const In* d_in, uint64_t M, int rows, Acc* d_out) {
     DevBuf d_cs;
     const uint32_t n_chunks = (uint32_t)((M + HML_SCAN_CHUNK - 1) / HML_SCAN_CHUNK);
-    HIPCHK(hipMalloc(&d_cs.p, ((uint64_t)n_chunks * rows + 1) * sizeof(Acc)));
+    HIPCHK(d_cs.alloc(((uint64_t)n_chunks * rows + 1) * sizeof(Acc)));
     const dim3 grid((unsigned)grid_for(n_chunks, 1, 1, 4096), (unsigned)rows);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_scan_partial<In, Acc>), grid, dim3(256), 0, s, d_in, (uint32_t)M, n_chunks, d_cs.as<Acc>());
     hipLaunchKernelGGL(hml_k_scan_chunks<Acc>, dim3(rows), dim3(1024), 0, s, d_cs.as<Acc>(), n_chunks);
@@ -76,7 +76,7 @@ static int table_segments(hml_ctx* c, const hml_count_table& tab, uint64_t* M_ou
     const uint32_t T = (uint32_t)c->T;
     uint64_t M = 0;
     if (int r = compact_boundaries(c->stream, tab.d_boundary, T, c->n_spans, &M, d_seg)) return r;
-    HIPCHK(hipMalloc(&d_g.p, std::max<uint64_t>(M, 1) * tab.ncol * sizeof(int32_t)));
+    HIPCHK(d_g.alloc(std::max<uint64_t>(M, 1) * tab.ncol * sizeof(int32_t)));
     hipLaunchKernelGGL(hml_k_marg_gather, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, c->stream, tab.d_diff, T, tab.ncol, d_seg.as<uint32_t>(), (uint32_t)M, d_g.as<int32_t>());
     KLAUNCH_CHECK();
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -92,8 +92,8 @@ static int table_rle(hml_ctx* c, const hml_count_table& tab, uint64_t M, const D
     const int ncol = tab.ncol;
     std::vector<uint32_t> h_seg(M);
     std::vector<int32_t> h_g(M * ncol);
-    HIPCHK(hipMemcpyAsync(h_seg.data(), d_seg.p, M * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(h_g.data(), d_g.p, M * ncol * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(h_seg.data(), d_seg.get(), M * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(h_g.data(), d_g.get(), M * ncol * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     lengths_of(h_seg.data(), M, (uint32_t)c->T, seg_len);
     if (!counts) return 0;
@@ -108,7 +108,7 @@ static int table_rle(hml_ctx* c, const hml_count_table& tab, uint64_t M, const D
 static int table_dense(hml_ctx* c, const hml_count_table& tab, const int32_t* d_perm, int32_t* out, DevBuf& d_cs) {
     const uint32_t T = (uint32_t)c->T;
     const uint32_t n_chunks = c->n_spans;
-    HIPCHK(hipMalloc(&d_cs.p, (uint64_t)tab.ncol * n_chunks * sizeof(int32_t)));
+    HIPCHK(d_cs.alloc((uint64_t)tab.ncol * n_chunks * sizeof(int32_t)));
     hipLaunchKernelGGL(hml_k_dense_partial, dim3(n_chunks, tab.ncol), dim3(256), 0, c->stream, tab.d_diff, T, tab.ncol, d_cs.as<int32_t>(), n_chunks);
     hipLaunchKernelGGL(hml_k_scan_chunks<int32_t>, dim3(tab.ncol), dim3(1024), 0, c->stream, d_cs.as<int32_t>(), n_chunks);
     hipLaunchKernelGGL(hml_k_dense_final, dim3(n_chunks, tab.ncol), dim3(256), 0, c->stream, tab.d_diff, T, tab.ncol, d_cs.as<int32_t>(), n_chunks, d_perm, out);
@@ -125,9 +125,9 @@ static int table_runs(hml_ctx* c, const hml_count_table& tab, Pick pick, uint64_
     DevBuf b_seg, b_g, b_cs, b_rc, b_key;
     if (int r = table_segments(c, tab, &M, b_seg, b_g)) return r;
     const uint32_t n_chunks = (uint32_t)((M + 255) / 256);
-    HIPCHK(hipMalloc(&b_cs.p, (uint64_t)ncol * n_chunks * sizeof(int32_t)));
-    HIPCHK(hipMalloc(&b_rc.p, ((uint64_t)n_chunks + 1) * sizeof(int32_t)));
-    HIPCHK(hipMalloc(&b_key.p, M * sizeof(int16_t)));
+    HIPCHK(b_cs.alloc((uint64_t)ncol * n_chunks * sizeof(int32_t)));
+    HIPCHK(b_rc.alloc(((uint64_t)n_chunks + 1) * sizeof(int32_t)));
+    HIPCHK(b_key.alloc(M * sizeof(int16_t)));
     int32_t *const d_cs = b_cs.as<int32_t>(), *const d_rc = b_rc.as<int32_t>();
     int16_t* const d_key = b_key.as<int16_t>();
     HIPCHK(hipMemsetAsync(d_rc + n_chunks, 0, sizeof(int32_t), c->stream));
@@ -143,14 +143,14 @@ static int table_runs(hml_ctx* c, const hml_count_table& tab, Pick pick, uint64_
     *n_runs = (uint64_t)R;
     if (!run_len) return 0;
     DevBuf b_rs, b_rq;
-    HIPCHK(hipMalloc(&b_rs.p, (uint64_t)R * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&b_rq.p, (uint64_t)R * sizeof(int16_t)));
+    HIPCHK(b_rs.alloc((uint64_t)R * sizeof(uint32_t)));
+    HIPCHK(b_rq.alloc((uint64_t)R * sizeof(int16_t)));
     hipLaunchKernelGGL(hml_k_seg_run_scatter, dim3(n_chunks), dim3(256), 0, c->stream, d_key, b_seg.as<uint32_t>(), (uint32_t)M, d_rc, b_rs.as<uint32_t>(), b_rq.as<int16_t>());
     KLAUNCH_CHECK();
     std::vector<uint32_t> h_rs(R);
     run_key.resize(R);
-    HIPCHK(hipMemcpyAsync(h_rs.data(), b_rs.p, (uint64_t)R * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(run_key.data(), b_rq.p, (uint64_t)R * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(h_rs.data(), b_rs.get(), (uint64_t)R * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(run_key.data(), b_rq.get(), (uint64_t)R * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     lengths_of(h_rs.data(), (uint64_t)R, (uint32_t)c->T, run_len);
     return 0;
@@ -216,8 +216,8 @@ int hml_marginals_dense_device(hml_ctx* c, void* out_dev, const int32_t* perm) {
             if (perm[k] < 0 || perm[k] >= K || ((seen >> perm[k]) & 1u)) return set_err(HML_ERR_ARG, "perm is not a permutation of the K states");
             seen |= (uint64_t)1 << perm[k];
         }
-        HIPCHK(hipMalloc(&b_perm.p, K * sizeof(int32_t)));
-        HIPCHK(hipMemcpyAsync(b_perm.p, perm, K * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(b_perm.alloc(K * sizeof(int32_t)));
+        HIPCHK(hipMemcpyAsync(b_perm.get(), perm, K * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     }
     if (int r = table_dense(c, marginal_table(c), b_perm.as<int32_t>(), out, b_cs)) return r;
     hipLaunchKernelGGL(hml_k_dense_boundary, dim3(grid_for(T, 256, 1, 65536)), dim3(256), 0, c->stream, c->d_boundary, T,
@@ -292,7 +292,7 @@ static int gather_level_segments(hml_ctx* c, uint64_t* M_out, DevBuf& d_seg, Dev
     const hml_recorder& rec = c->rec[HML_REC_LEVELS];
     uint64_t M = 0;
     if (int r = compact_boundaries(c->stream, rec.d_boundary, T, c->n_spans, &M, d_seg)) return r;
-    HIPCHK(hipMalloc(&d_sum.p, M * rows * sizeof(double)));
+    HIPCHK(d_sum.alloc(M * rows * sizeof(double)));
     hipLaunchKernelGGL(hml_k_rec_gather<double>, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, c->stream, rec.acc<double>(), T, rows, d_seg.as<uint32_t>(), (uint32_t)M, d_sum.as<double>());
     if (int r = scan_rows<double, double, false>(c->stream, d_sum.as<double>(), M, rows, d_sum.as<double>())) return r;
     *M_out = M;
@@ -315,8 +315,8 @@ int hml_levels_rle(hml_ctx* c, uint64_t* n_segments, uint64_t* n_recorded, uint6
     if (!seg_len) return 0;
     std::vector<uint32_t> h_seg(M);
     std::vector<double> h_sum(M * 2 * D);
-    HIPCHK(hipMemcpyAsync(h_seg.data(), b_seg.p, M * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(h_sum.data(), b_sum.p, M * 2 * D * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(h_seg.data(), b_seg.get(), M * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(h_sum.data(), b_sum.get(), M * 2 * D * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     lengths_of(h_seg.data(), M, T, seg_len);
     for (int d = 0; d < D; ++d) {
@@ -335,7 +335,7 @@ int hml_levels_dense_device(hml_ctx* c, void* out_dev) {
     uint64_t M = 0;
     DevBuf b_seg, b_sum, b_ms;
     if (int r = gather_level_segments(c, &M, b_seg, b_sum)) return r;
-    HIPCHK(hipMalloc(&b_ms.p, M * 2 * D * sizeof(float)));
+    HIPCHK(b_ms.alloc(M * 2 * D * sizeof(float)));
     hipLaunchKernelGGL(hml_k_levels_mean_sd, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, c->stream, b_sum.as<double>(), (uint32_t)M, D,
                        m.n_levels_recorded, b_ms.as<float>());
     hipLaunchKernelGGL(hml_k_levels_expand, dim3(grid_for(T, 256, 1, 65536)), dim3(256), 0, c->stream, b_ms.as<float>(), b_seg.as<uint32_t>(),
@@ -398,7 +398,7 @@ static int agreement_union(hml_ctx* const* ctxs, int n, hml_agree_chains& ch, ui
     memset(&ch, 0, sizeof ch);
     for (int i = 0; i < n; ++i) ch.boundary[i] = ctxs[i]->rec[HML_REC_LEVELS].d_boundary;
     DevBuf d_or;
-    HIPCHK(hipMalloc(&d_or.p, (uint64_t)words * sizeof(uint32_t)));
+    HIPCHK(d_or.alloc((uint64_t)words * sizeof(uint32_t)));
     hipLaunchKernelGGL(hml_k_agree_or, dim3(grid_for(words, 256, 1, 16384)), dim3(256), 0, a->stream, ch, n, words, d_or.as<uint32_t>());
     KLAUNCH_CHECK();
     return compact_boundaries(a->stream, d_or.as<uint32_t>(), T, a->n_spans, U_out, d_useg);   // (synchronises: d_or may go)
@@ -420,22 +420,22 @@ static int agreement_segments(hml_ctx* const* ctxs, int n, hml_agreement& ag) {
     for (int i = 0; i < n; ++i) {
         uint64_t M = 0;
         if (int r = gather_level_segments(ctxs[i], &M, b_seg[i], b_sum[i])) return r;
-        hipFree(b_seg[i].p); b_seg[i].p = nullptr;   // (the rank takes the place of the starts)
+        b_seg[i].free();   // (the rank takes the place of the starts)
         ch.sum[i] = b_sum[i].as<double>();
         ch.M[i] = (uint32_t)M;
     }
     // the chains' segments under the union's, by rank: flags, then the fixed scan over each chain's row
     DevBuf b_flag, b_rank;
-    HIPCHK(hipMalloc(&b_flag.p, (uint64_t)n * U * sizeof(uint8_t)));
-    HIPCHK(hipMalloc(&b_rank.p, (uint64_t)n * U * sizeof(uint32_t)));
+    HIPCHK(b_flag.alloc((uint64_t)n * U * sizeof(uint8_t)));
+    HIPCHK(b_rank.alloc((uint64_t)n * U * sizeof(uint32_t)));
     const dim3 grid(grid_for(U, 256, 1, 16384));
     hipLaunchKernelGGL(hml_k_agree_flags, grid, dim3(256), 0, a->stream, ch, n, ag.useg.as<uint32_t>(), (uint32_t)U, b_flag.as<uint8_t>());
     KLAUNCH_CHECK();
     if (int r = scan_rows<uint8_t, uint32_t, false>(a->stream, b_flag.as<uint8_t>(), U, n, b_rank.as<uint32_t>())) return r;
-    HIPCHK(hipMalloc(&ag.within.p, (uint64_t)D * U * sizeof(double)));
-    HIPCHK(hipMalloc(&ag.between.p, (uint64_t)D * U * sizeof(double)));
-    HIPCHK(hipMalloc(&ag.rhat.p, (uint64_t)D * U * sizeof(double)));
-    HIPCHK(hipMalloc(&ag.rhat_f.p, (uint64_t)D * U * sizeof(float)));
+    HIPCHK(ag.within.alloc((uint64_t)D * U * sizeof(double)));
+    HIPCHK(ag.between.alloc((uint64_t)D * U * sizeof(double)));
+    HIPCHK(ag.rhat.alloc((uint64_t)D * U * sizeof(double)));
+    HIPCHK(ag.rhat_f.alloc((uint64_t)D * U * sizeof(float)));
     hipLaunchKernelGGL(hml_k_agree_eval, grid, dim3(256), 0, a->stream, ch, n, D, b_rank.as<uint32_t>(), (uint32_t)U, (unsigned long long)ag.N,
                        ag.within.as<double>(), ag.between.as<double>(), ag.rhat.as<double>(), ag.rhat_f.as<float>());
     KLAUNCH_CHECK();
@@ -460,10 +460,10 @@ int hml_levels_agreement_rle(hml_ctx* const* ctxs, int n, uint64_t* n_segments, 
     const uint64_t U = ag.U, bytes = (uint64_t)a->D * U * sizeof(double);
     *n_segments = U;
     std::vector<uint32_t> h_seg(U);
-    HIPCHK(hipMemcpyAsync(h_seg.data(), ag.useg.p, U * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
-    if (within) HIPCHK(hipMemcpyAsync(within, ag.within.p, bytes, hipMemcpyDeviceToHost, a->stream));
-    if (between) HIPCHK(hipMemcpyAsync(between, ag.between.p, bytes, hipMemcpyDeviceToHost, a->stream));
-    if (rhat) HIPCHK(hipMemcpyAsync(rhat, ag.rhat.p, bytes, hipMemcpyDeviceToHost, a->stream));
+    HIPCHK(hipMemcpyAsync(h_seg.data(), ag.useg.get(), U * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
+    if (within) HIPCHK(hipMemcpyAsync(within, ag.within.get(), bytes, hipMemcpyDeviceToHost, a->stream));
+    if (between) HIPCHK(hipMemcpyAsync(between, ag.between.get(), bytes, hipMemcpyDeviceToHost, a->stream));
+    if (rhat) HIPCHK(hipMemcpyAsync(rhat, ag.rhat.get(), bytes, hipMemcpyDeviceToHost, a->stream));
     HIPCHK(hipStreamSynchronize(a->stream));
     lengths_of(h_seg.data(), U, (uint32_t)a->T, seg_len);
     return 0;
@@ -492,15 +492,15 @@ int hml_levels_agreement_summary(hml_ctx* const* ctxs, int n, double threshold, 
     const int D = a->D;
     const int blocks = grid_for(ag.U, 1024, 1, 256);
     DevBuf b_cnt, b_max;
-    HIPCHK(hipMalloc(&b_cnt.p, (uint64_t)blocks * D * 2 * sizeof(unsigned long long)));
-    HIPCHK(hipMalloc(&b_max.p, (uint64_t)blocks * D * sizeof(double)));
+    HIPCHK(b_cnt.alloc((uint64_t)blocks * D * 2 * sizeof(unsigned long long)));
+    HIPCHK(b_max.alloc((uint64_t)blocks * D * sizeof(double)));
     hipLaunchKernelGGL(hml_k_agree_summary, dim3(blocks), dim3(256), 0, a->stream, ag.rhat.as<double>(), ag.useg.as<uint32_t>(), (uint32_t)ag.U, (uint32_t)a->T,
                        D, threshold, b_cnt.as<unsigned long long>(), b_max.as<double>());
     KLAUNCH_CHECK();
     std::vector<unsigned long long> h_cnt((size_t)blocks * D * 2);
     std::vector<double> h_max((size_t)blocks * D);
-    HIPCHK(hipMemcpyAsync(h_cnt.data(), b_cnt.p, h_cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, a->stream));
-    HIPCHK(hipMemcpyAsync(h_max.data(), b_max.p, h_max.size() * sizeof(double), hipMemcpyDeviceToHost, a->stream));
+    HIPCHK(hipMemcpyAsync(h_cnt.data(), b_cnt.get(), h_cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, a->stream));
+    HIPCHK(hipMemcpyAsync(h_max.data(), b_max.get(), h_max.size() * sizeof(double), hipMemcpyDeviceToHost, a->stream));
     HIPCHK(hipStreamSynchronize(a->stream));
     // the second stage: integers and a maximum - the same answer in any order
     for (int d = 0; d < D; ++d) {
@@ -519,7 +519,7 @@ int hml_levels_agreement_summary(hml_ctx* const* ctxs, int n, double threshold, 
 
 // exclusive 64-bit prefix sums of M 32-bit values on `s`: d_pre[M + 1] (allocated here), d_pre[M] = the total
 static int breaks_scan(hipStream_t s, const uint32_t* d_v, uint64_t M, DevBuf& d_pre) {
-    HIPCHK(hipMalloc(&d_pre.p, (M + 1) * sizeof(unsigned long long)));
+    HIPCHK(d_pre.alloc((M + 1) * sizeof(unsigned long long)));
     return scan_rows<uint32_t, unsigned long long, true>(s, d_v, M, 1, d_pre.as<unsigned long long>());
 }
 
@@ -534,7 +534,7 @@ static int compact_break_positions(hml_ctx* c, uint64_t* M_out, DevBuf& d_list) 
 
 // C[pos] for the M break positions of d_list into d_cnt[M] (allocated here with one spare entry)
 static int gather_break_counts(hml_ctx* c, const DevBuf& d_list, uint64_t M, DevBuf& d_cnt) {
-    HIPCHK(hipMalloc(&d_cnt.p, (M + 1) * sizeof(uint32_t)));
+    HIPCHK(d_cnt.alloc((M + 1) * sizeof(uint32_t)));
     if (M) hipLaunchKernelGGL(hml_k_rec_gather<uint32_t>, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, c->stream, c->rec[HML_REC_BREAKS].acc<uint32_t>(), (uint32_t)c->T, 1,
                               d_list.as<uint32_t>() + 1, (uint32_t)M, d_cnt.as<uint32_t>());
     KLAUNCH_CHECK();
@@ -566,7 +566,7 @@ int hml_breaks_list(hml_ctx* c, uint64_t* n_breaks, uint64_t* n_recorded, uint32
     HIPCHK(hipMemcpyAsync(pos, b_list.as<uint32_t>() + 1, M * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     if (count) {
         if (int r = gather_break_counts(c, b_list, M, b_cnt)) return r;
-        HIPCHK(hipMemcpyAsync(count, b_cnt.p, M * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(count, b_cnt.get(), M * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
@@ -596,8 +596,8 @@ int hml_breaks_consensus(hml_ctx* c, uint32_t window, uint64_t min_count, uint64
     if (int r = gather_breaks(c, &M, b_list, b_cnt, b_pre)) return r;
     *n_selected = 0;
     if (M == 0) return 0;
-    HIPCHK(hipMalloc(&b_mass.p, M * sizeof(unsigned long long)));
-    HIPCHK(hipMalloc(&b_sel.p, M * sizeof(uint32_t)));
+    HIPCHK(b_mass.alloc(M * sizeof(unsigned long long)));
+    HIPCHK(b_sel.alloc(M * sizeof(uint32_t)));
     const uint32_t* d_pos = b_list.as<uint32_t>() + 1;
     hipLaunchKernelGGL(hml_k_breaks_select, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, c->stream, d_pos, b_cnt.as<uint32_t>(), b_pre.as<unsigned long long>(),
                        (uint32_t)M, window, (unsigned long long)(min_count > 1 ? min_count : 1), b_mass.as<unsigned long long>(), b_sel.as<uint32_t>());
@@ -608,15 +608,15 @@ int hml_breaks_consensus(hml_ctx* c, uint32_t window, uint64_t min_count, uint64
     HIPCHK(hipStreamSynchronize(c->stream));
     *n_selected = S;
     if (!pos || S == 0) return 0;
-    HIPCHK(hipMalloc(&b_opos.p, S * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&b_omass.p, S * sizeof(unsigned long long)));
-    HIPCHK(hipMalloc(&b_opeak.p, S * sizeof(uint32_t)));
+    HIPCHK(b_opos.alloc(S * sizeof(uint32_t)));
+    HIPCHK(b_omass.alloc(S * sizeof(unsigned long long)));
+    HIPCHK(b_opeak.alloc(S * sizeof(uint32_t)));
     hipLaunchKernelGGL(hml_k_breaks_compact, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, c->stream, d_pos, b_cnt.as<uint32_t>(), b_mass.as<unsigned long long>(),
                        b_sel.as<uint32_t>(), b_where.as<unsigned long long>(), (uint32_t)M, b_opos.as<uint32_t>(), b_omass.as<unsigned long long>(), b_opeak.as<uint32_t>());
     KLAUNCH_CHECK();
-    HIPCHK(hipMemcpyAsync(pos, b_opos.p, S * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    if (mass) HIPCHK(hipMemcpyAsync(mass, b_omass.p, S * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (peak) HIPCHK(hipMemcpyAsync(peak, b_opeak.p, S * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(pos, b_opos.get(), S * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (mass) HIPCHK(hipMemcpyAsync(mass, b_omass.get(), S * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (peak) HIPCHK(hipMemcpyAsync(peak, b_opeak.get(), S * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -638,10 +638,10 @@ int hml_levels_on_segments(hml_ctx* c, uint64_t n_cuts, const uint32_t* cuts, do
     DevBuf b_seg, b_val, b_w, b_cuts, b_out;
     if (int r = gather_level_segments(c, &M, b_seg, b_val)) return r;
     const uint64_t n_seg = n_cuts + 1;
-    HIPCHK(hipMalloc(&b_w.p, M * rows * sizeof(double)));
-    HIPCHK(hipMalloc(&b_cuts.p, (n_cuts + 1) * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&b_out.p, n_seg * rows * sizeof(double)));
-    if (n_cuts) HIPCHK(hipMemcpyAsync(b_cuts.p, cuts, n_cuts * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(b_w.alloc(M * rows * sizeof(double)));
+    HIPCHK(b_cuts.alloc((n_cuts + 1) * sizeof(uint32_t)));
+    HIPCHK(b_out.alloc(n_seg * rows * sizeof(double)));
+    if (n_cuts) HIPCHK(hipMemcpyAsync(b_cuts.get(), cuts, n_cuts * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(hml_k_levels_weigh, dim3(grid_for(M, 256, 1, 16384)), dim3(256), 0, c->stream, b_val.as<double>(), b_seg.as<uint32_t>(), (uint32_t)M, T, rows, b_w.as<double>());
     // the fixed-shape scan of the levels' read-out, now over len_i * value_i
     if (int r = scan_rows<double, double, false>(c->stream, b_w.as<double>(), M, rows, b_w.as<double>())) return r;
@@ -649,7 +649,7 @@ int hml_levels_on_segments(hml_ctx* c, uint64_t n_cuts, const uint32_t* cuts, do
                        (uint32_t)M, T, rows, b_cuts.as<uint32_t>(), (uint32_t)n_cuts, b_out.as<double>());
     KLAUNCH_CHECK();
     std::vector<double> h_out(n_seg * rows);
-    HIPCHK(hipMemcpyAsync(h_out.data(), b_out.p, n_seg * rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(h_out.data(), b_out.get(), n_seg * rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     for (int d = 0; d < D; ++d) {
         if (sum) memcpy(sum + (uint64_t)d * n_seg, h_out.data() + (uint64_t)(2 * d) * n_seg, n_seg * sizeof(double));
@@ -726,14 +726,14 @@ int hml_regions_ensure(hml_ctx* c) {
     const uint64_t n = g.start.size();
     const uint64_t acc_bytes = regions_acc_words(c) * n * 8u;
     const uint64_t chunk_bytes = (uint64_t)regions_chunk_stride(c) * ((uint64_t)c->D * sizeof(double) + (1u + (uint64_t)c->D) * sizeof(uint32_t));
-    HIPCHK(hipMalloc(&g.d_start, n * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&g.d_end, n * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&g.d_chunks, chunk_bytes));
-    HIPCHK(hipMalloc(&g.d_acc, acc_bytes));
+    HIPCHK(g.d_start.alloc(n));
+    HIPCHK(g.d_end.alloc(n));
+    HIPCHK(g.d_chunks.alloc(chunk_bytes));
+    HIPCHK(g.d_acc.alloc(acc_bytes));
     HIPCHK(hipMemcpyAsync(g.d_start, g.start.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(g.d_end, g.end.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemsetAsync(g.d_chunks, 0, chunk_bytes, c->stream));
-    HIPCHK(hipMemsetAsync(g.d_acc, 0, acc_bytes, c->stream));
+    HIPCHK(hipMemsetAsync(g.d_chunks.get(), 0, chunk_bytes, c->stream));
+    HIPCHK(hipMemsetAsync(g.d_acc.get(), 0, acc_bytes, c->stream));
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(c->stream, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone) HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
@@ -787,7 +787,7 @@ static int regions_fetch(hml_ctx* c, const char* whose, hml_regions_host& h) {
     if (int r = model_fault(m)) return r;
     h.n = c->rg.start.size(); h.N = m.n_regions_recorded; h.D = c->D; h.ncol = regions_columns(c);
     h.words.resize(regions_acc_words(c) * h.n);
-    HIPCHK(hipMemcpy(h.words.data(), c->rg.d_acc, h.words.size() * 8u, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h.words.data(), c->rg.d_acc.get(), h.words.size() * 8u, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -805,7 +805,7 @@ static int regions_add_host(hml_ctx* c, uint64_t N, const uint64_t* whole, const
     for (uint64_t i = 0; i < (uint64_t)h.D * h.n; ++i) { h.level_sum()[i] += level_sum[i]; h.level_sq()[i] += level_sq[i]; }
     for (uint64_t i = 0; i < h.n * (uint64_t)h.ncol; ++i) h.inband()[i] += inband[i];
     const unsigned long long total = h.N + N;
-    HIPCHK(hipMemcpy(c->rg.d_acc, h.words.data(), h.words.size() * 8u, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->rg.d_acc.get(), h.words.data(), h.words.size() * 8u, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(&c->d_mdl->n_regions_recorded, &total, sizeof total, hipMemcpyHostToDevice));
     return 0;
 }
@@ -963,13 +963,13 @@ static int payload_merge(hml_ctx* dst, int kind, const void* payload_dev, uint64
     const char* const cells = base + HML_RECPAY_FIXED_BYTES + 8u * ((M + 1u) / 2u);
     if (M) {
         DevBuf b_flag;
-        HIPCHK(hipMalloc(&b_flag.p, sizeof(uint32_t)));
-        HIPCHK(hipMemsetAsync(b_flag.p, 0, sizeof(uint32_t), dst->stream));
+        HIPCHK(b_flag.alloc(sizeof(uint32_t)));
+        HIPCHK(hipMemsetAsync(b_flag.get(), 0, sizeof(uint32_t), dst->stream));
         hipLaunchKernelGGL(hml_k_recpay_check, dim3(grid_for(M, 256, 1, 1024)), dim3(256), 0, dst->stream, d_pos, (uint32_t)M, (uint32_t)T, kind == HML_REC_BREAKS ? 1u : 0u,
                            b_flag.as<uint32_t>());
         KLAUNCH_CHECK();
         uint32_t bad = 0;
-        HIPCHK(hipMemcpyAsync(&bad, b_flag.p, sizeof bad, hipMemcpyDeviceToHost, dst->stream));
+        HIPCHK(hipMemcpyAsync(&bad, b_flag.get(), sizeof bad, hipMemcpyDeviceToHost, dst->stream));
         HIPCHK(hipStreamSynchronize(dst->stream));
         if (bad & HML_RECPAY_BAD_RANGE) return set_err(HML_ERR_ARG, "the payload lists a position beyond the last one");
         if (bad & HML_RECPAY_BAD_ZERO) return set_err(HML_ERR_ARG, "a breaks payload lists position 0, which is never a breakpoint");
@@ -1040,17 +1040,17 @@ int hml_recording_merge_across(hml_ctx* dst, hml_ctx* src, int kind) {
         if (int r = payload_positions(src, kind, &M, b_seg, &d_pos)) return r;
         bytes = payload_bytes(M, (uint64_t)recorder_rows(src, kind), rk.elem);
     }
-    HIPCHK(hipMalloc(&b_src.p, bytes));
+    HIPCHK(b_src.alloc(bytes));
     uint64_t written = 0;
-    if (int r = payload_export(src, kind, b_src.p, bytes, &written)) return r;
+    if (int r = payload_export(src, kind, b_src.get(), bytes, &written)) return r;
     if (written != bytes) return set_err(HML_ERR_HIP, "internal error: a recording changed between its sizing and its export");
-    if (dst->device == src->device) return payload_merge(dst, kind, b_src.p, bytes);
+    if (dst->device == src->device) return payload_merge(dst, kind, b_src.get(), bytes);
     // ... its bytes to the destination's device (no peer access needed), and the merge there
     if (int r = ctx_bind(dst)) return r;
-    HIPCHK(hipMalloc(&b_dst.p, bytes));
-    HIPCHK(hipMemcpyPeer(b_dst.p, dst->device, b_src.p, src->device, bytes));
+    HIPCHK(b_dst.alloc(bytes));
+    HIPCHK(hipMemcpyPeer(b_dst.get(), dst->device, b_src.get(), src->device, bytes));
     HIPCHK(hipDeviceSynchronize());
-    return payload_merge(dst, kind, b_dst.p, bytes);
+    return payload_merge(dst, kind, b_dst.get(), bytes);
 }
 
 }  // extern "C"

@@ -311,14 +311,13 @@ static int iterate_many_k(hml_ctx* const* cs, int n, uint64_t first, uint64_t it
         d.q = c->d_q; d.partial = c->d_partial; d.diff = c->d_diff; d.boundary = c->d_boundary; d.lay = c->lay_many;
     }
     if (c0->many_cap < n) {
-        if (c0->d_many) HIPCHK(hipFree(c0->d_many));
-        c0->d_many = nullptr; c0->many_cap = 0;
-        HIPCHK(hipMalloc(&c0->d_many, n * sizeof(hml_chain_dev)));
+        c0->many_cap = 0;
+        HIPCHK(c0->d_many.alloc(n * sizeof(hml_chain_dev)));
         c0->many_cap = n;
     }
-    HIPCHK(hipMemcpyAsync(c0->d_many, h.data(), n * sizeof(hml_chain_dev), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c0->d_many.get(), h.data(), n * sizeof(hml_chain_dev), hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s));   // (the staging vector goes out of scope below)
-    const hml_chain_dev* d_cs = (const hml_chain_dev*)c0->d_many;
+    const hml_chain_dev* d_cs = c0->d_many.as<const hml_chain_dev>();
     // The batch runs as G GROUPS of chains, each on a stream of its own (its first chain's), enqueued by this one host thread: a
     // group's latency-bound stretches - the one-workgroup kernels, the block kernel's hand-off, launch boundaries - are filled by
     // the other group's throughput-bound kernels (round 4, config 3, ms per round of sweeps: 2 chains 0.078 against 0.082, 4: 0.106 /

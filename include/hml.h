@@ -541,6 +541,16 @@ int hml_profile_get(hml_ctx* ctx, const char* name, double* total_ms, uint64_t* 
  * 5 gamma(alpha=a, beta=b) draw, 6 normal(mean=a, sd=b) draw, 7-10 double-precision kernels). */
 int hml_debug_eval(int device, int fn, const float* a, const float* b_or_null, float* out, uint64_t n, uint64_t seed);
 
+/* Device memory the library's contexts and read-outs hold at this moment, over the whole process: bytes and number of
+ * allocations.  Both are 0 once every context is destroyed (and without a GPU).  The pooling object (hml_pool_create) and the
+ * text reader keep their own and are not counted. */
+int hml_device_memory_live(uint64_t* bytes, uint64_t* allocations);
+
+/* Test hook for the out-of-memory paths: the `nth` device allocation from now (1: the next) fails once with
+ * hipErrorOutOfMemory - the call that made it returns HML_ERR_HIP - without the runtime being asked, then the hook is off again;
+ * 0 turns it off.  Returns the number of allocations made since the hook was last set.  Process-wide, like the totals above. */
+int hml_debug_fail_allocation(int64_t nth);
+
 /* synthetic piecewise-constant Gaussian trace, host buffer */
 int hml_synth_gauss(float* x, int16_t* states_or_null, uint64_t T, int K, const float* mu, float sigma,
                     double mean_dwell, uint64_t seed, int nthreads);

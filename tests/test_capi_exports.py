@@ -53,6 +53,20 @@ def test_no_gpu_means_a_loud_failure_not_a_fallback():
         hammlet_amd.Chain()
 
 
+def test_memory_diagnostics_answer_without_a_gpu():
+    """hml_device_memory_live and hml_debug_fail_allocation need no device: with no context alive the owners hold nothing,
+    and the hook reports the allocations made since it was set - none here."""
+    import torch
+    import hammlet_amd
+    hammlet_amd.debug_fail_allocation(0)
+    assert hammlet_amd.debug_fail_allocation(3) == 0    # armed: nothing was allocated in between
+    assert hammlet_amd.debug_fail_allocation(0) == 0    # ... and off again
+    live = hammlet_amd.device_memory_live()
+    if not torch.cuda.is_available():
+        assert live == (0, 0)
+    assert (live[0] == 0) == (live[1] == 0)
+
+
 def test_product_never_references_the_oracle():
     """Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may touch oracle/."""
     for root in ("hammlet_amd", "include"):
