@@ -173,6 +173,11 @@ static int create_inner(hml_ctx* c, void* stream) {
     return 0;
 }
 
+// a chunk length from the environment: the largest power of two up to the value, of at most `max_bits` bits
+static void env_chunk_length(const char* name, int max_bits, int* L) {
+    if (const char* e = getenv(name)) { const int l = std::max(1, atoi(e)); int sh = 0; while ((1 << (sh + 1)) <= l && sh < max_bits) ++sh; *L = 1 << sh; }
+}
+
 int hml_create(hml_ctx** out, int device, uint64_t seed, uint32_t chain_id, void* stream) {
     if (!out) return set_err(HML_ERR_ARG, "null output pointer");
     int n = 0;
@@ -182,26 +187,27 @@ int hml_create(hml_ctx** out, int device, uint64_t seed, uint32_t chain_id, void
     hml_ctx* c = new hml_ctx();
     c->device = device; c->seed = seed; c->chain = chain_id;
     if (int r = create_inner(c, stream)) { delete_ctx(c); return r; }
-    if (const char* e = getenv("HML_FWD_CHUNK")) { int l = std::max(1, atoi(e)); int sh = 0; while ((1 << (sh + 1)) <= l && sh < 10) ++sh; c->fwdL = 1 << sh; }
+    hml_sweep_knobs& kn = c->knobs;
+    env_chunk_length("HML_FWD_CHUNK", 10, &kn.geo[HML_GEO_SPARSE].L);
     if (const char* e = getenv("HML_FWD_WARMUP")) c->fwdW = c->fwdW_init = std::max(0, atoi(e));
     if (const char* e = getenv("HML_FWD_BURNIN_SWEEPS")) c->fwd_burnin_sweeps = (uint32_t)std::max(0, atoi(e));
     if (const char* e = getenv("HML_FWD_QUIET")) c->fwd_quiet_need = (uint32_t)std::max(1, atoi(e));
-    if (const char* e = getenv("HML_FWD_CHUNK_MANY")) { int l = std::max(1, atoi(e)); int sh = 0; while ((1 << (sh + 1)) <= l && sh < 6) ++sh; c->fwdL_many = 1 << sh; }
-    if (const char* e = getenv("HML_FWD_CHUNK_MID")) { int l = std::max(1, atoi(e)); int sh = 0; while ((1 << (sh + 1)) <= l && sh < 10) ++sh; c->fwdL_mid = 1 << sh; }
-    if (const char* e = getenv("HML_MID_MIN_BLOCKS")) c->mid_min_blocks = (uint32_t)strtoul(e, nullptr, 10);
-    if (const char* e = getenv("HML_FWD_CHUNK_DENSE")) { int l = std::max(1, atoi(e)); int sh = 0; while ((1 << (sh + 1)) <= l && sh < 10) ++sh; c->fwdL_dense = 1 << sh; }
-    if (const char* e = getenv("HML_DENSE_MIN_BLOCKS")) c->dense_min_blocks = (uint32_t)strtoul(e, nullptr, 10);
+    env_chunk_length("HML_FWD_CHUNK_MANY", 6, &kn.geo[HML_GEO_MANY].L);
+    env_chunk_length("HML_FWD_CHUNK_MID", 10, &kn.geo[HML_GEO_MID].L);
+    if (const char* e = getenv("HML_MID_MIN_BLOCKS")) kn.mid_min_blocks = (uint32_t)strtoul(e, nullptr, 10);
+    env_chunk_length("HML_FWD_CHUNK_DENSE", 10, &kn.geo[HML_GEO_DENSE].L);
+    if (const char* e = getenv("HML_DENSE_MIN_BLOCKS")) kn.dense_min_blocks = (uint32_t)strtoul(e, nullptr, 10);
     if (const char* e = getenv("HML_USE_GRAPH")) c->use_graph = atoi(e) != 0;
-    if (const char* e = getenv("HML_WEIGHT_KEYS")) c->use_keys = atoi(e) != 0;
-    if (const char* e = getenv("HML_FUSED_BLOCKS")) { c->fused_blocks = atoi(e) != 0; c->fused_keep = atoi(e) == 2; }   // 0: a GPU shared with other processes
-    if (const char* e = getenv("HML_TRELLIS_FUSED")) c->tre_fused = atoi(e) != 0;
+    if (const char* e = getenv("HML_WEIGHT_KEYS")) kn.use_keys = atoi(e) != 0;
+    if (const char* e = getenv("HML_FUSED_BLOCKS")) { kn.fused_blocks = atoi(e) != 0; kn.fused_keep = atoi(e) == 2; }   // 0: a GPU shared with other processes
+    if (const char* e = getenv("HML_TRELLIS_FUSED")) kn.tre_fused = atoi(e) != 0;
     if (const char* e = getenv("HML_TRELLIS_L")) { const int l = atoi(e); c->tre_L = (l <= 0) ? 0u : (l >= HML_TRE_MAX_L) ? (uint32_t)HML_TRE_MAX_L : (l < 32) ? 32u : (uint32_t)l / 32u * 32u; }   // a multiple of 32
     if (const char* e = getenv("HML_TRELLIS_CKPT")) c->tre_ckpt = atoi(e) != 0;
     if (const char* e = getenv("HML_TRELLIS_REFIT_ROUNDS")) { const int r = atoi(e); c->tre_refit_rounds = r < 0 ? 0u : r > 6 ? 6u : (uint32_t)r; }
-    if (const char* e = getenv("HML_STAGE_BITS")) c->stage_bits = atoi(e) != 0;
-    if (const char* e = getenv("HML_TRELLIS_ROWS")) c->tre_rows = atoi(e) != 0;   // 0: round 2's first pass (hml_k_trellis_tile) for comparison
-    if (const char* e = getenv("HML_LATE_RESCALE")) c->late_rescale = atoi(e) != 0;
-    if (const char* e = getenv("HML_PARAMS_SPREAD")) c->params_spread = atoi(e) != 0;
+    if (const char* e = getenv("HML_STAGE_BITS")) kn.stage_bits = atoi(e) != 0;
+    if (const char* e = getenv("HML_TRELLIS_ROWS")) kn.tre_rows = atoi(e) != 0;   // 0: round 2's first pass (hml_k_trellis_tile) for comparison
+    if (const char* e = getenv("HML_LATE_RESCALE")) kn.late_rescale = atoi(e) != 0;
+    if (const char* e = getenv("HML_PARAMS_SPREAD")) kn.params_spread = atoi(e) != 0;
     if (const char* e = getenv("HML_COMPAT_CHUNKS")) c->compat_chunks = atoi(e);   // (1: the sequential form; > 1: that many chunks)
     if (const char* e = getenv("HML_COMPAT_WARMUP")) c->compat_warmup = atoi(e);   // (tests: a warm-up too short to forget the start)
     if (const char* e = getenv("HML_WIDE_LANES")) c->wide_lanes = atoi(e);   // (0: models of more than 16 states with a state a lane)
@@ -247,7 +253,7 @@ void hml_destroy(hml_ctx* c) {
 // ---------------------------------------------------------------------------------------- load
 // 8-bit keys of the current weights, bucket window centred on the universal threshold of the noise estimate
 static int build_keys(hml_ctx* c) {
-    if (!c->use_keys) return 0;
+    if (!c->knobs.use_keys) return 0;
     const uint64_t T = c->T;
     if (!c->d_summary) {
         // one byte per 16-position group, padded with zeros to whole spans
@@ -463,7 +469,7 @@ int hml_attach_observations(hml_ctx* c, hml_ctx* src) {
     if (!src->loaded || !src->trace) return set_err(HML_ERR_ARG, "the source context has no observations loaded");
     if (c->loaded) return set_err(HML_ERR_ARG, "observations already loaded");
     if (c->device != src->device) return set_err(HML_ERR_ARG, "contexts that share observations must live on one device");
-    if (c->use_keys != src->use_keys) return set_err(HML_ERR_ARG, "option weight_keys differs from the source context's");
+    if (c->knobs.use_keys != src->knobs.use_keys) return set_err(HML_ERR_ARG, "option weight_keys differs from the source context's");
     if (int r = ctx_bind(c)) return r;
     HIPCHK(hipStreamSynchronize(src->stream));   // (a weight multiplier still on its way)
     c->T = src->T; c->D = src->D;
@@ -640,7 +646,8 @@ static int alloc_sweep_buffers(hml_ctx* c) {
         HIPCHK(hipMemsetAsync(c->d_wacc.get(), 0, sizeof(hml_wide_acc), c->stream));
         return 0;
     }
-    const int minL = std::min(std::min(std::min(c->fwdL, c->fwdL_dense), c->fwdL_many), c->fwdL_mid);
+    int minL = c->knobs.geo[0].L;
+    for (const hml_fwd_geo& g : c->knobs.geo) minL = std::min(minL, g.L);
     const uint64_t maxChunks = (cap + minL - 1) / minL + 1;   // per-chunk arrays serve either geometry
     uint64_t plane = 0;   // floats in one chunk-transposed [L][K][cstride] array
     auto layout = [&](int L, hml_layout& lay) {
@@ -649,10 +656,7 @@ static int alloc_sweep_buffers(hml_ctx* c) {
         lay.cstride = (uint32_t)(((cap + L - 1) / L + 1 + 63) / 64 * 64);
         plane = std::max(plane, (uint64_t)L * K * lay.cstride);
     };
-    layout(c->fwdL, c->lay);
-    layout(c->fwdL_dense, c->lay_dense);
-    layout(c->fwdL_mid, c->lay_mid);
-    layout(c->fwdL_many, c->lay_many);
+    for (hml_fwd_geo& g : c->knobs.geo) layout(g.L, g.lay);
     HIPCHK(c->d_em.alloc(plane));
     HIPCHK(c->d_gsc.alloc(plane));
     HIPCHK(c->d_rows.alloc(plane));
@@ -795,7 +799,7 @@ int hml_set_model(hml_ctx* c, int K, const float nig4[4], float a_off, float a_d
     c->K = K;
     // the parameter kernel's tree over 16 workgroups (hml_k_params.h) from 8 states: it reads 2 K x 8 KB of group partials -
     // config 4's sweep (10 states) 0.0938 -> 0.0869 ms, config 3's (5 states) unchanged either way
-    if (!getenv("HML_PARAMS_SPREAD")) c->params_spread = K >= 8;
+    if (!getenv("HML_PARAMS_SPREAD")) c->knobs.params_spread = K >= 8;
     const uint64_t T = c->T;
     if (int r = alloc_capacity_buffers(c, CAPBUF_SWEEP)) return r;
 
@@ -818,7 +822,7 @@ int hml_set_model(hml_ctx* c, int K, const float nig4[4], float a_off, float a_d
         for (int j = 0; j < K; ++j) { m.dirA[k * K + j] = (k == j) ? a_diag : a_off; m.A[k * K + j] = 1.0f / K; }
     }
     m.max_state_recorded = -1;
-    m.tre_fused = (c->tre_fused && c->D == 1) ? 1u : 0u;
+    m.tre_fused = (c->knobs.tre_fused && c->D == 1) ? 1u : 0u;
     m.tre_hi_shift = 17u; m.tre_lo_shift = 20u;
     if (const char* e = getenv("HML_TRE_REFIT_SHIFTS")) { unsigned a = 17, b = 20; if (sscanf(e, "%u,%u", &a, &b) == 2 && a < 32 && b < 32) { m.tre_hi_shift = a; m.tre_lo_shift = b; } }
     m.fwd_W0 = (uint32_t)c->fwdW;
@@ -894,6 +898,7 @@ int hml_set_static_blocks(hml_ctx* c) {
     hipLaunchKernelGGL(hml_k_set_dynamic, dim3(1), dim3(64), 0, c->stream, c->d_mdl, 0, 1);
     KLAUNCH_CHECK();
     c->dynamic = false;
+    drop_graph(c);   // (a captured sweep holds the block launches or not)
     if (!cap_limited(c)) {
         if (int r = launch_compact(c, false, 0.0f)) return r;
     } else {
@@ -922,6 +927,7 @@ int hml_set_dynamic(hml_ctx* c, int on) {
     hipLaunchKernelGGL(hml_k_set_dynamic, dim3(1), dim3(64), 0, c->stream, c->d_mdl, on ? 1 : 0, on ? 1 : 0);
     KLAUNCH_CHECK();
     c->dynamic = on != 0;
+    drop_graph(c);
     if (on) { c->blocks_valid = false; c->hint_stale = true; }
     return 0;
 }
@@ -1079,19 +1085,16 @@ static void launch_chunked_fb(hml_ctx* c, hipStream_t s, uint32_t C, const hml_c
 
 static int sweep_compat(hml_ctx* c, char method, bool record) {
     hipStream_t s = c->stream;
-    if (c->dynamic || !c->blocks_valid) {
-        if (int r = launch_compact(c, false, 0.0f)) return r;   // starts, block count, block statistics at the model's threshold
-        if (!c->dynamic) c->blocks_valid = true;
-    }
+    if (int r = launch_blocks_if_needed(c)) return r;
     refresh_hint(c);
-    const uint32_t hint = c->B_hint ? c->B_hint : (uint32_t)std::min<uint64_t>(c->T, 1u << 20);
+    const uint32_t hint = grid_hint(c);
     const int mix = method == HML_METHOD_MIXTURE ? 1 : 0;
     hml_mt_state* const mt = c->d_mt.as<hml_mt_state>();
     hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_compat_emission<hml_glibc_exp>), dim3(grid_for(hint, 256, 64, 16384)), dim3(256), 0, s, c->d_mdl, c->d_starts, c->d_bstat, c->d_em, c->d_gsc, mix,
-                       c->probes ? c->d_eprobe : nullptr);
+                       eprobe_of(c));
     if (mix) hipLaunchKernelGGL(hml_k_compat_mixture, dim3(1), dim3(64), 0, s, c->d_mdl, mt, c->d_em, c->d_q);
     else {
-        float* const aprobe = c->probes ? c->d_aprobe : nullptr;
+        float* const aprobe = aprobe_of(c);
         // filter and backward draws in chunks with a wavefront each, then one wavefront that checks the chunks in order
         // (hml_k_compat.h); one chunk - the sequential form - for short sweeps and when the rows are probed
         uint32_t C = 1u;
@@ -1134,11 +1137,7 @@ static int sweep_compat(hml_ctx* c, char method, bool record) {
         hipLaunchKernelGGL(hml_k_compat_part_scatter, dim3(tg), dim3(256), 0, s, c->d_mdl, c->d_q, c->d_starts, c->d_bstat, pl);
     }
     hipLaunchKernelGGL(hml_k_compat_update, dim3(1), dim3(by_state ? 256 : 64), 0, s, c->d_mdl, mt, c->d_starts, c->d_bstat, c->d_q, mix, pl, by_state);
-    if (record && c->rec_marginals) {
-        if (c->pooled) return set_err(HML_ERR_ARG, "the marginals of this context are pooled (common labels, several chains): further sweeps cannot be recorded into them");
-        if (int r = ensure_marginal_buffers(c)) return r;
-        hipLaunchKernelGGL(hml_k_record, dim3(grid_for(hint, 256, 64, 16384)), dim3(256), 0, s, c->d_q, c->d_starts, c->d_mdl, c->d_diff, c->d_boundary);
-    }
+    if (record) { if (int r = launch_marginals(c, s, hint, /*bracket*/ false)) return r; }
     if (record) { if (int r = launch_recorders(c, s, hint)) return r; }   // (hml_k_compat_update above is this sweep's parameter update)
     KLAUNCH_CHECK();
     return 0;
@@ -1149,12 +1148,9 @@ static int sweep_compat(hml_ctx* c, char method, bool record) {
 // uniforms of the draws from their Philox addresses ahead of them, the default path's count tree, hml_k_wide_params.
 static int sweep_wide(hml_ctx* c, char method, bool record) {
     hipStream_t s = c->stream;
-    if (c->dynamic || !c->blocks_valid) {
-        if (int r = launch_compact(c, false, 0.0f)) return r;   // starts, block count, block statistics at the model's threshold
-        if (!c->dynamic) c->blocks_valid = true;
-    }
+    if (int r = launch_blocks_if_needed(c)) return r;
     refresh_hint(c);
-    const uint32_t hint = c->B_hint ? c->B_hint : (uint32_t)std::min<uint64_t>(c->T, 1u << 20);
+    const uint32_t hint = grid_hint(c);
     const int mix = method == HML_METHOD_MIXTURE ? 1 : 0;
     // filter and backward draws with a chunk a lane over chunk-transposed arrays (hml_k_wide_lanes.h) - unless the rows are probed,
     // a test asked for a number of chunks of the other form, or the sweep has no filter at all
@@ -1203,11 +1199,11 @@ static int sweep_wide(hml_ctx* c, char method, bool record) {
     {
         ProfScope ps(c, "stats_emission");
         hipLaunchKernelGGL(hml_k_wide_emission, dim3(grid_for(hint, 256, 1, 4096)), dim3(256), 0, s, c->d_mdl, c->d_starts, c->d_bstat,
-                           c->d_em, c->d_gsc, mix, c->probes ? c->d_eprobe : nullptr);
+                           c->d_em, c->d_gsc, mix, eprobe_of(c));
     }
     if (mix) hipLaunchKernelGGL(hml_k_wide_mixture, dim3(grid_for(hint, 256, 1, 16384)), dim3(256), 0, s, c->d_mdl, c->d_em, c->d_q);
     else {
-        float* const aprobe = c->probes ? c->d_aprobe : nullptr;
+        float* const aprobe = aprobe_of(c);
         uint32_t C = 1u;   // (one chunk - the sequential form - for short sweeps and when the rows are probed)
         if (!c->probes && c->compat_chunks > 1) C = std::min<uint32_t>((uint32_t)c->compat_chunks, HML_COMPAT_MAX_CHUNKS);
         else if (!c->probes && c->compat_chunks == 0 && hint >= 2048u) C = std::min<uint32_t>((uint32_t)HML_COMPAT_MAX_CHUNKS, hint / 64u);
@@ -1222,11 +1218,7 @@ static int sweep_wide(hml_ctx* c, char method, bool record) {
         ProfScope ps(c, "counts");
         hipLaunchKernelGGL(hml_k_wide_counts, dim3(HML_REDUCE_GROUPS), dim3(256), 0, s, c->d_q, c->d_starts, c->d_bstat, c->d_mdl, c->d_partial, c->d_wacc.as<hml_wide_acc>());
     }
-    if (record && c->rec_marginals) {
-        if (c->pooled) return set_err(HML_ERR_ARG, "the marginals of this context are pooled (common labels, several chains): further sweeps cannot be recorded into them");
-        if (int r = ensure_marginal_buffers(c)) return r;
-        hipLaunchKernelGGL(hml_k_record, dim3(grid_for(hint, 256, 64, 16384)), dim3(256), 0, s, c->d_q, c->d_starts, c->d_mdl, c->d_diff, c->d_boundary);
-    }
+    if (record) { if (int r = launch_marginals(c, s, hint, /*bracket*/ false)) return r; }
     {
         ProfScope ps(c, "params");
         hipLaunchKernelGGL(hml_k_wide_params, dim3(1), dim3(1024), 0, s, c->d_mdl, c->d_partial, c->d_wacc.as<hml_wide_acc>(), 0);
@@ -1243,6 +1235,56 @@ static int sweep_dispatch(hml_ctx* c, char method, bool record) {
     return kt->sweep(c, method, record);
 }
 
+// One sweep of a chain and, on a recorded sweep with a callback: wait, settle if the chain halted (that runs the sweep again
+// and calls back), check the device error, call back.
+static int sweep_step(hml_ctx* c, char method, bool record, uint64_t i) {
+    log_sweep(c, method, record);
+    if (int r = sweep_dispatch(c, method, record)) return r;
+    if (!(record && c->cb)) return 0;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (chain_halted(c)) return hml_settle(c);
+    if (int r = check_device_error(c)) return r;
+    c->cb(c, i, c->cb_user);
+    return 0;
+}
+
+// HML_USE_GRAPH: replay a captured sweep.  It is captured again when there is none, when the plan of the coming sweep differs
+// from the one it was captured under (hml_sweep_plan.h: method, geometry, block path, scan variant, ...), when the grid hint left
+// [captured / 2, captured], or when the fused trellis path would take another chunk length.  *replayed: the sweep is enqueued.
+static int replay_captured(hml_ctx* c, char method, bool* replayed) {
+    *replayed = false;
+    const uint32_t hint = c->B_hint;
+    const hml_sweep_plan plan = plan_of(c, method == HML_METHOD_MIXTURE, c->h_B[1] != 0u);
+    if (plan.trellis && tre_wants_measurement(c, hint)) return 0;   // (a measuring sweep runs outside any graph)
+    bool unused = false;
+    const bool stale = !c->graph_exec || !(plan == c->captured.plan) || hint > c->captured.hint || hint * 2u < c->captured.hint ||
+                       (plan.trellis && c->captured.tre_L != tre_pick_L(c, hint, true, &unused));
+    if (stale && hint) {
+        drop_graph(c);
+        hipGraph_t g = nullptr;
+        HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+        // whatever happens below, the stream must leave capture mode (a failure in between would otherwise
+        // make every later call on this context fail) and a partial graph must not stay behind
+        int rr = sweep_dispatch(c, method, false);
+        const hipError_t ec = hipStreamEndCapture(c->stream, &g);
+        if (rr || ec != hipSuccess) {
+            if (g) hipGraphDestroy(g);
+            (void)hipGetLastError();
+            return rr ? rr : set_err(HML_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ec));
+        }
+        const hipError_t ei = hipGraphInstantiate(&c->graph_exec, g, nullptr, nullptr, 0);
+        hipGraphDestroy(g);
+        if (ei != hipSuccess) { c->graph_exec = nullptr; return set_err(HML_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ei)); }
+        c->captured.plan = plan; c->captured.hint = c->B_hint; c->captured.tre_L = c->tre_last_L;
+    }
+    if (!c->graph_exec) return 0;
+    log_sweep(c, method, false);
+    HIPCHK(hipGraphLaunch(c->graph_exec, c->stream));
+    if (plan.trellis) c->tre_dense_sweeps++;
+    *replayed = true;
+    return 0;
+}
+
 extern "C" {
 
 int hml_iterate(hml_ctx* c, char method, uint64_t iterations, uint64_t thinning) {
@@ -1251,61 +1293,18 @@ int hml_iterate(hml_ctx* c, char method, uint64_t iterations, uint64_t thinning)
         return set_err(HML_ERR_ARG, std::string("Unknown sampling type ") + method + "!");
     if (int r = ctx_bind(c)) return r;
     c->call_base = c->requested;
-    if (thinning > 0 && thinning <= iterations && c->rec_marginals && c->pooled)   // (before anything is enqueued: a sweep is not abandoned half-way)
-        return set_err(HML_ERR_ARG, "the marginals of this context are pooled (common labels, several chains): further sweeps cannot be recorded into them");
+    if (int r = pooled_refusal(c, thinning > 0 && thinning <= iterations, "this context")) return r;   // (before anything is enqueued: a sweep is not abandoned half-way)
     for (uint64_t i = 0; i < iterations; ++i) {
         const bool record = thinning > 0 && ((i + 1) % thinning == 0);
         // a chain with a reduced block capacity that halted (hml_state.h): larger buffers, the skipped sweeps again - then on
         if (chain_halted(c)) { if (int r = hml_settle(c)) return r; }
         refresh_hint(c);
-        const bool tre_path = c->tre_fused && c->D == 1 && method == HML_METHOD_FB && c->B_hint >= c->dense_min_blocks;
-        if (c->use_graph && !c->compat && !record && !c->profiling && !c->probes && (c->dynamic || c->blocks_valid) &&
-            !(tre_path && tre_wants_measurement(c, c->B_hint))) {
-            // replay a captured sweep; capture again when the launch geometry (grid hint / mode / chunk length) changed
-            const uint32_t hint = c->B_hint;
-            bool unused = false;
-            // (a captured sweep holds the fused block kernel or the scan + scatter pair: capture again when a second
-            // context appeared on the device, a bounded wait expired or the option changed)
-            const bool wants_fused = c->fused_blocks && !(c->h_B[1] && !c->fused_keep) && !shares_device(c);
-            const bool stale = !c->graph_exec || c->graph_method != method || c->graph_dynamic != c->dynamic ||
-                               hint > c->graph_hint || hint * 2u < c->graph_hint || c->graph_fused != wants_fused ||
-                               c->graph_dense != (hint >= c->dense_min_blocks) || c->graph_mid != (hint >= c->mid_min_blocks) ||
-                               (tre_path && c->graph_tre_L != tre_pick_L(c, hint, true, &unused));
-            if (stale && hint) {
-                drop_graph(c);
-                hipGraph_t g = nullptr;
-                HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-                // whatever happens below, the stream must leave capture mode (a failure in between would otherwise
-                // make every later call on this context fail) and a partial graph must not stay behind
-                int rr = sweep_dispatch(c, method, false);
-                const hipError_t ec = hipStreamEndCapture(c->stream, &g);
-                if (rr || ec != hipSuccess) {
-                    if (g) hipGraphDestroy(g);
-                    (void)hipGetLastError();
-                    return rr ? rr : set_err(HML_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ec));
-                }
-                const hipError_t ei = hipGraphInstantiate(&c->graph_exec, g, nullptr, nullptr, 0);
-                hipGraphDestroy(g);
-                if (ei != hipSuccess) { c->graph_exec = nullptr; return set_err(HML_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ei)); }
-                c->graph_method = method; c->graph_dynamic = c->dynamic; c->graph_hint = c->B_hint; c->graph_fused = wants_fused;
-                c->graph_dense = c->B_hint >= c->dense_min_blocks;
-                c->graph_mid = c->B_hint >= c->mid_min_blocks;
-            }
-            if (c->graph_exec) {
-                log_sweep(c, method, false);
-                HIPCHK(hipGraphLaunch(c->graph_exec, c->stream));
-                if (tre_path) c->tre_dense_sweeps++;
-                continue;
-            }
+        if (c->use_graph && !c->compat && !record && !c->profiling && !c->probes && (c->dynamic || c->blocks_valid)) {
+            bool replayed = false;
+            if (int r = replay_captured(c, method, &replayed)) return r;
+            if (replayed) continue;
         }
-        log_sweep(c, method, record);
-        if (int r = sweep_dispatch(c, method, record)) return r;
-        if (record && c->cb) {
-            HIPCHK(hipStreamSynchronize(c->stream));
-            if (chain_halted(c)) { if (int r = hml_settle(c)) return r; continue; }   // (runs the sweep again and calls back)
-            if (int r = check_device_error(c)) return r;
-            c->cb(c, i, c->cb_user);
-        }
+        if (int r = sweep_step(c, method, record, i)) return r;
     }
     return 0;
 }
@@ -1359,16 +1358,9 @@ extern "C" int hml_iterate_many(hml_ctx* const* cs, int n, char method, uint64_t
         for (int k = 0; k < n; ++k) {
             hml_ctx* c = cs[k];
             if (int r = ctx_bind(c)) return r;
-            if (record && c->rec_marginals && c->pooled) return set_err(HML_ERR_ARG, "the marginals of a context are pooled (common labels, several chains): further sweeps cannot be recorded into them");
+            if (int r = pooled_refusal(c, record, "a context")) return r;
             if (chain_halted(c)) { if (int r = hml_settle(c)) return r; }
-            log_sweep(c, method, record);
-            if (int r = sweep_dispatch(c, method, record)) return r;
-            if (record && c->cb) {
-                HIPCHK(hipStreamSynchronize(c->stream));
-                if (chain_halted(c)) { if (int r = hml_settle(c)) return r; continue; }   // (runs the sweep again and calls back)
-                if (int r = check_device_error(c)) return r;
-                c->cb(c, i, c->cb_user);
-            }
+            if (int r = sweep_step(c, method, record, i)) return r;
         }
     }
     return 0;
@@ -1380,8 +1372,8 @@ int hml_set_option(hml_ctx* c, const char* name, int value) {
     if (!c || !name) return set_err(HML_ERR_ARG, "null argument");
     if (std::string(name) == "weight_keys") {
         if (c->loaded) return set_err(HML_ERR_ARG, "weight_keys must be set before the observations are loaded");
-        c->use_keys = value != 0;
-        c->summary_always = value == 2;
+        c->knobs.use_keys = value != 0;
+        c->knobs.summary_always = value == 2;
         return 0;
     }
     if (std::string(name) == "max_blocks") {   // block capacity of the per-block buffers (hml_ctx.hpp)
@@ -1391,8 +1383,8 @@ int hml_set_option(hml_ctx* c, const char* name, int value) {
         return 0;
     }
     if (std::string(name) == "fused_blocks") {
-        c->fused_blocks = value != 0;
-        c->fused_keep = value == 2;
+        c->knobs.fused_blocks = value != 0;
+        c->knobs.fused_keep = value == 2;
         drop_graph(c);
         return 0;
     }

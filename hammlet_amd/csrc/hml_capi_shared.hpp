@@ -73,6 +73,10 @@ struct hml_ktab {
 extern std::atomic<int> hml_live_ctx[64];   // hml_capi.hip
 #define g_live_ctx hml_live_ctx
 static bool shares_device(const hml_ctx* c) { return c->device < 64 && g_live_ctx[c->device].load() > 1; }
+// the plan of the chain's next sweep from the hint as it stands (hml_sweep_plan.h; h_B[1]: a bounded wait of the fused block kernel expired)
+static hml_sweep_plan plan_of(const hml_ctx* c, bool mix, bool wait_expired) {
+    return hml_plan_sweep(c->knobs, c->T, c->D, mix, c->B_hint, !shares_device(c), wait_expired);
+}
 
 
 // ------------------------------------------------------------------------------------------------
@@ -115,6 +119,18 @@ struct ProfScope {
 // a captured sweep that no longer matches the context's settings or buffers goes (the context's device is current)
 static void drop_graph(hml_ctx* c) {
     if (c->graph_exec) { hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
+}
+
+// the block count the grids of a sweep are sized for: the hint, or a guess while no enumeration has reported yet
+static uint32_t grid_hint(const hml_ctx* c) { return c->B_hint ? c->B_hint : (uint32_t)std::min<uint64_t>(c->T, 1u << 20); }
+// where the probed emission terms / forward rows go (none unless hml_enable_probes)
+static float* eprobe_of(const hml_ctx* c) { return c->probes ? c->d_eprobe.get() : nullptr; }
+static float* aprobe_of(const hml_ctx* c) { return c->probes ? c->d_aprobe.get() : nullptr; }
+
+// is the stream being captured into a graph?  (an error of the query: no)
+static bool capturing(hipStream_t s) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
 }
 
 static int grid_for(uint64_t items, int per_block, int lo, int hi) {
@@ -169,14 +185,11 @@ static int check_device_error(hml_ctx* c) {
 static void launch_compact_pair(hml_ctx* c, int mode, float thr) {
     // mode 0: model threshold; 1: explicit threshold
     const uint32_t n_groups = (c->n_spans + HML_GROUP_SPANS - 1) / HML_GROUP_SPANS;
-    // the summary scan skips unopened groups; when most groups would be opened (weak compression) the plain
-    // float stream is the better access pattern - both give the same blocks
-    const bool dense = !c->summary_always && c->B_hint && (uint64_t)c->B_hint * 24u > c->T;
-    // ... and with B ~ T the scan stages the flags themselves (512 bytes per span) instead of 16-bit offsets (2 bytes per block)
-    const bool bits = dense && c->stage_bits;
+    const int scan = hml_plan_scan(c->knobs, c->T, c->B_hint);   // (summary, float stream, or float stream staging flags: hml_sweep_plan.h)
+    const bool bits = scan == HML_SCAN_FLAGS;
     {
         ProfScope ps(c, "blocks_compact", 1);
-        if (c->use_keys && !dense) {
+        if (scan == HML_SCAN_SUMMARY) {
             hipLaunchKernelGGL(hml_k_compact_scan_summary, dim3(n_groups), dim3(256), 0, c->stream, c->d_summary, c->d_w,
                                (uint32_t)c->T, c->d_mdl, thr, mode, c->key_base, c->d_stage, c->d_span_count, c->d_coarse1);
         } else if (bits) {
@@ -189,7 +202,7 @@ static void launch_compact_pair(hml_ctx* c, int mode, float thr) {
     }
     {
         ProfScope ps(c, "blocks_scatter");
-        if (!(c->use_keys && !dense))
+        if (scan != HML_SCAN_SUMMARY)
             hipLaunchKernelGGL(hml_k_group_totals, dim3((n_groups + 255) / 256), dim3(256), 0, c->stream, c->d_span_count,
                                c->n_spans, c->d_coarse1);
         if (bits)
@@ -206,12 +219,20 @@ static int launch_compact(hml_ctx* c, bool use_override, float thr) {
     KLAUNCH_CHECK();
     {
         ProfScope ps(c, "block_stats");
-        const uint32_t hint = c->B_hint ? c->B_hint : (uint32_t)std::min<uint64_t>(c->T, 1u << 20);
+        const uint32_t hint = grid_hint(c);
         for (int d = 0; d < c->D; ++d)   // the same enumeration for every dimension (dimension-major planes)
             hipLaunchKernelGGL(hml_k_block_stats, dim3(grid_for(hint, 256, 64, 16384)), dim3(256), 0, c->stream,
                                c->d_ia + (uint64_t)d * (c->T + 1), c->d_starts, c->d_mdl, c->d_bstat + (uint64_t)d * c->T);
     }
     KLAUNCH_CHECK();
+    return 0;
+}
+
+// how sweep_compat and sweep_wide begin: starts, block count, block statistics at the model's threshold
+static int launch_blocks_if_needed(hml_ctx* c) {
+    if (!c->dynamic && c->blocks_valid) return 0;
+    if (int r = launch_compact(c, false, 0.0f)) return r;
+    if (!c->dynamic) c->blocks_valid = true;
     return 0;
 }
 
@@ -242,6 +263,21 @@ static int ensure_marginal_buffers(hml_ctx* c) {
     HIPCHK(c->d_diff.alloc(n));   // (last: it is what tells that both are there)
     HIPCHK(hipMemsetAsync(c->d_diff, 0, n * sizeof(int32_t), c->stream));
     HIPCHK(hipMemsetAsync(c->d_boundary, 0, words * sizeof(uint32_t), c->stream));
+    return 0;
+}
+
+// recorded sweeps cannot go into marginals that are a pooled payload (`whose`: "this context" / "a context")
+static int pooled_refusal(const hml_ctx* c, bool record, const char* whose) {
+    if (!(record && c->rec_marginals && c->pooled)) return 0;
+    return set_err(HML_ERR_ARG, std::string("the marginals of ") + whose + " are pooled (common labels, several chains): further sweeps cannot be recorded into them");
+}
+// the state marginals of a recorded sweep (bracket: as profile family "marginals" - the default path's sweeps)
+static int launch_marginals(hml_ctx* c, hipStream_t s, uint32_t hint, bool bracket) {
+    if (!c->rec_marginals) return 0;
+    if (int r = pooled_refusal(c, true, "this context")) return r;
+    if (int r = ensure_marginal_buffers(c)) return r;
+    ProfScope ps(c, "marginals", bracket ? 2 : 1 << 30);
+    hipLaunchKernelGGL(hml_k_record, dim3(grid_for(hint, 256, 64, 16384)), dim3(256), 0, s, c->d_q, c->d_starts, c->d_mdl, c->d_diff, c->d_boundary);
     return 0;
 }
 
@@ -287,8 +323,7 @@ static int ensure_recorder_buffers(hml_ctx* c, int kind) {
     HIPCHK(r.d_acc.alloc(bytes));   // (last: it is what tells that both are there)
     HIPCHK(hipMemsetAsync(r.d_acc.get(), 0, bytes, c->stream));
     HIPCHK(hipMemsetAsync(r.d_boundary, 0, words * sizeof(uint32_t), c->stream));
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(c->stream, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone) HIPCHK(hipStreamSynchronize(c->stream));
+    if (!capturing(c->stream)) HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
 static int ensure_region_buffers(hml_ctx* c);   // (below)
@@ -411,7 +446,7 @@ static int launch_recorders(hml_ctx* c, hipStream_t s, uint32_t hint) {
 static uint32_t tre_default_L_old(uint32_t hint) { return hint >= (1u << 26) ? 128u : hint >= (1u << 24) ? 64u : (uint32_t)HML_TRE_MIN_L; }
 static int tre_candidates(const hml_ctx* c, uint32_t hint, uint32_t* out) {
     int n = 0;
-    if (!c->tre_rows || c->tre_slots <= 0) {
+    if (!c->knobs.tre_rows || c->tre_slots <= 0) {
         const uint32_t L0 = tre_default_L_old(hint);
         for (uint32_t q = 4; q <= 8; ++q) {   // L0 * {1, 1.25, 1.5, 1.75, 2}, multiples of 32
             const uint32_t l = L0 * q / 4u;
@@ -438,7 +473,7 @@ static int tre_candidates(const hml_ctx* c, uint32_t hint, uint32_t* out) {
     return n;
 }
 static uint32_t tre_default_L(const hml_ctx* c, uint32_t hint) {   // until the measurement: two rounds where there are blocks for them
-    if (!c->tre_rows || c->tre_slots <= 0) return tre_default_L_old(hint);
+    if (!c->knobs.tre_rows || c->tre_slots <= 0) return tre_default_L_old(hint);
     uint32_t cand[8];
     const int n = tre_candidates(c, hint, cand);
     return cand[n > 1 ? 1 : 0];
@@ -492,17 +527,18 @@ static bool many_eligible(hml_ctx* const* cs, int n, char method) {
     const hml_ctx* a = cs[0];
     for (int i = 0; i < n; ++i) {
         const hml_ctx* c = cs[i];
-        if (!c->model_set || c->device != a->device || c->K != a->K || c->T != a->T || c->D != 1 || c->compat || c->wide || !c->dynamic || !c->use_keys ||
-            c->probes || c->profiling || c->fwdL != a->fwdL || c->fwdL_many != a->fwdL_many || c->late_rescale != a->late_rescale || c->n_spans != a->n_spans)
+        if (!c->model_set || c->device != a->device || c->K != a->K || c->T != a->T || c->D != 1 || c->compat || c->wide || !c->dynamic || !c->knobs.use_keys ||
+            c->probes || c->profiling || c->knobs.geo[HML_GEO_SPARSE].L != a->knobs.geo[HML_GEO_SPARSE].L ||
+            c->knobs.geo[HML_GEO_MANY].L != a->knobs.geo[HML_GEO_MANY].L || c->knobs.late_rescale != a->knobs.late_rescale || c->n_spans != a->n_spans)
             return false;
         for (int j = 0; j < i; ++j) if (cs[j] == c) return false;
     }
     return true;
 }
-// weakly compressed sweeps (either criterion of sweep_k / launch_compact_pair) keep their own kernels: not batched
+// weakly compressed sweeps (many blocks, or the float stream: hml_sweep_plan.h) keep their own kernels: not batched
 static bool many_sparse(hml_ctx* c) {
     refresh_hint(c);
-    return !(c->B_hint >= c->dense_min_blocks) && !(!c->summary_always && c->B_hint && (uint64_t)c->B_hint * 24u > c->T);
+    return !hml_plan_many_blocks(c->knobs, c->B_hint) && !hml_plan_float_stream(c->knobs, c->T, c->B_hint);
 }
 
 

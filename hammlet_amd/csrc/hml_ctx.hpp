@@ -15,6 +15,7 @@
 #include "../../include/hml.h"
 #include "hml_host_common.hpp"
 #include "hml_state.h"
+#include "hml_sweep_plan.h"
 
 // The read-only construction of one observation trace on one device - breakpoint weights, their group summary, maxlet
 // coefficients, integral array(s) - shared by every chain that was attached to it (hml_attach_observations): the chains of a
@@ -74,10 +75,7 @@ struct hml_ctx {
     uint8_t* d_summary = nullptr;  // largest key of every 16-position group (what the scan streams)
     int32_t key_base = 0;
     double key_scale = 1.0;         // product of the weight multipliers applied so far
-    bool use_keys = true;
-    bool fused_blocks = true;       // option fused_blocks: 0 forces the scan + scatter + statistics launches
     uint64_t host_draws = 0;        // hml_categorical_draw calls so far (Philox sub-stream HOST)
-    bool summary_always = false;    // option weight_keys = 2: never fall back to the float stream (tests)
     float* d_coeff = nullptr;
     float2* d_ia = nullptr;
     // block structure
@@ -90,15 +88,12 @@ struct hml_ctx {
     DevArr<uint32_t> d_wave_total;                // split many-chain block kernels: starts per wavefront of a tile (hml_k_blocks_split_many.h)
     int fused_slots = 0;                          // workgroups of it that are resident at once (occupancy x compute units; 0: not asked yet)
     uint32_t fused_spin_limit = 4096;             // polls of a tile word before the waiting thread computes the word itself
-    bool fused_keep = false;                      // option fused_blocks = 2 (tests): keep the kernel after it reported trouble
     DevArr<unsigned long long> d_dbg;             // HML_FUSED_DEBUG: the block kernels' time stamps (hml_sync prints them)
-    // hipGraph replay of a non-recording sweep (launch-bound inner loop); re-captured when the grid hint moves
+    hml_sweep_knobs knobs;          // what steers which kernels a sweep launches (hml_sweep_plan.h)
+    // hipGraph replay of a non-recording sweep (launch-bound inner loop); re-captured when the plan or the grid hint moves
     bool use_graph = false;
     hipGraphExec_t graph_exec = nullptr;
-    char graph_method = 0;
-    uint32_t graph_hint = 0;
-    bool graph_dynamic = false, graph_valid_blocks = false;
-    bool graph_fused = false;       // the captured sweep was free to take the fused block kernel
+    struct { hml_sweep_plan plan; uint32_t hint = 0, tre_L = 0; } captured;   // what the captured sweep was recorded under
     // sweep buffers (allocated by set_model)
     DevArr<float> d_em, d_gsc, d_rows, d_eprobe, d_aprobe;
     DevArr<float> d_entry, d_exitA;
@@ -106,7 +101,6 @@ struct hml_ctx {
     DevArr<uint32_t> d_redo2;      // second list of stale chunks and the bitmap of the sequential finisher (fused trellis path)
     DevArr<uint32_t> d_tre_bitmap;
     DevArr<uint32_t> d_tre_ckpt;         // the first pass's forward vectors every 64 rows of a chunk (hml_k_trellis_rows.h): where a refit may stop
-    bool late_rescale = true;      // strongly compressed univariate sweeps: no plane of rescale factors (HML_LATE_RESCALE=0: keep it)
     uint32_t tre_L = 0;            // its chunk length (0: chosen from the number of blocks, then by measurement; HML_TRELLIS_L, option "trellis_L")
     // The best chunk length depends on how the wavefronts of hml_k_trellis_tile (64 chunks each, resident for the whole
     // launch) divide among the CUs' slots - a rounding effect no formula of ours predicted - so it is MEASURED: once the
@@ -119,15 +113,12 @@ struct hml_ctx {
     uint32_t tre_cand[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the candidate lengths of the measurement under way (frozen when it starts:
     int tre_cand_n = 0;                               // the list depends on the drifting block count)
     uint64_t tre_dense_sweeps = 0; // fused-trellis sweeps of this chain so far
-    uint32_t graph_tre_L = 0;      // chunk length of the captured sweep
+    uint32_t tre_last_L = 0;       // chunk length of the latest fused-trellis sweep
     int tre_slots = 0;             // wavefronts of hml_k_trellis_rows the device holds at once (0: not asked yet, -1: unknown)
-    bool stage_bits = true;        // weakly compressed sweeps stage block-start FLAGS between scan and scatter (HML_STAGE_BITS=0: 16-bit offsets)
     uint32_t tre_refit_rounds = 2; // parallel refit rounds before the sequential finisher (HML_TRELLIS_REFIT_ROUNDS, 0 ... 6: the rounds tag the chunks they list with 3 bits).
                                    // Four until the end of round 5: on configs 3u and 5 rounds 2-4 never had a chunk to refit in 240 sweeps and cost 9 us each
                                    // (two launches at the 4.6 us floor of a kernel in a stream; profiles/round5_refit_rounds.txt)
     bool tre_ckpt = true;          // refits stop where they meet the first pass's checkpoint again (HML_TRELLIS_CKPT=0: always the whole chunk)
-    bool tre_rows = true;          // its first pass is hml_k_trellis_rows (round 3); HML_TRELLIS_ROWS=0: hml_k_trellis_tile (round 2)
-    bool tre_fused = true;         // weakly compressed FB sweeps take the fused trellis kernels (HML_TRELLIS_FUSED=0: the separate ones)
     DevArr<uint32_t> d_touched;    // backward chunks whose rows the repair recomputed, tagged with the sweep
     DevArr<uint32_t> d_fb;
     DevArr<unsigned long long> d_smap, d_cmap;
@@ -135,7 +126,6 @@ struct hml_ctx {
     DevArr<uint8_t> d_bentry, d_bentry2;
     DevArr<int16_t> d_q;
     DevArr<double> d_partial;
-    bool params_spread = false;    // single-chain sweeps: the parameter kernel's tree over 16 workgroups (hml_k_params.h; HML_PARAMS_SPREAD)
     DevArr<int32_t> d_diff;
     DevArr<uint32_t> d_boundary;
     // the per-position recordings beside the state marginals (hml_recorder above), allocated by the first recorded sweep that wants them:
@@ -167,8 +157,8 @@ struct hml_ctx {
     uint32_t* d_hB = nullptr;       // device view of h_B (not an allocation of its own)
     uint32_t B_hint = 0;
     bool hint_stale = true;         // the hint predates the current parameters (new model, prior draw, mode switch)
-    // forward geometry
-    int fwdL = 4, fwdW = 12;   // W is the floor of the adaptive warm-up (measured: 12 beats 16 and 24 on C1-C4; 8 does not)
+    // warm-up of the forward chunks (their lengths and layouts: knobs.geo)
+    int fwdW = 12;   // W is the floor of the adaptive warm-up (measured: 12 beats 16 and 24 on C1-C4; 8 does not)
     // the warm-up policy of hml_k_params (HML_FWD_BURNIN_SWEEPS, HML_FWD_QUIET): the floor of a young chain holds for 64
     // sweeps and the warm-up shrinks by a quarter after 16 sweeps without a refit.  Measured over the first 400 sweeps
     // of configs 2 / 3 / 4 (tools/burnin_sweep.sh): 19.9 / 25.4 / 50.4 ms against 21.0 / 26.1 / 52.2 ms with (256, 32);
@@ -176,25 +166,6 @@ struct hml_ctx {
     uint32_t fwd_burnin_sweeps = 64, fwd_quiet_need = 16;
     int fwdW_init = 24;        // where a chain starts and the floor of its first fwd_burnin_sweeps sweeps: while the parameters are
                                // still far from settled the filter forgets slowly (131 refits in sweeps 20-220 of C3 with a floor of 12)
-    hml_layout lay = {2, 0};
-    // weakly compressed sweeps (B_hint >= dense_min_blocks): longer forward chunks - the warm-up is a smaller share
-    // of the work - in their own chunk-transposed layout; which geometry a sweep uses never changes its results
-    int fwdL_dense = 16;
-    hml_layout lay_dense = {4, 0};
-    // in between (B_hint >= mid_min_blocks = 2^18: 33 000 chunks of 8 still put a wavefront on every second SIMD): chunks of 8 - 32 filter
-    // steps per 8 blocks instead of 28 per 4.  Measured on config 3's trace with 8 / 10 / 12 / 16 states in the model (3.0 / 5.2 / 7.2 /
-    // 9.7 10^5 blocks per sweep): 0.188 / 0.228 / 0.489 / 0.498 -> 0.165 / 0.224 / 0.429 / 0.437 ms per sweep; with 5 states (1.8 10^5 blocks:
-    // below the threshold) chunks of 8 cost 0.063 against 0.060 ms (profiles/round5_wide_path.txt).  HML_FWD_CHUNK_MID, HML_MID_MIN_BLOCKS.
-    int fwdL_mid = 8;
-    hml_layout lay_mid = {3, 0};
-    uint32_t mid_min_blocks = 1u << 18;
-    // chains batched by hml_iterate_many are bound by throughput, not latency: chunks of 8 pay the warm-up over twice as many
-    // blocks (20 filter steps per 8 blocks instead of 16 per 4; measured with eight chains of config 3: 0.181 against 0.188 ms
-    // per round; 16 and 32 are slower again - too few wavefronts).  HML_FWD_CHUNK_MANY.
-    int fwdL_many = 8;
-    hml_layout lay_many = {3, 0};
-    uint32_t dense_min_blocks = 1u << 22;
-    bool graph_dense = false, graph_mid = false;
     bool probes = false;
     bool rec_marginals = true;
     hml_record_cb cb = nullptr;

@@ -78,7 +78,7 @@ def _fuzz(hml, n_cfg, seed, log, compat=False, wide=False, data=None):
         else: os.environ.pop("HML_FWD_WARMUP", None)
         os.environ["HML_LATE_RESCALE"] = str(int(rng.choice([1, 1, 0])))
         os.environ["HML_FWD_CHUNK"] = str(int(rng.choice([4, 4, 1, 2, 8])))
-        os.environ["HML_MID_MIN_BLOCKS"] = str(int(rng.choice([262144, 2000, 200])))   # (chunks of 8 from that many blocks on: hml_ctx.hpp)
+        os.environ["HML_MID_MIN_BLOCKS"] = str(int(rng.choice([262144, 2000, 200])))   # (chunks of 8 from that many blocks on: hml_sweep_plan.h)
         if compat or wide:   # chunks of the filter / backward draws: the default, the sequential form, many chunks with hardly any warm-up
             _setenv("HML_COMPAT_CHUNKS", rng.choice([None, None, 1, 7, 60, 500]))
             _setenv("HML_COMPAT_WARMUP", rng.choice([None, None, -1, 1, 4]))

@@ -19,8 +19,8 @@ from tests.test_gpu_parity import bits, compare_state, make_pair, setup_model
 
 pytestmark = pytest.mark.gpu
 
-DENSE_MIN = 1 << 22      # hml_ctx.hpp dense_min_blocks: the weakly compressed sweep from that many blocks on
-MID_MIN = 1 << 18        # hml_ctx.hpp mid_min_blocks: chunks of 8 from that many blocks on
+DENSE_MIN = 1 << 22      # hml_sweep_plan.h dense_min_blocks: the weakly compressed sweep from that many blocks on
+MID_MIN = 1 << 18        # hml_sweep_plan.h mid_min_blocks: chunks of 8 from that many blocks on
 TEXT_BELOW = 10 ** 6     # marginals are compared as text below that many segments, as arrays above
 REPAIR = ("forward_refits", "forward_serial", "fused_fallbacks", "buffer_growths")
 
