@@ -108,6 +108,14 @@ SIGNATURES = {
     "hml_regions_read": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_uint64), _P, _P, _P, _P, _P, _P]),
     "hml_regions_add": (C.c_int, [_P, C.c_uint64, _P, _P, _P, _P, _P, _P]),
     "hml_regions_merge": (C.c_int, [_P, _P]),
+    "hml_set_history": (C.c_int, [_P, C.c_int, C.c_uint64]),
+    "hml_history_size": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "hml_history_read": (C.c_int, [_P, C.c_uint64, C.c_uint64, _P]),
+    "hml_history_clear": (C.c_int, [_P]),
+    "hml_history_column": (C.c_char_p, [C.c_int]),
+    "hml_history_stats": (C.c_int, [_P, C.c_int, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P, C.POINTER(C.c_uint64)]),
+    "hml_history_summary": (C.c_int, [_P, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P,
+                                      C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "hml_recording_payload_size": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64)]),
     "hml_recording_export": (C.c_int, [_P, C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "hml_recording_merge_payload": (C.c_int, [_P, C.c_int, _P, C.c_uint64]),
@@ -621,6 +629,31 @@ class Chain:
         """add `other`'s region sums into this chain's (same positions, dimensions, regions and edges; any two GPUs)"""
         _check(self.lib.hml_regions_merge(self.h, other.h))
 
+    # ---- the chain's history: a row of scalars per sweep ----------------------------------------
+    def set_history(self, on=True, every=1):
+        """keep a row of HISTORY_COLUMNS per sweep whose number is a multiple of `every` (hml_set_history); turning it off and
+        on keeps the rows"""
+        _check(self.lib.hml_set_history(self.h, 1 if on else 0, int(every)))
+
+    def _history_size(self):
+        n, dropped = C.c_uint64(), C.c_uint64()
+        _check(self.lib.hml_history_size(self.h, C.byref(n), C.byref(dropped)))
+        return n.value, dropped.value
+
+    def history(self):
+        """the rows so far: float64 [n, 11], columns HISTORY_COLUMNS (hml_history_read)"""
+        n = self._history_size()[0]
+        rows = np.empty((n, HISTORY_COLS), np.float64)
+        _check(self.lib.hml_history_read(self.h, 0, n, rows.ctypes.data if n else None))
+        return rows
+
+    def history_dropped(self):
+        """rows that found the buffer full (0 unless something is wrong)"""
+        return self._history_size()[1]
+
+    def clear_history(self):
+        _check(self.lib.hml_history_clear(self.h))
+
     # ---- sparse payloads of the levels, breakpoints and bands (across GPUs) -------------------
     def recording_payload_size(self, kind):
         """bytes of the payload hml_recording_export would write now for RECORDING_LEVELS / _BREAKS / _BANDS"""
@@ -784,6 +817,51 @@ def iterate_many(chains, method, iterations, thinning=0):
 
 def _handles(chains):
     return C.cast((_P * len(chains))(*[c.h for c in chains]), _P)
+
+
+# ---- the chains' history (hml_set_history ... hml_history_summary of include/hml.h) ----
+HISTORY_COLS = 11
+HISTORY_COLUMNS = ("sweep", "method", "ll_emit", "ll_path", "lprior_theta", "lprior_path", "segments", "blocks", "states_used",
+                   "threshold", "chain")
+HISTORY_LOGLIK, HISTORY_LOGPOST = 100, 101      # ll_emit + ll_path; ... + lprior_theta + lprior_path
+
+
+def history_column(col):
+    """the name of column `col` (hml_history_column); None beyond the last"""
+    s = load_library().hml_history_column(int(col))
+    return s.decode() if s is not None else None
+
+
+def _history_result(n_chains, call):
+    rhat, ess, bad = C.c_double(), C.c_double(), C.c_uint64()
+    mean, sd = np.empty(n_chains, np.float64), np.empty(n_chains, np.float64)
+    extra = call(C.byref(rhat), C.byref(ess), mean.ctypes.data, sd.ctypes.data, C.byref(bad))
+    return dict(extra or {}, rhat=rhat.value, ess=ess.value, chain_mean=mean, chain_sd=sd, n_nonfinite=bad.value)
+
+
+def history_stats(x):
+    """split R-hat and effective sample size of one scalar over chains (hml_history_stats): x float64 [n_chains, n] (or [n]:
+    one chain) -> dict(rhat, ess, chain_mean[n_chains], chain_sd[n_chains], n_nonfinite)"""
+    x = np.ascontiguousarray(np.atleast_2d(np.asarray(x, np.float64)))
+    lib = load_library()
+
+    def call(rhat, ess, mean, sd, bad):
+        _check(lib.hml_history_stats(x.ctypes.data, x.shape[0], x.shape[1], rhat, ess, mean, sd, bad))
+    return _history_result(x.shape[0], call)
+
+
+def history_summary(chains, col, skip_sweeps=0):
+    """hml_history_stats of column `col` (an index, a name of HISTORY_COLUMNS, "loglik" or "logpost") of the chains' histories
+    (hml_history_summary): the rows with sweep <= skip_sweeps are left out, the last n_used rows of every chain are used"""
+    if isinstance(col, str):
+        col = {"loglik": HISTORY_LOGLIK, "logpost": HISTORY_LOGPOST}.get(col, HISTORY_COLUMNS.index(col) if col in HISTORY_COLUMNS else -1)
+    lib = load_library()
+    used = C.c_uint64()
+
+    def call(rhat, ess, mean, sd, bad):
+        _check(lib.hml_history_summary(_handles(chains), len(chains), int(col), int(skip_sweeps), rhat, ess, mean, sd, C.byref(used), bad))
+        return dict(n_used=used.value)
+    return _history_result(len(chains), call)
 
 
 def levels_agreement_rle(chains):

@@ -282,3 +282,20 @@ def pooled_recording(chain, kind, group=None, root=0):
                 part = part.contiguous()
                 chain.recording_merge_payload(kind, part.data_ptr(), part.numel())
     return parts
+
+
+def gathered_history(chain, group=None):
+    """One process per GPU: every rank's history rows (Chain.history(), float64 [n_r, 11]) gathered on the CPU, in rank order, on
+    every rank - a list of arrays.  The group's backend moves host tensors ("gloo"), or device tensors of the rank's GPU
+    ("nccl").  Without a process group: [chain.history()].  hammlet_amd.history_stats takes one column of the list's arrays,
+    cut to their common length: np.stack([h[-n:, col] for h in rows])."""
+    import torch
+    import torch.distributed as dist
+    rows = np.ascontiguousarray(chain.history())
+    if not (dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1):
+        return [rows]
+    raw = torch.from_numpy(rows.view(np.uint8).reshape(-1).copy())
+    if dist.get_backend(group) == "nccl":
+        raw = raw.to(torch.device("cuda", chain.device))
+    parts = gather_recording_payloads(raw, group)
+    return [p.cpu().numpy().view(np.float64).reshape(-1, rows.shape[1]) for p in parts]

@@ -1139,6 +1139,7 @@ static int sweep_compat(hml_ctx* c, char method, bool record) {
     hipLaunchKernelGGL(hml_k_compat_update, dim3(1), dim3(by_state ? 256 : 64), 0, s, c->d_mdl, mt, c->d_starts, c->d_bstat, c->d_q, mix, pl, by_state);
     if (record) { if (int r = launch_marginals(c, s, hint, /*bracket*/ false)) return r; }
     if (record) { if (int r = launch_recorders(c, s, hint)) return r; }   // (hml_k_compat_update above is this sweep's parameter update)
+    launch_history(c, method);   // (the sweep's row, where the chain keeps a history: hml_k_history.h)
     KLAUNCH_CHECK();
     return 0;
 }
@@ -1224,6 +1225,7 @@ static int sweep_wide(hml_ctx* c, char method, bool record) {
         hipLaunchKernelGGL(hml_k_wide_params, dim3(1), dim3(1024), 0, s, c->d_mdl, c->d_partial, c->d_wacc.as<hml_wide_acc>(), 0);
     }
     if (record) { if (int r = launch_recorders(c, s, hint)) return r; }   // (after the update: hml_k_levels.h)
+    launch_history(c, method);   // (the sweep's row, where the chain keeps a history: hml_k_history.h)
     KLAUNCH_CHECK();
     return 0;
 }
@@ -1294,6 +1296,7 @@ int hml_iterate(hml_ctx* c, char method, uint64_t iterations, uint64_t thinning)
     if (int r = ctx_bind(c)) return r;
     c->call_base = c->requested;
     if (int r = pooled_refusal(c, thinning > 0 && thinning <= iterations, "this context")) return r;   // (before anything is enqueued: a sweep is not abandoned half-way)
+    if (int r = hml_history_ensure(c, iterations)) return r;   // (room for the rows of this call, before anything is enqueued)
     for (uint64_t i = 0; i < iterations; ++i) {
         const bool record = thinning > 0 && ((i + 1) % thinning == 0);
         // a chain with a reduced block capacity that halted (hml_state.h): larger buffers, the skipped sweeps again - then on
@@ -1316,6 +1319,8 @@ extern "C" int hml_iterate_many(hml_ctx* const* cs, int n, char method, uint64_t
     for (int i = 0; i < n; ++i) if (!cs[i] || !cs[i]->model_set) return set_err(HML_ERR_ARG, "model not set");
     if (method != HML_METHOD_FB && method != HML_METHOD_MIXTURE) return set_err(HML_ERR_ARG, std::string("Unknown sampling type ") + method + "!");
     for (int i = 0; i < n; ++i) cs[i]->call_base = cs[i]->requested;
+    // room for the rows of this call in every chain that keeps a history - the batches and the chain-by-chain tail - before anything is enqueued
+    for (int i = 0; i < n; ++i) if (cs[i]->hist.on) { if (int r = ctx_bind(cs[i])) return r; if (int r = hml_history_ensure(cs[i], iterations)) return r; }
     uint64_t done = 0;
     while (done < iterations && many_eligible(cs, n, method)) {
         if (int r = ctx_bind(cs[0])) return r;

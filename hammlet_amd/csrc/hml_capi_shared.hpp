@@ -418,6 +418,20 @@ __attribute__((visibility("hidden"))) void hml_regions_launch(hml_ctx* c, hipStr
 static int ensure_region_buffers(hml_ctx* c) { return hml_regions_ensure(c); }
 static void launch_region_kernels(hml_ctx* c, hipStream_t s, uint32_t hint, bool bracket) { hml_regions_launch(c, s, hint, bracket); }
 
+// ---- the chain's history (hml_history, hml_ctx.hpp; hml_k_history.h) ----
+// hml_readout.hip, in that ONE object like the regions: room for the rows of `iterations` further sweeps, made on the host
+// before anything is enqueued (a larger buffer drops the captured graph), and the one launch behind a sweep's parameter
+// update, on stream `s`.
+__attribute__((visibility("hidden"))) int hml_history_ensure(hml_ctx* c, uint64_t iterations);
+__attribute__((visibility("hidden"))) void hml_history_launch(hml_ctx* c, hipStream_t s, char method);
+static inline bool history_due(const hml_ctx* c) { return c->hist.on && c->hist.d_buf; }
+// ... behind the update and the recorders of a sweep on the context's own stream; nothing without a history
+static inline void launch_history(hml_ctx* c, char method) {
+    if (!history_due(c)) return;
+    ProfScope ps(c, "history");
+    hml_history_launch(c, c->stream, method);
+}
+
 // the record kernels of a recorded sweep, on stream `s`, BEHIND the sweep's parameter update: the level (and its band) is mu
 // under the theta that hml_get_theta returns inside the sweep's record callback; the breakpoint kernel reads the sweep's
 // states and block starts only

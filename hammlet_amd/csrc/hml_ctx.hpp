@@ -56,6 +56,17 @@ struct hml_regions {
     DevBuf d_chunks;                  // chunk totals of a recorded sweep, sized by T (hml_regions_chunks)
 };
 
+// The chain's history (hml_set_history; hml_k_history.h): a row of scalars per due sweep, written on the device behind the
+// sweep's parameter update.  The host sizes the buffer ahead of the sweeps it enqueues and never looks at it in between.
+struct hml_history {
+    bool on = false;                  // sweeps launch the history kernel
+    uint64_t every = 1;               // a sweep is due when the chain's sweep counter is a multiple of it
+    DevBuf d_buf;                     // hml_history_head, then `cap` rows of HML_HISTORY_COLS doubles
+    uint64_t cap = 0;                 // rows the buffer holds
+    uint64_t expected = 0;            // rows it holds once everything enqueued has run (never less than that)
+    uint64_t grown = 0;               // times it was replaced by a larger one
+};
+
 struct hml_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -136,6 +147,7 @@ struct hml_ctx {
     //                   nothing recorded: one segment of zeros
     hml_recorder rec[HML_REC_KINDS];
     hml_regions rg;
+    hml_history hist;
     int n_band_edges = 0;           // the bands' edges last set (they stay when the recording is turned off)
     float band_edges[31] = {};
     DevArr<hml_model> d_mdl;

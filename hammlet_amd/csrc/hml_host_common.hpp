@@ -7,6 +7,7 @@
 #include <atomic>
 #include <cstdint>
 #include <string>
+#include <utility>
 
 #include "../../include/hml.h"
 
@@ -52,6 +53,7 @@ public:
         hml_dev_live_bytes -= bytes_; hml_dev_live_allocations--;
         p_ = nullptr; bytes_ = 0;
     }
+    void swap(DevBuf& o) { std::swap(p_, o.p_); std::swap(bytes_, o.bytes_); }   // (both stay counted: nothing is allocated or freed)
     explicit operator bool() const { return p_ != nullptr; }
     void* get() const { return p_; }
     template <class T> T* as() const { return static_cast<T*>(p_); }

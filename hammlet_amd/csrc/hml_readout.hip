@@ -1054,3 +1054,170 @@ int hml_recording_merge_across(hml_ctx* dst, hml_ctx* src, int kind) {
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------- history (hml_k_history.h)
+// A row of scalars per due sweep, written on the device behind the sweep's parameter update.  The host only makes room ahead
+// of the sweeps it enqueues, and reads the rows when asked.
+#include "hml_k_history.h"   // (launched from this object alone)
+#include "hml_history_stats.h"
+
+static_assert(HML_HIST_COLS == HML_HISTORY_COLS, "the kernel's row and the C ABI's");
+static const char* const hml_history_columns[HML_HISTORY_COLS] = {"sweep", "method", "ll_emit", "ll_path", "lprior_theta", "lprior_path",
+                                                                  "segments", "blocks", "states_used", "threshold", "chain"};
+static uint64_t history_bytes(uint64_t cap) { return sizeof(hml_history_head) + cap * HML_HISTORY_COLS * sizeof(double); }
+
+// the buffer's head as the device holds it (the context's device is current; the caller has settled the chain)
+static int history_head(hml_ctx* c, hml_history_head* h) {
+    memset(h, 0, sizeof *h);
+    if (!c->hist.d_buf) return 0;
+    HIPCHK(hipMemcpyAsync(h, c->hist.d_buf.get(), sizeof *h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// Room for the rows of `iterations` further sweeps: rows present + iterations / every + 1, at least.  `expected` counts the
+// rows the sweeps enqueued so far will have left (the chain's sweep counter is `requested` once they have run), so a call that
+// finds room adds no synchronisation.  Without room the stream is waited for, the count is taken from the device, and a
+// buffer of twice the size (or what is needed) takes the rows over, device to device; the captured graph holds the old one.
+int hml_history_ensure(hml_ctx* c, uint64_t iterations) {
+    hml_history& hs = c->hist;
+    if (!hs.on) return 0;
+    const uint64_t every = hs.every ? hs.every : 1;
+    const uint64_t due = (c->requested + iterations) / every - c->requested / every;
+    if (hs.d_buf && hs.expected + iterations / every + 1 <= hs.cap) { hs.expected += due; return 0; }
+    hml_history_head head;
+    memset(&head, 0, sizeof head);
+    if (hs.d_buf) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        // (a halted chain's skipped sweeps run again later and write behind what is there: they are counted in `expected`)
+        if (!chain_halted(c)) {
+            if (int r = history_head(c, &head)) return r;
+            hs.expected = head.n_rows;
+            if (hs.expected + iterations / every + 1 <= hs.cap) { hs.expected += due; return 0; }
+        }
+    }
+    const uint64_t need = hs.expected + iterations / every + 1;
+    const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(2 * hs.cap, need), 16);
+    DevBuf nb;
+    HIPCHK(nb.alloc(history_bytes(cap)));
+    if (hs.d_buf) HIPCHK(hipMemcpyAsync(nb.get(), hs.d_buf.get(), history_bytes(hs.cap), hipMemcpyDeviceToDevice, c->stream));
+    else HIPCHK(hipMemsetAsync(nb.get(), 0, sizeof(hml_history_head), c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));   // (chains batched by hml_iterate_many run on their group's stream; the old buffer goes below)
+    if (hs.d_buf) hs.grown++;
+    hs.d_buf.swap(nb);
+    hs.cap = cap;
+    hs.expected += due;
+    drop_graph(c);
+    return 0;
+}
+
+void hml_history_launch(hml_ctx* c, hipStream_t s, char method) {
+    hipLaunchKernelGGL(hml_k_history, dim3(1), dim3(64), 0, s, c->d_mdl.get(), c->d_q.get(), c->hist.d_buf.as<hml_history_head>(),
+                       (unsigned long long)c->hist.cap, (unsigned long long)(c->hist.every ? c->hist.every : 1), method == HML_METHOD_MIXTURE ? 1 : 0, c->chain);
+}
+
+// every row of a context, on the host
+static int history_fetch(hml_ctx* c, std::vector<double>& rows, uint64_t* n_rows, uint64_t* n_dropped) {
+    if (!c) return set_err(HML_ERR_ARG, "null context");
+    rows.clear();
+    *n_rows = 0;
+    if (n_dropped) *n_dropped = 0;
+    if (!c->hist.d_buf) return 0;
+    if (int r = ctx_bind(c)) return r;
+    if (int r = hml_settle(c)) return r;
+    hml_history_head head;
+    if (int r = history_head(c, &head)) return r;
+    const uint64_t n = std::min<uint64_t>(head.n_rows, c->hist.cap);
+    rows.resize(n * HML_HISTORY_COLS);
+    if (n) HIPCHK(hipMemcpy(rows.data(), c->hist.d_buf.as<char>() + sizeof(hml_history_head), n * HML_HISTORY_COLS * sizeof(double), hipMemcpyDeviceToHost));
+    *n_rows = n;
+    if (n_dropped) *n_dropped = head.dropped;
+    return 0;
+}
+
+extern "C" {
+
+int hml_set_history(hml_ctx* c, int on, uint64_t every) {
+    if (!c) return set_err(HML_ERR_ARG, "null context");
+    if (on && every < 1) return set_err(HML_ERR_ARG, "hml_set_history: every must be at least 1");
+    if (c->model_set || c->graph_exec) {
+        if (int r = ctx_bind(c)) return r;
+        // (sweeps a halted chain skipped run again under the setting they were enqueued with)
+        if (c->model_set) { if (int r = settle_if_limited(c)) return r; }
+        drop_graph(c);   // a captured sweep holds the launch, or lacks it
+    }
+    c->hist.on = on != 0;
+    if (on) c->hist.every = every;
+    return 0;
+}
+
+int hml_history_size(hml_ctx* c, uint64_t* n_rows, uint64_t* n_dropped) {
+    if (!c) return set_err(HML_ERR_ARG, "null context");
+    if (n_rows) *n_rows = 0;
+    if (n_dropped) *n_dropped = 0;
+    if (!c->hist.d_buf) return 0;
+    if (int r = ctx_bind(c)) return r;
+    if (int r = hml_settle(c)) return r;
+    hml_history_head head;
+    if (int r = history_head(c, &head)) return r;
+    if (n_rows) *n_rows = std::min<uint64_t>(head.n_rows, c->hist.cap);
+    if (n_dropped) *n_dropped = head.dropped;
+    return 0;
+}
+
+int hml_history_read(hml_ctx* c, uint64_t first, uint64_t n, double* rows) {
+    if (!c) return set_err(HML_ERR_ARG, "null context");
+    if (n == 0) return 0;
+    if (!rows) return set_err(HML_ERR_ARG, "null argument");
+    uint64_t have = 0;
+    if (int r = hml_history_size(c, &have, nullptr)) return r;
+    if (first > have || n > have - first) return set_err(HML_ERR_ARG, "hml_history_read: rows beyond the " + std::to_string(have) + " the history holds");
+    HIPCHK(hipMemcpy(rows, c->hist.d_buf.as<char>() + sizeof(hml_history_head) + first * HML_HISTORY_COLS * sizeof(double), n * HML_HISTORY_COLS * sizeof(double),
+                     hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int hml_history_clear(hml_ctx* c) {
+    if (!c) return set_err(HML_ERR_ARG, "null context");
+    c->hist.expected = 0;
+    if (!c->hist.d_buf) return 0;
+    if (int r = ctx_bind(c)) return r;
+    if (int r = hml_settle(c)) return r;
+    HIPCHK(hipMemsetAsync(c->hist.d_buf.get(), 0, sizeof(hml_history_head), c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+const char* hml_history_column(int col) { return col >= 0 && col < HML_HISTORY_COLS ? hml_history_columns[col] : nullptr; }
+
+int hml_history_stats(const double* x, int n_chains, uint64_t n, double* rhat, double* ess, double* chain_mean, double* chain_sd, uint64_t* n_nonfinite) {
+    const char* why = nullptr;
+    if (hml_history_stats_compute(x, n_chains, n, rhat, ess, chain_mean, chain_sd, n_nonfinite, &why)) return set_err(HML_ERR_ARG, why ? why : "history statistics");
+    return 0;
+}
+
+int hml_history_summary(hml_ctx* const* ctxs, int n, int col, uint64_t skip_sweeps, double* rhat, double* ess, double* chain_mean, double* chain_sd,
+                        uint64_t* n_used, uint64_t* n_nonfinite) {
+    if (!ctxs || n < 1) return set_err(HML_ERR_ARG, "no contexts");
+    if (!((col >= 0 && col < HML_HISTORY_COLS) || col == HML_HISTORY_LOGLIK || col == HML_HISTORY_LOGPOST))
+        return set_err(HML_ERR_ARG, "hml_history_summary: a column 0 ... 10, HML_HISTORY_LOGLIK or HML_HISTORY_LOGPOST");
+    std::vector<std::vector<double>> series((size_t)n);
+    uint64_t used = ~0ull;
+    for (int k = 0; k < n; ++k) {
+        std::vector<double> rows;
+        uint64_t have = 0;
+        if (int r = history_fetch(ctxs[k], rows, &have, nullptr)) return r;
+        for (uint64_t i = 0; i < have; ++i) {
+            const double* row = rows.data() + i * HML_HISTORY_COLS;
+            if (!(row[0] > (double)skip_sweeps)) continue;
+            series[k].push_back(col == HML_HISTORY_LOGLIK ? row[2] + row[3] : col == HML_HISTORY_LOGPOST ? ((row[2] + row[3]) + row[4]) + row[5] : row[col]);
+        }
+        used = std::min<uint64_t>(used, series[k].size());
+    }
+    if (n_used) *n_used = used;
+    std::vector<double> x((size_t)n * used);
+    for (int k = 0; k < n; ++k) std::copy(series[k].end() - (ptrdiff_t)used, series[k].end(), x.begin() + (ptrdiff_t)((uint64_t)k * used));
+    return hml_history_stats(x.data(), n, used, rhat, ess, chain_mean, chain_sd, n_nonfinite);
+}
+
+}  // extern "C"

@@ -265,6 +265,7 @@ static int sweep_k(hml_ctx* c, char method, bool record) {
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_params<KK>), dim3(1), dim3(1024), 0, e.s, c->d_mdl, c->d_partial, 0);
     }
     if (record) { if (int r = launch_recorders(c, e.s, hint)) return r; }   // (after the update: hml_k_levels.h)
+    launch_history(c, method);   // (the sweep's row, where the chain keeps a history: hml_k_history.h)
     KLAUNCH_CHECK();
     return 0;
 }
@@ -443,6 +444,7 @@ static int iterate_many_k(hml_ctx* const* cs, int n, uint64_t first, uint64_t it
             if (record) for (int kind = 0; kind < HML_REC_KINDS; ++kind)
                 for (int k = g0; k < g0 + gn; ++k) if (cs[k]->rec[kind].on) launch_record_kernel(cs[k], kind, s, dim3(gB));
             if (record) for (int k = g0; k < g0 + gn; ++k) if (cs[k]->rg.on) launch_region_kernels(cs[k], s, hint, /*bracket*/ false);   // (and their regions: hml_k_regions.h)
+            for (int k = g0; k < g0 + gn; ++k) if (history_due(cs[k])) hml_history_launch(cs[k], s, HML_METHOD_FB);   // (every sweep's row: hml_k_history.h)
         }
         KLAUNCH_CHECK();
         if (record) {

@@ -80,7 +80,17 @@ static const char* kHelp =
     "                                 region's mean level, with -bands per data dimension and band the sweeps in which the\n"
     "                                 whole region lay in that band, then the label; one line per region, in file order.\n"
     "                                 With -chains N the chains are added up, on one GPU or several (extension)\n"
-    "  -w, -overwrite                 allow overwriting output files\n"
+    "                    H            history: a header line, then per sweep (see -history-every) and chain, tab-separated: sweep,\n"
+    "                                 method (0 F, 1 M), ll_emit, ll_path, lprior_theta, lprior_path, segments, blocks, states_used,\n"
+    "                                 threshold, chain - the state after the sweep's parameter update; ll_emit + ll_path is the\n"
+    "                                 complete-data log-likelihood of the compressed model, what to plot against the sweep number to\n"
+    "                                 see burn-in and whether the chains sit in one mode (extension)\n"
+    "                    HS           historysummary: for loglik, logpost, segments and blocks a line NAME all RHAT ESS ROWS NONFINITE -\n"
+    "                                 split R-hat and effective sample size over the chains of -chains N, on any GPUs - and a line\n"
+    "                                 NAME CHAIN MEAN SD per chain.  R-hat well above 1, or a chain whose mean loglik lies far below\n"
+    "                                 the others: the chains have not reached the same mode, and what -chains N adds up mixes\n"
+    "                                 them (extension; see -history-skip)\n"
+    "  -w, -overwrite                allow overwriting output files\n"
     "  -s, -states K | C P D          number of states (default 3), or P parameters shared by P^D states over D dimensions\n"
     "  -e, -emissions normal VAR P    automatic prior: P(variance < VAR) = P (default normal 0.2 0.9)\n"
     "  -a, -auto-priors               (required) derive emission priors from the data\n"
@@ -106,6 +116,9 @@ static const char* kHelp =
     "  -regions FILE                  the regions of -O RG, one per line: start end [label ...], positions counted from 0, the\n"
     "                                 end not included; lines that begin with # and blank lines are skipped.  Regions may\n"
     "                                 overlap, nest and repeat (extension)\n"
+    "  -history-every N               -O H, HS: a row for every N-th sweep (default 1) (extension)\n"
+    "  -history-skip S                -O HS: leave out the rows of the first S sweeps (default: the first half of the scheme's\n"
+    "                                 sweeps) (extension)\n"
     "  -chains N                      N independent chains, one per GPU, marginals pooled over RCCL (extension);\n"
     "                                 chains beyond the number of GPUs share a GPU and the construction it holds.\n"
     "                                 The pooled marginals / maxsegmentation files use common labels (states by\n"
@@ -140,6 +153,8 @@ struct Job {
     vector<uint32_t> regionStart, regionEnd;   // -regions FILE (recorded when -O RG asks for them)
     vector<string> regionLabel;
     vector<float> regionEdges;       // ... and their edges: those of -bands
+    uint64_t historyEvery = 1;       // -history-every N (-O H, HS)
+    uint64_t historySkip = 0;        // -history-skip S
 };
 
 // Meeting point of the chain threads of `-chains N` and the main thread: a chain arrives with its context once its
@@ -491,6 +506,14 @@ static void writeContextFiles(const Job& job, hml_ctx* ctx) {
     if (job.outputs.at("regions")) writeRegions(job, ctx);
 }
 
+static string historyFileName(const Job& job) { return job.opref + "history" + job.osuff; }
+static string historySummaryFileName(const Job& job) { return job.opref + "historysummary" + job.osuff; }
+// the chains' histories, in chain order (hammlet/History.hpp): read through the host, whichever GPUs the chains are on
+static void writeHistoryFiles(const Job& job, const vector<hml_ctx*>& ctxs) {
+    if (job.outputs.at("history")) History::writeFile(historyFileName(job), ctxs);
+    if (job.outputs.at("historysummary")) History::writeSummaryFile(historySummaryFileName(job), ctxs, job.historySkip);
+}
+
 // One chain from its device context to its output files.  `index` > 0 (chains of `-chains N` beyond the first): the
 // per-sweep side files carry the infix "chainK." and the (pooled) marginals are left to chain 0.
 // `source` (chains sharing a GPU): the context whose construction this chain attaches to (nullptr: it builds its own).
@@ -552,6 +575,7 @@ struct ChainRun {
         if (job.outputs.at("regions"))   // the joint posteriors over the regions of -regions, under the edges of -bands (include/hml.h)
             hml_check(hml_set_regions(RNG.ctx(), job.regionStart.size(), job.regionStart.data(), job.regionEnd.data(), (int)job.regionEdges.size(),
                                       job.regionEdges.empty() ? nullptr : job.regionEdges.data()));
+        if (job.outputs.at("history") || job.outputs.at("historysummary")) History(RNG.ctx()).enable(job.historyEvery);   // a row per sweep from here on
         if (verbose) cout << "Setting block structure to dynamic" << endl << flush;
     }
     // a token of the scheme up to (not including) the sweeps of "F" / "M" (reference main.cpp:383-452): a pending prior draw
@@ -598,6 +622,7 @@ static void runChain(const Job& job, vector<real_t>& inputValues, bool steal, in
         if (run.token(st)) run.sweeps(st);
     hml_check(hml_sync(run.RNG.ctx()));
     if (!rendezvous) writeContextFiles(job, run.RNG.ctx());   // (several chains: the main thread merges and writes)
+    if (!rendezvous) writeHistoryFiles(job, {run.RNG.ctx()});
     if (rendezvous && !rendezvous->arrive(index, run.RNG.ctx())) run.records.discardMarginals();   // pooling failed elsewhere
     run.records.close();
 }
@@ -674,6 +699,8 @@ int main(int argc, const char* argv[]) {
         args.registerFlags({"-bandcall"}, "0");
         args.registerFlags({"-merge-gpus"});
         args.registerFlags({"-regions"});
+        args.registerFlags({"-history-every"}, "1");
+        args.registerFlags({"-history-skip"});
         args.parseArgs();
 
         if (args.isSet("-g")) args.print();
@@ -761,6 +788,8 @@ int main(int argc, const char* argv[]) {
         outputArgs.registerFlags({"LC", "bandcalls"});        // extension
         outputArgs.registerFlags({"R", "rhat"});              // extension
         outputArgs.registerFlags({"RG", "regions"});          // extension
+        outputArgs.registerFlags({"H", "history"});           // extension
+        outputArgs.registerFlags({"HS", "historysummary"});   // extension
         outputArgs.parseArgs();
 
         // ---- input
@@ -833,7 +862,7 @@ int main(int argc, const char* argv[]) {
         job.weightMultiplier = weightMultiplier; job.useSelfTrans = useSelfTrans;
         job.thetaParams = thetaParams; job.trans = trans; job.selfTrans = selfTrans; job.initialAlpha = initialAlpha;
         job.scheme = scheme;
-        for (const char* o : {"sequences", "parameters", "blocks", "compression", "marginals", "segments", "maxsegmentation", "levels", "breakpoints", "consensus", "bands", "bandcalls", "rhat", "regions"})
+        for (const char* o : {"sequences", "parameters", "blocks", "compression", "marginals", "segments", "maxsegmentation", "levels", "breakpoints", "consensus", "bands", "bandcalls", "rhat", "regions", "history", "historysummary"})
             job.outputs[o] = outputArgs.isSet(o);
         auto refuseExisting = [&](const string& fn) {
             if (!overwrite) { std::ifstream probe(fn); if (probe.good()) throw std::runtime_error("File " + fn + " already exists! Use -w to allow overwrite!"); }
@@ -879,6 +908,24 @@ int main(int argc, const char* argv[]) {
             readRegions(args.parse<string>("-regions"), T, job);
         }
         if (wantsRegions) refuseExisting(regionsFileName(job));
+        // the chains' history (include/hml.h): a row every -history-every sweeps; the summary leaves out the first -history-skip sweeps
+        const bool wantsHistory = job.outputs.at("history") || job.outputs.at("historysummary");
+        if (wantsHistory) {
+            const double every = args.parse<double>("-history-every", 0);
+            if (!(every >= 1 && every <= 4294967295.0) || every != std::floor(every)) throw std::runtime_error("The argument of -history-every must be a whole number of sweeps, at least 1!");
+            job.historyEvery = (uint64_t)every;
+            uint64_t total = 0;
+            for (const Step& st : scheme) total += st.iterations;
+            job.historySkip = total / 2;
+            if (args.isSet("-history-skip")) {
+                if (args.nrTokens("-history-skip") != 1) throw std::runtime_error("Not enough arguments for flag -history-skip!");
+                const double skip = args.parse<double>("-history-skip", 0);
+                if (!(skip >= 0 && skip <= 1.8e19) || skip != std::floor(skip)) throw std::runtime_error("The argument of -history-skip must be a whole number of sweeps!");
+                job.historySkip = (uint64_t)skip;
+            }
+            if (job.outputs.at("history")) refuseExisting(historyFileName(job));
+            if (job.outputs.at("historysummary")) refuseExisting(historySummaryFileName(job));
+        }
         if (job.outputs.at("bands")) refuseExisting(bandsFileName(job));
         if (job.outputs.at("bandcalls")) refuseExisting(bandCallsFileName(job));
         if (job.outputs.at("levels")) refuseExisting(levelsFileName(job));
@@ -980,6 +1027,9 @@ int main(int argc, const char* argv[]) {
                     if (wantsRegions) for (int k = 1; k < nrChains; ++k) hml_check(hml_regions_merge(ctxs[0], ctxs[k]));
                     writeContextFiles(job, ctxs[0]);
                 } catch (...) { poolError = std::current_exception(); }
+            }
+            if ((int)ctxs.size() == nrChains && wantsHistory && !poolError) {
+                try { writeHistoryFiles(job, ctxs); } catch (...) { poolError = std::current_exception(); }
             }
             rv.release(poolError == nullptr && (int)ctxs.size() == nrChains);
             for (auto& t : threads) t.join();

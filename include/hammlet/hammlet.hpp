@@ -617,6 +617,7 @@ template <> inline char StateSequence<Mixture>::method() { return HML_METHOD_MIX
 }  // namespace hammlet
 
 #include "Records.hpp"
+#include "History.hpp"
 
 namespace hammlet {
 

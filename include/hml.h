@@ -422,6 +422,61 @@ int hml_regions_add(hml_ctx* ctx, uint64_t n_recorded, const uint64_t* whole, co
  * two contexts may lie on any two devices.  `src` is unchanged and `dst` may go on recording. */
 int hml_regions_merge(hml_ctx* dst, hml_ctx* src);
 
+/* ---- the chain's history: a row of scalars per sweep, and convergence diagnostics over chains.  No counterpart in the
+ * reference. ----
+ * Every read-out above assumes that the chains behind it have converged to the same mode; the history is what shows whether
+ * they have: a scalar to plot against the sweep number, a burn-in to read off, R-hat and an effective sample size over chains.
+ * A row is the state of the chain AFTER a sweep - the sweep's states q through the counts hml_get_counts returns (transition
+ * counts N(i,j), occupancies n(s), float sums Sx(p), Sxx(p): the numbers the conjugate update used) under the theta, A and pi
+ * that the sweep's update drew - as HML_HISTORY_COLS doubles:
+ *    0 sweep         the chain's sweep counter after this sweep
+ *    1 method        0: forward-backward sweep, 1: mixture sweep
+ *    2 ll_emit       -sum_p [ n_p/2 log(2 pi var_p) + (Sxx_p - 2 mu_p Sx_p + n_p mu_p^2) / (2 var_p) ],  n_p the (position,
+ *                    dimension) terms of parameter p: n(p) for D = 1, sum_s n(s) #{d: map[s][d] = p} for "-s C P D"
+ *    3 ll_path       FB: log pi[first state] + sum_ij N(i,j) log A(i,j);  mixture: sum_s n(s) log pi(s)
+ *    4 lprior_theta  sum_p [ -(alpha + 1) log var_p - beta / var_p - 1/2 log var_p - nu (mu_p - mu0)^2 / (2 var_p) ]
+ *    5 lprior_path   sum_ij (a_ij - 1) log A(i,j) + (pi_alpha - 1) sum_s log pi(s)       (constants dropped in 4 and 5)
+ *    6 segments      1 + sum_{i != j} N(i,j)
+ *    7 blocks        blocks of the sweep
+ *    8 states_used   #{s: n(s) > 0}
+ *    9 threshold     the wavelet threshold after the update
+ *   10 chain         the context's chain_id
+ * N is what the sweep's count pass left, mixture sweeps included; like the reference it starts from state 0, so N holds one
+ * transition from state 0 into the first block (and `segments` is one more than the runs of equal state when the first block is
+ * not in state 0).  The threshold is the one of the theta just drawn - what the next sweep's enumeration uses.
+ * 2 + 3 is the COMPLETE-DATA log-likelihood of the compressed model (states given), not the marginal likelihood of the
+ * filter.  All arithmetic is in double on exactly widened floats, sums in a fixed order: the same chain gives the same bits
+ * on every run and behind every sweep path, hml_iterate_many and graph replay included.  A product whose count (or whose
+ * coefficient a - 1) is 0 is 0; everything else is stored as IEEE gives it - lprior_path is +inf when a Dirichlet draw
+ * underflowed to 0 under a_off < 1.
+ *
+ * hml_set_history turns the history on or off for the sweeps enqueued from now on; sweep s leaves a row when s is a multiple of
+ * `every` (>= 1).  Turning it off and on keeps the rows.  A sweep then launches one more small kernel behind its parameter
+ * update; with the history off a sweep launches exactly what it launches without this section.  The rows stay on the device -
+ * the buffer grows on the host before a call enqueues anything - until they are read; n_dropped counts rows that found no
+ * room (0 unless something is wrong).  hml_history_read copies rows [first, first + n). */
+#define HML_HISTORY_COLS 11
+#define HML_HISTORY_LOGLIK 100    /* columns 2 + 3 */
+#define HML_HISTORY_LOGPOST 101   /* columns 2 + 3 + 4 + 5 */
+int hml_set_history(hml_ctx* ctx, int on, uint64_t every);
+int hml_history_size(hml_ctx* ctx, uint64_t* n_rows, uint64_t* n_dropped);
+int hml_history_read(hml_ctx* ctx, uint64_t first, uint64_t n, double* rows /* n * HML_HISTORY_COLS */);
+int hml_history_clear(hml_ctx* ctx);
+const char* hml_history_column(int col);   /* "sweep", "method", ...; NULL beyond */
+/* Diagnostics of one scalar over chains, x[c * n + i] (host arrays).  Every chain is split in halves (n odd: the middle value
+ * is dropped): m = 2 n_chains sequences of length h = n / 2; W = the mean of their sample variances (divisor h - 1),
+ * B = h / (m - 1) sum_j (mean_j - mean)^2, var+ = (h - 1) / h W + B / h, R-hat = sqrt(var+ / W);
+ * rho_t = 1 - (W - mean_j acov_j(t)) / var+ (acov with divisor h), P_0 = 1 + rho_1, P_k = rho_2k + rho_2k+1, summed until the
+ * first P_k < 0 or 2 k + 1 > h - 1 with P_k replaced by min(P_k, P_k-1), tau = -1 + 2 sum P_k, ESS = m h / tau.
+ * Values that are not finite are counted in n_nonfinite and make R-hat and ESS not-a-number; chain_mean and chain_sd are taken
+ * over the finite ones.  A constant series gives not-a-number twice.  h < 4: HML_ERR_ARG.  Any output may be NULL. */
+int hml_history_stats(const double* x, int n_chains, uint64_t n, double* rhat, double* ess, double* chain_mean /*n_chains*/,
+                      double* chain_sd /*n_chains*/, uint64_t* n_nonfinite);
+/* The same from contexts (any devices of this process): column `col`, or HML_HISTORY_LOGLIK / HML_HISTORY_LOGPOST; the rows with
+ * sweep <= skip_sweeps are left out and the last n_used = min over the chains of the rows that remain are used of each. */
+int hml_history_summary(hml_ctx* const* ctxs, int n, int col, uint64_t skip_sweeps, double* rhat, double* ess, double* chain_mean /*n*/,
+                        double* chain_sd /*n*/, uint64_t* n_used, uint64_t* n_nonfinite);
+
 /* ---- sparse payloads: levels, breakpoints and bands across GPUs.  No counterpart in the reference. ----
  * The three recordings above keep a cell and a boundary bit per change of state, so what another GPU needs of one is a list:
  * the M positions with a cell and the cells there.  The PAYLOAD is one contiguous buffer in device memory, little endian,
