@@ -116,6 +116,10 @@ SIGNATURES = {
     "hml_history_stats": (C.c_int, [_P, C.c_int, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P, C.POINTER(C.c_uint64)]),
     "hml_history_summary": (C.c_int, [_P, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P,
                                       C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "hml_viterbi": (C.c_int, [_P, C.POINTER(C.c_uint64), _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    "hml_viterbi_states": (C.c_int, [_P, _P]),
+    "hml_viterbi_scores": (C.c_int, [_P, _P, _P, _P]),
+    "hml_viterbi_info": (C.c_int, [_P] + [C.POINTER(C.c_uint64)] * 6),
     "hml_recording_payload_size": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64)]),
     "hml_recording_export": (C.c_int, [_P, C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "hml_recording_merge_payload": (C.c_int, [_P, C.c_int, _P, C.c_uint64]),
@@ -653,6 +657,36 @@ class Chain:
 
     def clear_history(self):
         _check(self.lib.hml_history_clear(self.h))
+
+    # ---- Viterbi decode: the most probable path under the current parameters ------------------
+    def viterbi(self):
+        """(run_len[R], run_state[R], score): the jointly most probable state path over the current blocks under the current
+        parameters, adjacent blocks of equal state merged (hml_viterbi); score = (score_fixed, score in nats)"""
+        n, fixed, nats = C.c_uint64(), C.c_int64(), C.c_double()
+        _check(self.lib.hml_viterbi(self.h, C.byref(n), None, None, None, None))
+        ln = np.empty(n.value, np.uint64)
+        st = np.empty(n.value, np.int32)
+        _check(self.lib.hml_viterbi(self.h, C.byref(n), ln.ctypes.data, st.ctypes.data, C.byref(fixed), C.byref(nats)))
+        return ln, st, (fixed.value, nats.value)
+
+    def viterbi_states(self):
+        """the same path per block, int16 [B] (hml_viterbi_states)"""
+        q = np.empty(self.num_blocks(), np.int16)
+        _check(self.lib.hml_viterbi_states(self.h, q.ctypes.data))
+        return q
+
+    def viterbi_scores(self):
+        """(emit[B, K], trans[K, K], init[K]), int64 in units of 2^-20 nat: the tables a decode uses (hml_viterbi_scores)"""
+        B, K = self.num_blocks(), self.K
+        emit, trans, init = np.empty((B, K), np.int64), np.empty((K, K), np.int64), np.empty(K, np.int64)
+        _check(self.lib.hml_viterbi_scores(self.h, emit.ctypes.data, trans.ctypes.data, init.ctypes.data))
+        return emit, trans, init
+
+    def viterbi_info(self):
+        """of the last decode: dict(chunks, L, W, stale_chunks, rounds, serial_chunks) (hml_viterbi_info)"""
+        v = [C.c_uint64() for _ in range(6)]
+        _check(self.lib.hml_viterbi_info(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("chunks", "L", "W", "stale_chunks", "rounds", "serial_chunks"), (x.value for x in v)))
 
     # ---- sparse payloads of the levels, breakpoints and bands (across GPUs) -------------------
     def recording_payload_size(self, kind):

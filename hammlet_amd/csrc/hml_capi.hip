@@ -1403,6 +1403,17 @@ int hml_set_option(hml_ctx* c, const char* name, int value) {
         c->tre_L = (uint32_t)value;
         return 0;
     }
+    // the Viterbi decode's launch geometry (hml_k_viterbi.h): never part of its result
+    if (std::string(name) == "viterbi_W" || std::string(name) == "viterbi_L") {
+        if (value < 0 || value > (1 << 20)) return set_err(HML_ERR_ARG, std::string(name) + ": a number of blocks up to 2^20, or 0 for the default");
+        (name[8] == 'W' ? c->vit.W : c->vit.L) = (uint32_t)value;
+        return 0;
+    }
+    if (std::string(name) == "viterbi_rounds") {
+        if (value < 0 || value > 16) return set_err(HML_ERR_ARG, "viterbi_rounds: 0 to 16 parallel repair rounds");
+        c->vit.rounds = (uint32_t)value;
+        return 0;
+    }
     return set_err(HML_ERR_ARG, std::string("unknown option ") + name);
 }
 

@@ -207,6 +207,14 @@ struct hml_ctx {
     uint32_t prof_tick = 0;
     std::map<std::string, ProfAcc> prof;
     std::vector<hipEvent_t> ev_pool;
+    // The Viterbi decode (hml_viterbi; hml_k_viterbi.h).  Launch geometry only - options "viterbi_W", "viterbi_L",
+    // "viterbi_rounds" - and what the last decode did (hml_viterbi_info).  Its device memory lives for the length of a call.
+    struct {
+        uint32_t W = 0, L = 0;         // warm-up and chunk length in blocks (0: the defaults)
+        uint32_t rounds = 8;           // parallel repair rounds before the single lane
+        bool decoded = false;
+        uint64_t chunks = 0, used_L = 0, used_W = 0, stale = 0, rounds_run = 0, walked = 0;
+    } vit;
     // Every d_* above that is not a plain pointer owns its buffer (DevBuf / DevArr, hml_host_common.hpp): deleting the context
     // frees them, whatever a call that failed half-way left allocated, and allocating one again replaces what it held.
     ~hml_ctx() { if (h_B) (void)hipHostFree(h_B); }

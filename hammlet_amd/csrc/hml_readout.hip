@@ -1221,3 +1221,202 @@ int hml_history_summary(hml_ctx* const* ctxs, int n, int col, uint64_t skip_swee
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------- Viterbi decode (hml_k_viterbi.h)
+// The jointly most probable state path over the current blocks under the current parameters.  Everything a decode allocates
+// is local to the call: it goes on every path out, and the context keeps only the numbers of hml_viterbi_info.
+#include "hml_k_viterbi.h"   // (launched from this object alone)
+
+struct vit_tables { DevBuf par, trans, init; };
+struct vit_path { DevBuf q; long long score = 0; uint32_t B = 0; };
+
+// the launches templated on the states the recursion's vector is kept for
+template <int KM>
+static void vit_launch_forward(hml_ctx* c, const vit_tables& t, uint32_t L, uint32_t W, uint32_t n_chunks, long long* entry, long long* exitv, uint8_t* psi) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_vit_forward<KM>), dim3((n_chunks + 63u) / 64u), dim3(64), 0, c->stream, t.par.as<hml_vit_par>(), t.trans.as<long long>(),
+                       t.init.as<long long>(), c->d_ia, c->d_starts.get(), L, W, n_chunks, entry, exitv, psi);
+}
+template <int KM>
+static void vit_launch_rerun(hml_ctx* c, const vit_tables& t, uint32_t L, uint32_t n_chunks, const uint32_t* heads, uint32_t n_heads, const uint8_t* match, long long* entry,
+                             long long* exitv, uint8_t* psi) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_vit_rerun<KM>), dim3((n_heads + 63u) / 64u), dim3(64), 0, c->stream, t.par.as<hml_vit_par>(), t.trans.as<long long>(),
+                       t.init.as<long long>(), c->d_ia, c->d_starts.get(), L, n_chunks, heads, n_heads, match, entry, exitv, psi);
+}
+template <int KM>
+static void vit_launch_finish(hml_ctx* c, const vit_tables& t, uint32_t L, uint32_t n_chunks, const uint8_t* match, long long* entry, long long* exitv, uint8_t* psi,
+                              unsigned long long* walked) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_vit_finish<KM>), dim3(1), dim3(64), 0, c->stream, t.par.as<hml_vit_par>(), t.trans.as<long long>(), t.init.as<long long>(),
+                       c->d_ia, c->d_starts.get(), L, n_chunks, match, entry, exitv, psi, walked);
+}
+#define VIT_BY_K(K, fn, ...) do { if ((K) <= 8) fn<8>(__VA_ARGS__); else if ((K) <= 16) fn<16>(__VA_ARGS__); else fn<HML_CAP_K>(__VA_ARGS__); } while (0)
+
+// how a decode begins: a settled chain with blocks, and the tables (parameters, trans, init) on the device
+static int vit_begin(hml_ctx* c, vit_tables& t, uint32_t* B_out) {
+    hml_model m; if (int r = fetch_model(c, &m)) return r;
+    if (int r = model_fault(m)) return r;
+    if (m.halted) return set_err(HML_ERR_ARG, "hml_viterbi: the chain is halted; settle it with hml_sync first");
+    if (m.B == 0) return set_err(HML_ERR_ARG, "hml_viterbi: no blocks yet: run a sweep or hml_create_blocks first");
+    const int K = c->K;
+    HIPCHK(t.par.alloc(sizeof(hml_vit_par)));
+    HIPCHK(t.trans.alloc((uint64_t)K * K * sizeof(long long)));
+    HIPCHK(t.init.alloc((uint64_t)K * sizeof(long long)));
+    hipLaunchKernelGGL(hml_k_vit_tables, dim3(1), dim3(256), 0, c->stream, c->d_mdl.get(), t.par.as<hml_vit_par>(), t.trans.as<long long>(), t.init.as<long long>());
+    KLAUNCH_CHECK();
+    *B_out = m.B;
+    return 0;
+}
+
+// the decode: path (device, int16 per block) and score
+static int vit_decode(hml_ctx* c, vit_path& out) {
+    vit_tables t;
+    uint32_t B = 0;
+    if (int r = vit_begin(c, t, &B)) return r;
+    const int K = c->K;
+    const uint32_t L = c->vit.L ? c->vit.L : HML_VIT_DEFAULT_L;
+    const uint32_t W = c->vit.W ? c->vit.W : HML_VIT_DEFAULT_W;
+    const uint32_t n_chunks = (uint32_t)(((uint64_t)B + L - 1u) / L);
+    const uint32_t S = std::max<uint32_t>(1u, (uint32_t)std::ceil(std::sqrt((double)n_chunks)));   // chunks per group of the back-track
+    const uint32_t n_groups = (n_chunks + S - 1u) / S;
+    DevBuf b_entry, b_exit, b_psi, b_match, b_list, b_words, b_maps, b_gmaps, b_gend, b_cend;
+    HIPCHK(b_entry.alloc((uint64_t)n_chunks * K * sizeof(long long)));
+    HIPCHK(b_exit.alloc((uint64_t)n_chunks * K * sizeof(long long)));
+    HIPCHK(b_psi.alloc((uint64_t)B * K));
+    HIPCHK(b_match.alloc(n_chunks));
+    HIPCHK(b_list.alloc((uint64_t)n_chunks * sizeof(uint32_t)));
+    HIPCHK(b_words.alloc(4 * sizeof(unsigned long long)));   // [0] stale chunks and heads of their runs (32 bits each), [1] chunks the single lane ran, [2] the score
+    HIPCHK(b_maps.alloc((uint64_t)n_chunks * K));
+    HIPCHK(b_gmaps.alloc((uint64_t)n_groups * K));
+    HIPCHK(b_gend.alloc(n_groups));
+    HIPCHK(b_cend.alloc(n_chunks));
+    HIPCHK(out.q.alloc((uint64_t)B * sizeof(int16_t)));
+    long long *const entry = b_entry.as<long long>(), *const exitv = b_exit.as<long long>();
+    uint8_t *const psi = b_psi.as<uint8_t>(), *const match = b_match.as<uint8_t>();
+    uint32_t* const list = b_list.as<uint32_t>();
+    unsigned long long* const words = b_words.as<unsigned long long>();
+    HIPCHK(hipMemsetAsync(words, 0, 4 * sizeof(unsigned long long), c->stream));
+
+    VIT_BY_K(K, vit_launch_forward, c, t, L, W, n_chunks, entry, exitv, psi);
+    KLAUNCH_CHECK();
+    // verify; repair in rounds while chunks are stale; the single lane for what the rounds leave
+    uint32_t n_stale = 0, stale_first = 0, rounds_run = 0;
+    unsigned long long walked = 0;
+    for (uint32_t round = 0;; ++round) {
+        uint32_t h_cnt[2] = {0, 0};   // stale chunks, heads of their runs
+        HIPCHK(hipMemsetAsync(words, 0, sizeof h_cnt, c->stream));
+        hipLaunchKernelGGL(hml_k_vit_verify, dim3(grid_for(n_chunks, 256, 1, 4096)), dim3(256), 0, c->stream, entry, exitv, K, n_chunks, match, list, (uint32_t*)words,
+                           (uint32_t*)words + 1);
+        KLAUNCH_CHECK();
+        HIPCHK(hipMemcpyAsync(h_cnt, words, sizeof h_cnt, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        n_stale = h_cnt[0];
+        if (round == 0) stale_first = n_stale;
+        if (n_stale == 0 || round >= c->vit.rounds) break;
+        VIT_BY_K(K, vit_launch_rerun, c, t, L, n_chunks, list, h_cnt[1], match, entry, exitv, psi);
+        KLAUNCH_CHECK();
+        rounds_run = round + 1u;
+    }
+    if (n_stale) {
+        VIT_BY_K(K, vit_launch_finish, c, t, L, n_chunks, match, entry, exitv, psi, words + 1);
+        KLAUNCH_CHECK();
+    }
+    // back-track
+    const dim3 cgrid((n_chunks + 63u) / 64u), ggrid((n_groups + 63u) / 64u);
+    hipLaunchKernelGGL(hml_k_vit_chunk_maps, cgrid, dim3(64), 0, c->stream, psi, K, B, L, n_chunks, b_maps.as<uint8_t>());
+    hipLaunchKernelGGL(hml_k_vit_group_maps, ggrid, dim3(64), 0, c->stream, b_maps.as<uint8_t>(), K, n_chunks, S, n_groups, b_gmaps.as<uint8_t>());
+    hipLaunchKernelGGL(hml_k_vit_group_ends, dim3(1), dim3(64), 0, c->stream, exitv, b_gmaps.as<uint8_t>(), K, n_chunks, n_groups, b_gend.as<uint8_t>());
+    hipLaunchKernelGGL(hml_k_vit_chunk_ends, ggrid, dim3(64), 0, c->stream, b_maps.as<uint8_t>(), b_gend.as<uint8_t>(), K, n_chunks, S, n_groups, b_cend.as<uint8_t>());
+    hipLaunchKernelGGL(hml_k_vit_walk, cgrid, dim3(64), 0, c->stream, psi, b_cend.as<uint8_t>(), K, B, L, n_chunks, out.q.as<int16_t>());
+    hipLaunchKernelGGL(hml_k_vit_score, dim3(grid_for(B, 256, 1, 4096)), dim3(256), 0, c->stream, t.par.as<hml_vit_par>(), t.trans.as<long long>(), t.init.as<long long>(),
+                       c->d_ia, c->d_starts.get(), out.q.as<int16_t>(), words + 2);
+    KLAUNCH_CHECK();
+    unsigned long long h_words[4];
+    HIPCHK(hipMemcpyAsync(h_words, words, sizeof h_words, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));   // (the scratch goes with this frame)
+    walked = h_words[1];
+    out.score = (long long)h_words[2];
+    out.B = B;
+    c->vit.decoded = true;
+    c->vit.chunks = n_chunks; c->vit.used_L = L; c->vit.used_W = W; c->vit.stale = stale_first; c->vit.rounds_run = rounds_run; c->vit.walked = walked;
+    return 0;
+}
+
+extern "C" {
+
+int hml_viterbi(hml_ctx* c, uint64_t* n_runs, uint64_t* run_len, int32_t* run_state, int64_t* score_fixed, double* score) {
+    NEED_MODEL();
+    if (!n_runs) return set_err(HML_ERR_ARG, "null argument");
+    vit_path p;
+    if (int r = vit_decode(c, p)) return r;
+    if (score_fixed) *score_fixed = (int64_t)p.score;
+    if (score) *score = (double)p.score / 1048576.0;
+    // runs of equal state over the blocks: the flag / count / scatter steps of the segmentation read-out, on block starts
+    const uint32_t M = p.B;
+    const uint32_t n_chunks = (M + 255u) / 256u;
+    DevBuf b_rc, b_rs, b_rq;
+    HIPCHK(b_rc.alloc(((uint64_t)n_chunks + 1) * sizeof(int32_t)));
+    int32_t* const d_rc = b_rc.as<int32_t>();
+    HIPCHK(hipMemsetAsync(d_rc + n_chunks, 0, sizeof(int32_t), c->stream));
+    hipLaunchKernelGGL(hml_k_seg_run_count, dim3(n_chunks), dim3(256), 0, c->stream, p.q.as<int16_t>(), M, d_rc);
+    hipLaunchKernelGGL(hml_k_scan_chunks<int32_t>, dim3(1), dim3(1024), 0, c->stream, d_rc, n_chunks + 1u);   // d_rc[n_chunks] = total
+    KLAUNCH_CHECK();
+    int32_t R = 0;
+    HIPCHK(hipMemcpyAsync(&R, d_rc + n_chunks, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *n_runs = (uint64_t)R;
+    if (!run_len) return 0;
+    HIPCHK(b_rs.alloc((uint64_t)R * sizeof(uint32_t)));
+    HIPCHK(b_rq.alloc((uint64_t)R * sizeof(int16_t)));
+    hipLaunchKernelGGL(hml_k_seg_run_scatter, dim3(n_chunks), dim3(256), 0, c->stream, p.q.as<int16_t>(), c->d_starts.get(), M, d_rc, b_rs.as<uint32_t>(), b_rq.as<int16_t>());
+    KLAUNCH_CHECK();
+    std::vector<uint32_t> h_rs(R);
+    std::vector<int16_t> h_rq(R);
+    HIPCHK(hipMemcpyAsync(h_rs.data(), b_rs.get(), (uint64_t)R * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(h_rq.data(), b_rq.get(), (uint64_t)R * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    lengths_of(h_rs.data(), (uint64_t)R, (uint32_t)c->T, run_len);
+    if (run_state) std::copy(h_rq.begin(), h_rq.end(), run_state);
+    return 0;
+}
+
+int hml_viterbi_states(hml_ctx* c, int16_t* q) {
+    NEED_MODEL();
+    if (!q) return set_err(HML_ERR_ARG, "null argument");
+    vit_path p;
+    if (int r = vit_decode(c, p)) return r;
+    HIPCHK(hipMemcpyAsync(q, p.q.get(), (uint64_t)p.B * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int hml_viterbi_scores(hml_ctx* c, int64_t* emit, int64_t* trans, int64_t* init) {
+    NEED_MODEL();
+    vit_tables t;
+    uint32_t B = 0;
+    if (int r = vit_begin(c, t, &B)) return r;
+    const int K = c->K;
+    DevBuf b_emit;
+    if (emit) {
+        HIPCHK(b_emit.alloc((uint64_t)B * K * sizeof(long long)));
+        hipLaunchKernelGGL(hml_k_vit_emit_table, dim3(grid_for(B, 256, 1, 16384)), dim3(256), 0, c->stream, t.par.as<hml_vit_par>(), c->d_ia, c->d_starts.get(), b_emit.as<long long>());
+        KLAUNCH_CHECK();
+        HIPCHK(hipMemcpyAsync(emit, b_emit.get(), (uint64_t)B * K * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (trans) HIPCHK(hipMemcpyAsync(trans, t.trans.get(), (uint64_t)K * K * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    if (init) HIPCHK(hipMemcpyAsync(init, t.init.get(), (uint64_t)K * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int hml_viterbi_info(hml_ctx* c, uint64_t* chunks, uint64_t* L, uint64_t* W, uint64_t* stale_chunks, uint64_t* rounds, uint64_t* serial_chunks) {
+    if (!c) return set_err(HML_ERR_ARG, "null context");
+    if (!c->vit.decoded) return set_err(HML_ERR_ARG, "hml_viterbi_info: nothing was decoded yet");
+    if (chunks) *chunks = c->vit.chunks;
+    if (L) *L = c->vit.used_L;
+    if (W) *W = c->vit.used_W;
+    if (stale_chunks) *stale_chunks = c->vit.stale;
+    if (rounds) *rounds = c->vit.rounds_run;
+    if (serial_chunks) *serial_chunks = c->vit.walked;
+    return 0;
+}
+
+}  // extern "C"

@@ -21,6 +21,8 @@
 // number of recorded sweeps N, those in which the whole region was one segment, mean and standard deviation of the number of
 // breakpoints inside it and of its mean level, and - with -bands - the sweeps in which all of it lay in one band
 // (hml_set_regions, hml_regions_read); with -chains N the chains' sums are added into the first chain's, on any GPUs;
+// `-O V` (viterbi) writes PREFIXviterbiSUFFIX, the jointly most probable state path under the chain's final parameters and last block
+// structure, in the maxsegmentation file's format (hml_viterbi; with -chains N one file per chain, PREFIXchainK.viterbiSUFFIX);
 // -raw FILE reads float32 values instead of text; -device N selects
 // the GPU; -chain N selects the Philox sub-key of an independent chain; -chains N runs N independent chains (sub-keys
 // chain .. chain+N-1), chain k on GPU (device + k) mod #GPUs in its own host thread, and pools their recorded marginals
@@ -59,6 +61,9 @@ static const char* kHelp =
     "  -o, -output-pattern PRE SUF    output files are PRE{marginals,...}SUF (default: hammlet- .csv)\n"
     "  -O, -output-data M S P B C G   marginals sequences parameters blocks compression segments\n"
     "                    X            maxsegmentation: the maxSegmentation tool's output for the marginals (extension)\n"
+    "                    V            viterbi: the jointly most probable state path under the chain's final parameters and\n"
+    "                                 last block structure, decoded on the device after the scheme has run, in the\n"
+    "                                 maxsegmentation file's format; with -chains N one file per chain (extension)\n"
     "                    L            levels: length, then posterior mean and standard deviation of the emission level\n"
     "                                 per data dimension, one line per segment - the denoised trace (extension)\n"
     "                    BP           breakpoints: position, number of recorded sweeps that change state there, and that\n"
@@ -506,6 +511,12 @@ static void writeContextFiles(const Job& job, hml_ctx* ctx) {
     if (job.outputs.at("regions")) writeRegions(job, ctx);
 }
 
+// PREFIX[chainK.]viterbiSUFFIX: decoded once the scheme has run, under the chain's final theta and last block structure
+static string viterbiFileName(const Job& job, int index) { return job.opref + (index == 0 ? "" : "chain" + std::to_string(index) + ".") + "viterbi" + job.osuff; }
+static void writeViterbiFile(const Job& job, int index, hml_ctx* ctx) {
+    if (job.outputs.at("viterbi")) Viterbi(ctx).writeFile(viterbiFileName(job, index));
+}
+
 static string historyFileName(const Job& job) { return job.opref + "history" + job.osuff; }
 static string historySummaryFileName(const Job& job) { return job.opref + "historysummary" + job.osuff; }
 // the chains' histories, in chain order (hammlet/History.hpp): read through the host, whichever GPUs the chains are on
@@ -621,6 +632,7 @@ static void runChain(const Job& job, vector<real_t>& inputValues, bool steal, in
     for (const Step& st : job.scheme)
         if (run.token(st)) run.sweeps(st);
     hml_check(hml_sync(run.RNG.ctx()));
+    writeViterbiFile(job, index, run.RNG.ctx());
     if (!rendezvous) writeContextFiles(job, run.RNG.ctx());   // (several chains: the main thread merges and writes)
     if (!rendezvous) writeHistoryFiles(job, {run.RNG.ctx()});
     if (rendezvous && !rendezvous->arrive(index, run.RNG.ctx())) run.records.discardMarginals();   // pooling failed elsewhere
@@ -665,6 +677,7 @@ static void runDeviceGroup(const Job& job, vector<real_t>& inputValues, int devi
     }
     vector<hml_ctx*> ctxs;
     for (auto& r : runs) { hml_check(hml_sync(r->RNG.ctx())); ctxs.push_back(r->RNG.ctx()); }
+    for (auto& r : runs) writeViterbiFile(job, r->index, r->RNG.ctx());
     const bool pooled = !rendezvous || rendezvous->arrive(indices, ctxs);
     for (auto& r : runs) { if (!pooled) r->records.discardMarginals(); r->records.close(); }
 }
@@ -781,6 +794,7 @@ int main(int argc, const char* argv[]) {
         outputArgs.registerFlags({"D", "mapping"});
         outputArgs.registerFlags({"G", "segments"});
         outputArgs.registerFlags({"X", "maxsegmentation"});   // extension
+        outputArgs.registerFlags({"V", "viterbi"});           // extension
         outputArgs.registerFlags({"L", "levels"});            // extension
         outputArgs.registerFlags({"BP", "breakpoints"});      // extension (B and C are the reference's blocks and compression)
         outputArgs.registerFlags({"CS", "consensus"});        // extension
@@ -862,7 +876,7 @@ int main(int argc, const char* argv[]) {
         job.weightMultiplier = weightMultiplier; job.useSelfTrans = useSelfTrans;
         job.thetaParams = thetaParams; job.trans = trans; job.selfTrans = selfTrans; job.initialAlpha = initialAlpha;
         job.scheme = scheme;
-        for (const char* o : {"sequences", "parameters", "blocks", "compression", "marginals", "segments", "maxsegmentation", "levels", "breakpoints", "consensus", "bands", "bandcalls", "rhat", "regions", "history", "historysummary"})
+        for (const char* o : {"sequences", "parameters", "blocks", "compression", "marginals", "segments", "maxsegmentation", "viterbi", "levels", "breakpoints", "consensus", "bands", "bandcalls", "rhat", "regions", "history", "historysummary"})
             job.outputs[o] = outputArgs.isSet(o);
         auto refuseExisting = [&](const string& fn) {
             if (!overwrite) { std::ifstream probe(fn); if (probe.good()) throw std::runtime_error("File " + fn + " already exists! Use -w to allow overwrite!"); }
@@ -926,6 +940,8 @@ int main(int argc, const char* argv[]) {
             if (job.outputs.at("history")) refuseExisting(historyFileName(job));
             if (job.outputs.at("historysummary")) refuseExisting(historySummaryFileName(job));
         }
+        if (job.outputs.at("viterbi"))
+            for (long k = 0; k < (long)nrChains; ++k) refuseExisting(viterbiFileName(job, (int)k));
         if (job.outputs.at("bands")) refuseExisting(bandsFileName(job));
         if (job.outputs.at("bandcalls")) refuseExisting(bandCallsFileName(job));
         if (job.outputs.at("levels")) refuseExisting(levelsFileName(job));

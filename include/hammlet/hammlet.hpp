@@ -618,6 +618,7 @@ template <> inline char StateSequence<Mixture>::method() { return HML_METHOD_MIX
 
 #include "Records.hpp"
 #include "History.hpp"
+#include "Viterbi.hpp"
 
 namespace hammlet {
 

@@ -477,6 +477,38 @@ int hml_history_stats(const double* x, int n_chains, uint64_t n, double* rhat, d
 int hml_history_summary(hml_ctx* const* ctxs, int n, int col, uint64_t skip_sweeps, double* rhat, double* ess, double* chain_mean /*n*/,
                         double* chain_sd /*n*/, uint64_t* n_used, uint64_t* n_nonfinite);
 
+/* ---- Viterbi decode: the jointly most probable state path under the current parameters.  No counterpart in the reference. ----
+ * hml_max_segmentation takes the arg-max of every position's marginal on its own; this is the ONE path over the context's
+ * current blocks (those of the last enumeration: a sweep's, or hml_create_blocks') that maximises
+ *     log pi(q_0) + sum_b E_b(q_b) + sum_{b > 0} log A(q_{b-1}, q_b)
+ * under the parameters as they stand (the last update's, or hml_set_parameters'), E_b(s) being the float block term of the
+ * forward-backward sweep (hml_get_block_loglik) with the block statistics taken anew from the integral array.  Workflow for
+ * a point estimate: hml_set_parameters (for example posterior means by sorted state), optionally hml_create_blocks at a
+ * threshold of the caller's choice, then hml_viterbi.  The chain is only read: its next sweeps are the same with or without.
+ *
+ * The maximisation is carried out in FIXED POINT, so that the answer is one exact path on every device and under every
+ * launch geometry: every term is an int64 in units of 2^-20 nat, fx(x) = llrint(clamp(x, -2^38, 2^38) 2^20) with not-a-number
+ * taken as -2^38 (an exact 0 in A or pi is a very bad, finite score), init[j] = fx(logf pi_j), trans[i][j] = fx(logf A_ij),
+ * emit[b][j] = fx(E_b(j)), logf and the terms' normalisers derived from mean, variance and A by the library's own logf
+ * (a "compat" context decodes to the same tables).  d_0(j) = init[j] + emit[0][j], d_b(j) = max_i(d_{b-1}(i) + trans[i][j]) +
+ * emit[b][j] with max_j d_b(j) subtracted after every block; ties go to the SMALLEST index - in the back-pointer of every
+ * block and in the end state - so among the paths of maximal score the one returned is the smallest read from the last block
+ * backwards.  score_fixed is the int64 sum of the path's terms (two's complement; it cannot wrap unless a term is clamped),
+ * score the same in nats, (double)score_fixed / 2^20.  hammlet_amd/csrc/hml_viterbi_ref.h restates all of it for one host thread.
+ *
+ * hml_viterbi: run-length form over positions, adjacent blocks of equal state merged; call with run_len == NULL to obtain
+ * the number of runs.  hml_viterbi_states: the path per block.  hml_viterbi_scores: the tables a decode uses (any may be
+ * NULL).  Every call decodes anew, with device memory of its own that is released before it returns; the same input gives
+ * the same words.  A context without blocks (no sweep and no hml_create_blocks yet) is refused.
+ * hml_viterbi_info, of the last decode: chunks the blocks were cut into, their length L and warm-up W in blocks, the chunks
+ * found stale after the first pass, the parallel repair rounds run, the chunks the single finishing lane ran again (any
+ * may be NULL).  Options "viterbi_W", "viterbi_L" (blocks, up to 2^20; 0: the default of 64) and "viterbi_rounds" (0 ... 16,
+ * default 8) are launch geometry: the result never depends on them ("Viterbi decode"). */
+int hml_viterbi(hml_ctx* ctx, uint64_t* n_runs, uint64_t* run_len /*n_runs*/, int32_t* run_state /*n_runs*/, int64_t* score_fixed, double* score);
+int hml_viterbi_states(hml_ctx* ctx, int16_t* q /*B*/);
+int hml_viterbi_scores(hml_ctx* ctx, int64_t* emit /*B*K*/, int64_t* trans /*K*K*/, int64_t* init /*K*/);
+int hml_viterbi_info(hml_ctx* ctx, uint64_t* chunks, uint64_t* L, uint64_t* W, uint64_t* stale_chunks, uint64_t* rounds, uint64_t* serial_chunks);
+
 /* ---- sparse payloads: levels, breakpoints and bands across GPUs.  No counterpart in the reference. ----
  * The three recordings above keep a cell and a boundary bit per change of state, so what another GPU needs of one is a list:
  * the M positions with a cell and the cells there.  The PAYLOAD is one contiguous buffer in device memory, little endian,
