@@ -147,7 +147,15 @@ int hml_iterate(hml_ctx* ctx, char method, uint64_t iterations, uint64_t thinnin
 /* Records::setRecord* (src/Records.hpp:121-144).  marginals: accumulate state marginals on the
  * device.  The other four make hml_iterate call `cb` after every recorded sweep (with the stream
  * synchronised) so the host can pull blocks/states/theta and append its files
- * (src/Records.hpp:147-235). */
+ * (src/Records.hpp:147-235).
+ * SWITCHING A RECORDING BETWEEN CALLS.  This flag and every recording below (levels, breaks, bands, regions, history) may be
+ * switched between two calls of hml_iterate / hml_iterate_many, also after sweeps have been recorded and also for one chain of
+ * a batch alone: a switch governs the sweeps enqueued from then on.  A recording that is off skips its sweeps - the recorded
+ * sweeps; for the history, the sweeps whose number is a multiple of `every` - and keeps what it has accumulated and its own N;
+ * switched on again - with the same edges, regions or `every` - it goes on adding to the same accumulators.  Every recording
+ * counts its own N, the sweeps recorded while IT was on; hml_recorded_sweeps is the marginals' N and grows only while the
+ * marginals flag is on, whatever the other recordings do.  A read-out in the middle of a run settles the chain, reads, and
+ * changes nothing: the run continues as if it had not been taken. */
 typedef void (*hml_record_cb)(hml_ctx* ctx, uint64_t sweep_in_call, void* user);
 int hml_set_recording(hml_ctx* ctx, int marginals, hml_record_cb cb, void* user);
 
@@ -246,7 +254,8 @@ int hml_recorded_sweeps(hml_ctx* ctx, uint64_t* n);
  * squares over the recorded sweeps, in double; posterior mean S1 / N and standard deviation sqrt(max(0, S2 / N - (S1 / N)^2)).
  * Memory: 2 D (T + 1) doubles and (T + 32) / 32 words, allocated by the first recorded sweep that needs them; cost per
  * recorded sweep: proportional to the number of changes of state, like the marginals.
- * hml_set_level_recording: at any time before a recorded sweep; turning it off keeps what was accumulated.  Off by
+ * hml_set_level_recording: at any time, for the sweeps recorded from then on (switching between calls: hml_set_recording);
+ * turning it off keeps what was accumulated.  Off by
  * default (a sweep then launches what it launched before ABI 4).  Environment: HML_LEVELS=1. */
 int hml_set_level_recording(hml_ctx* ctx, int on);
 /* Run-length form: segments are cut wherever any recorded sweep had a boundary between runs of equal states.  sum[d *
@@ -321,7 +330,8 @@ int hml_levels_agreement_summary(hml_ctx* const* ctxs, int n, double threshold, 
  * depend on what the states are called, so it adds over sweeps and chains without relabelling; all of it is integers, so
  * every result below is exact.  Memory: T + 1 words and (T + 32) / 32 words, allocated by the first recorded sweep that
  * needs them; cost per recorded sweep: one launch, proportional to the number of blocks.
- * hml_set_break_recording: at any time before a recorded sweep; turning it off keeps what was accumulated.  Off by
+ * hml_set_break_recording: at any time, for the sweeps recorded from then on (switching between calls: hml_set_recording);
+ * turning it off keeps what was accumulated.  Off by
  * default (a sweep then launches what it launched before ABI 5).  Environment: HML_BREAKS=1. */
 int hml_set_break_recording(hml_ctx* ctx, int on);
 /* The positions with C > 0, ascending, and their counts; n_recorded = N.  Call with pos == NULL to obtain n_breaks and
@@ -355,7 +365,7 @@ int hml_breaks_consensus(hml_ctx* ctx, uint32_t window, uint64_t min_count, uint
  * adjacent runs of different states in the same bands leave none, so the band segments are coarser than the levels' and the
  * marginals'.  Memory: 4 n_columns (T + 1) bytes and (T + 32) / 32 words, allocated by the first recorded sweep that needs
  * them; cost per recorded sweep: one launch, proportional to the number of blocks.
- * hml_set_level_bands sets the edges and turns the recording on, at any time before a recorded sweep; n_edges = 0 turns it
+ * hml_set_level_bands sets the edges and turns the recording on, at any time, for the sweeps recorded from then on; n_edges = 0 turns it
  * off and keeps what was accumulated, and its edges.  Once a sweep has been recorded, edges that differ in any bit are
  * HML_ERR_ARG.  Off by default (a sweep then launches what it launched before).  Environment: HML_BANDS="e0,e1,...".
  * hml_get_level_bands: the edges last set (edges may be NULL). */

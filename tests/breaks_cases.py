@@ -44,7 +44,8 @@ DENSE_WINDOWS = [0, 1, 16]
 def checker(case, chain=0, seed=None):
     c = CASES[case] if isinstance(case, str) else case
     mode = (ol.RNG_MT, ol.MATH_LIBM, ol.REDUCE_REF) if c["compat"] else (ol.RNG_CTR, ol.MATH_DEV, ol.REDUCE_DEV)
-    o = ol.OracleChain(K=c["K"], seed=c["seed"] if seed is None else seed, chain=chain, rng=mode[0], math=mode[1], reduce=mode[2])
+    o = ol.OracleChain(K=c["K"], seed=c["seed"] if seed is None else seed, chain=chain, rng=mode[0], math=mode[1], reduce=mode[2],
+                       weight_mult=c.get("weight_mult", 1.0))
     if c["D"] > 1:
         o.set_dimensions(c["D"], c["P"])
     o.load(c["trace"]() if callable(c["trace"]) else c["trace"])
@@ -53,9 +54,10 @@ def checker(case, chain=0, seed=None):
     return o
 
 
-def checker_sweeps(o, scheme, recording=None):
+def checker_sweeps(o, scheme, recording=None, marginals=False):
     """the checker through the scheme one sweep per call: (starts, states, means) of every recorded sweep.
-    `recording`: per scheme token, whether the recording under test is on (None: always)"""
+    `recording`: per scheme token, whether the recording under test is on (None: always).  `marginals`: the checker counts
+    every recorded sweep into its own state marginals as well (a call of one sweep with thinning 1: the same chain)"""
     sweeps = []
     for k, tok in enumerate(scheme):
         if isinstance(tok, str):
@@ -63,8 +65,9 @@ def checker_sweeps(o, scheme, recording=None):
             continue
         m, n, t = tok
         for i in range(n):
-            o.iterate(m, 1, 0)
-            if t > 0 and (i + 1) % t == 0 and (recording is None or recording[k]):
+            recorded = t > 0 and (i + 1) % t == 0
+            o.iterate(m, 1, 1 if (marginals and recorded) else 0)
+            if recorded and (recording is None or recording[k]):
                 sweeps.append((o.blocks().copy(), o.states().copy(), o.theta()[0::2].copy()))
     return sweeps
 

@@ -27,7 +27,8 @@ U = 2.0 ** -52
 def checker(case, chain=0, seed=None):
     """the checker of a case (tests/breaks_cases.checker) and the prior it was given: (chain, nig4 float32)"""
     mode = (ol.RNG_MT, ol.MATH_LIBM, ol.REDUCE_REF) if case["compat"] else (ol.RNG_CTR, ol.MATH_DEV, ol.REDUCE_DEV)
-    o = ol.OracleChain(K=case["K"], seed=case["seed"] if seed is None else seed, chain=chain, rng=mode[0], math=mode[1], reduce=mode[2])
+    o = ol.OracleChain(K=case["K"], seed=case["seed"] if seed is None else seed, chain=chain, rng=mode[0], math=mode[1], reduce=mode[2],
+                       weight_mult=case.get("weight_mult", 1.0))
     if case["D"] > 1:
         o.set_dimensions(case["D"], case["P"])
     o.load(case["trace"]() if callable(case["trace"]) else case["trace"])

@@ -86,6 +86,7 @@ def assert_dense(g, C, N, windows, what=""):
     T = len(C)
     for w in windows:
         out = torch.full((T,), -7.0, dtype=torch.float32, device="cuda:0")
+        torch.cuda.synchronize()      # (the fill runs on torch's stream, the read-out on the chain's)
         g.breaks_dense(out.data_ptr(), w)
         got = out.cpu().numpy()
         assert np.array_equal(bits32(got), bits32(bu.dense(C, N, w))), (what, w)
