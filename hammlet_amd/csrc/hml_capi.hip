@@ -8,7 +8,8 @@ int hml_set_err(int code, const std::string& msg) { g_err = msg; return code; }
 
 // the table of K states, or nullptr (outside [2, 16]; a development build knows one K only: -DHML_ONLY_K=5, tools/dev_build.py)
 static const hml_ktab* ktab(int K);
-#define HML_KTAB(KV, tab) const hml_ktab* tab = ktab(KV); if (!tab) return set_err(HML_ERR_ARG, "number of states must be in [2,16]")
+// ... and the tables of the two paths that take the number of states at run time (hml_rtk_sweep.hpp)
+static const hml_ktab* rtk_tab(bool wide);
 
 std::atomic<int> hml_live_ctx[64];
 int hml_ctx_bind(hml_ctx* c) { return ctx_bind(c); }
@@ -208,14 +209,14 @@ int hml_create(hml_ctx** out, int device, uint64_t seed, uint32_t chain_id, void
     if (const char* e = getenv("HML_TRELLIS_ROWS")) kn.tre_rows = atoi(e) != 0;   // 0: round 2's first pass (hml_k_trellis_tile) for comparison
     if (const char* e = getenv("HML_LATE_RESCALE")) kn.late_rescale = atoi(e) != 0;
     if (const char* e = getenv("HML_PARAMS_SPREAD")) kn.params_spread = atoi(e) != 0;
-    if (const char* e = getenv("HML_COMPAT_CHUNKS")) c->compat_chunks = atoi(e);   // (1: the sequential form; > 1: that many chunks)
-    if (const char* e = getenv("HML_COMPAT_WARMUP")) c->compat_warmup = atoi(e);   // (tests: a warm-up too short to forget the start)
-    if (const char* e = getenv("HML_WIDE_LANES")) c->wide_lanes = atoi(e);   // (0: models of more than 16 states with a state a lane)
-    if (const char* e = getenv("HML_WIDE_W0")) c->wide_w0 = std::max(8, atoi(e));
-    if (const char* e = getenv("HML_WIDE_MAX_CHUNKS")) c->wide_max_chunks = (uint32_t)std::max(64, atoi(e));
+    if (const char* e = getenv("HML_COMPAT_CHUNKS")) c->rtk.compat_chunks = atoi(e);   // (1: the sequential form; > 1: that many chunks)
+    if (const char* e = getenv("HML_COMPAT_WARMUP")) c->rtk.compat_warmup = atoi(e);   // (tests: a warm-up too short to forget the start)
+    if (const char* e = getenv("HML_WIDE_LANES")) c->rtk.wide_lanes = atoi(e);   // (0: models of more than 16 states with a state a lane)
+    if (const char* e = getenv("HML_WIDE_W0")) c->rtk.wide_w0 = std::max(8, atoi(e));
+    if (const char* e = getenv("HML_WIDE_MAX_CHUNKS")) c->rtk.wide_max_chunks = (uint32_t)std::max(64, atoi(e));
     if (const char* e = getenv("HML_WIDE_L")) {   // (tests: chunks of that many blocks, a power of two)
         const int L = atoi(e);
-        if (L >= 1) { int sh = 0; while ((1 << sh) < L && sh < 20) ++sh; c->wide_lshift = sh; }
+        if (L >= 1) { int sh = 0; while ((1 << sh) < L && sh < 20) ++sh; c->rtk.wide_lshift = sh; }
     }
     if (const char* e = getenv("HML_COMPAT")) c->compat = atoi(e) != 0;   // option "compat" for unmodified callers (`hammlet -compat`)
     if (const char* e = getenv("HML_TRELLIS_TUNE")) c->tre_autotune = atoi(e) != 0;
@@ -290,7 +291,7 @@ static int alloc_block_buffers(hml_ctx* c) {
         const uint64_t n_tiles = (T + HML_FUSED_SUB_POSITIONS - 1) / HML_FUSED_SUB_POSITIONS;   // (tiles of one batch: the most there can be)
         HIPCHK(c->d_group_word.alloc(n_tiles + 1));
         HIPCHK(hipMemsetAsync(c->d_group_word, 0, (n_tiles + 1) * sizeof(unsigned long long), c->stream));
-        HIPCHK(c->d_wave_total.alloc((n_tiles + 1) * (HML_FUSED_WAVES + 2)));   // (+ tile_before, tile_prev)
+        HIPCHK(c->d_wave_total.DevBuf::alloc(hml_layout_wave_total(nullptr, n_tiles).bytes));
         if (getenv("HML_FUSED_DEBUG")) { HIPCHK(c->d_dbg.alloc(4096 * 8)); HIPCHK(hipMemset(c->d_dbg, 0, 4096 * 8 * 8)); }
     }
     if (int r = alloc_capacity_buffers(c, CAPBUF_BLOCKS)) return r;
@@ -591,61 +592,10 @@ int hml_autoprior(hml_ctx* c, float s2, float p, float out4[4]) {
 
 }  // extern "C"
 
-// entries of one array of the reference-compatible mode's lists by state (hml_compat_lists): the blocks and up to three entries of
-// padding per state, rounded to whole 16-byte groups
-static uint64_t compat_list_entries(const hml_ctx* c) { return (c->cap + 4u * (uint64_t)HML_CAP_K + 3u) & ~(uint64_t)3u; }
-
-// the most chunks a sweep of the path for more than 16 states is cut into (hml_k_wl_prepare): the arrays are sized for the chunk
-// length this bound gives at the context's capacity
-static uint32_t wide_max_chunks_of(const hml_ctx* c) {
-    if (c->wide_max_chunks) return std::min<uint32_t>(c->wide_max_chunks, HML_WL_MAX_CHUNKS);
-    return c->K <= HML_WL_TWO_WAVES_KC ? (uint32_t)HML_WL_MAX_CHUNKS : (uint32_t)HML_WL_MAX_CHUNKS / 2u;
-}
-
-// the per-block sweep buffers, sized by the context's block capacity (hml_ctx.hpp; c->K set)
-static int alloc_sweep_buffers(hml_ctx* c) {
+// the per-block sweep buffers of the default path, sized by the context's block capacity (hml_ctx.hpp; c->K set)
+int hml_alloc_sweep_default(hml_ctx* c) {
     const int K = c->K;
     const uint64_t cap = c->cap;
-    if (c->compat) {   // the reference-compatible mode (hml_k_compat.h): plain emission terms [b][s], a plain (B + 1) x K trellis, the states
-        HIPCHK(c->d_em.alloc(cap * K));
-        HIPCHK(c->d_gsc.alloc(cap * K));
-        HIPCHK(c->d_crows.alloc((cap + 1) * K));
-        // chunks of the filter and of the backward draws (hml_compat_chunks), the engine's outputs of a sweep (two per block)
-        HIPCHK(c->d_cchunk.alloc((uint64_t)HML_COMPAT_MAX_CHUNKS * (2 * K * sizeof(float) + 4 * sizeof(uint32_t)) + 64));
-        HIPCHK(c->d_cdraws.alloc(2 * cap));
-        // the count pass's lists by state (hml_compat_lists): statistics, sizes, per-tile counts, flags
-        // (three arrays of cap + 4 K entries, each 16-byte aligned: a state's list starts at a multiple of four entries)
-        HIPCHK(c->d_clists.alloc(3 * compat_list_entries(c) * sizeof(uint32_t) + (uint64_t)HML_CAP_K * HML_CAP_K * sizeof(unsigned long long) +
-                                        ((cap + HML_COMPAT_PART_TILE - 1) / HML_COMPAT_PART_TILE) * K * sizeof(uint32_t) + 2 * (HML_CAP_K + 1) * sizeof(uint32_t) + 64));
-        HIPCHK(c->d_q.alloc(cap));
-        return 0;
-    }
-    if (c->wide) {   // more than 16 states (hml_k_wide.h, hml_k_wide_lanes.h): [b][s] arrays or chunk-transposed ones, the default path's count tree
-        // (chunk-transposed: L K cstride floats with cstride = the chunks rounded up to 64 - at most K (B + 64 L), L the longest chunk
-        // hml_k_wl_prepare can choose for this capacity)
-        uint64_t Lmax = 1ull << HML_WL_MIN_LSHIFT;
-        if (c->wide_lshift >= 0) Lmax = std::max<uint64_t>(Lmax, 1ull << c->wide_lshift);
-        while ((cap + Lmax - 1) / Lmax > (uint64_t)wide_max_chunks_of(c)) Lmax *= 2;   // (the longest chunks hml_k_wl_prepare can choose: B <= cap)
-        const uint64_t plane = (cap + 1 + 64 * Lmax) * K;
-        HIPCHK(c->d_em.alloc(plane));
-        HIPCHK(c->d_gsc.alloc(plane));
-        HIPCHK(c->d_crows.alloc(plane));
-        // (per-chunk arrays: as many chunks as the shortest chunk length makes of the capacity - at least what the lane-per-state form may ask for)
-        const uint64_t Lmin = c->wide_lshift >= 0 ? (1ull << c->wide_lshift) : (1ull << HML_WL_MIN_LSHIFT);
-        c->wide_chunks_cap = std::max<uint64_t>(HML_COMPAT_MAX_CHUNKS, std::min<uint64_t>(HML_WL_MAX_CHUNKS, (cap + Lmin - 1) / Lmin + 64));
-        const uint64_t chunk_bytes = c->wide_chunks_cap * (2 * K * sizeof(float) + 4 * sizeof(uint32_t));
-        HIPCHK(c->d_cchunk.alloc(chunk_bytes + HML_WL_TOT_WORDS * sizeof(unsigned long long)));
-        HIPCHK(hipMemsetAsync(c->d_cchunk.as<char>() + chunk_bytes, 0, HML_WL_TOT_WORDS * sizeof(unsigned long long), c->stream));   // (counters and bit maps of wrong chunks)
-        HIPCHK(c->d_wA.alloc((uint64_t)HML_WL_PITCH * HML_WL_PITCH + (uint64_t)HML_CAP_K * HML_WL_GTAB));   // (... and the table of rescale factors behind it)
-        HIPCHK(c->d_cdraws.alloc(2 * (cap + 1)));
-        HIPCHK(c->d_q.alloc(cap));
-        const uint64_t n_partial = (uint64_t)HML_REDUCE_GROUPS * K * 2;
-        HIPCHK(c->d_partial.alloc(n_partial));
-        HIPCHK(hipMemsetAsync(c->d_partial, 0, n_partial * sizeof(double), c->stream));
-        HIPCHK(c->d_wacc.alloc(sizeof(hml_wide_acc)));
-        HIPCHK(hipMemsetAsync(c->d_wacc.get(), 0, sizeof(hml_wide_acc), c->stream));
-        return 0;
-    }
     int minL = c->knobs.geo[0].L;
     for (const hml_fwd_geo& g : c->knobs.geo) minL = std::min(minL, g.L);
     const uint64_t maxChunks = (cap + minL - 1) / minL + 1;   // per-chunk arrays serve either geometry
@@ -699,7 +649,7 @@ static int alloc_capacity_buffers(hml_ctx* c, int what) {
         HIPCHK(c->d_eprobe.alloc(c->cap * c->K));
         HIPCHK(c->d_aprobe.alloc((c->cap + 1) * c->K));
     }
-    return (what & CAPBUF_SWEEP) ? alloc_sweep_buffers(c) : 0;
+    return (what & CAPBUF_SWEEP) ? c->kt->alloc_sweep(c) : 0;   // (of the context's path: hml_ktab)
 }
 
 // More room for blocks: the per-block buffers are allocated again for at least `needed` blocks (half as many again, at least
@@ -724,8 +674,6 @@ static int grow_capacity(hml_ctx* c, uint64_t needed) {
     c->grown++;
     return 0;
 }
-
-static int sweep_dispatch(hml_ctx* c, char method, bool record);
 
 // The stream is idle and no sweep was left behind: a chain whose enumeration found more blocks than its buffers hold (it halts
 // on the device, hml_state.h) gets larger buffers, and the sweeps it skipped - everything enqueued since the model's sweep
@@ -755,7 +703,7 @@ int hml_settle(hml_ctx* c) {
         for (size_t i = 0; i < pending.size() && !halted_again; ++i) {
             const char method = (pending[i] & 1) ? HML_METHOD_MIXTURE : HML_METHOD_FB;
             const bool record = (pending[i] & 2) != 0;
-            if (int r = sweep_dispatch(c, method, record)) return r;
+            if (int r = c->kt->sweep(c, method, record)) return r;
             if (record && c->cb) {   // a recorded sweep the caller wants to see: it happens now (or, halted again, in the next round)
                 HIPCHK(hipStreamSynchronize(c->stream));
                 halted_again = chain_halted(c);
@@ -791,10 +739,11 @@ int hml_set_model(hml_ctx* c, int K, const float nig4[4], float a_off, float a_d
     if (!(nig4[0] > 0)) return set_err(HML_ERR_MODEL, "Alpha (" + std::to_string(nig4[0]) + ") must be positive!");
     if (!(nig4[1] > 0)) return set_err(HML_ERR_MODEL, "Beta (" + std::to_string(nig4[1]) + ") must be positive!");
     if (!(nig4[3] > 0)) return set_err(HML_ERR_MODEL, "Nu (" + std::to_string(nig4[3]) + ")must be positive!");
-    const hml_ktab* kt = nullptr;   // (before anything is allocated: a development build knows one K only; the reference-compatible mode takes K at run time)
     // more than 16 states: the kernels that take the number of states at run time (hml_k_wide.h; HML_WIDE=1: from 2 states - tests)
     c->wide = !c->compat && (K > HML_MAX_K || (getenv("HML_WIDE") && atoi(getenv("HML_WIDE")) != 0));
-    if (!c->compat && !c->wide) { kt = ktab(K); if (!kt) return set_err(HML_ERR_ARG, "number of states must be in [2,16]"); }
+    // the context's path, chosen ONCE, before anything is allocated (a development build knows one K only; the other two take K at run time)
+    c->kt = (c->compat || c->wide) ? rtk_tab(c->wide) : ktab(K);
+    if (!c->kt) return set_err(HML_ERR_ARG, "number of states must be in [2,16]");
     if (int r = ctx_bind(c)) return r;
     c->K = K;
     // the parameter kernel's tree over 16 workgroups (hml_k_params.h) from 8 states: it reads 2 K x 8 KB of group partials -
@@ -827,7 +776,7 @@ int hml_set_model(hml_ctx* c, int K, const float nig4[4], float a_off, float a_d
     if (const char* e = getenv("HML_TRE_REFIT_SHIFTS")) { unsigned a = 17, b = 20; if (sscanf(e, "%u,%u", &a, &b) == 2 && a < 32 && b < 32) { m.tre_hi_shift = a; m.tre_lo_shift = b; } }
     m.fwd_W0 = (uint32_t)c->fwdW;
     m.fwd_W = m.fwd_W_burnin = (uint32_t)std::max(c->fwdW, c->fwdW_init);
-    if (c->compat || c->wide) { m.fwd_W = 64u; m.fwd_W0 = c->wide ? (uint32_t)c->wide_w0 : 32u; }
+    if (c->compat || c->wide) { m.fwd_W = 64u; m.fwd_W0 = c->wide ? (uint32_t)c->rtk.wide_w0 : 32u; }
     m.wl_bwd_W = 64u; m.wl_bwd_quiet = 0u; m.wl_retry = 0u; m.wl_W_need = 0u; m.wl_need_age = 0u;   // the chunked lane-per-state kernels' own policy (hml_chunk_warmup_adapt)
     m.fwd_burnin_sweeps = c->fwd_burnin_sweeps;
     m.fwd_quiet_need = c->fwd_quiet_need;
@@ -839,24 +788,17 @@ int hml_set_model(hml_ctx* c, int K, const float nig4[4], float a_off, float a_d
     HIPCHK(hipStreamSynchronize(c->stream));
     c->dynamic = true;
     c->hint_stale = true;
-    // Theta's constructor samples once from the prior (src/Theta.hpp:126-127)
     if (c->compat) {
-        // reference-compatible mode (hml_k_compat.h): the reference's engine, seeded like `rng_t RNG(seed)` (main.cpp:107-108),
-        // and a plain (B + 1) x K trellis.  Chain 0 is the reference's run at this seed; further chains of a run (`-chains N`,
-        // chain ids 1, 2, ...) are the reference's runs at seed + chain id - N copies of one chain would pool to N times its
-        // marginals.
+        // reference-compatible mode (hml_k_compat.h): the reference's engine, seeded like `rng_t RNG(seed)` (main.cpp:107-108).
+        // Chain 0 is the reference's run at this seed; further chains of a run (`-chains N`, chain ids 1, 2, ...) are the
+        // reference's runs at seed + chain id - N copies of one chain would pool to N times its marginals.
         hml_mt_state h;
         hml_mt_seed(&h, c->seed + (uint64_t)c->chain);
         HIPCHK(c->d_mt.alloc(sizeof(hml_mt_state)));
         HIPCHK(hipMemcpyAsync(c->d_mt.get(), &h, sizeof h, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
-        hipLaunchKernelGGL(hml_k_compat_draw, dim3(1), dim3(64), 0, c->stream, c->d_mdl, c->d_mt.as<hml_mt_state>(), 2);
-        KLAUNCH_CHECK();
-        c->model_set = true;
-        return 0;
     }
-    if (c->wide) hipLaunchKernelGGL(hml_k_wide_params, dim3(1), dim3(1024), 0, c->stream, c->d_mdl, c->d_partial, c->d_wacc.as<hml_wide_acc>(), 2);
-    else kt->params(c, 2);
+    c->kt->params(c, 2);   // Theta's constructor samples once from the prior (src/Theta.hpp:126-127)
     KLAUNCH_CHECK();
     c->model_set = true;
     return 0;
@@ -866,11 +808,7 @@ int hml_sample_prior(hml_ctx* c) {
     if (!c || !c->model_set) return set_err(HML_ERR_ARG, "model not set");
     if (int r = ctx_bind(c)) return r;
     if (int r = settle_if_limited(c)) return r;
-    if (c->compat) {
-        hipLaunchKernelGGL(hml_k_compat_draw, dim3(1), dim3(64), 0, c->stream, c->d_mdl, c->d_mt.as<hml_mt_state>(), 1);
-    } else if (c->wide) {
-        hipLaunchKernelGGL(hml_k_wide_params, dim3(1), dim3(1024), 0, c->stream, c->d_mdl, c->d_partial, c->d_wacc.as<hml_wide_acc>(), 1);
-    } else { HML_KTAB(c->K, kt); kt->params(c, 1); }
+    c->kt->params(c, 1);
     KLAUNCH_CHECK();
     if (c->dynamic) c->blocks_valid = false;
     c->hint_stale = true;
@@ -1047,201 +985,13 @@ int hml_enable_probes(hml_ctx* c, int on) {
 
 int hml_ctx_ensure_marginal_buffers(hml_ctx* c) { return ensure_marginal_buffers(c); }
 
-// A sweep of the reference-compatible mode (hml_k_compat.h): block starts and block statistics by the default path's
-// kernels, the order-dependent part in the reference's order (the number of states is a run-time value there), the
-// marginals by hml_k_record.
-static hml_compat_chunks chunk_views(const hml_ctx* c) {   // the arrays of d_cchunk (alloc_sweep_buffers)
-    hml_compat_chunks ch;
-    char* base = c->d_cchunk.as<char>();
-    const uint64_t n = c->wide ? c->wide_chunks_cap : (uint64_t)HML_COMPAT_MAX_CHUNKS;
-    ch.entry = (float*)base; base += n * c->K * sizeof(float);
-    ch.exitv = (float*)base; base += n * c->K * sizeof(float);
-    ch.nfb = (uint32_t*)base; base += n * sizeof(uint32_t);
-    ch.in_state = (int32_t*)base; base += n * sizeof(int32_t);
-    ch.out_state = (int32_t*)base; base += n * sizeof(int32_t);
-    ch.bad = (uint32_t*)base; base += n * sizeof(uint32_t);
-    ch.tot = (unsigned long long*)base;
-    ch.W = 0u;
-    return ch;
-}
-
-// filter and backward draws in C chunks with a wavefront each (hml_k_compat.h): the chunks' entry rows against the exit rows
-// before them by as many threads as there are elements, then one wavefront that runs the rare wrong chunk again; the same for
-// the backward draws.  KC / PAD: the number of states at compile time, or (PAD) an upper bound of the model's.
-template <int KC, class M, bool PAD>
-static void launch_chunked_fb(hml_ctx* c, hipStream_t s, uint32_t C, const hml_compat_chunks& ch, float* aprobe) {
-    {
-        ProfScope ps(c, "forward");
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_compat_forward<KC, M, PAD>), dim3(C), dim3(64), 0, s, c->d_mdl, c->d_em, c->d_gsc, c->d_crows, aprobe, ch);
-        if (C > 1u) hipLaunchKernelGGL(hml_k_compat_forward_verify, dim3(grid_for((uint64_t)C * c->K, 256, 1, 4096)), dim3(256), 0, s, c->d_mdl, ch, C);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_compat_forward_check<KC, PAD>), dim3(1), dim3(256), 0, s, c->d_mdl, c->d_em, c->d_gsc, c->d_crows, ch, C);
-    }
-    {
-        ProfScope ps(c, "backward_maps");
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_compat_backward<KC, PAD>), dim3(C), dim3(64), 0, s, c->d_mdl, c->d_crows, c->d_cdraws, c->d_q, ch);
-        if (C > 1u) hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_compat_backward_check<KC, PAD>), dim3(1), dim3(256), 0, s, c->d_mdl, c->d_crows, c->d_cdraws, c->d_q, ch, C);
-    }
-}
-
-static int sweep_compat(hml_ctx* c, char method, bool record) {
-    hipStream_t s = c->stream;
-    if (int r = launch_blocks_if_needed(c)) return r;
-    refresh_hint(c);
-    const uint32_t hint = grid_hint(c);
-    const int mix = method == HML_METHOD_MIXTURE ? 1 : 0;
-    hml_mt_state* const mt = c->d_mt.as<hml_mt_state>();
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_compat_emission<hml_glibc_exp>), dim3(grid_for(hint, 256, 64, 16384)), dim3(256), 0, s, c->d_mdl, c->d_starts, c->d_bstat, c->d_em, c->d_gsc, mix,
-                       eprobe_of(c));
-    if (mix) hipLaunchKernelGGL(hml_k_compat_mixture, dim3(1), dim3(64), 0, s, c->d_mdl, mt, c->d_em, c->d_q);
-    else {
-        float* const aprobe = aprobe_of(c);
-        // filter and backward draws in chunks with a wavefront each, then one wavefront that checks the chunks in order
-        // (hml_k_compat.h); one chunk - the sequential form - for short sweeps and when the rows are probed
-        uint32_t C = 1u;
-        if (!c->probes && c->compat_chunks > 1) C = std::min<uint32_t>((uint32_t)c->compat_chunks, HML_COMPAT_MAX_CHUNKS);   // (tests: any sweep in that many chunks)
-        else if (!c->probes && c->compat_chunks == 0 && hint >= 8192u) C = std::min<uint32_t>((uint32_t)HML_COMPAT_MAX_CHUNKS, hint / 64u);
-        hml_compat_chunks ch = chunk_views(c);
-        ch.W = c->compat_warmup > 0 ? (uint32_t)c->compat_warmup : c->compat_warmup < 0 ? 0u : HML_CHUNK_W_ADAPTIVE;   // (< 0: none - tests)
-        hipLaunchKernelGGL(hml_k_compat_draws, dim3(1), dim3(256), 0, s, c->d_mdl, mt, c->d_cdraws, 2u);
-        // (up to 16 states: the number of states as a compile-time value - A in registers, loops unrolled; beyond: loops unrolled
-        // over 32 or 64 in groups of four that stop at the model's value)
-#define HML_COMPAT_FB(KC) case KC: launch_chunked_fb<KC, hml_glibc_exp, false>(c, s, C, ch, aprobe); break;
-        switch (c->K <= HML_MAX_K ? c->K : 0) {
-            HML_COMPAT_FB(2) HML_COMPAT_FB(3) HML_COMPAT_FB(4) HML_COMPAT_FB(5) HML_COMPAT_FB(6) HML_COMPAT_FB(7) HML_COMPAT_FB(8) HML_COMPAT_FB(9)
-            HML_COMPAT_FB(10) HML_COMPAT_FB(11) HML_COMPAT_FB(12) HML_COMPAT_FB(13) HML_COMPAT_FB(14) HML_COMPAT_FB(15) HML_COMPAT_FB(16)
-            default:
-                if (c->K <= 32) launch_chunked_fb<32, hml_glibc_exp, true>(c, s, C, ch, aprobe);
-                else launch_chunked_fb<64, hml_glibc_exp, true>(c, s, C, ch, aprobe);
-        }
-#undef HML_COMPAT_FB
-    }
-    // the count pass: by state (partition, then one wavefront over all lists) for long univariate sweeps, in block order otherwise
-    hml_compat_lists pl;
-    {
-        const uint64_t tiles = (c->cap + HML_COMPAT_PART_TILE - 1) / HML_COMPAT_PART_TILE;
-        char* base = c->d_clists.as<char>();
-        pl.sx = (float*)base; base += compat_list_entries(c) * sizeof(float);
-        pl.sq = (float*)base; base += compat_list_entries(c) * sizeof(float);
-        pl.n = (uint32_t*)base; base += compat_list_entries(c) * sizeof(uint32_t);
-        pl.offdiag = (unsigned long long*)base; base += (uint64_t)HML_CAP_K * HML_CAP_K * sizeof(unsigned long long);
-        pl.tile_count = (uint32_t*)base; base += tiles * c->K * sizeof(uint32_t);
-        pl.state_off = (uint32_t*)base;
-    }
-    // (by state: a block's size and a flag share a word of the lists - traces below 2^31 positions)
-    const int by_state = (c->D == 1 && c->T < (1ull << 31) && (c->compat_chunks > 1 || (c->compat_chunks == 0 && hint >= 8192u))) ? 1 : 0;
-    if (by_state) {
-        const unsigned tiles_now = (unsigned)(((uint64_t)hint + hint / 8 + HML_COMPAT_PART_TILE) / HML_COMPAT_PART_TILE);   // (kernels find B themselves; tiles beyond it return)
-        const unsigned tg = std::min<uint64_t>(std::max(1u, tiles_now), (c->cap + HML_COMPAT_PART_TILE - 1) / HML_COMPAT_PART_TILE);
-        hipLaunchKernelGGL(hml_k_compat_part_count, dim3(tg), dim3(256), 0, s, c->d_mdl, c->d_q, pl);
-        hipLaunchKernelGGL(hml_k_compat_part_scan, dim3(1), dim3(64), 0, s, c->d_mdl, pl);
-        hipLaunchKernelGGL(hml_k_compat_part_scatter, dim3(tg), dim3(256), 0, s, c->d_mdl, c->d_q, c->d_starts, c->d_bstat, pl);
-    }
-    hipLaunchKernelGGL(hml_k_compat_update, dim3(1), dim3(by_state ? 256 : 64), 0, s, c->d_mdl, mt, c->d_starts, c->d_bstat, c->d_q, mix, pl, by_state);
-    if (record) { if (int r = launch_marginals(c, s, hint, /*bracket*/ false)) return r; }
-    if (record) { if (int r = launch_recorders(c, s, hint)) return r; }   // (hml_k_compat_update above is this sweep's parameter update)
-    launch_history(c, method);   // (the sweep's row, where the chain keeps a history: hml_k_history.h)
-    KLAUNCH_CHECK();
-    return 0;
-}
-
-// A sweep of a model with more than 16 states (hml_k_wide.h): block starts and block statistics by the default path's kernels,
-// emission terms / filter / backward draws by the lane-per-state kernels of hml_k_compat.h in this path's arithmetic, the
-// uniforms of the draws from their Philox addresses ahead of them, the default path's count tree, hml_k_wide_params.
-static int sweep_wide(hml_ctx* c, char method, bool record) {
-    hipStream_t s = c->stream;
-    if (int r = launch_blocks_if_needed(c)) return r;
-    refresh_hint(c);
-    const uint32_t hint = grid_hint(c);
-    const int mix = method == HML_METHOD_MIXTURE ? 1 : 0;
-    // filter and backward draws with a chunk a lane over chunk-transposed arrays (hml_k_wide_lanes.h) - unless the rows are probed,
-    // a test asked for a number of chunks of the other form, or the sweep has no filter at all
-    const bool lanes = c->wide_lanes != 0 && !c->probes && !mix && c->compat_chunks == 0;
-    if (lanes) {
-        hml_compat_chunks ch = chunk_views(c);
-        ch.W = c->compat_warmup > 0 ? (uint32_t)c->compat_warmup : c->compat_warmup < 0 ? 0u : HML_CHUNK_W_ADAPTIVE;
-        const uint64_t room = (uint64_t)hint + hint / 4 + 1024;   // (the kernels find B themselves: their loops stride over any grid)
-        hipLaunchKernelGGL(hml_k_wl_prepare, dim3(1), dim3(256), 0, s, c->d_mdl, c->d_wA, c->wide_lshift, wide_max_chunks_of(c));
-        hipLaunchKernelGGL(hml_k_wl_gtable, dim3(grid_for((uint64_t)c->K * HML_WL_GTAB, 256, 1, 512)), dim3(256), 0, s, c->d_mdl, c->d_wA + HML_WL_PITCH * HML_WL_PITCH);
-        {
-            ProfScope ps(c, "stats_emission");
-            // (a wavefront: 64 chunks x HML_WL_EMIT_ROWS rows)
-            hipLaunchKernelGGL(hml_k_wl_emission, dim3(grid_for(room, 64 * HML_WL_EMIT_ROWS * 4, 1, 32768)), dim3(256), 0, s, c->d_mdl, c->d_starts, c->d_bstat, c->d_em, c->d_gsc, c->d_wA + HML_WL_PITCH * HML_WL_PITCH);
-        }
-        const uint64_t minL = c->wide_lshift >= 0 ? (1ull << c->wide_lshift) : (1ull << HML_WL_MIN_LSHIFT);
-        const int tiles = grid_for(room, (int)std::min<uint64_t>(64 * minL, 1u << 30), 1, HML_WL_MAX_CHUNKS / 64);
-#define HML_WL_FB(KC)                                                                                                                                   \
-        case KC: {                                                                                                                                      \
-            constexpr int KS = (KC <= 32) ? 32 : 64;                                                                                                    \
-            {                                                                                                                                           \
-                ProfScope ps(c, "forward");                                                                                                             \
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_wl_forward<KC>), dim3(tiles), dim3(64), 0, s, c->d_mdl, c->d_wA, c->d_em, c->d_gsc, c->d_crows, ch, 0); \
-                hipLaunchKernelGGL(hml_k_wl_forward_verify, dim3(grid_for(room / 16 * c->K, 256, 1, 4096)), dim3(256), 0, s, c->d_mdl, ch, 0);          \
-                /* many wrong chunks: the filter once more with a longer warm-up (the three launches return at once otherwise) */                      \
-                hipLaunchKernelGGL(hml_k_wl_retry_decide, dim3(1), dim3(256), 0, s, c->d_mdl, ch);                                                      \
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_wl_forward<KC>), dim3(tiles), dim3(64), 0, s, c->d_mdl, c->d_wA, c->d_em, c->d_gsc, c->d_crows, ch, 1); \
-                hipLaunchKernelGGL(hml_k_wl_forward_verify, dim3(grid_for(room / 16 * c->K, 256, 1, 4096)), dim3(256), 0, s, c->d_mdl, ch, 1);          \
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_wl_forward_check<KS>), dim3(1), dim3(256), 0, s, c->d_mdl, c->d_em, c->d_gsc, c->d_crows, ch);  \
-            }                                                                                                                                           \
-            {                                                                                                                                           \
-                ProfScope ps(c, "backward_maps");                                                                                                       \
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_wl_backward<KC>), dim3(tiles), dim3(64), 0, s, c->d_mdl, c->d_crows, c->d_q, ch);               \
-                hipLaunchKernelGGL(hml_k_wl_backward_verify, dim3(grid_for(room / 16, 256, 1, 256)), dim3(256), 0, s, c->d_mdl, ch);                     \
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_wl_backward_check<KS>), dim3(1), dim3(256), 0, s, c->d_mdl, c->d_crows, c->d_q, ch);          \
-            }                                                                                                                                           \
-        } break;
-        switch ((c->K + 3) / 4 * 4) {
-            HML_WL_FB(4) HML_WL_FB(8) HML_WL_FB(12) HML_WL_FB(16)   // (HML_WIDE=1: this path for any model - tests)
-            HML_WL_FB(20) HML_WL_FB(24) HML_WL_FB(28) HML_WL_FB(32) HML_WL_FB(36) HML_WL_FB(40) HML_WL_FB(44) HML_WL_FB(48) HML_WL_FB(52) HML_WL_FB(56)
-            HML_WL_FB(60) HML_WL_FB(64)
-            default: return set_err(HML_ERR_HIP, "internal error: a model of this many states on the path for more than 16");
-        }
-#undef HML_WL_FB
-    } else {
-    {
-        ProfScope ps(c, "stats_emission");
-        hipLaunchKernelGGL(hml_k_wide_emission, dim3(grid_for(hint, 256, 1, 4096)), dim3(256), 0, s, c->d_mdl, c->d_starts, c->d_bstat,
-                           c->d_em, c->d_gsc, mix, eprobe_of(c));
-    }
-    if (mix) hipLaunchKernelGGL(hml_k_wide_mixture, dim3(grid_for(hint, 256, 1, 16384)), dim3(256), 0, s, c->d_mdl, c->d_em, c->d_q);
-    else {
-        float* const aprobe = aprobe_of(c);
-        uint32_t C = 1u;   // (one chunk - the sequential form - for short sweeps and when the rows are probed)
-        if (!c->probes && c->compat_chunks > 1) C = std::min<uint32_t>((uint32_t)c->compat_chunks, HML_COMPAT_MAX_CHUNKS);
-        else if (!c->probes && c->compat_chunks == 0 && hint >= 2048u) C = std::min<uint32_t>((uint32_t)HML_COMPAT_MAX_CHUNKS, hint / 64u);
-        hml_compat_chunks ch = chunk_views(c);
-        ch.W = c->compat_warmup > 0 ? (uint32_t)c->compat_warmup : c->compat_warmup < 0 ? 0u : HML_CHUNK_W_ADAPTIVE;
-        hipLaunchKernelGGL(hml_k_wide_uniforms, dim3(grid_for((hint + 1u) / 2u, 256, 1, 4096)), dim3(256), 0, s, c->d_mdl, c->d_cdraws);
-        if (c->K <= 32) launch_chunked_fb<32, hml_dev_exp, true>(c, s, C, ch, aprobe);
-        else launch_chunked_fb<64, hml_dev_exp, true>(c, s, C, ch, aprobe);
-    }
-    }
-    {
-        ProfScope ps(c, "counts");
-        hipLaunchKernelGGL(hml_k_wide_counts, dim3(HML_REDUCE_GROUPS), dim3(256), 0, s, c->d_q, c->d_starts, c->d_bstat, c->d_mdl, c->d_partial, c->d_wacc.as<hml_wide_acc>());
-    }
-    if (record) { if (int r = launch_marginals(c, s, hint, /*bracket*/ false)) return r; }
-    {
-        ProfScope ps(c, "params");
-        hipLaunchKernelGGL(hml_k_wide_params, dim3(1), dim3(1024), 0, s, c->d_mdl, c->d_partial, c->d_wacc.as<hml_wide_acc>(), 0);
-    }
-    if (record) { if (int r = launch_recorders(c, s, hint)) return r; }   // (after the update: hml_k_levels.h)
-    launch_history(c, method);   // (the sweep's row, where the chain keeps a history: hml_k_history.h)
-    KLAUNCH_CHECK();
-    return 0;
-}
-
-static int sweep_dispatch(hml_ctx* c, char method, bool record) {
-    if (c->compat) return sweep_compat(c, method, record);
-    if (c->wide) return sweep_wide(c, method, record);
-    HML_KTAB(c->K, kt);
-    return kt->sweep(c, method, record);
-}
+#include "hml_rtk_sweep.hpp"   // sweep_compat, sweep_wide and their tables
 
 // One sweep of a chain and, on a recorded sweep with a callback: wait, settle if the chain halted (that runs the sweep again
 // and calls back), check the device error, call back.
 static int sweep_step(hml_ctx* c, char method, bool record, uint64_t i) {
     log_sweep(c, method, record);
-    if (int r = sweep_dispatch(c, method, record)) return r;
+    if (int r = c->kt->sweep(c, method, record)) return r;
     if (!(record && c->cb)) return 0;
     HIPCHK(hipStreamSynchronize(c->stream));
     if (chain_halted(c)) return hml_settle(c);
@@ -1267,7 +1017,7 @@ static int replay_captured(hml_ctx* c, char method, bool* replayed) {
         HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
         // whatever happens below, the stream must leave capture mode (a failure in between would otherwise
         // make every later call on this context fail) and a partial graph must not stay behind
-        int rr = sweep_dispatch(c, method, false);
+        int rr = c->kt->sweep(c, method, false);
         const hipError_t ec = hipStreamEndCapture(c->stream, &g);
         if (rr || ec != hipSuccess) {
             if (g) hipGraphDestroy(g);
@@ -1335,10 +1085,8 @@ extern "C" int hml_iterate_many(hml_ctx* const* cs, int n, char method, uint64_t
             c->hint_stale = false;
             drop_graph(c);
         }
-        int r = 0;
         uint64_t reached = done;
-        { HML_KTAB(cs[0]->K, kt); r = kt->iterate_many(cs, n, done, iterations, thinning, &reached); }
-        if (r) return r;
+        if (int r = cs[0]->kt->iterate_many(cs, n, done, iterations, thinning, &reached)) return r;   // (many_eligible: a table that has one)
         // the other chains' streams continue behind the batch
         hipEvent_t ev = ev_get(cs[0]);
         HIPCHK(hipEventRecord(ev, cs[0]->stream));
@@ -1530,9 +1278,7 @@ int hml_set_parameters(hml_ctx* c, const float* mean_var, const float* A, const 
     memcpy(m.A, A, (size_t)K * K * sizeof(float));
     memcpy(m.pi, pi, (size_t)K * sizeof(float));
     HIPCHK(hipMemcpyAsync(c->d_mdl, &m, sizeof m, hipMemcpyHostToDevice, c->stream));
-    if (c->compat) hipLaunchKernelGGL(hml_k_compat_derive, dim3(1), dim3(64), 0, c->stream, c->d_mdl);   // (glibc's logf)
-    else if (c->wide) hipLaunchKernelGGL(hml_k_wide_derive, dim3(1), dim3(64), 0, c->stream, c->d_mdl);
-    else { HML_KTAB(K, kt); kt->derive(c); }
+    c->kt->derive(c);
     KLAUNCH_CHECK();
     HIPCHK(hipStreamSynchronize(c->stream));
     if (c->dynamic) c->blocks_valid = false;

@@ -1,5 +1,7 @@
 // Shared by the three kinds of translation unit of libhammlet_hip.so's chain code (hammlet_amd/build.py):
-//   hml_capi.hip  - the C ABI (include/hml.h) and everything that does not depend on the number of states K: one object;
+//   hml_capi.hip  - the C ABI (include/hml.h) and everything that does not depend on the number of states K: one object.  It
+//                   includes hml_rtk_sweep.hpp, the sweeps of the two paths that take K at run time (the reference-compatible mode,
+//                   more than 16 states) behind tables of their own (hml_ktab_compat, hml_ktab_wide): their kernels stay in this object;
 //   hml_readout.hip - the C ABI's read-outs of what the recorded sweeps accumulated (marginals, levels, breaks, bands, regions): one object;
 //   hml_sweep.hip - the sweep for K states: the kernels templated on K and the host code that launches them, behind a table
 //                   of function pointers (hml_ktab): fifteen objects, -DHML_TU_K=2 ... 16, compiled in parallel.
@@ -8,6 +10,10 @@
 // one 19 MB object with every kernel for 2 ... 16 states - 45 ms of a short run's start-up - and the library
 // builds in a fifth of the time.  Kernels that are not templates have internal linkage (HML_KERNEL) so that the objects may
 // each hold the ones they launch.  (Round 4: this header and the two files were one file sliced by the preprocessor.)
+// The core reaches a context's sweep, parameter kernel and buffer allocation through the table hml_set_model chose for it
+// (hml_ctx::kt) and never asks which path it is.  What a sweep launches is decided by a pure function per family of paths
+// (hml_sweep_plan.h, hml_rtk_plan.h), where the arrays of a carved buffer lie by one layout function per buffer
+// (hml_layouts.h); neither header needs HIP, and the CPU tests hold them to their rules.
 // Development builds for one K (tools/dev_build.py): both files with -DHML_ONLY_K=k.
 #ifndef HML_CAPI_SHARED_HPP
 #define HML_CAPI_SHARED_HPP
@@ -55,13 +61,18 @@ int hml_set_err(int code, const std::string& msg);   // hml_capi.hip (the thread
 static int set_err(int code, const std::string& msg) { return hml_set_err(code, msg); }
 
 
-// what the core calls of the K-dependent part: one table per number of states (defined at the end of hml_sweep.hip)
+// What the core calls of a context's path: one table per number of states on the default path (defined at the end of
+// hml_sweep.hip), one each for the reference-compatible mode and for more than 16 states (hml_rtk_sweep.hpp).  hml_set_model
+// chooses the table and the context keeps it (hml_ctx::kt).
 struct hml_ktab {
     int (*sweep)(hml_ctx* c, char method, bool record);
+    // (null where chains are never batched: many_eligible refuses them)
     int (*iterate_many)(hml_ctx* const* cs, int n, uint64_t first, uint64_t iterations, uint64_t thinning, uint64_t* done);
-    void (*params)(hml_ctx* c, int mode);        // hml_k_params<K>: 1 = draw from the priors, 2 = Theta's constructor draw
-    void (*derive)(hml_ctx* c);                  // hml_k_derive<K>
+    void (*params)(hml_ctx* c, int mode);        // the parameter kernel: 1 = draw from the priors, 2 = Theta's constructor draw
+    void (*derive)(hml_ctx* c);                  // what the kernels derive from parameters that were set (hml_set_parameters)
+    int (*alloc_sweep)(hml_ctx* c);              // the per-block sweep buffers, sized by the context's block capacity (c->K set)
 };
+__attribute__((visibility("hidden"))) int hml_alloc_sweep_default(hml_ctx* c);   // hml_capi.hip: ... of the default path, whatever its K
 
 // Live contexts per device.  The fused block kernel hands block offsets from workgroup to workgroup inside one launch
 // (a workgroup spins on the words of lower-numbered ones); that is safe while all lower-numbered workgroups are resident

@@ -14,6 +14,7 @@
 
 #include "../../include/hml.h"
 #include "hml_host_common.hpp"
+#include "hml_layouts.h"
 #include "hml_state.h"
 #include "hml_sweep_plan.h"
 
@@ -66,6 +67,8 @@ struct hml_history {
     uint64_t expected = 0;            // rows it holds once everything enqueued has run (never less than that)
     uint64_t grown = 0;               // times it was replaced by a larger one
 };
+
+struct hml_ktab;   // hml_capi_shared.hpp
 
 struct hml_ctx {
     int device = 0;
@@ -191,16 +194,11 @@ struct hml_ctx {
     DevBuf d_cchunk;               // chunks of its filter / backward draws (hml_compat_chunks, hml_k_compat.h)
     DevArr<uint32_t> d_cdraws;     // the engine's outputs of a sweep's categorical draws
     DevBuf d_clists;               // its count pass's lists by state (hml_compat_lists)
-    int compat_chunks = 0;         // 0: chosen from the block count; 1: the sequential form (HML_COMPAT_CHUNKS)
-    int compat_warmup = 0;         // blocks a chunk runs ahead of its first; 0: 64 (128 beyond 16 states) (HML_COMPAT_WARMUP)
-    bool wide = false;             // more than 16 states on the default path: the number of states is a run-time value, a state a lane (hml_k_wide.h)
+    hml_rtk_knobs rtk;             // what steers the sweeps of the two paths that take the number of states at run time (hml_rtk_plan.h)
+    const hml_ktab* kt = nullptr;  // the sweep, parameter and allocation functions of the context's path (hml_set_model; hml_capi_shared.hpp)
+    bool wide = false;            // more than 16 states on the default path: the number of states is a run-time value, a state a lane (hml_k_wide.h)
     DevBuf d_wacc;                 // its integer counts of a sweep (hml_wide_acc)
     DevArr<float> d_wA;            // ... the transition matrix padded to 64 x 64 (hml_k_wide_lanes.h)
-    int wide_lanes = 1;            // ... filter and backward draws with a chunk a lane (0: a state a lane, hml_k_compat.h's kernels) (HML_WIDE_LANES)
-    int wide_w0 = 32;              // ... the floor of its chunks' adaptive warm-up, blocks (HML_WIDE_W0)
-    uint32_t wide_max_chunks = 0;  // ... the most chunks a sweep is cut into (HML_WIDE_MAX_CHUNKS; 0: HML_WL_MAX_CHUNKS)
-    uint64_t wide_chunks_cap = 0;  // ... chunks its per-chunk arrays hold (alloc_sweep_buffers)
-    int wide_lshift = -1;          // ... log2 of a forced chunk length (tests: HML_WIDE_L), -1: from the block count
     bool pooled = false;           // the marginals are a pooled payload (hml_pool_install): common labels, counts of several chains
     std::vector<int32_t> pool_perm;   // perm[pooled label] = this chain's label, from the export that preceded the pooling
     int profiling = 0;             // 0 off, 1 dominant kernel only (blocks_compact, every 32nd launch), 2 every kernel family

@@ -6,6 +6,7 @@
 
 #include "hml_k_blocks.h"
 #include "hml_k_forward.h"
+#include "hml_layouts.h"
 
 // ------------------------------------------------------------------------------------------
 // One workgroup of 8 wavefronts per TILE of n_sub * 2^17 positions; wavefront w owns the tile's w-th eighth and walks it
@@ -37,7 +38,7 @@
 // from the next sweep on (hml_capi.hip).  Slow when it happens, never wrong, never stuck.
 // Same results as hml_k_compact_scan(+_summary) + hml_k_compact_scatter + hml_k_stats_emission, bit for bit.
 // ------------------------------------------------------------------------------------------
-#define HML_FUSED_WAVES 8                                                        // wavefronts per workgroup
+// (HML_FUSED_WAVES, the wavefronts per workgroup: hml_layouts.h)
 #define HML_FUSED_WAVE_BATCH (HML_SUM_SPANS * HML_SPAN)                           // positions a wavefront scans per batch (16384)
 #define HML_FUSED_SUB_POSITIONS (HML_FUSED_WAVES * HML_FUSED_WAVE_BATCH)          // positions per workgroup and batch (2^17)
 #define HML_FUSED_MAX_SUB 4                                                      // batches per workgroup (16-bit offsets into a wavefront's eighth)

@@ -21,6 +21,7 @@
 
 #include "hml_dist.h"
 #include "hml_k_forward.h"
+#include "hml_layouts.h"
 #include "hml_math_glibc.h"
 #include "hml_state.h"
 
@@ -168,7 +169,6 @@ HML_KERNEL __launch_bounds__(64) void hml_k_compat_draw(hml_model* __restrict__ 
 //                           draws.
 // ------------------------------------------------------------------------------------------------------------------------
 #define HML_COMPAT_TILE 1024   // floats staged per tile: min(64, 1024 / K) blocks
-#define HML_COMPAT_MAX_CHUNKS 16384   // (round 5: 2048 before - a chunk is one wavefront, and the machine holds 8000 of them)
 
 __device__ __forceinline__ float hml_lane_f32(float v, int i) {   // (i wave-uniform)
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), i));
@@ -325,17 +325,7 @@ HML_KERNEL __launch_bounds__(256) void hml_k_compat_emission(hml_model* __restri
 // compares, and runs the rare chunk that was wrong again from the right value (then the next comparison uses what it left).
 // The first chunk starts from the true value, so by induction every stored row / state is the sequential one.  One chunk
 // (gridDim.x = 1) is the sequential form: probes, short sweeps.
-struct hml_compat_chunks {
-    float* entry;        // [C][K] filter: the row a chunk reached at its first block (from its warm-up)
-    float* exitv;        // [C][K] ... and the unscaled row it left behind its last block
-    uint32_t* bad;       // [C] filter: the chunk's entry row is not what the chunk before it left (hml_k_compat_forward_verify)
-    uint32_t* nfb;       // [C] uniform fallbacks inside the chunk's own blocks
-    int32_t* in_state;   // [C] backward draws: the state above the chunk's first row (from its warm-up)
-    int32_t* out_state;  // [C] ... and the state of its last row
-    uint32_t W;          // warm-up, blocks; HML_CHUNK_W_ADAPTIVE: the model's own (mdl->fwd_W: it follows the chunks that had to run again)
-    unsigned long long* tot;   // [3] (hml_k_wide_lanes.h) wrong chunks of the filter, the sum of nfb, wrong chunks of the backward draws
-};
-#define HML_CHUNK_W_ADAPTIVE 0xffffffffu
+// (struct hml_compat_chunks, the views of d_cchunk: hml_layouts.h)
 // The warm-up of the chunks (results never depend on it: a chunk is accepted only on bit equality with what the chunk before it
 // left).  Adaptive (round 5): it starts at 64 blocks, doubles when a sweep had chunks that ran again and falls by a quarter after
 // sixteen sweeps without one, down to a floor of 32 (mdl->fwd_W / fwd_W0 / fwd_quiet, which the kernels of this family own in
@@ -851,20 +841,7 @@ HML_KERNEL __launch_bounds__(64) void hml_k_compat_mixture(hml_model* __restrict
 // float) only ever see the blocks of that state, in block order; the off-diagonal transition counts are exact increments.  So the
 // blocks are PARTITIONED by state, stably (per tile of 4096 blocks a histogram, a scan over the tiles, a ranked scatter), and one
 // wavefront walks all lists at once, lane s its own: max_s(blocks of state s) steps instead of B.
-#define HML_COMPAT_PART_TILE 4096
-struct hml_compat_lists {
-    uint32_t* tile_count;   // [tiles][K] blocks of state s in the tile, then their exclusive prefix over the tiles
-    uint32_t* state_off;    // [2 (K + 1)] first list position of state s (a multiple of four), then from K + 1 on the length of its list
-    unsigned long long* offdiag;   // [K * K] transitions between different states
-    // per list position, one array per quantity (round 5: each of the four wavefronts of the walk reads only what its chain adds -
-    // sixteen entries are one 64-byte run per lane and array where they were sixteen 16-byte structures):
-    float* sx;              // the block's Sx
-    float* sq;              // the block's Sxx
-    uint32_t* n;            // its size (below 2^31: the host takes the walk in block order for longer traces) and, in bit 31, whether
-                            // the block before it has the same state (prev_0 = 0, ForwardBackward.hpp:172)
-    // (every state's list starts at a multiple of four entries and the arrays are 16-byte aligned: four entries are one load;
-    // the arrays hold B + 4 K entries)
-};
+// (struct hml_compat_lists, the views of d_clists: hml_layouts.h)
 HML_KERNEL __launch_bounds__(256) void hml_k_compat_part_count(const hml_model* __restrict__ mdl, const int16_t* __restrict__ q, const hml_compat_lists pl) {
     __shared__ uint32_t h[HML_CAP_K];
     if (mdl->halted != 0u) return;

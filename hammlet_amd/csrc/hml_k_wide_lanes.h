@@ -29,19 +29,7 @@
 
 #if defined(__HIPCC__)
 
-#define HML_WL_MAX_CHUNKS 131072
-#define HML_WL_MIN_LSHIFT 2
-#define HML_WL_MAP_WORDS (HML_WL_MAX_CHUNKS / 64)
-#define HML_WL_PITCH 64   // floats between the rows of the padded transition matrix
-// the filter's registers let two wavefronts onto a SIMD up to this many (padded) states - up to 32 as the compiler allocates them, at
-// 36 when told to and with the step's loads asked for behind the products (219 registers; 40 states fit too, 240 registers, and gain
-// nothing; from 48 on the kernel would spill) - and a sweep is then cut into twice the chunks (hml_k_wl_prepare)
-#define HML_WL_TWO_WAVES_KC 36
-// hml_compat_chunks::tot on this path: [0] wrong chunks of the filter, [1] the sum of nfb, [2] wrong chunks of the backward draws,
-// then a bit per wrong chunk of the filter and of the backward draws (set by the verifying launches, cleared by the checking ones)
-#define HML_WL_MAP_F 4
-#define HML_WL_MAP_B (HML_WL_MAP_F + HML_WL_MAP_WORDS)
-#define HML_WL_TOT_WORDS (HML_WL_MAP_B + HML_WL_MAP_WORDS)
+// (the path's geometry constants and hml_compat_chunks::tot on this path: hml_rtk_plan.h, hml_layouts.h)
 
 // element (block b, state s) of a chunk-transposed array (chunks of 1 << lshift blocks)
 __device__ __forceinline__ uint64_t hml_wl_at(const uint32_t lshift, const int K, const uint32_t b, const int s) {
@@ -80,7 +68,6 @@ HML_KERNEL __launch_bounds__(256) void hml_k_wl_prepare(hml_model* mdl, float* _
 // The rescale factors g_s(N) = expf((N - 1) log A(s, s)) of the block sizes below HML_WL_GTAB, [s][N]: the emission kernel looks
 // a block's K factors up instead of evaluating them (40 of its 142 instructions per block and state; the same expression, the same
 // floats) - a model's blocks are mostly short (of 3.4 10^6 blocks at 64 states on config 3's trace none reaches 2048 positions).
-#define HML_WL_GTAB 2048
 HML_KERNEL __launch_bounds__(256) void hml_k_wl_gtable(const hml_model* __restrict__ mdl, float* __restrict__ gtab) {
     if (mdl->halted != 0u || mdl->self_trans == 0) return;
     const int K = mdl->K;

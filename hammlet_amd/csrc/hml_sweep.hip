@@ -397,8 +397,9 @@ static int iterate_many_k(hml_ctx* const* cs, int n, uint64_t first, uint64_t it
                     for (int k = 0; k < nk; ++k) {
                         hml_ctx* c = cs[k0 + k];
                         hml_fs_chain& f = fa.c[k];
-                        f.mdl = c->d_mdl; f.group_word = c->d_group_word; f.wave_total = c->d_wave_total; f.stage = c->d_stage; f.starts = c->d_starts;
-                        f.tile_before = c->d_wave_total + (m.fs_tiles1 + 1) * HML_FUSED_WAVES; f.tile_prev = f.tile_before + (m.fs_tiles1 + 1);
+                        const hml_wave_total_layout wt = hml_layout_wave_total(c->d_wave_total.get(), m.fs_tiles1);
+                        f.mdl = c->d_mdl; f.group_word = c->d_group_word; f.wave_total = wt.wave_total; f.stage = c->d_stage; f.starts = c->d_starts;
+                        f.tile_before = wt.tile_before; f.tile_prev = wt.tile_prev;
                         f.bstat = c->d_bstat; f.em = c->d_em; f.gsc = with_gsc ? c->d_gsc : nullptr; f.host_words = c->d_hB; f.lay = c->knobs.geo[HML_GEO_MANY].lay;
                     }
                     hipLaunchKernelGGL(hml_m_blocks_list, dim3(m.fs.wg), dim3(HML_FUSED_WAVES * 64), 0, s, c0->d_summary, c0->d_w, T, c0->key_base, fa, nk, m.fs.sub);
@@ -496,7 +497,7 @@ static int iterate_many_k(hml_ctx* const* cs, int n, uint64_t first, uint64_t it
     }                                                                                                                              \
     HML_KERNEL_ORDER(KK)                                                                                                           \
     extern hml_ktab hml_ktab_##KK;                                                                                                 \
-    hml_ktab hml_ktab_##KK = {&sweep_k<KK>, &iterate_many_k<KK>, &hml_kt_params_##KK, &hml_kt_derive_##KK};
+    hml_ktab hml_ktab_##KK = {&sweep_k<KK>, &iterate_many_k<KK>, &hml_kt_params_##KK, &hml_kt_derive_##KK, &hml_alloc_sweep_default};
 #if defined(HML_TU_K)
 #define HML_DEFINE_KTAB_(K) HML_DEFINE_KTAB(K)
 HML_DEFINE_KTAB_(HML_TU_K)
