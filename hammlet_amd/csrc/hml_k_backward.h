@@ -6,23 +6,9 @@
 
 #include "hml_dist.h"
 #include "hml_k_forward.h"
+#include "hml_maps.h"
 #include "hml_philox.h"
 #include "hml_state.h"
-
-#define HML_MAP_IDENTITY 0xfedcba9876543210ull
-
-// (f o g)(x) = f(g(x)) on maps [K]->[K] packed 4 bits per entry
-template <int K>
-__device__ __forceinline__ unsigned long long hml_map_compose(unsigned long long f, unsigned long long g) {
-    unsigned long long r = 0ull;   // entries x >= K are never read
-#pragma unroll
-    for (int x = 0; x < K; ++x) {
-        const unsigned y = (unsigned)(g >> (4 * x)) & 15u;
-        const unsigned long long z = (f >> (4 * y)) & 15ull;
-        r |= z << (4 * x);
-    }
-    return r;
-}
 
 __device__ __forceinline__ unsigned long long hml_shfl_down_u64(unsigned long long v, int d) {
     const unsigned lo = (unsigned)v, hi = (unsigned)(v >> 32);
@@ -175,27 +161,26 @@ template <int K>
 __device__ __forceinline__ void hml_bwd_chunk_maps(const float (&r)[K], hml_model* __restrict__ mdl, const hml_bwd_ctx<K>& bx,
                                                    unsigned long long* __restrict__ smap, unsigned long long* __restrict__ cmap,
                                                    uint32_t c, int lane, uint32_t B, unsigned long long epoch, const hml_key key) {
+    using MF = hml_mapfmt<K>;   // a byte per entry up to 8 states, 4 bits beyond (hml_maps.h)
     const uint32_t t = c * HML_BWD_CHUNK + (uint32_t)lane + 1u;
-    unsigned long long map = HML_MAP_IDENTITY;
+    unsigned long long map = MF::identity();
     if (t <= B) {
         const double u = hml_cat_uniform(key, epoch, t);
-        map = 0ull;
+        map = MF::empty();
         // "Negative backward variable!" (ForwardBackward.hpp:147-149): the products r_i A(i, x) below are negative exactly
         // when r_i is (A holds probabilities), so the row is checked once instead of K * K times with a branch each
 #pragma unroll
         for (int i = 0; i < K; ++i)
             if (r[i] < 0.0f) hml_raise(mdl, HML_DEVERR_NEG_BACKWARD, r[i]);
         if (t == B) {
-            const unsigned long long st = (unsigned long long)hml_categorical_k<K>(r, u);
-#pragma unroll
-            for (int x = 0; x < K; ++x) map |= st << (4 * x);
+            map = MF::broadcast((unsigned)hml_categorical_k<K>(r, u));
         } else {
 #pragma unroll
             for (int x = 0; x < K; ++x) {
                 float w[K];
 #pragma unroll
                 for (int i = 0; i < K; ++i) w[i] = r[i] * bx.A[i * K + x];
-                map |= (unsigned long long)hml_categorical_k<K>(w, u) << (4 * x);
+                map = MF::put(map, x, (unsigned)hml_categorical_k<K>(w, u));
             }
         }
     }
@@ -203,8 +188,8 @@ __device__ __forceinline__ void hml_bwd_chunk_maps(const float (&r)[K], hml_mode
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         unsigned long long o = hml_shfl_down_u64(map, d);
-        if (lane + d >= 64) o = HML_MAP_IDENTITY;
-        map = hml_map_compose<K>(map, o);
+        if (lane + d >= 64) o = MF::identity();
+        map = MF::compose(map, o);
     }
     if (t <= B) smap[t] = map;
     if (lane == 0) cmap[c] = map;
@@ -285,23 +270,22 @@ HML_KERNEL __launch_bounds__(HML_BWD_MAPS_THREADS) void hml_k_backward_maps(cons
 template <int K>
 __device__ __forceinline__ unsigned long long hml_bwd_row_map(const float (&r)[K], hml_model* __restrict__ mdl, const hml_bwd_ctx<K>& bx,
                                                               uint32_t t, uint32_t B, double u) {
-    if (t > B) return HML_MAP_IDENTITY;
-    unsigned long long map = 0ull;
+    using MF = hml_mapfmt<K>;
+    if (t > B) return MF::identity();
+    unsigned long long map = MF::empty();
     // "Negative backward variable!" (ForwardBackward.hpp:147-149), checked once per row (see hml_bwd_chunk_maps)
 #pragma unroll
     for (int i = 0; i < K; ++i)
         if (r[i] < 0.0f) hml_raise(mdl, HML_DEVERR_NEG_BACKWARD, r[i]);
     if (t == B) {
-        const unsigned long long st = (unsigned long long)hml_categorical_k<K>(r, u);
-#pragma unroll
-        for (int x = 0; x < K; ++x) map |= st << (4 * x);
+        map = MF::broadcast((unsigned)hml_categorical_k<K>(r, u));
     } else {
 #pragma unroll
         for (int x = 0; x < K; ++x) {
             float w[K];
 #pragma unroll
             for (int i = 0; i < K; ++i) w[i] = r[i] * bx.A[i * K + x];
-            map |= (unsigned long long)hml_categorical_k<K>(w, u) << (4 * x);
+            map = MF::put(map, x, (unsigned)hml_categorical_k<K>(w, u));
         }
     }
     return map;
@@ -371,21 +355,22 @@ __device__ __forceinline__ void hml_b_backward_maps2(const float* __restrict__ r
         double u0, u1;
         hml_cat_uniform_pair(key, epoch, (t0 - 1u) >> 1, u0, u1);
         const bool live = !my_fail && c < nchunks;
-        const unsigned long long m0 = live ? hml_bwd_row_map<K>(r0, mdl, bx, t0, B, u0) : HML_MAP_IDENTITY;
-        const unsigned long long m1 = live ? hml_bwd_row_map<K>(r1, mdl, bx, t0 + 1u, B, u1) : HML_MAP_IDENTITY;
+        using MF = hml_mapfmt<K>;
+        const unsigned long long m0 = live ? hml_bwd_row_map<K>(r0, mdl, bx, t0, B, u0) : MF::identity();
+        const unsigned long long m1 = live ? hml_bwd_row_map<K>(r1, mdl, bx, t0 + 1u, B, u1) : MF::identity();
         // suffix scan of the pairs within each half of the wavefront
-        unsigned long long P = hml_map_compose<K>(m0, m1);
+        unsigned long long P = MF::compose(m0, m1);
 #pragma unroll
         for (int d = 1; d < 32; d <<= 1) {
             unsigned long long o = hml_shfl_down_u64(P, d);
-            if (li + d >= 32) o = HML_MAP_IDENTITY;
-            P = hml_map_compose<K>(P, o);
+            if (li + d >= 32) o = MF::identity();
+            P = MF::compose(P, o);
         }
         unsigned long long later = hml_shfl_down_u64(P, 1);   // the pairs behind this one
-        if (li == 31) later = HML_MAP_IDENTITY;
+        if (li == 31) later = MF::identity();
         if (live) {
             if (t0 <= B) smap[t0] = P;
-            if (t0 + 1u <= B) smap[t0 + 1u] = hml_map_compose<K>(m1, later);
+            if (t0 + 1u <= B) smap[t0 + 1u] = MF::compose(m1, later);
             if (li == 0) cmap[c] = P;
         }
     }
@@ -405,6 +390,7 @@ __device__ __forceinline__ void hml_b_backward_chain(unsigned long long* __restr
                                                              int mode, int super_level, const uint32_t* __restrict__ starts) {
     // mode: bit 0 = repair step, bit 1 = chain.  super_level: the chain runs over the maps of super-chunks (64 backward
     // chunks each, hml_k_backward_super) - `cmap` and `entry_state` are then the super-level arrays.
+    using MF = hml_mapfmt<K>;
     __shared__ unsigned long long P[1024];
     __shared__ hml_repair_lds sh;
     const uint32_t B = mdl->B;
@@ -458,14 +444,14 @@ __device__ __forceinline__ void hml_b_backward_chain(unsigned long long* __restr
     // writable pointer each was a cache round trip of its own, twice.
     constexpr int CACHED = 4;
     unsigned long long mine[CACHED];
-    unsigned long long prod = HML_MAP_IDENTITY;
+    unsigned long long prod = MF::identity();
     if (per <= (uint32_t)CACHED) {   // workgroup-uniform
 #pragma unroll
-        for (int j = 0; j < CACHED; ++j) mine[j] = (a + (uint32_t)j < b) ? cmap[a + (uint32_t)j] : HML_MAP_IDENTITY;
+        for (int j = 0; j < CACHED; ++j) mine[j] = (a + (uint32_t)j < b) ? cmap[a + (uint32_t)j] : MF::identity();
 #pragma unroll
-        for (int j = CACHED - 1; j >= 0; --j) prod = hml_map_compose<K>(mine[j], prod);
+        for (int j = CACHED - 1; j >= 0; --j) prod = MF::compose(mine[j], prod);
     } else {
-        for (uint32_t c = b; c > a; --c) prod = hml_map_compose<K>(cmap[c - 1], prod);
+        for (uint32_t c = b; c > a; --c) prod = MF::compose(cmap[c - 1], prod);
     }
     // suffix products over the 1024 threads, Q[tid] = P[tid] o P[tid+1] o ... o P[1023]: inside a wavefront by shuffles
     // (S), the sixteen wavefront products by the first sixteen lanes (LDS, two barriers instead of twenty)
@@ -473,41 +459,41 @@ __device__ __forceinline__ void hml_b_backward_chain(unsigned long long* __restr
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         unsigned long long o = hml_shfl_down_u64(S, d);
-        if (lane + d >= 64) o = HML_MAP_IDENTITY;
-        S = hml_map_compose<K>(S, o);
+        if (lane + d >= 64) o = MF::identity();
+        S = MF::compose(S, o);
     }
     if (lane == 0) P[wave] = S;
     __syncthreads();
     if (tid < 64) {
-        unsigned long long w = (tid < 16) ? P[tid] : HML_MAP_IDENTITY;
+        unsigned long long w = (tid < 16) ? P[tid] : MF::identity();
 #pragma unroll
         for (int d = 1; d < 16; d <<= 1) {
             unsigned long long o = hml_shfl_down_u64(w, d);
-            if (tid + d >= 16) o = HML_MAP_IDENTITY;
-            w = hml_map_compose<K>(w, o);
+            if (tid + d >= 16) o = MF::identity();
+            w = MF::compose(w, o);
         }
         if (tid < 16) P[16 + tid] = w;   // P[16 + w] = product of the wavefronts w .. 15
     }
     __syncthreads();
-    const unsigned long long after_wave = (wave < 15) ? P[16 + wave + 1] : HML_MAP_IDENTITY;
+    const unsigned long long after_wave = (wave < 15) ? P[16 + wave + 1] : MF::identity();
     // the composition of everything behind this thread: Q[tid + 1]
     unsigned long long next_S = hml_shfl_down_u64(S, 1);
-    const unsigned long long later = (lane < 63) ? hml_map_compose<K>(next_S, after_wave) : after_wave;
+    const unsigned long long later = (lane < 63) ? MF::compose(next_S, after_wave) : after_wave;
     if (a >= b) return;
     // state entering this thread's last chunk = (composition of all later chunks)(dummy 0)
-    unsigned x = (unsigned)(later & 15ull);
+    unsigned x = MF::get(later, 0u);
     if (per <= (uint32_t)CACHED) {
 #pragma unroll
         for (int j = CACHED - 1; j >= 0; --j) {
             if (a + (uint32_t)j < b) {
                 entry_state[a + (uint32_t)j] = (uint8_t)x;
-                x = (unsigned)(mine[j] >> (4 * x)) & 15u;
+                x = MF::get(mine[j], x);
             }
         }
     } else {
         for (uint32_t c = b; c > a; --c) {
             entry_state[c - 1] = (uint8_t)x;
-            x = (unsigned)(cmap[c - 1] >> (4 * x)) & 15u;
+            x = MF::get(cmap[c - 1], x);
         }
     }
 }
@@ -532,32 +518,34 @@ HML_KERNEL __launch_bounds__(1024) void hml_k_backward_chain(unsigned long long*
 template <int K>
 HML_KERNEL __launch_bounds__(256) void hml_k_backward_super(const unsigned long long* __restrict__ cmap, const hml_model* __restrict__ mdl,
                                                             unsigned long long* __restrict__ scmap, unsigned long long* __restrict__ super) {
+    using MF = hml_mapfmt<K>;
     const uint32_t NC = (mdl->B + HML_BWD_CHUNK - 1u) / HML_BWD_CHUNK;
     const uint32_t NS = (NC + 63u) / 64u;
     const int lane = threadIdx.x & 63;
     const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
     for (uint32_t S = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; S < NS; S += nwaves) {
         const uint32_t c = S * 64u + (uint32_t)lane;
-        unsigned long long map = c < NC ? cmap[c] : HML_MAP_IDENTITY;
+        unsigned long long map = c < NC ? cmap[c] : MF::identity();
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
             unsigned long long o = hml_shfl_down_u64(map, d);
-            if (lane + d >= 64) o = HML_MAP_IDENTITY;
-            map = hml_map_compose<K>(map, o);
+            if (lane + d >= 64) o = MF::identity();
+            map = MF::compose(map, o);
         }
         if (c < NC) scmap[c] = map;
         if (lane == 0) super[S] = map;
     }
 }
 
+// (`bits`: the entry width of the maps' format, hml_mapfmt<K>::BITS - the one kernel here that is compiled once for all K)
 HML_KERNEL __launch_bounds__(256) void hml_k_backward_entries(const unsigned long long* __restrict__ scmap, const uint8_t* __restrict__ entry2,
-                                                              const hml_model* __restrict__ mdl, uint8_t* __restrict__ entry_state) {
+                                                              const hml_model* __restrict__ mdl, uint8_t* __restrict__ entry_state, uint32_t bits) {
     const uint32_t NC = (mdl->B + HML_BWD_CHUNK - 1u) / HML_BWD_CHUNK;
     const uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t c = blockIdx.x * blockDim.x + threadIdx.x; c < NC; c += stride) {
         const unsigned e2 = entry2[c >> 6];
         const bool last = (c & 63u) == 63u || c + 1u == NC;
-        entry_state[c] = last ? (uint8_t)e2 : (uint8_t)((scmap[c + 1u] >> (4u * e2)) & 15ull);
+        entry_state[c] = last ? (uint8_t)e2 : (uint8_t)hml_map_get_bits(scmap[c + 1u], e2, bits);
     }
 }
 
@@ -698,8 +686,8 @@ __device__ __forceinline__ void hml_b_counts(int16_t* __restrict__ q, const uint
         if (b < B) {
             int st, prev;
             if (FB) {
-                st = (int)((cur.m1 >> (4 * cur.e1)) & 15ull);
-                prev = (b == 0) ? 0 : (int)((cur.m0 >> (4 * cur.e0)) & 15ull);
+                st = (int)hml_mapfmt<K>::get(cur.m1, cur.e1);
+                prev = (b == 0) ? 0 : (int)hml_mapfmt<K>::get(cur.m0, cur.e0);
                 q[b] = (int16_t)st;
             } else {
                 st = cur.q1;
@@ -858,8 +846,8 @@ HML_KERNEL __launch_bounds__(256) void hml_k_counts_dense(int16_t* __restrict__ 
         const bool in = b < B;
         int st, prev;
         if (FB) {
-            st = (int)((cur.m1 >> (4 * cur.e1)) & 15ull);
-            prev = (b == 0) ? 0 : (int)((cur.m0 >> (4 * cur.e0)) & 15ull);
+            st = (int)hml_mapfmt<K>::get(cur.m1, cur.e1);
+            prev = (b == 0) ? 0 : (int)hml_mapfmt<K>::get(cur.m0, cur.e0);
         } else {
             st = cur.q1;
             prev = (b == 0) ? 0 : (int)cur.q0;

@@ -200,7 +200,8 @@ static void launch_forward_backward(hml_ctx* c, const hml_sweep_env& e, uint32_t
     chain(c->d_cmap, c->d_bentry, 1, 0);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_backward_super<KK>), dim3(grid_for(bch, 256, 16, 1 << 16)), dim3(256), 0, s, c->d_cmap, c->d_mdl, c->d_scmap, c->d_super);
     chain(c->d_super, c->d_bentry2, 2, 1);
-    hipLaunchKernelGGL(hml_k_backward_entries, dim3(grid_for(bch, 256, 16, 1 << 16)), dim3(256), 0, s, c->d_scmap, c->d_bentry2, c->d_mdl, c->d_bentry);
+    hipLaunchKernelGGL(hml_k_backward_entries, dim3(grid_for(bch, 256, 16, 1 << 16)), dim3(256), 0, s, c->d_scmap, c->d_bentry2, c->d_mdl, c->d_bentry,
+                       (uint32_t)hml_mapfmt<KK>::BITS);
 }
 
 // Sufficient statistics of the sweep's states.  MAPS: the states are still packed in the backward maps (the forward-backward
