@@ -120,6 +120,10 @@ SIGNATURES = {
     "hml_viterbi_states": (C.c_int, [_P, _P]),
     "hml_viterbi_scores": (C.c_int, [_P, _P, _P, _P]),
     "hml_viterbi_info": (C.c_int, [_P] + [C.POINTER(C.c_uint64)] * 6),
+    "hml_posterior": (C.c_int, [_P, _P, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    "hml_posterior_rle": (C.c_int, [_P, C.POINTER(C.c_uint64), _P, _P, _P]),
+    "hml_posterior_terms": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "hml_posterior_info": (C.c_int, [_P] + [C.POINTER(C.c_uint64)] * 7),
     "hml_recording_payload_size": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64)]),
     "hml_recording_export": (C.c_int, [_P, C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "hml_recording_merge_payload": (C.c_int, [_P, C.c_int, _P, C.c_uint64]),
@@ -687,6 +691,39 @@ class Chain:
         v = [C.c_uint64() for _ in range(6)]
         _check(self.lib.hml_viterbi_info(self.h, *[C.byref(x) for x in v]))
         return dict(zip(("chunks", "L", "W", "stale_chunks", "rounds", "serial_chunks"), (x.value for x in v)))
+
+    # ---- smoothing: state posteriors and log p(y | theta) under the current parameters ---------
+    def posterior(self):
+        """(gamma[B, K] float64, loglik, degenerate): p(q_b = j | y, theta) per block over the current blocks under the current
+        parameters, the marginal log-likelihood log p(y | theta) of the compressed model, and the number of blocks no path
+        reaches (hml_posterior)"""
+        gamma = np.empty((self.num_blocks(), self.K), np.float64)
+        loglik, degenerate = C.c_double(), C.c_uint64()
+        _check(self.lib.hml_posterior(self.h, gamma.ctypes.data, C.byref(loglik), C.byref(degenerate)))
+        return gamma, loglik.value, degenerate.value
+
+    def posterior_rle(self):
+        """(run_len[R], run_state[R], run_conf[R]): per block the most probable state, adjacent blocks of equal state merged,
+        lengths in positions; run_conf is the smallest posterior of that state over the run's blocks (hml_posterior_rle)"""
+        n, B = C.c_uint64(), self.num_blocks()      # (room for a run per block: one call, one computation)
+        ln, st, cf = np.empty(B, np.uint64), np.empty(B, np.int32), np.empty(B, np.float64)
+        _check(self.lib.hml_posterior_rle(self.h, C.byref(n), ln.ctypes.data, st.ctypes.data, cf.ctypes.data))
+        return ln[:n.value].copy(), st[:n.value].copy(), cf[:n.value].copy()
+
+    def posterior_terms(self):
+        """(e[B, K] float32, m[B] float32, alpha[B, K], c[B], beta[B, K] float64): the tables and rows a call uses
+        (hml_posterior_terms)"""
+        B, K = self.num_blocks(), self.K
+        e, m = np.empty((B, K), np.float32), np.empty(B, np.float32)
+        alpha, c, beta = np.empty((B, K), np.float64), np.empty(B, np.float64), np.empty((B, K), np.float64)
+        _check(self.lib.hml_posterior_terms(self.h, e.ctypes.data, m.ctypes.data, alpha.ctypes.data, c.ctypes.data, beta.ctypes.data))
+        return e, m, alpha, c, beta
+
+    def posterior_info(self):
+        """of the last call: dict(chunks, L, W, stale_fwd, stale_bwd, rounds, serial_chunks) (hml_posterior_info)"""
+        v = [C.c_uint64() for _ in range(7)]
+        _check(self.lib.hml_posterior_info(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("chunks", "L", "W", "stale_fwd", "stale_bwd", "rounds", "serial_chunks"), (x.value for x in v)))
 
     # ---- sparse payloads of the levels, breakpoints and bands (across GPUs) -------------------
     def recording_payload_size(self, kind):

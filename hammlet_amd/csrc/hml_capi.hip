@@ -1162,6 +1162,17 @@ int hml_set_option(hml_ctx* c, const char* name, int value) {
         c->vit.rounds = (uint32_t)value;
         return 0;
     }
+    // ... and the smoothing read-out's (hml_k_posterior.h)
+    if (std::string(name) == "posterior_W" || std::string(name) == "posterior_L") {
+        if (value < 0 || value > (1 << 20)) return set_err(HML_ERR_ARG, std::string(name) + ": a number of blocks up to 2^20, or 0 for the default");
+        (name[10] == 'W' ? c->post.W : c->post.L) = (uint32_t)value;
+        return 0;
+    }
+    if (std::string(name) == "posterior_rounds") {
+        if (value < 0 || value > 16) return set_err(HML_ERR_ARG, "posterior_rounds: 0 to 16 parallel repair rounds");
+        c->post.rounds = (uint32_t)value;
+        return 0;
+    }
     return set_err(HML_ERR_ARG, std::string("unknown option ") + name);
 }
 

@@ -213,6 +213,14 @@ struct hml_ctx {
         bool decoded = false;
         uint64_t chunks = 0, used_L = 0, used_W = 0, stale = 0, rounds_run = 0, walked = 0;
     } vit;
+    // Smoothing (hml_posterior; hml_k_posterior.h): the same - options "posterior_W", "posterior_L", "posterior_rounds" and
+    // what the last call did (hml_posterior_info).
+    struct {
+        uint32_t W = 0, L = 0;
+        uint32_t rounds = 8;
+        bool computed = false;
+        uint64_t chunks = 0, used_L = 0, used_W = 0, stale_fwd = 0, stale_bwd = 0, rounds_run = 0, walked = 0;
+    } post;
     // Every d_* above that is not a plain pointer owns its buffer (DevBuf / DevArr, hml_host_common.hpp): deleting the context
     // frees them, whatever a call that failed half-way left allocated, and allocating one again replaces what it held.
     ~hml_ctx() { if (h_B) (void)hipHostFree(h_B); }

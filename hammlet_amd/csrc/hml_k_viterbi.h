@@ -46,10 +46,9 @@ struct hml_vit_par {
     uint8_t map[HML_CAP_K][HML_MAX_D];
 };
 
-// one workgroup of 256: the parameters, init[K] and trans[K][K]
-HML_KERNEL __launch_bounds__(256) void hml_k_vit_tables(const hml_model* __restrict__ mdl, hml_vit_par* __restrict__ par,
-                                                        long long* __restrict__ trans, long long* __restrict__ init) {
-    const int tid = threadIdx.x, K = mdl->K, D = mdl->D, P = mdl->P;
+// the parameters, by the first K lanes of a workgroup
+__device__ __forceinline__ void hml_vit_par_fill(const hml_model* __restrict__ mdl, hml_vit_par* __restrict__ par, int tid) {
+    const int K = mdl->K, D = mdl->D, P = mdl->P;
     if (tid == 0) { par->K = K; par->D = D; par->P = P; par->self = mdl->self_trans != 0; par->T = mdl->T; par->B = mdl->B; }
     if (tid < P) {
         const float v = mdl->var[tid];
@@ -66,8 +65,15 @@ HML_KERNEL __launch_bounds__(256) void hml_k_vit_tables(const hml_model* __restr
         par->logNs[tid] = r;
         par->logA[tid] = hml_logf(mdl->A[tid * K + tid]);
         for (int d = 0; d < HML_MAX_D; ++d) par->map[tid][d] = mdl->map[tid][d];
-        init[tid] = hml_vit_fx((double)hml_logf(mdl->pi[tid]));
     }
+}
+
+// one workgroup of 256: the parameters, init[K] and trans[K][K]
+HML_KERNEL __launch_bounds__(256) void hml_k_vit_tables(const hml_model* __restrict__ mdl, hml_vit_par* __restrict__ par,
+                                                        long long* __restrict__ trans, long long* __restrict__ init) {
+    const int tid = threadIdx.x, K = mdl->K;
+    hml_vit_par_fill(mdl, par, tid);
+    if (tid < K) init[tid] = hml_vit_fx((double)hml_logf(mdl->pi[tid]));
     for (int i = tid; i < K * K; i += 256) trans[i] = hml_vit_fx((double)hml_logf(mdl->A[i]));
 }
 
@@ -85,8 +91,8 @@ __device__ __forceinline__ void hml_vit_block_load(const hml_vit_par* __restrict
         if (d < D) hml_block_stats_one(ia + (uint64_t)d * plane, st, en, blk.sx[d], blk.sq[d]);
     blk.N = (float)(en - st);
 }
-// emit[b][s]: E of hml_emit_compute / hml_k_emission_mv, quantised
-__device__ __forceinline__ long long hml_vit_emit(const hml_vit_par* __restrict__ par, const hml_vit_block& blk, int s) {
+// E_b(s) of hml_emit_compute / hml_k_emission_mv
+__device__ __forceinline__ float hml_vit_emit_float(const hml_vit_par* __restrict__ par, const hml_vit_block& blk, int s) {
     const int D = par->D;
     float r = 0.0f;
 #pragma unroll
@@ -98,7 +104,11 @@ __device__ __forceinline__ long long hml_vit_emit(const hml_vit_par* __restrict_
     }
     float e = r - blk.N * par->logNs[s];
     if (par->self) e += (blk.N - 1.0f) * par->logA[s];
-    return hml_vit_fx((double)e);
+    return e;
+}
+// emit[b][s]: the same, quantised
+__device__ __forceinline__ long long hml_vit_emit(const hml_vit_par* __restrict__ par, const hml_vit_block& blk, int s) {
+    return hml_vit_fx((double)hml_vit_emit_float(par, blk, s));
 }
 
 // probe: the whole table emit[B][K], a lane per block

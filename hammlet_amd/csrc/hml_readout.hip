@@ -1420,3 +1420,240 @@ int hml_viterbi_info(hml_ctx* c, uint64_t* chunks, uint64_t* L, uint64_t* W, uin
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------- smoothing (hml_k_posterior.h)
+// State posteriors per block, log p(y | theta) and the call with a confidence per run: the sum-product sibling of the decode
+// above, with the same relation to the chain (read only) and to device memory (all of it local to the call).
+#include "hml_k_posterior.h"   // (launched from this object alone)
+
+struct post_tables { DevBuf par, A, pi; };
+struct post_result {
+    DevBuf gamma, q, conf, alpha, cval, beta;   // gamma only if asked for
+    double loglik = 0.0;
+    uint64_t degenerate = 0;
+    uint32_t B = 0;
+};
+
+template <int KM, int DIR>
+static void post_launch_first(hml_ctx* c, const hml_post_args& a, size_t lds) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_post_first<KM, DIR>), dim3((a.n_chunks + 63u) / 64u), dim3(64), lds, c->stream, a);
+}
+template <int KM, int DIR>
+static void post_launch_rerun(hml_ctx* c, const hml_post_args& a, size_t lds, const uint32_t* heads, uint32_t n_heads, const uint8_t* match) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_post_rerun<KM, DIR>), dim3((n_heads + 63u) / 64u), dim3(64), lds, c->stream, a, heads, n_heads, match);
+}
+template <int KM, int DIR>
+static void post_launch_finish(hml_ctx* c, const hml_post_args& a, size_t lds, const uint8_t* match, unsigned long long* walked) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_post_finish<KM, DIR>), dim3(1), dim3(64), lds, c->stream, a, match, walked);
+}
+#define POST_BY_K(K, DIR, fn, ...) do { if ((K) <= 8) fn<8, DIR>(__VA_ARGS__); else if ((K) <= 16) fn<16, DIR>(__VA_ARGS__); else fn<HML_CAP_K, DIR>(__VA_ARGS__); } while (0)
+
+// how a call begins: a settled chain with blocks, and the tables (parameters, A and pi in double) on the device
+static int post_begin(hml_ctx* c, post_tables& t, uint32_t* B_out) {
+    hml_model m; if (int r = fetch_model(c, &m)) return r;
+    if (int r = model_fault(m)) return r;
+    if (m.halted) return set_err(HML_ERR_ARG, "hml_posterior: the chain is halted; settle it with hml_sync first");
+    if (m.B == 0) return set_err(HML_ERR_ARG, "hml_posterior: no blocks yet: run a sweep or hml_create_blocks first");
+    const int K = c->K;
+    HIPCHK(t.par.alloc(sizeof(hml_vit_par)));
+    HIPCHK(t.A.alloc((uint64_t)K * K * sizeof(double)));
+    HIPCHK(t.pi.alloc((uint64_t)K * sizeof(double)));
+    hipLaunchKernelGGL(hml_k_post_tables, dim3(1), dim3(256), 0, c->stream, c->d_mdl.get(), t.par.as<hml_vit_par>(), t.A.as<double>(), t.pi.as<double>());
+    KLAUNCH_CHECK();
+    *B_out = m.B;
+    return 0;
+}
+
+// one direction: first run, then verify / repair in rounds / the single lane, as vit_decode does it
+template <int DIR>
+static int post_direction(hml_ctx* c, const hml_post_args& a, int K, uint8_t* match, uint32_t* list, unsigned long long* words, uint64_t* stale_first_out,
+                          uint64_t* rounds_out, bool* finished_out) {
+    const size_t lds = ((size_t)K * K + K) * sizeof(double);
+    POST_BY_K(K, DIR, post_launch_first, c, a, lds);
+    KLAUNCH_CHECK();
+    uint32_t n_stale = 0;
+    uint64_t rounds_run = 0;
+    for (uint32_t round = 0;; ++round) {
+        uint32_t h_cnt[2] = {0, 0};   // stale chunks, heads of their runs
+        HIPCHK(hipMemsetAsync(words, 0, sizeof h_cnt, c->stream));
+        hipLaunchKernelGGL(hml_k_vit_verify, dim3(grid_for(a.n_chunks, 256, 1, 4096)), dim3(256), 0, c->stream, reinterpret_cast<const long long*>(a.entry),
+                           reinterpret_cast<const long long*>(a.exitv), K, a.n_chunks, match, list, (uint32_t*)words, (uint32_t*)words + 1);
+        KLAUNCH_CHECK();
+        HIPCHK(hipMemcpyAsync(h_cnt, words, sizeof h_cnt, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        n_stale = h_cnt[0];
+        if (round == 0) *stale_first_out = n_stale;
+        if (n_stale == 0 || round >= c->post.rounds) break;
+        POST_BY_K(K, DIR, post_launch_rerun, c, a, lds, list, h_cnt[1], match);
+        KLAUNCH_CHECK();
+        rounds_run = round + 1u;
+    }
+    if (n_stale) {
+        POST_BY_K(K, DIR, post_launch_finish, c, a, lds, match, words + 1);
+        KLAUNCH_CHECK();
+    }
+    *rounds_out = rounds_run;
+    *finished_out = n_stale != 0;
+    return 0;
+}
+
+// the whole computation; the rows alpha, c and beta stay in `out` for the probe
+static int post_compute(hml_ctx* c, bool want_gamma, post_result& out) {
+    post_tables t;
+    uint32_t B = 0;
+    if (int r = post_begin(c, t, &B)) return r;
+    const int K = c->K;
+    const uint32_t L = c->post.L ? c->post.L : HML_POST_DEFAULT_L;
+    const uint32_t W = c->post.W ? c->post.W : HML_POST_DEFAULT_W;
+    const uint32_t n_chunks = (uint32_t)(((uint64_t)B + L - 1u) / L);
+    const uint64_t n1 = ((uint64_t)B + 63u) / 64u, n2 = (n1 + 63u) / 64u;   // the first two levels of the tree
+    DevBuf b_entry, b_exit, b_match, b_list, b_words, b_ell, b_t1, b_t2;
+    HIPCHK(out.alpha.alloc((uint64_t)B * K * sizeof(double)));
+    HIPCHK(out.beta.alloc((uint64_t)B * K * sizeof(double)));
+    HIPCHK(out.cval.alloc((uint64_t)B * sizeof(double)));
+    HIPCHK(b_ell.alloc((uint64_t)B * sizeof(double)));
+    HIPCHK(b_entry.alloc((uint64_t)n_chunks * K * sizeof(double)));
+    HIPCHK(b_exit.alloc((uint64_t)n_chunks * K * sizeof(double)));
+    HIPCHK(b_match.alloc(n_chunks));
+    HIPCHK(b_list.alloc((uint64_t)n_chunks * sizeof(uint32_t)));
+    HIPCHK(b_words.alloc(4 * sizeof(unsigned long long)));   // [0] stale chunks and heads (32 bits each), [1] chunks the single lane ran, [2] degenerate blocks, [3] log-likelihood
+    HIPCHK(b_t1.alloc(n1 * sizeof(double)));
+    HIPCHK(b_t2.alloc(n2 * sizeof(double)));
+    HIPCHK(out.q.alloc((uint64_t)B * sizeof(int16_t)));
+    HIPCHK(out.conf.alloc((uint64_t)B * sizeof(double)));
+    if (want_gamma) HIPCHK(out.gamma.alloc((uint64_t)B * K * sizeof(double)));
+    unsigned long long* const words = b_words.as<unsigned long long>();
+    HIPCHK(hipMemsetAsync(words, 0, 4 * sizeof(unsigned long long), c->stream));
+
+    hml_post_args a;
+    a.par = t.par.as<hml_vit_par>(); a.A = t.A.as<double>(); a.pi = t.pi.as<double>();
+    a.ia = c->d_ia; a.starts = c->d_starts.get();
+    a.L = L; a.W = W; a.n_chunks = n_chunks;
+    a.entry = b_entry.as<double>(); a.exitv = b_exit.as<double>();
+    uint64_t stale[2] = {0, 0}, rounds[2] = {0, 0};
+    bool finished[2] = {false, false};
+    a.rows = out.alpha.as<double>(); a.cval = out.cval.as<double>(); a.ell = b_ell.as<double>();
+    if (int r = post_direction<0>(c, a, K, b_match.as<uint8_t>(), b_list.as<uint32_t>(), words, &stale[0], &rounds[0], &finished[0])) return r;
+    a.rows = out.beta.as<double>(); a.cval = nullptr; a.ell = nullptr;   // (entry, exit, match and list are used again)
+    if (int r = post_direction<1>(c, a, K, b_match.as<uint8_t>(), b_list.as<uint32_t>(), words, &stale[1], &rounds[1], &finished[1])) return r;
+
+    hipLaunchKernelGGL(hml_k_post_combine, dim3(grid_for(B, 256, 1, 16384)), dim3(256), 0, c->stream, out.alpha.as<double>(), out.beta.as<double>(), out.cval.as<double>(), K, B,
+                       want_gamma ? out.gamma.as<double>() : nullptr, out.q.as<int16_t>(), out.conf.as<double>(), words + 2);
+    // the tree over l_b: levels until one value is left
+    const double* level = b_ell.as<double>();
+    uint64_t n = B;
+    double* bufs[2] = {b_t1.as<double>(), b_t2.as<double>()};
+    for (int k = 0; n > 1; ++k) {
+        double* const dst = bufs[k & 1];
+        hipLaunchKernelGGL(hml_k_post_tree, dim3(grid_for((n + 63u) / 64u, 256, 1, 4096)), dim3(256), 0, c->stream, level, n, dst);
+        level = dst;
+        n = (n + 63u) / 64u;
+    }
+    KLAUNCH_CHECK();
+    unsigned long long h_words[4];
+    HIPCHK(hipMemcpyAsync(h_words, words, sizeof h_words, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&out.loglik, level, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));   // (the scratch goes with this frame)
+    out.degenerate = h_words[2];
+    out.B = B;
+    c->post.computed = true;
+    c->post.chunks = n_chunks; c->post.used_L = L; c->post.used_W = W; c->post.stale_fwd = stale[0]; c->post.stale_bwd = stale[1];
+    c->post.rounds_run = std::max(rounds[0], rounds[1]); c->post.walked = (finished[0] || finished[1]) ? h_words[1] : 0;
+    return 0;
+}
+
+extern "C" {
+
+int hml_posterior(hml_ctx* c, double* gamma, double* loglik, uint64_t* degenerate) {
+    NEED_MODEL();
+    post_result p;
+    if (int r = post_compute(c, gamma != nullptr, p)) return r;
+    if (gamma) {
+        HIPCHK(hipMemcpyAsync(gamma, p.gamma.get(), (uint64_t)p.B * c->K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    if (loglik) *loglik = p.loglik;
+    if (degenerate) *degenerate = p.degenerate;
+    return 0;
+}
+
+int hml_posterior_rle(hml_ctx* c, uint64_t* n_runs, uint64_t* run_len, int32_t* run_state, double* run_conf) {
+    NEED_MODEL();
+    if (!n_runs) return set_err(HML_ERR_ARG, "null argument");
+    post_result p;
+    if (int r = post_compute(c, false, p)) return r;
+    // runs of equal state over the blocks, as hml_viterbi forms them, each with the minimum of its blocks' posteriors
+    const uint32_t M = p.B;
+    const uint32_t n_chunks = (M + 255u) / 256u;
+    DevBuf b_rc, b_rs, b_rq, b_rconf;
+    HIPCHK(b_rc.alloc(((uint64_t)n_chunks + 1) * sizeof(int32_t)));
+    int32_t* const d_rc = b_rc.as<int32_t>();
+    HIPCHK(hipMemsetAsync(d_rc + n_chunks, 0, sizeof(int32_t), c->stream));
+    hipLaunchKernelGGL(hml_k_seg_run_count, dim3(n_chunks), dim3(256), 0, c->stream, p.q.as<int16_t>(), M, d_rc);
+    hipLaunchKernelGGL(hml_k_scan_chunks<int32_t>, dim3(1), dim3(1024), 0, c->stream, d_rc, n_chunks + 1u);   // d_rc[n_chunks] = total
+    KLAUNCH_CHECK();
+    int32_t R = 0;
+    HIPCHK(hipMemcpyAsync(&R, d_rc + n_chunks, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *n_runs = (uint64_t)R;
+    if (!run_len) return 0;
+    HIPCHK(b_rs.alloc((uint64_t)R * sizeof(uint32_t)));
+    HIPCHK(b_rq.alloc((uint64_t)R * sizeof(int16_t)));
+    HIPCHK(b_rconf.alloc((uint64_t)R * sizeof(double)));
+    HIPCHK(hipMemsetAsync(b_rconf.get(), 0xff, (uint64_t)R * sizeof(double), c->stream));
+    hipLaunchKernelGGL(hml_k_post_run_scatter, dim3(n_chunks), dim3(256), 0, c->stream, p.q.as<int16_t>(), p.conf.as<double>(), c->d_starts.get(), M, d_rc, b_rs.as<uint32_t>(),
+                       b_rq.as<int16_t>(), b_rconf.as<unsigned long long>());
+    KLAUNCH_CHECK();
+    std::vector<uint32_t> h_rs(R);
+    std::vector<int16_t> h_rq(R);
+    HIPCHK(hipMemcpyAsync(h_rs.data(), b_rs.get(), (uint64_t)R * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(h_rq.data(), b_rq.get(), (uint64_t)R * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
+    if (run_conf) HIPCHK(hipMemcpyAsync(run_conf, b_rconf.get(), (uint64_t)R * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    lengths_of(h_rs.data(), (uint64_t)R, (uint32_t)c->T, run_len);
+    if (run_state) std::copy(h_rq.begin(), h_rq.end(), run_state);
+    return 0;
+}
+
+int hml_posterior_terms(hml_ctx* c, float* e, float* m, double* alpha, double* cval, double* beta) {
+    NEED_MODEL();
+    const int K = c->K;
+    if (e || m) {
+        post_tables t;
+        uint32_t B = 0;
+        if (int r = post_begin(c, t, &B)) return r;
+        DevBuf b_e, b_m;
+        if (e) HIPCHK(b_e.alloc((uint64_t)B * K * sizeof(float)));
+        if (m) HIPCHK(b_m.alloc((uint64_t)B * sizeof(float)));
+        hipLaunchKernelGGL(hml_k_post_term_table, dim3(grid_for(B, 256, 1, 16384)), dim3(256), 0, c->stream, t.par.as<hml_vit_par>(), c->d_ia, c->d_starts.get(), b_e.as<float>(),
+                           b_m.as<float>());
+        KLAUNCH_CHECK();
+        if (e) HIPCHK(hipMemcpyAsync(e, b_e.get(), (uint64_t)B * K * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        if (m) HIPCHK(hipMemcpyAsync(m, b_m.get(), (uint64_t)B * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    if (alpha || cval || beta || !(e || m)) {
+        post_result p;
+        if (int r = post_compute(c, false, p)) return r;
+        if (alpha) HIPCHK(hipMemcpyAsync(alpha, p.alpha.get(), (uint64_t)p.B * K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (cval) HIPCHK(hipMemcpyAsync(cval, p.cval.get(), (uint64_t)p.B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (beta) HIPCHK(hipMemcpyAsync(beta, p.beta.get(), (uint64_t)p.B * K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    return 0;
+}
+
+int hml_posterior_info(hml_ctx* c, uint64_t* chunks, uint64_t* L, uint64_t* W, uint64_t* stale_fwd, uint64_t* stale_bwd, uint64_t* rounds, uint64_t* serial_chunks) {
+    if (!c) return set_err(HML_ERR_ARG, "null context");
+    if (!c->post.computed) return set_err(HML_ERR_ARG, "hml_posterior_info: nothing was computed yet");
+    if (chunks) *chunks = c->post.chunks;
+    if (L) *L = c->post.used_L;
+    if (W) *W = c->post.used_W;
+    if (stale_fwd) *stale_fwd = c->post.stale_fwd;
+    if (stale_bwd) *stale_bwd = c->post.stale_bwd;
+    if (rounds) *rounds = c->post.rounds_run;
+    if (serial_chunks) *serial_chunks = c->post.walked;
+    return 0;
+}
+
+}  // extern "C"

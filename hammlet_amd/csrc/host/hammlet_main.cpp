@@ -23,6 +23,9 @@
 // (hml_set_regions, hml_regions_read); with -chains N the chains' sums are added into the first chain's, on any GPUs;
 // `-O V` (viterbi) writes PREFIXviterbiSUFFIX, the jointly most probable state path under the chain's final parameters and last block
 // structure, in the maxsegmentation file's format (hml_viterbi; with -chains N one file per chain, PREFIXchainK.viterbiSUFFIX);
+// `-O PD` (posterior) writes PREFIXposteriorSUFFIX under the same parameters and blocks: log p(y | theta) and the number of degenerate
+// blocks, then per run of equal called state its length, the state and its smallest posterior (hml_posterior, hml_posterior_rle;
+// with -chains N one file per chain, PREFIXchainK.posteriorSUFFIX);
 // -raw FILE reads float32 values instead of text; -device N selects
 // the GPU; -chain N selects the Philox sub-key of an independent chain; -chains N runs N independent chains (sub-keys
 // chain .. chain+N-1), chain k on GPU (device + k) mod #GPUs in its own host thread, and pools their recorded marginals
@@ -64,6 +67,11 @@ static const char* kHelp =
     "                    V            viterbi: the jointly most probable state path under the chain's final parameters and\n"
     "                                 last block structure, decoded on the device after the scheme has run, in the\n"
     "                                 maxsegmentation file's format; with -chains N one file per chain (extension)\n"
+    "                    PD           posterior: smoothing under the chain's final parameters and last block structure, computed\n"
+    "                                 on the device after the scheme has run - first line log p(y|theta) and the number of\n"
+    "                                 blocks no path reaches, then one line per run of equal most probable state: length, state\n"
+    "                                 and the smallest posterior of that state over the run; with -chains N one file per chain;\n"
+    "                                 needs a scheme with forward-backward sweeps (extension)\n"
     "                    L            levels: length, then posterior mean and standard deviation of the emission level\n"
     "                                 per data dimension, one line per segment - the denoised trace (extension)\n"
     "                    BP           breakpoints: position, number of recorded sweeps that change state there, and that\n"
@@ -517,6 +525,12 @@ static void writeViterbiFile(const Job& job, int index, hml_ctx* ctx) {
     if (job.outputs.at("viterbi")) Viterbi(ctx).writeFile(viterbiFileName(job, index));
 }
 
+// PREFIX[chainK.]posteriorSUFFIX: smoothing at the same moment
+static string posteriorFileName(const Job& job, int index) { return job.opref + (index == 0 ? "" : "chain" + std::to_string(index) + ".") + "posterior" + job.osuff; }
+static void writePosteriorFile(const Job& job, int index, hml_ctx* ctx) {
+    if (job.outputs.at("posterior")) Posterior(ctx).writeFile(posteriorFileName(job, index));
+}
+
 static string historyFileName(const Job& job) { return job.opref + "history" + job.osuff; }
 static string historySummaryFileName(const Job& job) { return job.opref + "historysummary" + job.osuff; }
 // the chains' histories, in chain order (hammlet/History.hpp): read through the host, whichever GPUs the chains are on
@@ -633,6 +647,7 @@ static void runChain(const Job& job, vector<real_t>& inputValues, bool steal, in
         if (run.token(st)) run.sweeps(st);
     hml_check(hml_sync(run.RNG.ctx()));
     writeViterbiFile(job, index, run.RNG.ctx());
+    writePosteriorFile(job, index, run.RNG.ctx());
     if (!rendezvous) writeContextFiles(job, run.RNG.ctx());   // (several chains: the main thread merges and writes)
     if (!rendezvous) writeHistoryFiles(job, {run.RNG.ctx()});
     if (rendezvous && !rendezvous->arrive(index, run.RNG.ctx())) run.records.discardMarginals();   // pooling failed elsewhere
@@ -678,6 +693,7 @@ static void runDeviceGroup(const Job& job, vector<real_t>& inputValues, int devi
     vector<hml_ctx*> ctxs;
     for (auto& r : runs) { hml_check(hml_sync(r->RNG.ctx())); ctxs.push_back(r->RNG.ctx()); }
     for (auto& r : runs) writeViterbiFile(job, r->index, r->RNG.ctx());
+    for (auto& r : runs) writePosteriorFile(job, r->index, r->RNG.ctx());
     const bool pooled = !rendezvous || rendezvous->arrive(indices, ctxs);
     for (auto& r : runs) { if (!pooled) r->records.discardMarginals(); r->records.close(); }
 }
@@ -795,6 +811,7 @@ int main(int argc, const char* argv[]) {
         outputArgs.registerFlags({"G", "segments"});
         outputArgs.registerFlags({"X", "maxsegmentation"});   // extension
         outputArgs.registerFlags({"V", "viterbi"});           // extension
+        outputArgs.registerFlags({"PD", "posterior"});        // extension (P is the reference's parameters)
         outputArgs.registerFlags({"L", "levels"});            // extension
         outputArgs.registerFlags({"BP", "breakpoints"});      // extension (B and C are the reference's blocks and compression)
         outputArgs.registerFlags({"CS", "consensus"});        // extension
@@ -876,7 +893,7 @@ int main(int argc, const char* argv[]) {
         job.weightMultiplier = weightMultiplier; job.useSelfTrans = useSelfTrans;
         job.thetaParams = thetaParams; job.trans = trans; job.selfTrans = selfTrans; job.initialAlpha = initialAlpha;
         job.scheme = scheme;
-        for (const char* o : {"sequences", "parameters", "blocks", "compression", "marginals", "segments", "maxsegmentation", "viterbi", "levels", "breakpoints", "consensus", "bands", "bandcalls", "rhat", "regions", "history", "historysummary"})
+        for (const char* o : {"sequences", "parameters", "blocks", "compression", "marginals", "segments", "maxsegmentation", "viterbi", "posterior", "levels", "breakpoints", "consensus", "bands", "bandcalls", "rhat", "regions", "history", "historysummary"})
             job.outputs[o] = outputArgs.isSet(o);
         auto refuseExisting = [&](const string& fn) {
             if (!overwrite) { std::ifstream probe(fn); if (probe.good()) throw std::runtime_error("File " + fn + " already exists! Use -w to allow overwrite!"); }
@@ -942,6 +959,13 @@ int main(int argc, const char* argv[]) {
         }
         if (job.outputs.at("viterbi"))
             for (long k = 0; k < (long)nrChains; ++k) refuseExisting(viterbiFileName(job, (int)k));
+        if (job.outputs.at("posterior")) {
+            // smoothing sums over paths with transitions: a scheme of mixture sweeps alone never samples A
+            bool anyFB = false;
+            for (const Step& st : scheme) anyFB = anyFB || st.method == "F";
+            if (!anyFB) throw std::runtime_error("The output posterior (PD) needs a model with transitions: the scheme has mixture sweeps only!");
+            for (long k = 0; k < (long)nrChains; ++k) refuseExisting(posteriorFileName(job, (int)k));
+        }
         if (job.outputs.at("bands")) refuseExisting(bandsFileName(job));
         if (job.outputs.at("bandcalls")) refuseExisting(bandCallsFileName(job));
         if (job.outputs.at("levels")) refuseExisting(levelsFileName(job));

@@ -1,0 +1,84 @@
+// Posterior - smoothing under the chain's current parameters (include/hml.h, hml_posterior ... hml_posterior_info; no
+// counterpart in the reference): the marginal log-likelihood log p(y | theta) of the compressed model, the call per position
+// with a confidence per run, and the file the driver writes from them:
+//   PREFIXposteriorSUFFIX   `-O PD`: first line "loglik<TAB>degenerate" (%.17g, integer), then "length<TAB>state<TAB>confidence"
+//                           per run of equal called state - the maxsegmentation file's columns and, as %.17g, the smallest
+//                           posterior of that state over the run's blocks
+// A thin handle over a context that something else owns (the chain's rng_t), next to Viterbi.  Every call computes anew; the
+// chain is only read.
+#ifndef HAMMLET_POSTERIOR_HPP
+#define HAMMLET_POSTERIOR_HPP
+
+#include <cstdio>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "../hml.h"
+
+namespace hammlet {
+
+class Posterior {
+    hml_ctx* mCtx;
+    static void check(int rc) { if (rc != 0) throw std::runtime_error(hml_last_error()); }
+
+public:
+    struct Runs {
+        std::vector<uint64_t> length;   // positions per run
+        std::vector<int32_t> state;
+        std::vector<double> confidence; // min over the run's blocks of p(q_b = state | y, theta)
+    };
+    struct Info { uint64_t chunks = 0, L = 0, W = 0, staleForward = 0, staleBackward = 0, rounds = 0, serialChunks = 0; };
+
+    explicit Posterior(hml_ctx* ctx) : mCtx(ctx) {}
+    // launch geometry only (0: the defaults): never part of the result
+    void setGeometry(int W, int L, int rounds) {
+        check(hml_set_option(mCtx, "posterior_W", W));
+        check(hml_set_option(mCtx, "posterior_L", L));
+        check(hml_set_option(mCtx, "posterior_rounds", rounds));
+    }
+    // log p(y | theta); `degenerate` (if given): the blocks no path reaches - the value is then -inf or not a number
+    double loglik(uint64_t* degenerate = nullptr) const {
+        double l = 0;
+        check(hml_posterior(mCtx, nullptr, &l, degenerate));
+        return l;
+    }
+    // gamma[B][K], row-major, for the model's K states
+    std::vector<double> gamma(int K) const {
+        uint64_t B = 0;
+        check(hml_get_num_blocks(mCtx, &B));
+        std::vector<double> g(B * (uint64_t)K);
+        check(hml_posterior(mCtx, g.data(), nullptr, nullptr));
+        return g;
+    }
+    Runs runs() const {
+        Runs r;
+        uint64_t n = 0;
+        check(hml_posterior_rle(mCtx, &n, nullptr, nullptr, nullptr));
+        r.length.resize(n);
+        r.state.resize(n);
+        r.confidence.resize(n);
+        check(hml_posterior_rle(mCtx, &n, r.length.data(), r.state.data(), r.confidence.data()));
+        return r;
+    }
+    Info info() const {
+        Info i;
+        check(hml_posterior_info(mCtx, &i.chunks, &i.L, &i.W, &i.staleForward, &i.staleBackward, &i.rounds, &i.serialChunks));
+        return i;
+    }
+
+    void writeFile(const std::string& fn) const {
+        uint64_t degenerate = 0;
+        const double l = loglik(&degenerate);
+        const Runs r = runs();
+        FILE* out = fopen(fn.c_str(), "w");
+        if (!out) throw std::runtime_error("Cannot write to file " + fn + "!");
+        fprintf(out, "%.17g\t%llu\n", l, (unsigned long long)degenerate);
+        for (size_t i = 0; i < r.length.size(); ++i) fprintf(out, "%llu\t%d\t%.17g\n", (unsigned long long)r.length[i], (int)r.state[i], r.confidence[i]);
+        if (fclose(out) != 0) throw std::runtime_error("Cannot write to file " + fn + "!");
+    }
+};
+
+}  // namespace hammlet
+
+#endif

@@ -619,6 +619,7 @@ template <> inline char StateSequence<Mixture>::method() { return HML_METHOD_MIX
 #include "Records.hpp"
 #include "History.hpp"
 #include "Viterbi.hpp"
+#include "Posterior.hpp"
 
 namespace hammlet {
 

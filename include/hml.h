@@ -519,6 +519,40 @@ int hml_viterbi_states(hml_ctx* ctx, int16_t* q /*B*/);
 int hml_viterbi_scores(hml_ctx* ctx, int64_t* emit /*B*K*/, int64_t* trans /*K*K*/, int64_t* init /*K*/);
 int hml_viterbi_info(hml_ctx* ctx, uint64_t* chunks, uint64_t* L, uint64_t* W, uint64_t* stale_chunks, uint64_t* rounds, uint64_t* serial_chunks);
 
+/* ---- smoothing: state posteriors per block and log p(y | theta).  No counterpart in the reference. ----
+ * The sum over paths where hml_viterbi takes the maximum: with the weight of a path q over the context's current B blocks
+ *     pi(q_0) prod_b exp E_b(q_b) prod_{b > 0} A(q_{b-1}, q_b)
+ * (E_b(s) as above: the float hml_viterbi quantises), gamma[b][j] = p(q_b = j | y, theta) is the share of the paths through
+ * state j at block b, and loglik = log p(y | theta) the logarithm of the sum of all weights - the MARGINAL likelihood of the
+ * compressed model, which no sampled path enters (the history's ll columns are the complete-data values).  The chain is only
+ * read: its next sweeps are the same with or without.
+ *
+ * The tables m_b = max_j E_b(j) and e_b(j) = expf(E_b(j) - m_b) are the sweep's floats.  Everything after them is IEEE double
+ * on exactly widened floats in one fixed order, so that the same input gives the same words on every device and under every
+ * launch geometry: the forward recursion normalised per block (a_b(j) = e_b(j) sum_i alpha_{b-1}(i) A_ij, c_b = sum_j a_b(j),
+ * alpha_b = a_b / c_b), the backward recursion normalised likewise from beta_{B-1} = 1 / K, gamma_b = alpha_b beta_b over its
+ * sum, and loglik = the fan-in-64 tree sum of l_b = m_b + log c_b.  A block no path reaches (c_b not a positive finite number)
+ * is DEGENERATE: alpha_b restarts from 1 / K, loglik is what IEEE gives (-inf or not-a-number) and `degenerate` counts such
+ * blocks; gamma holds no not-a-number.  hammlet_amd/csrc/hml_posterior_ref.h states every step and restates it for one host
+ * thread.
+ *
+ * hml_posterior: gamma (may be NULL), loglik, degenerate (either may be NULL).  hml_posterior_rle: the call per position -
+ * per block the smallest state at the maximum of gamma_b, adjacent blocks of equal state merged into runs over positions,
+ * run_conf the minimum over a run's blocks of the posterior of its state; call with run_len == NULL to obtain the number of
+ * runs (run_state and run_conf may be NULL).  hml_posterior_terms: the tables and rows a call uses (probe; any may be NULL).
+ * Every call computes anew, with device memory of its own that is released before it returns.  A context without blocks is
+ * refused.  A context always holds a transition matrix; a model meant as a mixture alone (no transitions) is not this
+ * read-out's subject, and the driver refuses the output for a scheme of mixture sweeps only.
+ * hml_posterior_info, of the last call: chunks the blocks were cut into, their length L and warm-up W in blocks, the chunks
+ * found stale after the first pass of the forward and of the backward recursion, the parallel repair rounds run (the larger
+ * of the two directions'), the chunks the single finishing lane ran again (both directions; any may be NULL).  Options
+ * "posterior_W", "posterior_L" (blocks, up to 2^20; 0: the defaults of 256 and 64) and "posterior_rounds" (0 ... 16, default
+ * 8) are launch geometry: no word of any result depends on them ("Smoothing"). */
+int hml_posterior(hml_ctx* ctx, double* gamma /*B*K, may be NULL*/, double* loglik, uint64_t* degenerate);
+int hml_posterior_rle(hml_ctx* ctx, uint64_t* n_runs, uint64_t* run_len /*n_runs*/, int32_t* run_state /*n_runs*/, double* run_conf /*n_runs*/);
+int hml_posterior_terms(hml_ctx* ctx, float* e /*B*K*/, float* m /*B*/, double* alpha /*B*K*/, double* c /*B*/, double* beta /*B*K*/);
+int hml_posterior_info(hml_ctx* ctx, uint64_t* chunks, uint64_t* L, uint64_t* W, uint64_t* stale_fwd, uint64_t* stale_bwd, uint64_t* rounds, uint64_t* serial_chunks);
+
 /* ---- sparse payloads: levels, breakpoints and bands across GPUs.  No counterpart in the reference. ----
  * The three recordings above keep a cell and a boundary bit per change of state, so what another GPU needs of one is a list:
  * the M positions with a cell and the cells there.  The PAYLOAD is one contiguous buffer in device memory, little endian,
