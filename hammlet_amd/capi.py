@@ -124,6 +124,9 @@ SIGNATURES = {
     "hml_posterior_rle": (C.c_int, [_P, C.POINTER(C.c_uint64), _P, _P, _P]),
     "hml_posterior_terms": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "hml_posterior_info": (C.c_int, [_P] + [C.POINTER(C.c_uint64)] * 7),
+    "hml_expected_counts": (C.c_int, [_P] * 7 + [C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "hml_em_step": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    "hml_em_fit": (C.c_int, [_P, C.c_int, C.c_uint64, C.c_double, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
     "hml_recording_payload_size": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64)]),
     "hml_recording_export": (C.c_int, [_P, C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "hml_recording_merge_payload": (C.c_int, [_P, C.c_int, _P, C.c_uint64]),
@@ -158,6 +161,9 @@ ABI_VERSION = 5   # hml_abi_version() of include/hml.h this mirror was written a
 
 # the kinds of recording of the sparse payloads (HML_RECORDING_* of include/hml.h)
 RECORDING_LEVELS, RECORDING_BREAKS, RECORDING_BANDS = 0, 1, 2
+
+# why a fit stopped (HML_EM_* of include/hml.h)
+EM_MAX_STEPS, EM_CONVERGED, EM_DEGENERATE = 0, 1, 2
 
 
 def load_library(path=None):
@@ -724,6 +730,35 @@ class Chain:
         v = [C.c_uint64() for _ in range(7)]
         _check(self.lib.hml_posterior_info(self.h, *[C.byref(x) for x in v]))
         return dict(zip(("chunks", "L", "W", "stale_fwd", "stale_bwd", "rounds", "serial_chunks"), (x.value for x in v)))
+
+    # ---- expectation-maximisation: expected counts, and a fit of theta, A and pi ----------------
+    def expected_counts(self):
+        """dict(xi[K, K], first[K], stay[K], occ[K], sum[K, D], sum_sq[K, D] float64, loglik, degenerate, xi_degenerate): the
+        E-step over the current blocks under the current parameters; the chain is only read (hml_expected_counts)"""
+        K, D = self.K, self.D
+        xi, first, stay, occ = np.empty((K, K), np.float64), np.empty(K, np.float64), np.empty(K, np.float64), np.empty(K, np.float64)
+        sx, sxx = np.empty((K, D), np.float64), np.empty((K, D), np.float64)
+        loglik, degenerate, xi_degenerate = C.c_double(), C.c_uint64(), C.c_uint64()
+        _check(self.lib.hml_expected_counts(self.h, xi.ctypes.data, first.ctypes.data, stay.ctypes.data, occ.ctypes.data, sx.ctypes.data, sxx.ctypes.data,
+                                            C.byref(loglik), C.byref(degenerate), C.byref(xi_degenerate)))
+        return dict(xi=xi, first=first, stay=stay, occ=occ, sum=sx, sum_sq=sxx, loglik=loglik.value, degenerate=degenerate.value,
+                    xi_degenerate=xi_degenerate.value)
+
+    def em_step(self, use_prior=False):
+        """one E-step, the M-step and the installation of its result: (objective of the parameters it started from, kept)
+        (hml_em_step)"""
+        obj, kept = C.c_double(), C.c_uint64()
+        _check(self.lib.hml_em_step(self.h, 1 if use_prior else 0, C.byref(obj), C.byref(kept)))
+        return obj.value, kept.value
+
+    def em_fit(self, max_steps, rel_tol=0.0, use_prior=False):
+        """(trace[steps + 1] float64, steps, reason, kept): at most max_steps M-steps over the current blocks - which are never
+        rebuilt inside a fit -, trace[k] the objective after k of them; reason is EM_MAX_STEPS, EM_CONVERGED or EM_DEGENERATE
+        (hml_em_fit)"""
+        trace = np.empty(int(max_steps) + 1, np.float64)
+        steps, reason, kept = C.c_uint64(), C.c_int(), C.c_uint64()
+        _check(self.lib.hml_em_fit(self.h, 1 if use_prior else 0, int(max_steps), float(rel_tol), trace.ctypes.data, C.byref(steps), C.byref(reason), C.byref(kept)))
+        return trace[:steps.value + 1].copy(), steps.value, reason.value, kept.value
 
     # ---- sparse payloads of the levels, breakpoints and bands (across GPUs) -------------------
     def recording_payload_size(self, kind):

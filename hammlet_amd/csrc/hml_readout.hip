@@ -1497,9 +1497,8 @@ static int post_direction(hml_ctx* c, const hml_post_args& a, int K, uint8_t* ma
     return 0;
 }
 
-// the whole computation; the rows alpha, c and beta stay in `out` for the probe
-static int post_compute(hml_ctx* c, bool want_gamma, post_result& out) {
-    post_tables t;
+// the whole computation; the rows alpha, c and beta stay in `out` for the probe, the tables in `t` for the E-step
+static int post_compute(hml_ctx* c, bool want_gamma, post_result& out, post_tables& t) {
     uint32_t B = 0;
     if (int r = post_begin(c, t, &B)) return r;
     const int K = c->K;
@@ -1560,6 +1559,11 @@ static int post_compute(hml_ctx* c, bool want_gamma, post_result& out) {
     c->post.chunks = n_chunks; c->post.used_L = L; c->post.used_W = W; c->post.stale_fwd = stale[0]; c->post.stale_bwd = stale[1];
     c->post.rounds_run = std::max(rounds[0], rounds[1]); c->post.walked = (finished[0] || finished[1]) ? h_words[1] : 0;
     return 0;
+}
+
+static int post_compute(hml_ctx* c, bool want_gamma, post_result& out) {
+    post_tables t;
+    return post_compute(c, want_gamma, out, t);
 }
 
 extern "C" {
@@ -1653,6 +1657,170 @@ int hml_posterior_info(hml_ctx* c, uint64_t* chunks, uint64_t* L, uint64_t* W, u
     if (stale_bwd) *stale_bwd = c->post.stale_bwd;
     if (rounds) *rounds = c->post.rounds_run;
     if (serial_chunks) *serial_chunks = c->post.walked;
+    return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------- expectation-maximisation (hml_k_em.h)
+// The E-step's expected counts behind a smoothing pass, the M-step of hml_em_ref.h on the host, and the fit.  Device memory is
+// local to a call, as the smoothing's is.
+#include "hml_em_ref.h"
+#include "hml_k_em.h"   // (launched from this object alone)
+
+template <int KM>
+static void em_launch_norm(hml_ctx* c, const hml_post_args& a, size_t lds, uint32_t B, const double* alpha, const double* beta, double* X, unsigned long long* n_bad) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_em_norm<KM>), dim3((B - 1u + 63u) / 64u), dim3(64), lds, c->stream, a, alpha, beta, X, n_bad);
+}
+#define EM_BY_K(K, fn, ...) do { if ((K) <= 8) fn<8>(__VA_ARGS__); else if ((K) <= 16) fn<16>(__VA_ARGS__); else fn<HML_CAP_K>(__VA_ARGS__); } while (0)
+
+// the E-step: a smoothing pass, then the counts
+static int em_estep(hml_ctx* c, hml_em_counts& out) {
+    post_tables t;
+    post_result p;
+    if (int r = post_compute(c, false, p, t)) return r;
+    const int K = c->K, D = c->D, KK = K * K;
+    const uint32_t B = p.B;
+    const uint32_t ncols = (uint32_t)(KK + K * (2 + 2 * D));
+    const uint64_t n1 = ((uint64_t)B + 63u) / 64u, n2 = (n1 + 63u) / 64u;
+    DevBuf b_X, b_p1, b_p2, b_first, b_bad;
+    const bool small = K <= 16;   // one wavefront per group, X_b computed where it is used (hml_k_em_reduce_small)
+    if (!small) HIPCHK(b_X.alloc((uint64_t)B * sizeof(double)));
+    HIPCHK(b_p1.alloc(n1 * ncols * sizeof(double)));
+    HIPCHK(b_p2.alloc(n2 * ncols * sizeof(double)));
+    HIPCHK(b_first.alloc((uint64_t)K * sizeof(double)));
+    HIPCHK(b_bad.alloc(sizeof(unsigned long long)));
+    HIPCHK(hipMemsetAsync(b_bad.get(), 0, sizeof(unsigned long long), c->stream));
+    if (B > 1u && !small) {
+        hml_post_args a;
+        a.par = t.par.as<hml_vit_par>(); a.A = t.A.as<double>(); a.pi = t.pi.as<double>();
+        a.ia = c->d_ia; a.starts = c->d_starts.get();
+        a.L = 0; a.W = 0; a.n_chunks = 0; a.entry = nullptr; a.exitv = nullptr; a.rows = nullptr; a.cval = nullptr; a.ell = nullptr;
+        EM_BY_K(K, em_launch_norm, c, a, ((size_t)KK + K) * sizeof(double), B, p.alpha.as<double>(), p.beta.as<double>(), b_X.as<double>(), b_bad.as<unsigned long long>());
+        KLAUNCH_CHECK();
+    }
+    hml_em_args e;
+    e.par = t.par.as<hml_vit_par>(); e.A = t.A.as<double>(); e.ia = c->d_ia; e.starts = c->d_starts.get();
+    e.alpha = p.alpha.as<double>(); e.beta = p.beta.as<double>(); e.X = b_X.as<double>();
+    e.part = b_p1.as<double>(); e.first = b_first.as<double>();
+    if (K <= 8) hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_em_reduce_small<8>), dim3((uint32_t)n1), dim3(64), 0, c->stream, e, b_bad.as<unsigned long long>());
+    else if (small) hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_em_reduce_small<16>), dim3((uint32_t)n1), dim3(64), 0, c->stream, e, b_bad.as<unsigned long long>());
+    else hipLaunchKernelGGL(hml_k_em_reduce, dim3((uint32_t)n1), dim3(256), 0, c->stream, e);
+    // the upper levels of the trees: xi's has B - 1 leaves, the others' B
+    const double* level = b_p1.as<double>();
+    uint64_t n_x = ((uint64_t)B - 1u + 63u) / 64u, n_o = n1;
+    double* bufs[2] = {b_p2.as<double>(), b_p1.as<double>()};
+    for (int k = 0; n_o > 1; ++k) {
+        double* const dst = bufs[k & 1];
+        hipLaunchKernelGGL(hml_k_em_tree, dim3(grid_for(((n_o + 63u) / 64u) * ncols, 256, 1, 4096)), dim3(256), 0, c->stream, level, n_x, n_o, ncols, (uint32_t)KK, dst);
+        level = dst;
+        n_x = (n_x + 63u) / 64u; n_o = (n_o + 63u) / 64u;
+    }
+    KLAUNCH_CHECK();
+    std::vector<double> cols(ncols);
+    unsigned long long n_bad = 0;
+    out.first.resize(K);
+    HIPCHK(hipMemcpyAsync(cols.data(), level, (uint64_t)ncols * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out.first.data(), b_first.get(), (uint64_t)K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&n_bad, b_bad.get(), sizeof n_bad, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));   // (the scratch goes with this frame)
+    out.xi.assign(cols.begin(), cols.begin() + KK);
+    if (B == 1u) out.xi.assign((size_t)KK, 0.0);
+    out.occ.assign(cols.begin() + KK, cols.begin() + KK + K);
+    out.stay.assign(cols.begin() + KK + K, cols.begin() + KK + 2 * K);
+    out.sx.resize((size_t)K * D); out.sxx.resize((size_t)K * D);
+    for (int j = 0; j < K; ++j)
+        for (int d = 0; d < D; ++d) {
+            out.sx[j * D + d] = cols[KK + (2 + d) * K + j];
+            out.sxx[j * D + d] = cols[KK + (2 + D + d) * K + j];
+        }
+    out.loglik = p.loglik;
+    out.degenerate = p.degenerate;
+    out.xi_degenerate = n_bad;
+    return 0;
+}
+
+// the context's float parameters and priors, as the M-step and the objective take them
+struct em_params {
+    std::vector<float> mv, A, pi;
+    hml_em_prior pr;
+    int P = 0, self_trans = 1;
+};
+static int em_fetch(hml_ctx* c, em_params& q) {
+    hml_model m; if (int r = fetch_model(c, &m)) return r;
+    const int K = c->K;
+    q.P = m.P; q.self_trans = m.self_trans != 0;
+    q.mv.resize(2 * (size_t)m.P);
+    for (int k = 0; k < m.P; ++k) { q.mv[2 * k] = m.mu[k]; q.mv[2 * k + 1] = m.var[k]; }
+    q.A.assign(m.A, m.A + K * K);
+    q.pi.assign(m.pi, m.pi + K);
+    q.pr.alpha = (double)m.nig_prior[0]; q.pr.beta = (double)m.nig_prior[1]; q.pr.mu0 = (double)m.nig_prior[2]; q.pr.nu = (double)m.nig_prior[3];
+    q.pr.a_off = (double)m.a_off; q.pr.a_diag = (double)m.a_diag; q.pr.pi_alpha = (double)m.pi_alpha;
+    return 0;
+}
+
+// one E-step, the objective of the current parameters, and whether the E-step was degenerate
+static int em_expect(hml_ctx* c, int use_prior, em_params& q, hml_em_counts& n, double* objective) {
+    if (int r = em_estep(c, n)) return r;
+    if (int r = em_fetch(c, q)) return r;
+    *objective = hml_em_objective(c->K, q.P, use_prior, q.pr, n.loglik, q.mv.data(), q.A.data(), q.pi.data());
+    return 0;
+}
+// the M-step and the installation of its result
+static int em_maximise(hml_ctx* c, int use_prior, em_params& q, const hml_em_counts& n, uint64_t* kept) {
+    *kept += hml_em_mstep(c->K, c->D, q.P, q.self_trans, use_prior, q.pr, n, q.mv.data(), q.A.data(), q.pi.data());
+    return hml_set_parameters(c, q.mv.data(), q.A.data(), q.pi.data());
+}
+
+extern "C" {
+
+int hml_expected_counts(hml_ctx* c, double* xi, double* first, double* stay, double* occ, double* sum, double* sum_sq, double* loglik, uint64_t* degenerate,
+                        uint64_t* xi_degenerate) {
+    NEED_MODEL();
+    hml_em_counts n;
+    if (int r = em_estep(c, n)) return r;
+    if (xi) std::copy(n.xi.begin(), n.xi.end(), xi);
+    if (first) std::copy(n.first.begin(), n.first.end(), first);
+    if (stay) std::copy(n.stay.begin(), n.stay.end(), stay);
+    if (occ) std::copy(n.occ.begin(), n.occ.end(), occ);
+    if (sum) std::copy(n.sx.begin(), n.sx.end(), sum);
+    if (sum_sq) std::copy(n.sxx.begin(), n.sxx.end(), sum_sq);
+    if (loglik) *loglik = n.loglik;
+    if (degenerate) *degenerate = n.degenerate;
+    if (xi_degenerate) *xi_degenerate = n.xi_degenerate;
+    return 0;
+}
+
+int hml_em_step(hml_ctx* c, int use_prior, double* objective_before, uint64_t* kept) {
+    NEED_MODEL();
+    em_params q;
+    hml_em_counts n;
+    double obj = 0.0;
+    uint64_t k = 0;
+    if (int r = em_expect(c, use_prior, q, n, &obj)) return r;
+    if (int r = em_maximise(c, use_prior, q, n, &k)) return r;
+    if (objective_before) *objective_before = obj;
+    if (kept) *kept = k;
+    return 0;
+}
+
+int hml_em_fit(hml_ctx* c, int use_prior, uint64_t max_steps, double rel_tol, double* trace, uint64_t* steps, int* reason, uint64_t* kept) {
+    NEED_MODEL();
+    uint64_t k_total = 0, k = 0;
+    int why = HML_EM_MAX_STEPS;
+    double last[2] = {0.0, 0.0};   // trace[k - 1], trace[k]
+    for (;; ++k) {
+        em_params q;
+        hml_em_counts n;
+        last[0] = last[1];
+        if (int r = em_expect(c, use_prior, q, n, &last[1])) return r;
+        if (trace) trace[k] = last[1];
+        if (hml_em_stops(last[0], last[1], k, max_steps, rel_tol, n.degenerate + n.xi_degenerate, &why)) break;
+        if (int r = em_maximise(c, use_prior, q, n, &k_total)) return r;
+    }
+    if (steps) *steps = k;
+    if (reason) *reason = why;
+    if (kept) *kept = k_total;
     return 0;
 }
 

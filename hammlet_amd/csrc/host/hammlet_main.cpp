@@ -26,6 +26,11 @@
 // `-O PD` (posterior) writes PREFIXposteriorSUFFIX under the same parameters and blocks: log p(y | theta) and the number of degenerate
 // blocks, then per run of equal called state its length, the state and its smallest posterior (hml_posterior, hml_posterior_rle;
 // with -chains N one file per chain, PREFIXchainK.posteriorSUFFIX);
+// `-em STEPS [TOL]` fits theta, A and pi by expectation-maximisation once the scheme has run - at most STEPS M-steps over the last
+// block structure, from the chain's final parameters, until the objective gains no more than TOL of its size (hml_em_fit); `-em-prior`
+// makes the objective the posterior mode under the chain's priors instead of the maximum likelihood.  The fit runs before
+// -O V, -O PD and the other end-of-run outputs, which are then under the fitted parameters; `-O EM` writes PREFIXemSUFFIX: the
+// trace (step, objective), why the fit stopped, and the fitted means, variances, A and pi (PREFIXchainK.emSUFFIX per chain);
 // -raw FILE reads float32 values instead of text; -device N selects
 // the GPU; -chain N selects the Philox sub-key of an independent chain; -chains N runs N independent chains (sub-keys
 // chain .. chain+N-1), chain k on GPU (device + k) mod #GPUs in its own host thread, and pools their recorded marginals
@@ -72,6 +77,9 @@ static const char* kHelp =
     "                                 blocks no path reaches, then one line per run of equal most probable state: length, state\n"
     "                                 and the smallest posterior of that state over the run; with -chains N one file per chain;\n"
     "                                 needs a scheme with forward-backward sweeps (extension)\n"
+    "                    EM           em: the fit of -em - one line per step: step, objective; then the reason it stopped, the\n"
+    "                                 parameters kept for want of support, and the fitted means, variances, A and pi; with\n"
+    "                                 -chains N one file per chain (extension; needs -em)\n"
     "                    L            levels: length, then posterior mean and standard deviation of the emission level\n"
     "                                 per data dimension, one line per segment - the denoised trace (extension)\n"
     "                    BP           breakpoints: position, number of recorded sweeps that change state there, and that\n"
@@ -129,6 +137,12 @@ static const char* kHelp =
     "  -regions FILE                  the regions of -O RG, one per line: start end [label ...], positions counted from 0, the\n"
     "                                 end not included; lines that begin with # and blank lines are skipped.  Regions may\n"
     "                                 overlap, nest and repeat (extension)\n"
+    "  -em STEPS [TOL]                once the scheme has run, fit theta, A and pi by expectation-maximisation over the last block\n"
+    "                                 structure: at most STEPS M-steps, stopping when a step gains no more than TOL (default 0) of\n"
+    "                                 the objective's size; -O V, PD and the other end-of-run outputs are then under the fitted\n"
+    "                                 parameters; needs a scheme with forward-backward sweeps (extension)\n"
+    "  -em-prior                      the fit's objective is the posterior mode under the chain's priors, not the maximum\n"
+    "                                 likelihood (extension)\n"
     "  -history-every N               -O H, HS: a row for every N-th sweep (default 1) (extension)\n"
     "  -history-skip S                -O HS: leave out the rows of the first S sweeps (default: the first half of the scheme's\n"
     "                                 sweeps) (extension)\n"
@@ -168,6 +182,9 @@ struct Job {
     vector<float> regionEdges;       // ... and their edges: those of -bands
     uint64_t historyEvery = 1;       // -history-every N (-O H, HS)
     uint64_t historySkip = 0;        // -history-skip S
+    bool em = false, emPrior = false;   // -em STEPS [TOL], -em-prior
+    uint64_t emSteps = 0;
+    double emTol = 0;
 };
 
 // Meeting point of the chain threads of `-chains N` and the main thread: a chain arrives with its context once its
@@ -531,6 +548,15 @@ static void writePosteriorFile(const Job& job, int index, hml_ctx* ctx) {
     if (job.outputs.at("posterior")) Posterior(ctx).writeFile(posteriorFileName(job, index));
 }
 
+// -em: the fit once the scheme has run, before every end-of-run output; PREFIX[chainK.]emSUFFIX
+static string emFileName(const Job& job, int index) { return job.opref + (index == 0 ? "" : "chain" + std::to_string(index) + ".") + "em" + job.osuff; }
+static void runFit(const Job& job, int index, hml_ctx* ctx) {
+    if (!job.em) return;
+    Fit fit(ctx);
+    const Fit::Result r = fit.fit(job.emSteps, job.emTol, job.emPrior);
+    if (job.outputs.at("em")) fit.writeFile(emFileName(job, index), r);
+}
+
 static string historyFileName(const Job& job) { return job.opref + "history" + job.osuff; }
 static string historySummaryFileName(const Job& job) { return job.opref + "historysummary" + job.osuff; }
 // the chains' histories, in chain order (hammlet/History.hpp): read through the host, whichever GPUs the chains are on
@@ -646,6 +672,7 @@ static void runChain(const Job& job, vector<real_t>& inputValues, bool steal, in
     for (const Step& st : job.scheme)
         if (run.token(st)) run.sweeps(st);
     hml_check(hml_sync(run.RNG.ctx()));
+    runFit(job, index, run.RNG.ctx());
     writeViterbiFile(job, index, run.RNG.ctx());
     writePosteriorFile(job, index, run.RNG.ctx());
     if (!rendezvous) writeContextFiles(job, run.RNG.ctx());   // (several chains: the main thread merges and writes)
@@ -692,6 +719,7 @@ static void runDeviceGroup(const Job& job, vector<real_t>& inputValues, int devi
     }
     vector<hml_ctx*> ctxs;
     for (auto& r : runs) { hml_check(hml_sync(r->RNG.ctx())); ctxs.push_back(r->RNG.ctx()); }
+    for (auto& r : runs) runFit(job, r->index, r->RNG.ctx());
     for (auto& r : runs) writeViterbiFile(job, r->index, r->RNG.ctx());
     for (auto& r : runs) writePosteriorFile(job, r->index, r->RNG.ctx());
     const bool pooled = !rendezvous || rendezvous->arrive(indices, ctxs);
@@ -730,6 +758,8 @@ int main(int argc, const char* argv[]) {
         args.registerFlags({"-regions"});
         args.registerFlags({"-history-every"}, "1");
         args.registerFlags({"-history-skip"});
+        args.registerFlags({"-em"});
+        args.registerFlags({"-em-prior"});
         args.parseArgs();
 
         if (args.isSet("-g")) args.print();
@@ -812,6 +842,7 @@ int main(int argc, const char* argv[]) {
         outputArgs.registerFlags({"X", "maxsegmentation"});   // extension
         outputArgs.registerFlags({"V", "viterbi"});           // extension
         outputArgs.registerFlags({"PD", "posterior"});        // extension (P is the reference's parameters)
+        outputArgs.registerFlags({"EM", "em"});               // extension
         outputArgs.registerFlags({"L", "levels"});            // extension
         outputArgs.registerFlags({"BP", "breakpoints"});      // extension (B and C are the reference's blocks and compression)
         outputArgs.registerFlags({"CS", "consensus"});        // extension
@@ -893,7 +924,7 @@ int main(int argc, const char* argv[]) {
         job.weightMultiplier = weightMultiplier; job.useSelfTrans = useSelfTrans;
         job.thetaParams = thetaParams; job.trans = trans; job.selfTrans = selfTrans; job.initialAlpha = initialAlpha;
         job.scheme = scheme;
-        for (const char* o : {"sequences", "parameters", "blocks", "compression", "marginals", "segments", "maxsegmentation", "viterbi", "posterior", "levels", "breakpoints", "consensus", "bands", "bandcalls", "rhat", "regions", "history", "historysummary"})
+        for (const char* o : {"sequences", "parameters", "blocks", "compression", "marginals", "segments", "maxsegmentation", "viterbi", "posterior", "em", "levels", "breakpoints", "consensus", "bands", "bandcalls", "rhat", "regions", "history", "historysummary"})
             job.outputs[o] = outputArgs.isSet(o);
         auto refuseExisting = [&](const string& fn) {
             if (!overwrite) { std::ifstream probe(fn); if (probe.good()) throw std::runtime_error("File " + fn + " already exists! Use -w to allow overwrite!"); }
@@ -965,6 +996,24 @@ int main(int argc, const char* argv[]) {
             for (const Step& st : scheme) anyFB = anyFB || st.method == "F";
             if (!anyFB) throw std::runtime_error("The output posterior (PD) needs a model with transitions: the scheme has mixture sweeps only!");
             for (long k = 0; k < (long)nrChains; ++k) refuseExisting(posteriorFileName(job, (int)k));
+        }
+        if (job.outputs.at("em") && !args.isSet("-em")) throw std::runtime_error("The output em (EM) needs a fit: ask for one with -em STEPS [TOL]!");
+        if (args.isSet("-em")) {
+            // the fit's E-step sums over paths with transitions, as the smoothing does
+            bool anyFB = false;
+            for (const Step& st : scheme) anyFB = anyFB || st.method == "F";
+            if (!anyFB) throw std::runtime_error("The fit (-em) needs a model with transitions: the scheme has mixture sweeps only!");
+            if (args.nrTokens("-em") < 1) throw std::runtime_error("Not enough arguments for flag -em!");
+            if (args.nrTokens("-em") > 2) throw std::runtime_error("Too many arguments for flag -em: STEPS and, optionally, TOL!");
+            const double steps = args.parse<double>("-em", 0);
+            if (!(steps >= 0 && steps <= 1e6) || steps != std::floor(steps)) throw std::runtime_error("The first argument of -em must be a whole number of steps, at most 1000000!");
+            job.em = true;
+            job.emSteps = (uint64_t)steps;
+            job.emTol = args.nrTokens("-em") > 1 ? args.parse<double>("-em", 1) : 0.0;
+            if (!(job.emTol == job.emTol)) throw std::runtime_error("The tolerance of -em must be a number!");
+            job.emPrior = args.isSet("-em-prior");
+            if (job.outputs.at("em"))
+                for (long k = 0; k < (long)nrChains; ++k) refuseExisting(emFileName(job, (int)k));
         }
         if (job.outputs.at("bands")) refuseExisting(bandsFileName(job));
         if (job.outputs.at("bandcalls")) refuseExisting(bandCallsFileName(job));

@@ -1,0 +1,101 @@
+// Fit - expectation-maximisation over the chain's current blocks (include/hml.h, hml_expected_counts, hml_em_step, hml_em_fit;
+// no counterpart in the reference): the expected counts of the E-step, one step, the fit of theta, A and pi to a mode of
+// log p(y | theta) - or of that plus the log density of the chain's own priors -, and the file the driver writes from a fit:
+//   PREFIXemSUFFIX   `-O EM`: "step<TAB>objective" (%.17g) per trace entry - the objective of the parameters after that many
+//                    M-steps -, then "reason<TAB>max_steps|converged|degenerate", "kept<TAB>n", "means<TAB>...",
+//                    "variances<TAB>..." (one value per emission parameter, %.9g), "A<TAB>..." per row and "pi<TAB>..."
+// A thin handle over a context that something else owns, next to Viterbi and Posterior.  Blocks are never rebuilt inside a
+// fit: it is over the context's current block structure; call hml_create_blocks between fits to let the threshold follow.
+#ifndef HAMMLET_FIT_HPP
+#define HAMMLET_FIT_HPP
+
+#include <cstdio>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "../hml.h"
+
+namespace hammlet {
+
+class Fit {
+    hml_ctx* mCtx;
+    static void check(int rc) { if (rc != 0) throw std::runtime_error(hml_last_error()); }
+    // data dimensions D, emission parameters P and states K = P^D of the context's model
+    void shape(int* D, int* P, int* K) const {
+        check(hml_get_dimensions(mCtx, D, P));
+        *K = 1;
+        for (int d = 0; d < *D; ++d) *K *= *P;
+    }
+
+public:
+    struct Counts {
+        std::vector<double> xi, first, stay, occ, sum, sumSq;   // [K][K], [K], [K], [K], [K][D], [K][D]
+        double loglik = 0;
+        uint64_t degenerate = 0, xiDegenerate = 0;
+    };
+    struct Result {
+        std::vector<double> trace;   // steps + 1 values; the last belongs to the installed parameters
+        uint64_t steps = 0, kept = 0;
+        int reason = HML_EM_MAX_STEPS;
+    };
+
+    explicit Fit(hml_ctx* ctx) : mCtx(ctx) {}
+    // the E-step alone; the chain is only read
+    Counts expectedCounts() const {
+        int D = 1, P = 0, K = 0;
+        shape(&D, &P, &K);
+        Counts n;
+        n.xi.resize((size_t)K * K); n.first.resize(K); n.stay.resize(K); n.occ.resize(K);
+        n.sum.resize((size_t)K * D); n.sumSq.resize((size_t)K * D);
+        check(hml_expected_counts(mCtx, n.xi.data(), n.first.data(), n.stay.data(), n.occ.data(), n.sum.data(), n.sumSq.data(), &n.loglik, &n.degenerate, &n.xiDegenerate));
+        return n;
+    }
+    // one E-step, M-step and installation; returns the objective of the parameters the step started from
+    double step(bool usePrior = false, uint64_t* kept = nullptr) {
+        double objective = 0;
+        check(hml_em_step(mCtx, usePrior ? 1 : 0, &objective, kept));
+        return objective;
+    }
+    Result fit(uint64_t maxSteps, double relTol = 0.0, bool usePrior = false) {
+        Result r;
+        r.trace.resize(maxSteps + 1);
+        check(hml_em_fit(mCtx, usePrior ? 1 : 0, maxSteps, relTol, r.trace.data(), &r.steps, &r.reason, &r.kept));
+        r.trace.resize(r.steps + 1);
+        return r;
+    }
+    static const char* reasonName(int reason) {
+        return reason == HML_EM_CONVERGED ? "converged" : reason == HML_EM_DEGENERATE ? "degenerate" : "max_steps";
+    }
+
+    // the fit's trace and the context's parameters as they are now
+    void writeFile(const std::string& fn, const Result& r) const {
+        int D = 1, P = 0, K = 0;
+        shape(&D, &P, &K);
+        std::vector<float> mv(2 * (size_t)P), A((size_t)K * K), pi(K);
+        check(hml_get_theta(mCtx, mv.data()));
+        check(hml_get_transitions(mCtx, A.data(), pi.data()));
+        FILE* out = fopen(fn.c_str(), "w");
+        if (!out) throw std::runtime_error("Cannot write to file " + fn + "!");
+        for (size_t k = 0; k < r.trace.size(); ++k) fprintf(out, "%llu\t%.17g\n", (unsigned long long)k, r.trace[k]);
+        fprintf(out, "reason\t%s\nkept\t%llu\n", reasonName(r.reason), (unsigned long long)r.kept);
+        fprintf(out, "means");
+        for (int p = 0; p < P; ++p) fprintf(out, "\t%.9g", (double)mv[2 * p]);
+        fprintf(out, "\nvariances");
+        for (int p = 0; p < P; ++p) fprintf(out, "\t%.9g", (double)mv[2 * p + 1]);
+        fprintf(out, "\n");
+        for (int i = 0; i < K; ++i) {
+            fprintf(out, "A");
+            for (int j = 0; j < K; ++j) fprintf(out, "\t%.9g", (double)A[(size_t)i * K + j]);
+            fprintf(out, "\n");
+        }
+        fprintf(out, "pi");
+        for (int j = 0; j < K; ++j) fprintf(out, "\t%.9g", (double)pi[j]);
+        fprintf(out, "\n");
+        if (fclose(out) != 0) throw std::runtime_error("Cannot write to file " + fn + "!");
+    }
+};
+
+}  // namespace hammlet
+
+#endif

@@ -620,6 +620,7 @@ template <> inline char StateSequence<Mixture>::method() { return HML_METHOD_MIX
 #include "History.hpp"
 #include "Viterbi.hpp"
 #include "Posterior.hpp"
+#include "Fit.hpp"
 
 namespace hammlet {
 

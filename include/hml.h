@@ -553,6 +553,44 @@ int hml_posterior_rle(hml_ctx* ctx, uint64_t* n_runs, uint64_t* run_len /*n_runs
 int hml_posterior_terms(hml_ctx* ctx, float* e /*B*K*/, float* m /*B*/, double* alpha /*B*K*/, double* c /*B*/, double* beta /*B*K*/);
 int hml_posterior_info(hml_ctx* ctx, uint64_t* chunks, uint64_t* L, uint64_t* W, uint64_t* stale_fwd, uint64_t* stale_bwd, uint64_t* rounds, uint64_t* serial_chunks);
 
+/* ---- expectation-maximisation: expected counts, and a fit of theta, A and pi.  No counterpart in the reference. ----
+ * The other half of Baum-Welch over the context's current B blocks, for the path weight stated under smoothing.  The E-step
+ * runs a smoothing pass and reduces, in IEEE double and one fixed order (fan-in-64 tree sums over the blocks, as loglik's):
+ *     xi[i][j]   the expected number of transitions i -> j between adjacent blocks: the sum over b = 1 ... B - 1 of
+ *                alpha_{b-1}(i) A_ij e_b(j) beta_b(j) over its sum X_b (a block with X_b not a positive finite number gives
+ *                zeros and is counted in xi_degenerate)
+ *     first[j]   gamma_0(j)
+ *     occ[j]     the expected number of positions in state j, sum_b n_b gamma_b(j); stay[j] the same with n_b - 1: the expected
+ *                self-transitions inside blocks, which count for A_jj when self-transitions are on
+ *     sum[j][d], sum_sq[j][d]   sum_b gamma_b(j) Sx_{d,b}, and the same with the block's sum of squares
+ * and returns loglik and degenerate as hml_posterior does.  This is the E-step of that path weight, NOT the sweep's count
+ * pass, which feeds pi's posterior the full occupancies and books a transition into the first block.
+ * The M-step (host, K-sized) gives the theta, A and pi that maximise the expected complete-data log-likelihood - use_prior = 0,
+ * maximum likelihood - or that plus the log density of the chain's own priors (hml_set_model) - use_prior = 1, the posterior
+ * mode: the joint mode of the normal-inverse-gamma posterior per emission parameter, (count + a - 1) normalised per row of A
+ * and for pi, negative values raised to 0.  A parameter or a row without support keeps its old values and is counted in
+ * `kept`.  The result is installed exactly as hml_set_parameters installs it.  hammlet_amd/csrc/hml_em_ref.h states every step,
+ * restates the E-step for one host thread, and holds the M-step and the objective the library itself calls.
+ *
+ * hml_expected_counts: any pointer may be NULL; the chain is only read.  hml_em_step: one E-step, the M-step and the
+ * installation; objective_before is the objective of the parameters the step started from (either pointer may be NULL).
+ * hml_em_fit: trace[k] is the objective - loglik, with use_prior = 1 plus the log prior density up to constants - of the
+ * parameters after k M-steps.  Before each M-step the fit stops when the E-step reports degenerate + xi_degenerate > 0
+ * (HML_EM_DEGENERATE), when k >= 1 and trace[k] - trace[k-1] <= rel_tol |trace[k-1]| (HML_EM_CONVERGED), or after max_steps
+ * M-steps (HML_EM_MAX_STEPS), so that it runs at most max_steps M-steps and one E-step more, and the last trace entry always
+ * belongs to the installed parameters.  steps = the M-steps run (trace holds steps + 1 values), kept sums over them.
+ * BLOCKS ARE NEVER REBUILT inside a fit: it is over the context's current block structure, as the decode and the smoothing
+ * are; a caller who wants the threshold to follow the fitted parameters calls hml_create_blocks between fits.  The refusals
+ * are hml_posterior's (a halted chain, no blocks, no model); hml_posterior_info reports the E-step's last smoothing pass.
+ * Device memory is local to a call and released before it returns. */
+#define HML_EM_MAX_STEPS 0
+#define HML_EM_CONVERGED 1
+#define HML_EM_DEGENERATE 2
+int hml_expected_counts(hml_ctx* ctx, double* xi /*K*K*/, double* first /*K*/, double* stay /*K*/, double* occ /*K*/, double* sum /*K*D*/, double* sum_sq /*K*D*/,
+                        double* loglik, uint64_t* degenerate, uint64_t* xi_degenerate);
+int hml_em_step(hml_ctx* ctx, int use_prior, double* objective_before, uint64_t* kept);
+int hml_em_fit(hml_ctx* ctx, int use_prior, uint64_t max_steps, double rel_tol, double* trace /*max_steps+1, may be NULL*/, uint64_t* steps, int* reason, uint64_t* kept);
+
 /* ---- sparse payloads: levels, breakpoints and bands across GPUs.  No counterpart in the reference. ----
  * The three recordings above keep a cell and a boundary bit per change of state, so what another GPU needs of one is a list:
  * the M positions with a cell and the cells there.  The PAYLOAD is one contiguous buffer in device memory, little endian,
