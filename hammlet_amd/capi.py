@@ -127,6 +127,9 @@ SIGNATURES = {
     "hml_expected_counts": (C.c_int, [_P] * 7 + [C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "hml_em_step": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "hml_em_fit": (C.c_int, [_P, C.c_int, C.c_uint64, C.c_double, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
+    "hml_posterior_breaks": (C.c_int, [_P, C.c_double, C.POINTER(C.c_uint64), _P, _P, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    "hml_posterior_regions": (C.c_int, [_P, C.c_uint64] + [_P] * 7 + [C.POINTER(C.c_uint64)]),
+    "hml_posterior_pair_terms": (C.c_int, [_P] * 6),
     "hml_recording_payload_size": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64)]),
     "hml_recording_export": (C.c_int, [_P, C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "hml_recording_merge_payload": (C.c_int, [_P, C.c_int, _P, C.c_uint64]),
@@ -759,6 +762,47 @@ class Chain:
         steps, reason, kept = C.c_uint64(), C.c_int(), C.c_uint64()
         _check(self.lib.hml_em_fit(self.h, 1 if use_prior else 0, int(max_steps), float(rel_tol), trace.ctypes.data, C.byref(steps), C.byref(reason), C.byref(kept)))
         return trace[:steps.value + 1].copy(), steps.value, reason.value, kept.value
+
+    # ---- pairwise read-outs of the smoothing: breakpoint and region posteriors ------------------
+    def posterior_breaks(self, min_prob=0.0):
+        """dict(pos[n] uint32, prob[n] float64, expected_breaks, pair_degenerate): the block boundaries whose posterior
+        probability of a change of state under the current parameters is at least min_prob, by ascending position, and the
+        expected number of breakpoints in the trace (hml_posterior_breaks)"""
+        n, B = C.c_uint64(), self.num_blocks()      # (room for every boundary: one call, one computation)
+        pos, prob = np.empty(B, np.uint32), np.empty(B, np.float64)
+        total, bad = C.c_double(), C.c_uint64()
+        _check(self.lib.hml_posterior_breaks(self.h, float(min_prob), C.byref(n), pos.ctypes.data, prob.ctypes.data, C.byref(total), C.byref(bad)))
+        return dict(pos=pos[:n.value].copy(), prob=prob[:n.value].copy(), expected_breaks=total.value, pair_degenerate=bad.value)
+
+    def posterior_regions(self, start, end, raw=False):
+        """dict(whole[n], whole_state[n, K], expected_breaks[n], share[n, K] float64, pair_degenerate, and with raw=True
+        raw[n, 2 K + 1] uint64): per region [start[r], end[r]) the probability that it holds no breakpoint, that all of it is
+        in state j, the expected number of breakpoints inside it and the expected share of its positions in state j, under the
+        current parameters (hml_posterior_regions); independent of set_regions()"""
+        start, end = _region_positions(start, "start"), _region_positions(end, "end")
+        if start.shape != end.shape:
+            raise ValueError("start and end: two one-dimensional arrays of one length")
+        n, K = start.size, self.K
+        out = dict(whole=np.empty(n, np.float64), whole_state=np.empty((n, K), np.float64), expected_breaks=np.empty(n, np.float64),
+                   share=np.empty((n, K), np.float64))
+        words = np.empty((n, 2 * K + 1), np.uint64) if raw else None
+        bad = C.c_uint64()
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        _check(self.lib.hml_posterior_regions(self.h, n, ptr(start), ptr(end), ptr(out["whole"]), ptr(out["whole_state"]), ptr(out["expected_breaks"]),
+                                              ptr(out["share"]), ptr(words), C.byref(bad)))
+        out["pair_degenerate"] = bad.value
+        if raw:
+            out["raw"] = words
+        return out
+
+    def posterior_pair_terms(self):
+        """dict(p[B], r[B, K] float64, pfx[B], cost[B, K], mass[B, K] uint64): the terms the two calls above are built from
+        (hml_posterior_pair_terms)"""
+        B, K = self.num_blocks(), self.K
+        out = dict(p=np.empty(B, np.float64), r=np.empty((B, K), np.float64), pfx=np.empty(B, np.uint64), cost=np.empty((B, K), np.uint64),
+                   mass=np.empty((B, K), np.uint64))
+        _check(self.lib.hml_posterior_pair_terms(self.h, *[out[k].ctypes.data for k in ("p", "r", "pfx", "cost", "mass")]))
+        return out
 
     # ---- sparse payloads of the levels, breakpoints and bands (across GPUs) -------------------
     def recording_payload_size(self, kind):

@@ -1825,3 +1825,155 @@ int hml_em_fit(hml_ctx* c, int use_prior, uint64_t max_steps, double rel_tol, do
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------- pairwise read-outs (hml_k_pairs.h)
+// Breakpoint and region posteriors under the current parameters: exact functions of the rows alpha and beta a smoothing pass
+// leaves behind.  The chain is only read; device memory is local to a call, as the smoothing's is.
+#include "hml_k_pairs.h"   // (launched from this object alone; it brings hml_pairs_ref.h)
+
+struct pairs_result {
+    post_result post;   // alpha and beta (c_b, the calls and their confidences are released)
+    DevBuf col, p, r;   // [2 K + 1][B] words: the terms, then their inclusive prefix sums; p[B]; r[B][K] for the probe alone
+    uint64_t bad = 0;
+    uint32_t B = 0;
+};
+
+template <int KM>
+static void pairs_launch_terms(hml_ctx* c, const hml_post_args& a, size_t lds, uint32_t B, const double* alpha, const double* beta, unsigned long long* col, double* p,
+                               double* r, unsigned long long* n_bad) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_pair_terms<KM>), dim3((B + 63u) / 64u), dim3(64), lds, c->stream, a, alpha, beta, col, p, r, n_bad);
+}
+
+// a smoothing pass, then the terms per block; the prefix sums only if asked (the probe reads the terms themselves)
+static int pairs_compute(hml_ctx* c, bool want_r, bool scan, pairs_result& out) {
+    post_tables t;
+    if (int r = post_compute(c, false, out.post, t)) return r;
+    out.post.cval.free(); out.post.conf.free(); out.post.q.free();
+    const int K = c->K;
+    const uint32_t B = out.post.B;
+    const int rows = 2 * K + 1;
+    DevBuf b_bad;
+    HIPCHK(out.col.alloc((uint64_t)rows * B * sizeof(unsigned long long)));
+    HIPCHK(out.p.alloc((uint64_t)B * sizeof(double)));
+    if (want_r) HIPCHK(out.r.alloc((uint64_t)B * K * sizeof(double)));
+    HIPCHK(b_bad.alloc(sizeof(unsigned long long)));
+    HIPCHK(hipMemsetAsync(b_bad.get(), 0, sizeof(unsigned long long), c->stream));
+    hml_post_args a;
+    a.par = t.par.as<hml_vit_par>(); a.A = t.A.as<double>(); a.pi = t.pi.as<double>();
+    a.ia = c->d_ia; a.starts = c->d_starts.get();
+    a.L = 0; a.W = 0; a.n_chunks = 0; a.entry = nullptr; a.exitv = nullptr; a.rows = nullptr; a.cval = nullptr; a.ell = nullptr;
+    EM_BY_K(K, pairs_launch_terms, c, a, ((size_t)K * K + K) * sizeof(double), B, out.post.alpha.as<double>(), out.post.beta.as<double>(), out.col.as<unsigned long long>(),
+            out.p.as<double>(), out.r.as<double>(), b_bad.as<unsigned long long>());
+    KLAUNCH_CHECK();
+    unsigned long long n_bad = 0;
+    HIPCHK(hipMemcpyAsync(&n_bad, b_bad.get(), sizeof n_bad, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));   // (the tables go with this frame)
+    if (scan)
+        if (int r = scan_rows<unsigned long long, unsigned long long, false>(c->stream, out.col.as<unsigned long long>(), B, rows, out.col.as<unsigned long long>())) return r;
+    out.bad = n_bad;
+    out.B = B;
+    return 0;
+}
+
+extern "C" {
+
+int hml_posterior_breaks(hml_ctx* c, double min_prob, uint64_t* n, uint32_t* pos, double* prob, double* expected_breaks, uint64_t* pair_degenerate) {
+    NEED_MODEL();
+    if (!n) return set_err(HML_ERR_ARG, "null argument");
+    if (min_prob != min_prob) return set_err(HML_ERR_ARG, "hml_posterior_breaks: min_prob is not a number");
+    pairs_result pr;
+    if (int r = pairs_compute(c, false, true, pr)) return r;
+    const uint32_t B = pr.B;
+    if (B > 0x7fffffffu) return set_err(HML_ERR_ARG, "hml_posterior_breaks: more than 2^31 - 1 blocks: the list's counts are 32-bit");
+    const uint32_t n_chunks = (uint32_t)(((uint64_t)B + 255u) / 256u);
+    DevBuf b_cnt, b_pos, b_prob;
+    HIPCHK(b_cnt.alloc(((uint64_t)n_chunks + 1) * sizeof(int32_t)));
+    int32_t* const d_cnt = b_cnt.as<int32_t>();
+    HIPCHK(hipMemsetAsync(d_cnt + n_chunks, 0, sizeof(int32_t), c->stream));
+    hipLaunchKernelGGL(hml_k_pair_break_count, dim3(n_chunks), dim3(256), 0, c->stream, pr.p.as<double>(), B, min_prob, d_cnt);
+    hipLaunchKernelGGL(hml_k_scan_chunks<int32_t>, dim3(1), dim3(1024), 0, c->stream, d_cnt, n_chunks + 1u);   // d_cnt[n_chunks] = total
+    KLAUNCH_CHECK();
+    int32_t M = 0;
+    unsigned long long units = 0;
+    HIPCHK(hipMemcpyAsync(&M, d_cnt + n_chunks, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&units, pr.col.as<unsigned long long>() + (B - 1u), sizeof units, hipMemcpyDeviceToHost, c->stream));   // N[B - 1]
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *n = (uint64_t)M;
+    if (expected_breaks) *expected_breaks = (double)units * (1.0 / 4294967296.0);
+    if (pair_degenerate) *pair_degenerate = pr.bad;
+    if (!pos || M == 0) return 0;
+    HIPCHK(b_pos.alloc((uint64_t)M * sizeof(uint32_t)));
+    HIPCHK(b_prob.alloc((uint64_t)M * sizeof(double)));
+    hipLaunchKernelGGL(hml_k_pair_break_scatter, dim3(n_chunks), dim3(256), 0, c->stream, pr.p.as<double>(), c->d_starts.get(), B, min_prob, d_cnt, b_pos.as<uint32_t>(),
+                       b_prob.as<double>());
+    KLAUNCH_CHECK();
+    HIPCHK(hipMemcpyAsync(pos, b_pos.get(), (uint64_t)M * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (prob) HIPCHK(hipMemcpyAsync(prob, b_prob.get(), (uint64_t)M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int hml_posterior_regions(hml_ctx* c, uint64_t n, const uint32_t* start, const uint32_t* end, double* whole, double* whole_state, double* expected_breaks, double* share,
+                          uint64_t* raw, uint64_t* pair_degenerate) {
+    NEED_MODEL();
+    if (n && (!start || !end)) return set_err(HML_ERR_ARG, "null argument");
+    for (uint64_t i = 0; i < n; ++i)
+        if (!hml_pairs_region_ok(start[i], end[i], c->T)) {
+            char buf[160];
+            snprintf(buf, sizeof buf, "hml_posterior_regions: region %llu is [%u, %u): it must hold a position and end at or before T = %llu", (unsigned long long)i, start[i],
+                     end[i], (unsigned long long)c->T);
+            return set_err(HML_ERR_ARG, buf);
+        }
+    pairs_result pr;
+    if (int r = pairs_compute(c, false, true, pr)) return r;
+    if (pair_degenerate) *pair_degenerate = pr.bad;
+    if (n == 0) return 0;
+    const int K = c->K;
+    const uint64_t nk = n * (uint64_t)K, nraw = n * (uint64_t)(2 * K + 1);
+    DevBuf b_st, b_en, b_whole, b_ws, b_eb, b_share, b_raw;
+    HIPCHK(b_st.alloc(n * sizeof(uint32_t)));
+    HIPCHK(b_en.alloc(n * sizeof(uint32_t)));
+    HIPCHK(b_whole.alloc(n * sizeof(double)));
+    HIPCHK(b_ws.alloc(nk * sizeof(double)));
+    HIPCHK(b_eb.alloc(n * sizeof(double)));
+    HIPCHK(b_share.alloc(nk * sizeof(double)));
+    HIPCHK(b_raw.alloc(nraw * sizeof(unsigned long long)));
+    HIPCHK(hipMemcpyAsync(b_st.get(), start, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(b_en.get(), end, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    hml_pair_regions_out o;
+    o.whole = b_whole.as<double>(); o.whole_state = b_ws.as<double>(); o.expected_breaks = b_eb.as<double>(); o.share = b_share.as<double>();
+    o.raw = b_raw.as<unsigned long long>();
+    hipLaunchKernelGGL(hml_k_pair_regions, dim3(grid_for(n, 256, 1, 4096)), dim3(256), 0, c->stream, c->d_starts.get(), pr.B, K, pr.post.alpha.as<double>(),
+                       pr.post.beta.as<double>(), pr.col.as<unsigned long long>(), b_st.as<uint32_t>(), b_en.as<uint32_t>(), n, o);
+    KLAUNCH_CHECK();
+    if (whole) HIPCHK(hipMemcpyAsync(whole, b_whole.get(), n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (whole_state) HIPCHK(hipMemcpyAsync(whole_state, b_ws.get(), nk * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (expected_breaks) HIPCHK(hipMemcpyAsync(expected_breaks, b_eb.get(), n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (share) HIPCHK(hipMemcpyAsync(share, b_share.get(), nk * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (raw) HIPCHK(hipMemcpyAsync(raw, b_raw.get(), nraw * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));   // (the scratch goes with this frame)
+    return 0;
+}
+
+int hml_posterior_pair_terms(hml_ctx* c, double* p, double* r, uint64_t* pfx, uint64_t* cost, uint64_t* mass) {
+    NEED_MODEL();
+    pairs_result pr;
+    if (int rc = pairs_compute(c, r != nullptr, false, pr)) return rc;
+    const int K = c->K;
+    const uint64_t B = pr.B;
+    std::vector<uint64_t> cols;
+    if (cost || mass) cols.resize((uint64_t)(2 * K + 1) * B);
+    if (p) HIPCHK(hipMemcpyAsync(p, pr.p.get(), B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (r) HIPCHK(hipMemcpyAsync(r, pr.r.get(), B * K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (pfx) HIPCHK(hipMemcpyAsync(pfx, pr.col.get(), B * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (!cols.empty()) HIPCHK(hipMemcpyAsync(cols.data(), pr.col.get(), cols.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (uint64_t b = 0; b < B && !cols.empty(); ++b)   // the columns, by block
+        for (int j = 0; j < K; ++j) {
+            if (cost) cost[b * K + j] = cols[(uint64_t)(1 + j) * B + b];
+            if (mass) mass[b * K + j] = cols[(uint64_t)(1 + K + j) * B + b];
+        }
+    return 0;
+}
+
+}  // extern "C"

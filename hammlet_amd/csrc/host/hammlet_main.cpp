@@ -26,6 +26,11 @@
 // `-O PD` (posterior) writes PREFIXposteriorSUFFIX under the same parameters and blocks: log p(y | theta) and the number of degenerate
 // blocks, then per run of equal called state its length, the state and its smallest posterior (hml_posterior, hml_posterior_rle;
 // with -chains N one file per chain, PREFIXchainK.posteriorSUFFIX);
+// `-O PB` (posteriorbreaks) writes PREFIXposteriorbreaksSUFFIX, the block boundaries whose posterior probability of a change of state
+// under those parameters is at least `-pbreak P`, with the expected number of breakpoints in the first line, and `-O PR`
+// (posteriorregions) writes PREFIXposteriorregionsSUFFIX, per region of `-regions FILE` the probability of no breakpoint inside, the
+// expected number of breakpoints, and per state the probability that all of the region is in it and its expected share
+// (hml_posterior_breaks, hml_posterior_regions: exact under the parameters, no recorded sweeps needed; one file per chain);
 // `-em STEPS [TOL]` fits theta, A and pi by expectation-maximisation once the scheme has run - at most STEPS M-steps over the last
 // block structure, from the chain's final parameters, until the objective gains no more than TOL of its size (hml_em_fit); `-em-prior`
 // makes the objective the posterior mode under the chain's priors instead of the maximum likelihood.  The fit runs before
@@ -77,6 +82,14 @@ static const char* kHelp =
     "                                 blocks no path reaches, then one line per run of equal most probable state: length, state\n"
     "                                 and the smallest posterior of that state over the run; with -chains N one file per chain;\n"
     "                                 needs a scheme with forward-backward sweeps (extension)\n"
+    "                    PB           posteriorbreaks: first line the expected number of breakpoints, the boundaries without a\n"
+    "                                 defined probability and P; then position and probability of every block boundary whose\n"
+    "                                 posterior probability of a change of state, under the parameters of -O PD, is at least the\n"
+    "                                 P of -pbreak; with -chains N one file per chain (extension)\n"
+    "                    PR           posteriorregions: per region of -regions, tab-separated: start, end, the probability of no\n"
+    "                                 breakpoint inside, the expected number of breakpoints, per state the probability that\n"
+    "                                 all of the region is in it, per state its expected share of the region, the label; exact\n"
+    "                                 under the parameters of -O PD; with -chains N one file per chain (extension)\n"
     "                    EM           em: the fit of -em - one line per step: step, objective; then the reason it stopped, the\n"
     "                                 parameters kept for want of support, and the fitted means, variances, A and pi; with\n"
     "                                 -chains N one file per chain (extension; needs -em)\n"
@@ -134,7 +147,8 @@ static const char* kHelp =
     "                                 sweeps, whatever the states are called (-O LB, -O LC) (extension)\n"
     "  -bandcall P                    the call of -O LC: 0 (default) the most probable band, 0 < P <= 1 the band of the\n"
     "                                 P-quantile of the recorded levels (0.5: the median) (extension)\n"
-    "  -regions FILE                  the regions of -O RG, one per line: start end [label ...], positions counted from 0, the\n"
+    "  -pbreak P                      the least probability of -O PB (default 0.5) (extension)\n"
+    "  -regions FILE                  the regions of -O RG and -O PR, one per line: start end [label ...], positions counted from 0, the\n"
     "                                 end not included; lines that begin with # and blank lines are skipped.  Regions may\n"
     "                                 overlap, nest and repeat (extension)\n"
     "  -em STEPS [TOL]                once the scheme has run, fit theta, A and pi by expectation-maximisation over the last block\n"
@@ -177,6 +191,7 @@ struct Job {
     double consensusShare = 0.5;
     size_t nrBandEdges = 0;          // -bands
     double bandCall = 0;             // -bandcall P
+    double posteriorBreak = 0.5;     // -pbreak P (-O PB)
     vector<uint32_t> regionStart, regionEnd;   // -regions FILE (recorded when -O RG asks for them)
     vector<string> regionLabel;
     vector<float> regionEdges;       // ... and their edges: those of -bands
@@ -544,8 +559,14 @@ static void writeViterbiFile(const Job& job, int index, hml_ctx* ctx) {
 
 // PREFIX[chainK.]posteriorSUFFIX: smoothing at the same moment
 static string posteriorFileName(const Job& job, int index) { return job.opref + (index == 0 ? "" : "chain" + std::to_string(index) + ".") + "posterior" + job.osuff; }
+static string posteriorBreaksFileName(const Job& job, int index) { return job.opref + (index == 0 ? "" : "chain" + std::to_string(index) + ".") + "posteriorbreaks" + job.osuff; }
+static string posteriorRegionsFileName(const Job& job, int index) { return job.opref + (index == 0 ? "" : "chain" + std::to_string(index) + ".") + "posteriorregions" + job.osuff; }
 static void writePosteriorFile(const Job& job, int index, hml_ctx* ctx) {
     if (job.outputs.at("posterior")) Posterior(ctx).writeFile(posteriorFileName(job, index));
+    // the pairwise read-outs of the same smoothing: breakpoints and the regions of -regions, under the same parameters
+    if (job.outputs.at("posteriorbreaks")) Posterior(ctx).writeBreaksFile(posteriorBreaksFileName(job, index), job.posteriorBreak);
+    if (job.outputs.at("posteriorregions"))
+        Posterior(ctx).writeRegionsFile(posteriorRegionsFileName(job, index), job.regionStart, job.regionEnd, job.regionLabel, (int)job.nrStates);
 }
 
 // -em: the fit once the scheme has run, before every end-of-run output; PREFIX[chainK.]emSUFFIX
@@ -754,6 +775,7 @@ int main(int argc, const char* argv[]) {
         args.registerFlags({"-consensus"}, "16 0.5");
         args.registerFlags({"-bands"});
         args.registerFlags({"-bandcall"}, "0");
+        args.registerFlags({"-pbreak"}, "0.5");
         args.registerFlags({"-merge-gpus"});
         args.registerFlags({"-regions"});
         args.registerFlags({"-history-every"}, "1");
@@ -843,6 +865,8 @@ int main(int argc, const char* argv[]) {
         outputArgs.registerFlags({"V", "viterbi"});           // extension
         outputArgs.registerFlags({"PD", "posterior"});        // extension (P is the reference's parameters)
         outputArgs.registerFlags({"EM", "em"});               // extension
+        outputArgs.registerFlags({"PB", "posteriorbreaks"});  // extension
+        outputArgs.registerFlags({"PR", "posteriorregions"}); // extension
         outputArgs.registerFlags({"L", "levels"});            // extension
         outputArgs.registerFlags({"BP", "breakpoints"});      // extension (B and C are the reference's blocks and compression)
         outputArgs.registerFlags({"CS", "consensus"});        // extension
@@ -924,7 +948,7 @@ int main(int argc, const char* argv[]) {
         job.weightMultiplier = weightMultiplier; job.useSelfTrans = useSelfTrans;
         job.thetaParams = thetaParams; job.trans = trans; job.selfTrans = selfTrans; job.initialAlpha = initialAlpha;
         job.scheme = scheme;
-        for (const char* o : {"sequences", "parameters", "blocks", "compression", "marginals", "segments", "maxsegmentation", "viterbi", "posterior", "em", "levels", "breakpoints", "consensus", "bands", "bandcalls", "rhat", "regions", "history", "historysummary"})
+        for (const char* o : {"sequences", "parameters", "blocks", "compression", "marginals", "segments", "maxsegmentation", "viterbi", "posterior", "posteriorbreaks", "posteriorregions", "em", "levels", "breakpoints", "consensus", "bands", "bandcalls", "rhat", "regions", "history", "historysummary"})
             job.outputs[o] = outputArgs.isSet(o);
         auto refuseExisting = [&](const string& fn) {
             if (!overwrite) { std::ifstream probe(fn); if (probe.good()) throw std::runtime_error("File " + fn + " already exists! Use -w to allow overwrite!"); }
@@ -996,6 +1020,21 @@ int main(int argc, const char* argv[]) {
             for (const Step& st : scheme) anyFB = anyFB || st.method == "F";
             if (!anyFB) throw std::runtime_error("The output posterior (PD) needs a model with transitions: the scheme has mixture sweeps only!");
             for (long k = 0; k < (long)nrChains; ++k) refuseExisting(posteriorFileName(job, (int)k));
+        }
+        if (job.outputs.at("posteriorbreaks") || job.outputs.at("posteriorregions")) {
+            // exact functions of the smoothing's rows: they need what -O PD needs
+            bool anyFB = false;
+            for (const Step& st : scheme) anyFB = anyFB || st.method == "F";
+            if (!anyFB)
+                throw std::runtime_error("The outputs posteriorbreaks (PB) and posteriorregions (PR) need a model with transitions: the scheme has mixture sweeps only!");
+            if (job.outputs.at("posteriorbreaks")) {
+                job.posteriorBreak = args.parse<double>("-pbreak", 0);
+                for (long k = 0; k < (long)nrChains; ++k) refuseExisting(posteriorBreaksFileName(job, (int)k));
+            }
+            if (job.outputs.at("posteriorregions")) {
+                if (!args.isSet("-regions")) throw std::runtime_error("The output posteriorregions (PR) needs the regions: give them with -regions FILE!");
+                for (long k = 0; k < (long)nrChains; ++k) refuseExisting(posteriorRegionsFileName(job, (int)k));
+            }
         }
         if (job.outputs.at("em") && !args.isSet("-em")) throw std::runtime_error("The output em (EM) needs a fit: ask for one with -em STEPS [TOL]!");
         if (args.isSet("-em")) {

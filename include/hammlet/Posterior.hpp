@@ -4,6 +4,11 @@
 //   PREFIXposteriorSUFFIX   `-O PD`: first line "loglik<TAB>degenerate" (%.17g, integer), then "length<TAB>state<TAB>confidence"
 //                           per run of equal called state - the maxsegmentation file's columns and, as %.17g, the smallest
 //                           posterior of that state over the run's blocks
+//   PREFIXposteriorbreaksSUFFIX   `-O PB`: first line "expected_breaks<TAB>pair_degenerate<TAB>min_prob" (%.17g, integer, %.17g),
+//                           then "position<TAB>probability" (%.17g) per block boundary whose posterior probability of a change of
+//                           state is at least `-pbreak P`, by ascending position (hml_posterior_breaks)
+//   PREFIXposteriorregionsSUFFIX  `-O PR`: per region of `-regions FILE`, tab-separated: start, end, whole, expected_breaks,
+//                           K whole_state, K share (%.17g), then the region's label (hml_posterior_regions)
 // A thin handle over a context that something else owns (the chain's rng_t), next to Viterbi.  Every call computes anew; the
 // chain is only read.
 #ifndef HAMMLET_POSTERIOR_HPP
@@ -27,6 +32,17 @@ public:
         std::vector<uint64_t> length;   // positions per run
         std::vector<int32_t> state;
         std::vector<double> confidence; // min over the run's blocks of p(q_b = state | y, theta)
+    };
+    struct Breaks {
+        std::vector<uint32_t> position;    // starts[b] of the boundaries with p_b >= minProb, ascending
+        std::vector<double> probability;   // p_b
+        double expectedBreaks = 0;         // in the whole trace
+        uint64_t pairDegenerate = 0;
+    };
+    struct Regions {
+        std::vector<double> whole, expectedBreaks;   // [n]
+        std::vector<double> wholeState, share;       // [n][K], row-major
+        uint64_t pairDegenerate = 0;
     };
     struct Info { uint64_t chunks = 0, L = 0, W = 0, staleForward = 0, staleBackward = 0, rounds = 0, serialChunks = 0; };
 
@@ -61,6 +77,28 @@ public:
         check(hml_posterior_rle(mCtx, &n, r.length.data(), r.state.data(), r.confidence.data()));
         return r;
     }
+    // the block boundaries whose posterior probability of a change of state is at least minProb
+    Breaks breaks(double minProb) const {
+        Breaks b;
+        uint64_t n = 0;
+        check(hml_get_num_blocks(mCtx, &n));   // (room for every boundary: one call, one computation)
+        b.position.resize(n);
+        b.probability.resize(n);
+        check(hml_posterior_breaks(mCtx, minProb, &n, b.position.data(), b.probability.data(), &b.expectedBreaks, &b.pairDegenerate));
+        b.position.resize(n);
+        b.probability.resize(n);
+        return b;
+    }
+    // per region [start[r], end[r]): no breakpoint inside, all of it in state j, expected breakpoints, expected share of state j
+    Regions regions(const std::vector<uint32_t>& start, const std::vector<uint32_t>& end, int K) const {
+        if (start.size() != end.size()) throw std::runtime_error("Posterior::regions: as many starts as ends");
+        Regions r;
+        const size_t n = start.size();
+        r.whole.resize(n); r.expectedBreaks.resize(n); r.wholeState.resize(n * (size_t)K); r.share.resize(n * (size_t)K);
+        check(hml_posterior_regions(mCtx, n, start.data(), end.data(), r.whole.data(), r.wholeState.data(), r.expectedBreaks.data(), r.share.data(), nullptr,
+                                    &r.pairDegenerate));
+        return r;
+    }
     Info info() const {
         Info i;
         check(hml_posterior_info(mCtx, &i.chunks, &i.L, &i.W, &i.staleForward, &i.staleBackward, &i.rounds, &i.serialChunks));
@@ -75,6 +113,28 @@ public:
         if (!out) throw std::runtime_error("Cannot write to file " + fn + "!");
         fprintf(out, "%.17g\t%llu\n", l, (unsigned long long)degenerate);
         for (size_t i = 0; i < r.length.size(); ++i) fprintf(out, "%llu\t%d\t%.17g\n", (unsigned long long)r.length[i], (int)r.state[i], r.confidence[i]);
+        if (fclose(out) != 0) throw std::runtime_error("Cannot write to file " + fn + "!");
+    }
+
+    void writeBreaksFile(const std::string& fn, double minProb) const {
+        const Breaks b = breaks(minProb);
+        FILE* out = fopen(fn.c_str(), "w");
+        if (!out) throw std::runtime_error("Cannot write to file " + fn + "!");
+        fprintf(out, "%.17g\t%llu\t%.17g\n", b.expectedBreaks, (unsigned long long)b.pairDegenerate, minProb);
+        for (size_t i = 0; i < b.position.size(); ++i) fprintf(out, "%u\t%.17g\n", b.position[i], b.probability[i]);
+        if (fclose(out) != 0) throw std::runtime_error("Cannot write to file " + fn + "!");
+    }
+
+    void writeRegionsFile(const std::string& fn, const std::vector<uint32_t>& start, const std::vector<uint32_t>& end, const std::vector<std::string>& label, int K) const {
+        const Regions r = regions(start, end, K);
+        FILE* out = fopen(fn.c_str(), "w");
+        if (!out) throw std::runtime_error("Cannot write to file " + fn + "!");
+        for (size_t i = 0; i < start.size(); ++i) {
+            fprintf(out, "%u\t%u\t%.17g\t%.17g", start[i], end[i], r.whole[i], r.expectedBreaks[i]);
+            for (int j = 0; j < K; ++j) fprintf(out, "\t%.17g", r.wholeState[i * (size_t)K + j]);
+            for (int j = 0; j < K; ++j) fprintf(out, "\t%.17g", r.share[i * (size_t)K + j]);
+            fprintf(out, "\t%s\n", i < label.size() ? label[i].c_str() : "");
+        }
         if (fclose(out) != 0) throw std::runtime_error("Cannot write to file " + fn + "!");
     }
 };

@@ -591,6 +591,49 @@ int hml_expected_counts(hml_ctx* ctx, double* xi /*K*K*/, double* first /*K*/, d
 int hml_em_step(hml_ctx* ctx, int use_prior, double* objective_before, uint64_t* kept);
 int hml_em_fit(hml_ctx* ctx, int use_prior, uint64_t max_steps, double rel_tol, double* trace /*max_steps+1, may be NULL*/, uint64_t* steps, int* reason, uint64_t* kept);
 
+/* ---- pairwise read-outs of the smoothing: breakpoint and region posteriors under the current parameters.  No counterpart in
+ * the reference. ----
+ * The joint questions of "joint posteriors over regions" above, asked of a fitted model instead of recorded sweeps: where the
+ * breakpoints are and how sure each is, whether a whole region is one segment or all of it in one state, how many breakpoints
+ * to expect inside it.  Under fixed parameters these are exact functions of the rows alpha and beta of a smoothing pass - no
+ * Monte-Carlo error - and none of them follows from gamma.  They bear labels, which a fitted model can afford.
+ * With e, alpha, beta, gamma as smoothing defines them, IEEE double, + x / only, sums from 0.0 in ascending index:
+ *   per boundary b = 1 ... B - 1 (between blocks b - 1 and b):  v(j) = e_b(j) beta_b(j);  x(i, j) = (alpha_{b-1}(i) A_ij) v(j);
+ *     d_b = sum_j x(j, j);  o_b = sum_i sum_{j != i} x(i, j) (i outer, j inner);
+ *     p_b = o_b / (d_b + o_b), the posterior probability of a change of state at position starts[b].  The off-diagonal mass is
+ *     summed directly and never formed as one minus the rest, so a probability of 1e-20 stays one.  If d_b + o_b is not a
+ *     positive finite number, p_b = 0 and the boundary is counted in pair_degenerate.
+ *     u(j) = sum_k A_jk v(k);  r_b(j) = (A_jj v(j)) / u(j) = p(q_b = j | q_{b-1} = j, y, theta), and 0 where u(j) is not a
+ *     positive finite number (the quotient would be 0 / 0): no output holds a not-a-number.
+ *   in fixed point (integers: their prefix sums are associative, so no result depends on how a scan is cut):
+ *     pfx_b = llrint(p_b 2^32);  cost_b(j) = 1023 2^22 (the cap) if u(j) is not positive finite or r_b(j) is not > 0, else
+ *     min(llrint(max(-log r_b(j), 0) 2^22), cap), in units of 2^-22 nat;  mass_b(j) = n_b llrint(gamma_b(j) 2^32) for
+ *     b = 0 ... B - 1.  Block 0 has no boundary: p_0, r_0, pfx_0 and cost_0 are 0.  N, C_j and G_j are their inclusive prefix
+ *     sums over b, in uint64.  e^x is taken as exactly 0 below -700: one capped boundary makes a joint probability exactly 0.
+ *   per region [start, end) (positions, half open, in any order, overlapping or repeated), ba and be the blocks of start and end - 1:
+ *     whole_state[j]  = gamma_ba(j) exp(-(C_j[be] - C_j[ba]) 2^-22): the probability that every position of it is in state j
+ *     whole           = sum_j whole_state[j]: the probability of no breakpoint inside it
+ *     expected_breaks = (N[be] - N[ba]) 2^-32
+ *     share[j]        = (M_j 2^-32) / (end - start), M_j the sum of mass(j) over blocks ba ... be less (start - starts[ba])
+ *                       llrint(gamma_ba(j) 2^32) and (starts[be + 1] - end) llrint(gamma_be(j) 2^32): the expected fraction of
+ *                       its positions in state j.  The region's expected level is sum_j share[j] mu_d(j), on the host.
+ *   A cost is off by at most 2^-23 nat, so whole_state by at most (be - ba) 2^-23 relative (1e-3 over 10^4 blocks);
+ *   expected_breaks by at most (be - ba) 2^-33; share[j] by at most 2^-33.  hammlet_amd/csrc/hml_pairs_ref.h states every step
+ *   and restates it for one host thread; the device gives those very words.
+ * hml_posterior_breaks: the boundaries with p_b >= min_prob by ascending position (pos == NULL: the count alone; prob may be
+ * NULL; B - 1 entries always suffice); expected_breaks = N[B - 1] 2^-32, the expected number of breakpoints in the trace.  A
+ * min_prob that is not a number is HML_ERR_ARG, and so are more than 2^31 - 1 blocks: the list's counts are 32-bit.
+ * hml_posterior_regions: the regions are arguments - they are not hml_set_regions' and disturb no recording;
+ * start >= end or end > T is HML_ERR_ARG; n = 0 succeeds; any output may be NULL; raw holds per region the break units
+ * N[be] - N[ba], the K cost differences and the K masses M_j.  hml_posterior_pair_terms: the terms themselves (probe; any may be
+ * NULL).  The refusals are hml_posterior's (a halted chain, no blocks, no model); hml_posterior_info reports the smoothing pass
+ * behind the call.  The chain is only read.  Device memory - (2 K + 2) 8 bytes per block on top of the smoothing's - is local
+ * to a call and released before it returns. */
+int hml_posterior_breaks(hml_ctx* ctx, double min_prob, uint64_t* n, uint32_t* pos /*n*/, double* prob /*n*/, double* expected_breaks, uint64_t* pair_degenerate);
+int hml_posterior_regions(hml_ctx* ctx, uint64_t n, const uint32_t* start /*n*/, const uint32_t* end /*n*/, double* whole /*n*/, double* whole_state /*n*K*/,
+                          double* expected_breaks /*n*/, double* share /*n*K*/, uint64_t* raw /*n*(2K+1), may be NULL*/, uint64_t* pair_degenerate);
+int hml_posterior_pair_terms(hml_ctx* ctx, double* p /*B*/, double* r /*B*K*/, uint64_t* pfx /*B*/, uint64_t* cost /*B*K*/, uint64_t* mass /*B*K*/);
+
 /* ---- sparse payloads: levels, breakpoints and bands across GPUs.  No counterpart in the reference. ----
  * The three recordings above keep a cell and a boundary bit per change of state, so what another GPU needs of one is a list:
  * the M positions with a cell and the cells there.  The PAYLOAD is one contiguous buffer in device memory, little endian,
