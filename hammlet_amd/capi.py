@@ -127,6 +127,10 @@ SIGNATURES = {
     "hml_expected_counts": (C.c_int, [_P] * 7 + [C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "hml_em_step": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "hml_em_fit": (C.c_int, [_P, C.c_int, C.c_uint64, C.c_double, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
+    "hml_em_fit_many": (C.c_int, [_P, C.c_uint64, _P, _P, _P, C.c_int, C.c_uint64, C.c_double, C.c_int] + [_P] * 8 + [C.POINTER(C.c_int64)]),
+    "hml_em_starts": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_double, _P, _P, _P]),
+    "hml_em_many_info": (C.c_int, [_P] + [C.POINTER(C.c_uint64)] * 9),
+    "hml_set_em_batch_bytes": (C.c_int, [_P, C.c_uint64]),
     "hml_posterior_breaks": (C.c_int, [_P, C.c_double, C.POINTER(C.c_uint64), _P, _P, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "hml_posterior_regions": (C.c_int, [_P, C.c_uint64] + [_P] * 7 + [C.POINTER(C.c_uint64)]),
     "hml_posterior_pair_terms": (C.c_int, [_P] * 6),
@@ -762,6 +766,52 @@ class Chain:
         steps, reason, kept = C.c_uint64(), C.c_int(), C.c_uint64()
         _check(self.lib.hml_em_fit(self.h, 1 if use_prior else 0, int(max_steps), float(rel_tol), trace.ctypes.data, C.byref(steps), C.byref(reason), C.byref(kept)))
         return trace[:steps.value + 1].copy(), steps.value, reason.value, kept.value
+
+    # ---- EM from many starts ----------------------------------------------------------------------
+    def em_starts(self, n, seed, spread=1.0):
+        """(mean_var[n, 2 P], A[n, K, K], pi[n, K] float32): member 0 the current parameters, the others' means drawn over the
+        current means' range widened by `spread` and sorted, A and pi the current ones (hml_em_starts)"""
+        n, K, P = int(n), self.K, self.P or self.K
+        mv, A, pi = np.empty((n, 2 * P), np.float32), np.empty((n, K, K), np.float32), np.empty((n, K), np.float32)
+        _check(self.lib.hml_em_starts(self.h, n, int(seed), float(spread), mv.ctypes.data, A.ctypes.data, pi.ctypes.data))
+        return mv, A, pi
+
+    def em_fit_many(self, starts=None, n_starts=None, seed=0, spread=1.0, max_steps=30, rel_tol=0.0, use_prior=False, install=True):
+        """A batch of fits, member r exactly set_parameters(start r) + em_fit(max_steps, rel_tol, use_prior): dict(trace[R,
+        max_steps + 1] float64 - NaN past a member's last entry -, steps, reason, kept, mean_var[R, 2 P], A[R, K, K], pi[R, K],
+        objective[R], best).  starts = (mean_var, A, pi) arrays, or n_starts members from em_starts(n_starts, seed, spread).
+        install: the winner's parameters become the chain's; best = -1 (no member is a candidate) leaves them (hml_em_fit_many)"""
+        K, P = self.K, self.P or self.K
+        if starts is None:
+            if n_starts is None:
+                raise ValueError("em_fit_many: give starts or n_starts")
+            starts = self.em_starts(n_starts, seed, spread)
+        mv = np.ascontiguousarray(starts[0], np.float32)
+        R = mv.size // (2 * P)
+        A = np.ascontiguousarray(starts[1], np.float32)
+        pi = np.ascontiguousarray(starts[2], np.float32)
+        if mv.size != R * 2 * P or A.size != R * K * K or pi.size != R * K:
+            raise ValueError("em_fit_many: starts must be mean_var[R, 2 P], A[R, K, K], pi[R, K]")
+        n = int(max_steps) + 1
+        trace = np.empty((R, n), np.float64)
+        steps, reason, kept = np.empty(R, np.uint64), np.empty(R, np.int32), np.empty(R, np.uint64)
+        fmv, fA, fpi = np.empty((R, 2 * P), np.float32), np.empty((R, K, K), np.float32), np.empty((R, K), np.float32)
+        obj, best = np.empty(R, np.float64), C.c_int64()
+        _check(self.lib.hml_em_fit_many(self.h, R, mv.ctypes.data, A.ctypes.data, pi.ctypes.data, 1 if use_prior else 0, int(max_steps), float(rel_tol),
+                                        1 if install else 0, trace.ctypes.data, steps.ctypes.data, reason.ctypes.data, kept.ctypes.data, fmv.ctypes.data,
+                                        fA.ctypes.data, fpi.ctypes.data, obj.ctypes.data, C.byref(best)))
+        return dict(trace=trace, steps=steps, reason=reason, kept=kept, mean_var=fmv, A=fA, pi=fpi, objective=obj, best=best.value)
+
+    def em_many_info(self):
+        """of the last em_fit_many: dict(members, groups, group_size, esteps, launch_sets, stale_fwd, stale_bwd, rounds,
+        serial_chunks) (hml_em_many_info)"""
+        v = [C.c_uint64() for _ in range(9)]
+        _check(self.lib.hml_em_many_info(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("members", "groups", "group_size", "esteps", "launch_sets", "stale_fwd", "stale_bwd", "rounds", "serial_chunks"), (x.value for x in v)))
+
+    def set_em_batch_bytes(self, n_bytes=0):
+        """the device memory a group of em_fit_many's members may take (0: the default) (hml_set_em_batch_bytes)"""
+        _check(self.lib.hml_set_em_batch_bytes(self.h, int(n_bytes)))
 
     # ---- pairwise read-outs of the smoothing: breakpoint and region posteriors ------------------
     def posterior_breaks(self, min_prob=0.0):

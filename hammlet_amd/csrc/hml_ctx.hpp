@@ -221,6 +221,13 @@ struct hml_ctx {
         bool computed = false;
         uint64_t chunks = 0, used_L = 0, used_W = 0, stale_fwd = 0, stale_bwd = 0, rounds_run = 0, walked = 0;
     } post;
+    // EM from many starts (hml_em_fit_many; hml_k_em_many.h): the byte budget of a group's device memory (0: the default) and what
+    // the last call did (hml_em_many_info).
+    struct {
+        uint64_t batch_bytes = 0;
+        bool computed = false;
+        uint64_t members = 0, groups = 0, group_size = 0, esteps = 0, launch_sets = 0, stale_fwd = 0, stale_bwd = 0, rounds_run = 0, walked = 0;
+    } em_many;
     // Every d_* above that is not a plain pointer owns its buffer (DevBuf / DevArr, hml_host_common.hpp): deleting the context
     // frees them, whatever a call that failed half-way left allocated, and allocating one again replaces what it held.
     ~hml_ctx() { if (h_B) (void)hipHostFree(h_B); }

@@ -25,13 +25,10 @@
 
 // X_b for b = 1 ... B - 1 (X[0] is not written); blocks with bad(X_b) are counted.  Dynamic LDS: (K K + K) doubles
 template <int KM>
-HML_KERNEL __launch_bounds__(64) void hml_k_em_norm(const hml_post_args a, const double* __restrict__ alpha, const double* __restrict__ beta,
-                                                    double* __restrict__ X, unsigned long long* __restrict__ n_bad) {
-    extern __shared__ double hml_post_lds[];
+__device__ __forceinline__ void hml_em_norm_block(const hml_post_args& a, const double* sA, const double* __restrict__ alpha, const double* __restrict__ beta,
+                                                  double* __restrict__ X, unsigned long long* __restrict__ n_bad) {
     constexpr int UF = KM <= 16 ? KM : 1;
     const int K = a.par->K;
-    hml_post_stage(a, K, hml_post_lds);
-    const double* const sA = hml_post_lds;
     const uint64_t b64 = (uint64_t)blockIdx.x * 64u + threadIdx.x + 1u;
     if (b64 >= (uint64_t)a.par->B) return;
     const uint32_t b = (uint32_t)b64;
@@ -54,6 +51,13 @@ HML_KERNEL __launch_bounds__(64) void hml_k_em_norm(const hml_post_args a, const
     X[b] = s;
     if (hml_post_bad(s)) atomicAdd(n_bad, 1ull);
 }
+template <int KM>
+HML_KERNEL __launch_bounds__(64) void hml_k_em_norm(const hml_post_args a, const double* __restrict__ alpha, const double* __restrict__ beta,
+                                                    double* __restrict__ X, unsigned long long* __restrict__ n_bad) {
+    extern __shared__ double hml_post_lds[];
+    hml_post_stage(a, a.par->K, hml_post_lds);
+    hml_em_norm_block<KM>(a, hml_post_lds, alpha, beta, X, n_bad);
+}
 
 struct hml_em_args {
     const hml_vit_par* par;
@@ -68,7 +72,7 @@ struct hml_em_args {
 
 // level 1 of every column's tree: workgroup g owns leaves 64 g ... 64 g + 63 of both trees.  Column order: xi row-major, then
 // occ[K], stay[K], sx[D][K], sxx[D][K]
-HML_KERNEL __launch_bounds__(256) void hml_k_em_reduce(const hml_em_args a) {
+__device__ __forceinline__ void hml_em_reduce_group(const hml_em_args& a) {
     __shared__ double sAl[HML_EM_TL][HML_CAP_K], sBe[HML_EM_TL + 1][HML_CAP_K], sV[HML_EM_TL][HML_CAP_K], sG[HML_EM_TL][HML_CAP_K];
     __shared__ float sE[HML_EM_TL][HML_CAP_K];
     __shared__ double sX[HML_EM_TL], sN[HML_EM_TL], sS[HML_EM_TL][2 * HML_MAX_D];
@@ -172,6 +176,7 @@ HML_KERNEL __launch_bounds__(256) void hml_k_em_reduce(const hml_em_args a) {
         if (col < ncols && (col >= KK || has_x)) a.part[(uint64_t)blockIdx.x * ncols + col] = acc[q];
     }
 }
+HML_KERNEL __launch_bounds__(256) void hml_k_em_reduce(const hml_em_args a) { hml_em_reduce_group(a); }
 
 // The same level 1 for K <= KS <= 16, where the shape above leaves most lanes without a column: ONE WAVEFRONT per group, all 64
 // leaves in one tile.  While staging, lane l owns block base + l: it reads alpha_b and beta_b (adjacent lanes adjacent rows), stores
@@ -179,7 +184,7 @@ HML_KERNEL __launch_bounds__(256) void hml_k_em_reduce(const hml_em_args a) {
 // terms, v and X_{b+1} with its K K additions in the prescribed order (A in LDS), so hml_k_em_norm and the array X are not needed;
 // then a lane per column makes the 64 in-order additions.  Rows are padded to KS + 1 doubles against bank conflicts.
 template <int KS>
-HML_KERNEL __launch_bounds__(64) void hml_k_em_reduce_small(const hml_em_args a, unsigned long long* __restrict__ n_bad) {
+__device__ __forceinline__ void hml_em_reduce_small_group(const hml_em_args& a, unsigned long long* __restrict__ n_bad) {
     constexpr int NQ = (KS * KS + KS * (2 + 2 * HML_MAX_D) + 63) / 64;
     __shared__ double sA[KS * KS], sAl[64][KS + 1], sV[64][KS + 1], sG[64][KS + 1];
     __shared__ double sX[64], sN[64], sS[64][2 * HML_MAX_D + 1];
@@ -269,10 +274,12 @@ HML_KERNEL __launch_bounds__(64) void hml_k_em_reduce_small(const hml_em_args a,
         a.part[(uint64_t)blockIdx.x * ncols + col] = s;
     }
 }
+template <int KS>
+HML_KERNEL __launch_bounds__(64) void hml_k_em_reduce_small(const hml_em_args a, unsigned long long* __restrict__ n_bad) { hml_em_reduce_small_group<KS>(a, n_bad); }
 
 // one level of all columns' trees: rows of ncols values; the first KK columns have n_x rows, the others n_o >= n_x
-HML_KERNEL __launch_bounds__(256) void hml_k_em_tree(const double* __restrict__ in, uint64_t n_x, uint64_t n_o, uint32_t ncols, uint32_t KK,
-                                                     double* __restrict__ out) {
+__device__ __forceinline__ void hml_em_tree_level(const double* __restrict__ in, uint64_t n_x, uint64_t n_o, uint32_t ncols, uint32_t KK,
+                                                  double* __restrict__ out) {
     const uint64_t total = ((n_o + 63u) / 64u) * ncols;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += stride) {
@@ -286,5 +293,7 @@ HML_KERNEL __launch_bounds__(256) void hml_k_em_tree(const double* __restrict__ 
         out[i * ncols + col] = s;
     }
 }
+HML_KERNEL __launch_bounds__(256) void hml_k_em_tree(const double* __restrict__ in, uint64_t n_x, uint64_t n_o, uint32_t ncols, uint32_t KK,
+                                                     double* __restrict__ out) { hml_em_tree_level(in, n_x, n_o, ncols, KK, out); }
 
 #endif

@@ -236,18 +236,12 @@ __device__ __forceinline__ bool hml_post_same(const double* p, const double* q, 
 }
 
 // A repair round: a lane per run of stale chunks, from its head - the walk of hml_k_vit_rerun (see there for why it stops
-// where it stops), over chain indices
+// where it stops), over chain indices.  hml_post_rerun_walk is one lane's walk from the head x (never 0)
 template <int KM, int DIR>
-HML_KERNEL __launch_bounds__(64) void hml_k_post_rerun(const hml_post_args a, const uint32_t* __restrict__ heads, uint32_t n_heads,
-                                                       const uint8_t* __restrict__ match) {
-    extern __shared__ double hml_post_lds[];
+__device__ __forceinline__ void hml_post_rerun_walk(const hml_post_args& a, const double* sA, uint32_t x, const uint8_t* __restrict__ match) {
     const int K = a.par->K;
-    hml_post_stage(a, K, hml_post_lds);
-    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
-    if (i >= n_heads) return;
-    uint32_t x = heads[i];   // (never 0)
     for (;;) {
-        hml_post_run_chunk<KM, DIR>(a, hml_post_lds, x, a.exitv + (uint64_t)(x - 1u) * K);
+        hml_post_run_chunk<KM, DIR>(a, sA, x, a.exitv + (uint64_t)(x - 1u) * K);
         for (;;) {
             const uint32_t nx = x + 1u;
             if (nx >= a.n_chunks) return;
@@ -263,15 +257,22 @@ HML_KERNEL __launch_bounds__(64) void hml_k_post_rerun(const hml_post_args a, co
         }
     }
 }
+template <int KM, int DIR>
+HML_KERNEL __launch_bounds__(64) void hml_k_post_rerun(const hml_post_args a, const uint32_t* __restrict__ heads, uint32_t n_heads,
+                                                       const uint8_t* __restrict__ match) {
+    extern __shared__ double hml_post_lds[];
+    hml_post_stage(a, a.par->K, hml_post_lds);
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n_heads) return;
+    hml_post_rerun_walk<KM, DIR>(a, hml_post_lds, heads[i], match);
+}
 
 // what the rounds left: one wavefront walks the chain in increasing order, its first lane runs what does not match - the walk
-// of hml_k_vit_finish
+// of hml_k_vit_finish.  hml_post_finish_walk is that wavefront's walk (all 64 lanes call)
 template <int KM, int DIR>
-HML_KERNEL __launch_bounds__(64) void hml_k_post_finish(const hml_post_args a, const uint8_t* __restrict__ match, unsigned long long* __restrict__ walked) {
-    extern __shared__ double hml_post_lds[];
+__device__ __forceinline__ void hml_post_finish_walk(const hml_post_args& a, const double* sA, const uint8_t* __restrict__ match,
+                                                     unsigned long long* __restrict__ walked) {
     const int K = a.par->K;
-    hml_post_stage(a, K, hml_post_lds);
-    if (blockIdx.x != 0u || blockDim.x != 64u) return;
     const int lane = threadIdx.x;
     const uint32_t n_chunks = a.n_chunks;
     unsigned long long n_walked = 0ull;
@@ -290,7 +291,7 @@ HML_KERNEL __launch_bounds__(64) void hml_k_post_finish(const hml_post_args a, c
             }
             if (need) {
                 if (lane == 0) {
-                    hml_post_run_chunk<KM, DIR>(a, hml_post_lds, x, a.exitv + (uint64_t)(x - 1u) * K);
+                    hml_post_run_chunk<KM, DIR>(a, sA, x, a.exitv + (uint64_t)(x - 1u) * K);
                     __threadfence();
                 }
                 ++n_walked;
@@ -300,6 +301,13 @@ HML_KERNEL __launch_bounds__(64) void hml_k_post_finish(const hml_post_args a, c
         }
     }
     if (lane == 0) *walked += n_walked;
+}
+template <int KM, int DIR>
+HML_KERNEL __launch_bounds__(64) void hml_k_post_finish(const hml_post_args a, const uint8_t* __restrict__ match, unsigned long long* __restrict__ walked) {
+    extern __shared__ double hml_post_lds[];
+    hml_post_stage(a, a.par->K, hml_post_lds);
+    if (blockIdx.x != 0u || blockDim.x != 64u) return;
+    hml_post_finish_walk<KM, DIR>(a, hml_post_lds, match, walked);
 }
 
 // a lane per block: gamma_b (stored if asked), the called state and its posterior; degenerate blocks - bad(c_b) - are counted
@@ -326,8 +334,8 @@ HML_KERNEL __launch_bounds__(256) void hml_k_post_combine(const double* __restri
     }
 }
 
-// one level of the fan-in-64 tree: out[i] = in[64 i] + in[64 i + 1] + ... in this order
-HML_KERNEL __launch_bounds__(256) void hml_k_post_tree(const double* __restrict__ in, uint64_t n, double* __restrict__ out) {
+// one level of the fan-in-64 tree: out[i] = in[64 i] + in[64 i + 1] + ... in this order (the lanes of grid dimension x share it)
+__device__ __forceinline__ void hml_post_tree_level(const double* __restrict__ in, uint64_t n, double* __restrict__ out) {
     const uint64_t n_out = (n + 63u) / 64u;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_out; i += stride) {
@@ -337,6 +345,7 @@ HML_KERNEL __launch_bounds__(256) void hml_k_post_tree(const double* __restrict_
         out[i] = s;
     }
 }
+HML_KERNEL __launch_bounds__(256) void hml_k_post_tree(const double* __restrict__ in, uint64_t n, double* __restrict__ out) { hml_post_tree_level(in, n, out); }
 
 // hml_k_seg_run_scatter with the run's confidence: run r starts at position start[i] with state q[i]; every block lowers the
 // minimum of its run (words preset to all ones; posteriors are non-negative doubles, ordered as their words are)

@@ -1449,11 +1449,15 @@ static void post_launch_finish(hml_ctx* c, const hml_post_args& a, size_t lds, c
 #define POST_BY_K(K, DIR, fn, ...) do { if ((K) <= 8) fn<8, DIR>(__VA_ARGS__); else if ((K) <= 16) fn<16, DIR>(__VA_ARGS__); else fn<HML_CAP_K, DIR>(__VA_ARGS__); } while (0)
 
 // how a call begins: a settled chain with blocks, and the tables (parameters, A and pi in double) on the device
-static int post_begin(hml_ctx* c, post_tables& t, uint32_t* B_out) {
-    hml_model m; if (int r = fetch_model(c, &m)) return r;
+static int post_ready(const hml_model& m) {
     if (int r = model_fault(m)) return r;
     if (m.halted) return set_err(HML_ERR_ARG, "hml_posterior: the chain is halted; settle it with hml_sync first");
     if (m.B == 0) return set_err(HML_ERR_ARG, "hml_posterior: no blocks yet: run a sweep or hml_create_blocks first");
+    return 0;
+}
+static int post_begin(hml_ctx* c, post_tables& t, uint32_t* B_out) {
+    hml_model m; if (int r = fetch_model(c, &m)) return r;
+    if (int r = post_ready(m)) return r;
     const int K = c->K;
     HIPCHK(t.par.alloc(sizeof(hml_vit_par)));
     HIPCHK(t.A.alloc((uint64_t)K * K * sizeof(double)));
@@ -1746,9 +1750,13 @@ struct em_params {
     hml_em_prior pr;
     int P = 0, self_trans = 1;
 };
+static void em_params_of(const hml_model& m, int K, em_params& q);
 static int em_fetch(hml_ctx* c, em_params& q) {
     hml_model m; if (int r = fetch_model(c, &m)) return r;
-    const int K = c->K;
+    em_params_of(m, c->K, q);
+    return 0;
+}
+static void em_params_of(const hml_model& m, int K, em_params& q) {
     q.P = m.P; q.self_trans = m.self_trans != 0;
     q.mv.resize(2 * (size_t)m.P);
     for (int k = 0; k < m.P; ++k) { q.mv[2 * k] = m.mu[k]; q.mv[2 * k + 1] = m.var[k]; }
@@ -1756,7 +1764,6 @@ static int em_fetch(hml_ctx* c, em_params& q) {
     q.pi.assign(m.pi, m.pi + K);
     q.pr.alpha = (double)m.nig_prior[0]; q.pr.beta = (double)m.nig_prior[1]; q.pr.mu0 = (double)m.nig_prior[2]; q.pr.nu = (double)m.nig_prior[3];
     q.pr.a_off = (double)m.a_off; q.pr.a_diag = (double)m.a_diag; q.pr.pi_alpha = (double)m.pi_alpha;
-    return 0;
 }
 
 // one E-step, the objective of the current parameters, and whether the E-step was degenerate
@@ -1821,6 +1828,326 @@ int hml_em_fit(hml_ctx* c, int use_prior, uint64_t max_steps, double rel_tol, do
     if (steps) *steps = k;
     if (reason) *reason = why;
     if (kept) *kept = k_total;
+    return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------- EM from many starts (hml_k_em_many.h)
+// A batch of fits over the same blocks, each hml_set_parameters(start) + hml_em_fit word for word: the E-steps of the members
+// still running go through one set of launches per group, the member being grid dimension y; objective, stopping rule and
+// M-step are the header's functions per member on the host, as in hml_em_fit.  The context's parameters are not touched before
+// the winner is installed.  Device memory is local to the call.
+#include <limits>
+
+#include "hml_em_many_ref.h"
+#include "hml_k_em_many.h"   // (launched from this object alone)
+
+#define HML_EM_MANY_DEFAULT_BYTES (4ull << 30)   // of a group's device memory (hml_set_em_batch_bytes)
+
+struct em_many_geom {
+    int K = 0, D = 0, P = 0;
+    uint32_t B = 0, L = 0, W = 0, n_chunks = 0, ncols = 0;
+    uint64_t n1 = 0, n2 = 0, nfloats = 0, nresult = 0;
+    bool small = false;
+};
+struct em_many_bufs {
+    DevBuf alpha, beta, cval, ell, entry, exitv, match, heads, cnt, words, lt1, lt2, X, p1, p2, first, par, A, pi, mdl, floats, result, recs;
+};
+struct em_many_stats { uint64_t launch_sets = 0, stale[2] = {0, 0}, rounds = 0, walked = 0; };
+
+// (array, bytes per member) in the order they are allocated
+static std::vector<std::pair<DevBuf*, uint64_t>> em_many_layout(em_many_bufs& b, const em_many_geom& g) {
+    const uint64_t B = g.B, K = g.K, dbl = sizeof(double);
+    std::vector<std::pair<DevBuf*, uint64_t>> v = {
+        {&b.alpha, B * K * dbl}, {&b.beta, B * K * dbl}, {&b.cval, B * dbl}, {&b.ell, B * dbl}, {&b.entry, (uint64_t)g.n_chunks * K * dbl},
+        {&b.exitv, (uint64_t)g.n_chunks * K * dbl}, {&b.match, g.n_chunks}, {&b.heads, (uint64_t)g.n_chunks * sizeof(uint32_t)}, {&b.cnt, 2 * sizeof(uint32_t)},
+        {&b.words, HML_EMM_WORDS * sizeof(unsigned long long)}, {&b.lt1, g.n1 * dbl}, {&b.lt2, g.n2 * dbl}, {&b.p1, g.n1 * g.ncols * dbl},
+        {&b.p2, g.n2 * g.ncols * dbl}, {&b.first, K * dbl}, {&b.par, sizeof(hml_vit_par)}, {&b.A, K * K * dbl}, {&b.pi, K * dbl}, {&b.mdl, sizeof(hml_model)},
+        {&b.floats, g.nfloats * sizeof(float)}, {&b.result, g.nresult * dbl}, {&b.recs, sizeof(hml_em_many_rec)}};
+    if (!g.small) v.push_back({&b.X, B * dbl});
+    return v;
+}
+
+template <int KM, int DIR>
+static void em_many_launch_first(hml_ctx* c, const hml_em_many_rec* recs, const em_many_geom& g, uint32_t n, size_t lds) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_em_many_first<KM, DIR>), dim3((g.n_chunks + 63u) / 64u, n), dim3(64), lds, c->stream, recs);
+}
+template <int KM, int DIR>
+static void em_many_launch_rerun(hml_ctx* c, const hml_em_many_rec* recs, uint32_t max_heads, uint32_t n, size_t lds) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_em_many_rerun<KM, DIR>), dim3((max_heads + 63u) / 64u, n), dim3(64), lds, c->stream, recs);
+}
+template <int KM, int DIR>
+static void em_many_launch_finish(hml_ctx* c, const hml_em_many_rec* recs, uint32_t n, size_t lds) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_em_many_finish<KM, DIR>), dim3(1, n), dim3(64), lds, c->stream, recs);
+}
+template <int KM>
+static void em_many_launch_norm(hml_ctx* c, const hml_em_many_rec* recs, const em_many_geom& g, uint32_t n, size_t lds) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_em_many_norm<KM>), dim3((g.B - 1u + 63u) / 64u, n), dim3(64), lds, c->stream, recs);
+}
+
+// one direction of the smoothing for the first n records: post_direction's rounds, the counts of all members in one copy each
+template <int DIR>
+static int em_many_direction(hml_ctx* c, const em_many_geom& g, em_many_bufs& b, uint32_t n, em_many_stats& st) {
+    const hml_em_many_rec* const recs = b.recs.as<hml_em_many_rec>();
+    const size_t lds = ((size_t)g.K * g.K + g.K) * sizeof(double);
+    POST_BY_K(g.K, DIR, em_many_launch_first, c, recs, g, n, lds);
+    KLAUNCH_CHECK();
+    std::vector<uint32_t> h_cnt(2 * (size_t)n);
+    bool any = false;
+    for (uint32_t round = 0;; ++round) {
+        HIPCHK(hipMemsetAsync(b.cnt.get(), 0, h_cnt.size() * sizeof(uint32_t), c->stream));
+        hipLaunchKernelGGL(hml_k_em_many_verify, dim3(grid_for(g.n_chunks, 256, 1, 4096), n), dim3(256), 0, c->stream, recs, DIR, g.K);
+        KLAUNCH_CHECK();
+        HIPCHK(hipMemcpyAsync(h_cnt.data(), b.cnt.get(), h_cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        uint64_t stale = 0;
+        uint32_t max_heads = 0;
+        for (uint32_t i = 0; i < n; ++i) { stale += h_cnt[2 * i]; max_heads = std::max(max_heads, h_cnt[2 * i + 1]); }
+        if (round == 0) st.stale[DIR] += stale;
+        any = stale != 0;
+        if (!any || round >= c->post.rounds) break;
+        POST_BY_K(g.K, DIR, em_many_launch_rerun, c, recs, max_heads, n, lds);
+        KLAUNCH_CHECK();
+        st.rounds = std::max<uint64_t>(st.rounds, round + 1u);
+    }
+    if (any) {
+        POST_BY_K(g.K, DIR, em_many_launch_finish, c, recs, n, lds);
+        KLAUNCH_CHECK();
+    }
+    return 0;
+}
+
+// The E-step of n members, whose floats (mean_var, A, pi per member) are h_floats: their result rows into h_result.
+static int em_many_estep(hml_ctx* c, const em_many_geom& g, em_many_bufs& b, uint32_t n, const float* h_floats, double* h_result, em_many_stats& st) {
+    const hml_em_many_rec* const recs = b.recs.as<hml_em_many_rec>();
+    const int K = g.K;
+    HIPCHK(hipMemcpyAsync(b.floats.get(), h_floats, (uint64_t)n * g.nfloats * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(b.words.get(), 0, (uint64_t)n * HML_EMM_WORDS * sizeof(unsigned long long), c->stream));
+    hipLaunchKernelGGL(hml_k_em_many_model, dim3(1, n), dim3(256), 0, c->stream, c->d_mdl.get(), recs);
+    hipLaunchKernelGGL(hml_k_em_many_tables, dim3(1, n), dim3(256), 0, c->stream, recs);
+    KLAUNCH_CHECK();
+    ++st.launch_sets;
+    if (int r = em_many_direction<0>(c, g, b, n, st)) return r;
+    if (int r = em_many_direction<1>(c, g, b, n, st)) return r;
+    hipLaunchKernelGGL(hml_k_em_many_degenerate, dim3(grid_for(g.B, 256, 1, 16384), n), dim3(256), 0, c->stream, recs, g.B);
+    int l_levels = 0, p_levels = 0;
+    for (uint64_t m = g.B; m > 1; m = (m + 63u) / 64u, ++l_levels)
+        hipLaunchKernelGGL(hml_k_em_many_ltree, dim3(grid_for((m + 63u) / 64u, 256, 1, 4096), n), dim3(256), 0, c->stream, recs, l_levels, m);
+    KLAUNCH_CHECK();
+    if (g.B > 1u && !g.small) {
+        EM_BY_K(K, em_many_launch_norm, c, recs, g, n, ((size_t)K * K + K) * sizeof(double));
+        KLAUNCH_CHECK();
+    }
+    if (K <= 8) hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_em_many_reduce_small<8>), dim3((uint32_t)g.n1, n), dim3(64), 0, c->stream, recs);
+    else if (g.small) hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_em_many_reduce_small<16>), dim3((uint32_t)g.n1, n), dim3(64), 0, c->stream, recs);
+    else hipLaunchKernelGGL(hml_k_em_many_reduce, dim3((uint32_t)g.n1, n), dim3(256), 0, c->stream, recs);
+    uint64_t n_x = ((uint64_t)g.B - 1u + 63u) / 64u, n_o = g.n1;
+    for (; n_o > 1; ++p_levels) {
+        hipLaunchKernelGGL(hml_k_em_many_tree, dim3(grid_for(((n_o + 63u) / 64u) * g.ncols, 256, 1, 4096), n), dim3(256), 0, c->stream, recs, p_levels, n_x, n_o, g.ncols,
+                           (uint32_t)(K * K));
+        n_x = (n_x + 63u) / 64u; n_o = (n_o + 63u) / 64u;
+    }
+    hipLaunchKernelGGL(hml_k_em_many_gather, dim3(1, n), dim3(256), 0, c->stream, recs, l_levels, p_levels, g.ncols, K);
+    KLAUNCH_CHECK();
+    HIPCHK(hipMemcpyAsync(h_result, b.result.get(), (uint64_t)n * g.nresult * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// a member's result row as the counts em_estep returns
+static void em_many_counts(const em_many_geom& g, const double* row, hml_em_counts& out, uint64_t* walked) {
+    const int K = g.K, D = g.D, KK = K * K;
+    out.xi.assign(row, row + KK);
+    if (g.B == 1u) out.xi.assign((size_t)KK, 0.0);
+    out.occ.assign(row + KK, row + KK + K);
+    out.stay.assign(row + KK + K, row + KK + 2 * K);
+    out.sx.resize((size_t)K * D); out.sxx.resize((size_t)K * D);
+    for (int j = 0; j < K; ++j)
+        for (int d = 0; d < D; ++d) {
+            out.sx[j * D + d] = row[KK + (2 + d) * K + j];
+            out.sxx[j * D + d] = row[KK + (2 + D + d) * K + j];
+        }
+    const double* const tail = row + g.ncols;
+    out.first.assign(tail, tail + K);
+    out.loglik = tail[K];
+    uint64_t w[HML_EMM_WORDS];
+    memcpy(w, tail + K + 1, sizeof w);
+    *walked = w[HML_EMM_W_WALKED];
+    out.degenerate = w[HML_EMM_W_DEGENERATE];
+    out.xi_degenerate = w[HML_EMM_W_XI_BAD];
+}
+
+// hml_set_parameters' refusal of a start, or "" if it takes it
+static std::string em_many_refusal(int P, const float* mean_var) {
+    for (int k = 0; k < P; ++k) {
+        const float mean = mean_var[2 * k], var = mean_var[2 * k + 1];
+        if (!std::isfinite(mean)) return "Mean (" + std::to_string(mean) + ") must be set to a finite value!";
+        if (!std::isfinite(var)) return "Variance(" + std::to_string(var) + ") must be set to a finite value!";
+        if (var <= 0) return "Variance (" + std::to_string(var) + ") must be positive!";
+    }
+    return "";
+}
+
+extern "C" {
+
+int hml_em_fit_many(hml_ctx* c, uint64_t R, const float* mean_var, const float* A, const float* pi, int use_prior, uint64_t max_steps, double rel_tol, int install,
+                    double* trace, uint64_t* steps, int* reason, uint64_t* kept, float* fit_mean_var, float* fit_A, float* fit_pi, double* objective, int64_t* best) {
+    NEED_MODEL();
+    if (R < 1u || R > HML_EM_MANY_MAX_R) return set_err(HML_ERR_ARG, "hml_em_fit_many: the number of members must be 1 ... " + std::to_string(HML_EM_MANY_MAX_R));
+    if (!mean_var || !A || !pi) return set_err(HML_ERR_ARG, "null argument");
+    hml_model m; if (int r = fetch_model(c, &m)) return r;
+    if (int r = post_ready(m)) return r;
+    em_many_geom g;
+    g.K = c->K; g.D = c->D; g.P = m.P; g.B = m.B;
+    const int K = g.K, KK = K * K, P = g.P;
+    for (uint64_t r = 0; r < R; ++r) {
+        const std::string why = em_many_refusal(P, mean_var + r * 2u * P);
+        if (!why.empty()) return set_err(HML_ERR_MODEL, why + " (start " + std::to_string(r) + ")");
+    }
+    em_params q0;
+    em_params_of(m, K, q0);
+    g.L = c->post.L ? c->post.L : HML_POST_DEFAULT_L;
+    g.W = c->post.W ? c->post.W : HML_POST_DEFAULT_W;
+    g.n_chunks = (uint32_t)(((uint64_t)g.B + g.L - 1u) / g.L);
+    g.ncols = (uint32_t)(KK + K * (2 + 2 * g.D));
+    g.n1 = ((uint64_t)g.B + 63u) / 64u; g.n2 = (g.n1 + 63u) / 64u;
+    g.nfloats = 2u * P + KK + K;
+    g.nresult = (uint64_t)g.ncols + K + 1u + HML_EMM_WORDS;
+    g.small = K <= 16;
+
+    // the group: as many members as the byte budget holds
+    em_many_bufs b;
+    const auto layout = em_many_layout(b, g);
+    uint64_t member_bytes = 0;
+    for (const auto& e : layout) member_bytes += e.second;
+    const uint64_t budget = c->em_many.batch_bytes ? c->em_many.batch_bytes : HML_EM_MANY_DEFAULT_BYTES;
+    const uint64_t G0 = std::min<uint64_t>(std::max<uint64_t>(budget / member_bytes, 1u), R);
+    for (const auto& e : layout) HIPCHK(e.first->alloc(G0 * e.second));
+    {
+        std::vector<hml_em_many_rec> recs(G0);
+        for (uint64_t i = 0; i < G0; ++i) {
+            hml_em_many_rec& r = recs[i];
+            const uint64_t BK = (uint64_t)g.B * K, CK = (uint64_t)g.n_chunks * K;
+            r.floats = b.floats.as<float>() + i * g.nfloats;
+            r.mdl = b.mdl.as<hml_model>() + i;
+            r.par = b.par.as<hml_vit_par>() + i;
+            r.A = b.A.as<double>() + i * KK; r.pi = b.pi.as<double>() + i * K;
+            r.match = b.match.as<uint8_t>() + i * g.n_chunks;
+            r.heads = b.heads.as<uint32_t>() + i * g.n_chunks;
+            r.cnt = b.cnt.as<uint32_t>() + 2 * i;
+            r.words = b.words.as<unsigned long long>() + i * HML_EMM_WORDS;
+            r.lt[0] = b.lt1.as<double>() + i * g.n1; r.lt[1] = b.lt2.as<double>() + i * g.n2;
+            r.pt[0] = b.p1.as<double>() + i * g.n1 * g.ncols; r.pt[1] = b.p2.as<double>() + i * g.n2 * g.ncols;
+            r.X = g.small ? nullptr : b.X.as<double>() + i * g.B;
+            r.result = b.result.as<double>() + i * g.nresult;
+            hml_post_args& f = r.dir[0];
+            f.par = r.par; f.A = r.A; f.pi = r.pi; f.ia = c->d_ia; f.starts = c->d_starts.get();
+            f.L = g.L; f.W = g.W; f.n_chunks = g.n_chunks;
+            f.entry = b.entry.as<double>() + i * CK; f.exitv = b.exitv.as<double>() + i * CK;
+            f.rows = b.alpha.as<double>() + i * BK; f.cval = b.cval.as<double>() + i * g.B; f.ell = b.ell.as<double>() + i * g.B;
+            r.dir[1] = f;
+            r.dir[1].rows = b.beta.as<double>() + i * BK; r.dir[1].cval = nullptr; r.dir[1].ell = nullptr;   // (entry, exit, match and heads are used again)
+            hml_em_args& e = r.em;
+            e.par = r.par; e.A = r.A; e.ia = c->d_ia; e.starts = c->d_starts.get();
+            e.alpha = f.rows; e.beta = r.dir[1].rows; e.X = r.X; e.part = r.pt[0]; e.first = b.first.as<double>() + i * K;
+        }
+        HIPCHK(hipMemcpyAsync(b.recs.get(), recs.data(), G0 * sizeof(hml_em_many_rec), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));   // (the records leave this frame)
+    }
+
+    // the members: their floats, the last two trace entries, and who still runs
+    std::vector<float> mv(mean_var, mean_var + R * 2u * P), tA(A, A + R * (uint64_t)KK), tpi(pi, pi + R * (uint64_t)K);
+    std::vector<double> prev(R, 0.0), cur(R, 0.0);
+    std::vector<uint64_t> n_steps(R, 0), n_kept(R, 0);
+    std::vector<int> why(R, HML_EM_MAX_STEPS);
+    std::vector<uint64_t> active(R), next;
+    for (uint64_t r = 0; r < R; ++r) active[r] = r;
+    if (trace) std::fill(trace, trace + R * (max_steps + 1u), std::numeric_limits<double>::quiet_NaN());
+    std::vector<float> h_floats(G0 * g.nfloats);
+    std::vector<double> h_result(G0 * g.nresult);
+    em_many_stats st;
+    uint64_t esteps = 0, first_groups = 0;
+    for (uint64_t k = 0; !active.empty(); ++k, ++esteps) {
+        next.clear();
+        const uint64_t G = std::min<uint64_t>(G0, active.size());
+        if (k == 0) first_groups = (active.size() + G - 1u) / G;
+        for (uint64_t off = 0; off < active.size(); off += G) {
+            const uint32_t n = (uint32_t)std::min<uint64_t>(G, active.size() - off);
+            for (uint32_t i = 0; i < n; ++i) {
+                const uint64_t r = active[off + i];
+                float* const f = h_floats.data() + i * g.nfloats;
+                std::copy(mv.begin() + r * 2u * P, mv.begin() + (r + 1u) * 2u * P, f);
+                std::copy(tA.begin() + r * KK, tA.begin() + (r + 1u) * KK, f + 2 * P);
+                std::copy(tpi.begin() + r * K, tpi.begin() + (r + 1u) * K, f + 2 * P + KK);
+            }
+            if (int r = em_many_estep(c, g, b, n, h_floats.data(), h_result.data(), st)) return r;
+            for (uint32_t i = 0; i < n; ++i) {
+                const uint64_t r = active[off + i];
+                hml_em_counts cnt;
+                uint64_t walked = 0;
+                em_many_counts(g, h_result.data() + i * g.nresult, cnt, &walked);
+                st.walked += walked;
+                float* const rmv = mv.data() + r * 2u * P;
+                float* const rA = tA.data() + r * KK;
+                float* const rpi = tpi.data() + r * K;
+                prev[r] = cur[r];
+                cur[r] = hml_em_objective(K, P, use_prior, q0.pr, cnt.loglik, rmv, rA, rpi);
+                if (trace) trace[r * (max_steps + 1u) + k] = cur[r];
+                if (hml_em_stops(prev[r], cur[r], k, max_steps, rel_tol, cnt.degenerate + cnt.xi_degenerate, &why[r])) { n_steps[r] = k; continue; }
+                n_kept[r] += hml_em_mstep(K, g.D, P, q0.self_trans, use_prior, q0.pr, cnt, rmv, rA, rpi);
+                next.push_back(r);
+            }
+        }
+        active.swap(next);
+    }
+    const int64_t win = hml_em_many_best(R, why.data(), cur.data());
+    if (install && win >= 0)
+        if (int r = hml_set_parameters(c, mv.data() + (uint64_t)win * 2u * P, tA.data() + (uint64_t)win * KK, tpi.data() + (uint64_t)win * K)) return r;
+    if (steps) std::copy(n_steps.begin(), n_steps.end(), steps);
+    if (reason) std::copy(why.begin(), why.end(), reason);
+    if (kept) std::copy(n_kept.begin(), n_kept.end(), kept);
+    if (fit_mean_var) std::copy(mv.begin(), mv.end(), fit_mean_var);
+    if (fit_A) std::copy(tA.begin(), tA.end(), fit_A);
+    if (fit_pi) std::copy(tpi.begin(), tpi.end(), fit_pi);
+    if (objective) std::copy(cur.begin(), cur.end(), objective);
+    if (best) *best = win;
+    c->em_many.computed = true;
+    c->em_many.members = R; c->em_many.groups = first_groups; c->em_many.group_size = G0; c->em_many.esteps = esteps; c->em_many.launch_sets = st.launch_sets;
+    c->em_many.stale_fwd = st.stale[0]; c->em_many.stale_bwd = st.stale[1]; c->em_many.rounds_run = st.rounds; c->em_many.walked = st.walked;
+    return 0;
+}
+
+int hml_em_starts(hml_ctx* c, uint64_t R, uint64_t seed, double spread, float* mean_var, float* A, float* pi) {
+    NEED_MODEL();
+    if (R < 1u || R > HML_EM_MANY_MAX_R) return set_err(HML_ERR_ARG, "hml_em_starts: the number of members must be 1 ... " + std::to_string(HML_EM_MANY_MAX_R));
+    if (!mean_var) return set_err(HML_ERR_ARG, "null argument");
+    em_params q;
+    if (int r = em_fetch(c, q)) return r;
+    if (!hml_em_many_starts(c->K, q.P, R, seed, spread, q.mv.data(), q.A.data(), q.pi.data(), mean_var, A, pi))
+        return set_err(HML_ERR_ARG, "hml_em_starts: spread must be finite and positive");
+    return 0;
+}
+
+int hml_em_many_info(hml_ctx* c, uint64_t* members, uint64_t* groups, uint64_t* group_size, uint64_t* esteps, uint64_t* launch_sets, uint64_t* stale_fwd,
+                     uint64_t* stale_bwd, uint64_t* rounds, uint64_t* serial_chunks) {
+    if (!c) return set_err(HML_ERR_ARG, "null context");
+    if (!c->em_many.computed) return set_err(HML_ERR_ARG, "hml_em_many_info: nothing was computed yet");
+    if (members) *members = c->em_many.members;
+    if (groups) *groups = c->em_many.groups;
+    if (group_size) *group_size = c->em_many.group_size;
+    if (esteps) *esteps = c->em_many.esteps;
+    if (launch_sets) *launch_sets = c->em_many.launch_sets;
+    if (stale_fwd) *stale_fwd = c->em_many.stale_fwd;
+    if (stale_bwd) *stale_bwd = c->em_many.stale_bwd;
+    if (rounds) *rounds = c->em_many.rounds_run;
+    if (serial_chunks) *serial_chunks = c->em_many.walked;
+    return 0;
+}
+
+int hml_set_em_batch_bytes(hml_ctx* c, uint64_t bytes) {
+    if (!c) return set_err(HML_ERR_ARG, "null context");
+    c->em_many.batch_bytes = bytes;
     return 0;
 }
 

@@ -92,7 +92,10 @@ static const char* kHelp =
     "                                 under the parameters of -O PD; with -chains N one file per chain (extension)\n"
     "                    EM           em: the fit of -em - one line per step: step, objective; then the reason it stopped, the\n"
     "                                 parameters kept for want of support, and the fitted means, variances, A and pi; with\n"
-    "                                 -chains N one file per chain (extension; needs -em)\n"
+    "                                 -chains N one file per chain (extension; needs -em); with -em-starts the winner's\n"
+    "                    EMS          emstarts: the batch of -em-starts - one line per member, tab-separated: index, objective,\n"
+    "                                 steps, reason, parameters kept, the fitted means, the fitted variances, and * on the\n"
+    "                                 winner's line; with -chains N one file per chain (extension; needs -em-starts)\n"
     "                    L            levels: length, then posterior mean and standard deviation of the emission level\n"
     "                                 per data dimension, one line per segment - the denoised trace (extension)\n"
     "                    BP           breakpoints: position, number of recorded sweeps that change state there, and that\n"
@@ -157,6 +160,10 @@ static const char* kHelp =
     "                                 parameters; needs a scheme with forward-backward sweeps (extension)\n"
     "  -em-prior                      the fit's objective is the posterior mode under the chain's priors, not the maximum\n"
     "                                 likelihood (extension)\n"
+    "  -em-starts R [SEED [SPREAD]]   the fit of -em from R starts at once, the best kept: start 0 is the chain's parameters, the\n"
+    "                                 others have their means drawn (SEED, default 0) over the range of the chain's means\n"
+    "                                 widened by SPREAD (default 1); the member with the greatest objective is installed; if\n"
+    "                                 none qualifies the chain keeps its parameters (extension; needs -em)\n"
     "  -history-every N               -O H, HS: a row for every N-th sweep (default 1) (extension)\n"
     "  -history-skip S                -O HS: leave out the rows of the first S sweeps (default: the first half of the scheme's\n"
     "                                 sweeps) (extension)\n"
@@ -200,6 +207,8 @@ struct Job {
     bool em = false, emPrior = false;   // -em STEPS [TOL], -em-prior
     uint64_t emSteps = 0;
     double emTol = 0;
+    uint64_t emStarts = 0, emStartsSeed = 0;   // -em-starts R [SEED [SPREAD]]; 0: a single fit
+    double emSpread = 1.0;
 };
 
 // Meeting point of the chain threads of `-chains N` and the main thread: a chain arrives with its context once its
@@ -571,9 +580,22 @@ static void writePosteriorFile(const Job& job, int index, hml_ctx* ctx) {
 
 // -em: the fit once the scheme has run, before every end-of-run output; PREFIX[chainK.]emSUFFIX
 static string emFileName(const Job& job, int index) { return job.opref + (index == 0 ? "" : "chain" + std::to_string(index) + ".") + "em" + job.osuff; }
+static string emStartsFileName(const Job& job, int index) { return job.opref + (index == 0 ? "" : "chain" + std::to_string(index) + ".") + "emstarts" + job.osuff; }
 static void runFit(const Job& job, int index, hml_ctx* ctx) {
     if (!job.em) return;
     Fit fit(ctx);
+    if (job.emStarts) {
+        // a batch from job.emStarts starts, the winner installed; the em file is the winner's
+        const Fit::ManyResult m = fit.fitMany(fit.starts(job.emStarts, job.emStartsSeed, job.emSpread), job.emSteps, job.emTol, job.emPrior, true);
+        if (job.outputs.at("emstarts")) fit.writeStartsFile(emStartsFileName(job, index), m);
+        if (m.best < 0) {
+            std::cerr << "[WARNING] -em-starts: no member of the batch is a candidate (all degenerate or without a finite objective); the chain keeps its parameters." << std::endl;
+            if (job.outputs.at("em")) fit.writeFile(emFileName(job, index), m.members.at(0));
+            return;
+        }
+        if (job.outputs.at("em")) fit.writeFile(emFileName(job, index), m.winner());
+        return;
+    }
     const Fit::Result r = fit.fit(job.emSteps, job.emTol, job.emPrior);
     if (job.outputs.at("em")) fit.writeFile(emFileName(job, index), r);
 }
@@ -782,6 +804,7 @@ int main(int argc, const char* argv[]) {
         args.registerFlags({"-history-skip"});
         args.registerFlags({"-em"});
         args.registerFlags({"-em-prior"});
+        args.registerFlags({"-em-starts"});
         args.parseArgs();
 
         if (args.isSet("-g")) args.print();
@@ -865,6 +888,7 @@ int main(int argc, const char* argv[]) {
         outputArgs.registerFlags({"V", "viterbi"});           // extension
         outputArgs.registerFlags({"PD", "posterior"});        // extension (P is the reference's parameters)
         outputArgs.registerFlags({"EM", "em"});               // extension
+        outputArgs.registerFlags({"EMS", "emstarts"});        // extension
         outputArgs.registerFlags({"PB", "posteriorbreaks"});  // extension
         outputArgs.registerFlags({"PR", "posteriorregions"}); // extension
         outputArgs.registerFlags({"L", "levels"});            // extension
@@ -948,7 +972,7 @@ int main(int argc, const char* argv[]) {
         job.weightMultiplier = weightMultiplier; job.useSelfTrans = useSelfTrans;
         job.thetaParams = thetaParams; job.trans = trans; job.selfTrans = selfTrans; job.initialAlpha = initialAlpha;
         job.scheme = scheme;
-        for (const char* o : {"sequences", "parameters", "blocks", "compression", "marginals", "segments", "maxsegmentation", "viterbi", "posterior", "posteriorbreaks", "posteriorregions", "em", "levels", "breakpoints", "consensus", "bands", "bandcalls", "rhat", "regions", "history", "historysummary"})
+        for (const char* o : {"sequences", "parameters", "blocks", "compression", "marginals", "segments", "maxsegmentation", "viterbi", "posterior", "posteriorbreaks", "posteriorregions", "em", "emstarts", "levels", "breakpoints", "consensus", "bands", "bandcalls", "rhat", "regions", "history", "historysummary"})
             job.outputs[o] = outputArgs.isSet(o);
         auto refuseExisting = [&](const string& fn) {
             if (!overwrite) { std::ifstream probe(fn); if (probe.good()) throw std::runtime_error("File " + fn + " already exists! Use -w to allow overwrite!"); }
@@ -1053,6 +1077,24 @@ int main(int argc, const char* argv[]) {
             job.emPrior = args.isSet("-em-prior");
             if (job.outputs.at("em"))
                 for (long k = 0; k < (long)nrChains; ++k) refuseExisting(emFileName(job, (int)k));
+        }
+        if (job.outputs.at("emstarts") && !args.isSet("-em-starts")) throw std::runtime_error("The output emstarts (EMS) needs a batch: ask for one with -em-starts R [SEED [SPREAD]]!");
+        if (args.isSet("-em-starts")) {
+            if (!args.isSet("-em")) throw std::runtime_error("The flag -em-starts needs a fit: ask for one with -em STEPS [TOL]!");
+            if (args.nrTokens("-em-starts") < 1) throw std::runtime_error("Not enough arguments for flag -em-starts!");
+            if (args.nrTokens("-em-starts") > 3) throw std::runtime_error("Too many arguments for flag -em-starts: R and, optionally, SEED and SPREAD!");
+            const double n = args.parse<double>("-em-starts", 0);
+            if (!(n >= 1 && n <= 4096) || n != std::floor(n)) throw std::runtime_error("The first argument of -em-starts must be a whole number of starts, 1 to 4096!");
+            job.emStarts = (uint64_t)n;
+            if (args.nrTokens("-em-starts") > 1) {
+                const double seed = args.parse<double>("-em-starts", 1);
+                if (!(seed >= 0 && seed <= 9007199254740992.0) || seed != std::floor(seed)) throw std::runtime_error("The seed of -em-starts must be a whole number, 0 to 2^53!");
+                job.emStartsSeed = (uint64_t)seed;
+            }
+            if (args.nrTokens("-em-starts") > 2) job.emSpread = args.parse<double>("-em-starts", 2);
+            if (!(job.emSpread > 0 && job.emSpread <= 1.7976931348623157e308)) throw std::runtime_error("The spread of -em-starts must be a positive number!");
+            if (job.outputs.at("emstarts"))
+                for (long k = 0; k < (long)nrChains; ++k) refuseExisting(emStartsFileName(job, (int)k));
         }
         if (job.outputs.at("bands")) refuseExisting(bandsFileName(job));
         if (job.outputs.at("bandcalls")) refuseExisting(bandCallsFileName(job));

@@ -4,6 +4,9 @@
 //   PREFIXemSUFFIX   `-O EM`: "step<TAB>objective" (%.17g) per trace entry - the objective of the parameters after that many
 //                    M-steps -, then "reason<TAB>max_steps|converged|degenerate", "kept<TAB>n", "means<TAB>...",
 //                    "variances<TAB>..." (one value per emission parameter, %.9g), "A<TAB>..." per row and "pi<TAB>..."
+//   PREFIXemstartsSUFFIX   `-O EMS`: the batch of `-em-starts` (hml_em_starts, hml_em_fit_many) - one line per member,
+//                    tab-separated: index, objective (%.17g), steps, reason, kept, the fitted means, the fitted variances (%.9g),
+//                    and "*" as a last field on the winner's line
 // A thin handle over a context that something else owns, next to Viterbi and Posterior.  Blocks are never rebuilt inside a
 // fit: it is over the context's current block structure; call hml_create_blocks between fits to let the threshold follow.
 #ifndef HAMMLET_FIT_HPP
@@ -66,6 +69,66 @@ public:
     }
     static const char* reasonName(int reason) {
         return reason == HML_EM_CONVERGED ? "converged" : reason == HML_EM_DEGENERATE ? "degenerate" : "max_steps";
+    }
+
+    // ---- EM from many starts (hml_em_starts, hml_em_fit_many): member r is set-parameters(start r) + fit(), word for word ----
+    struct Starts {
+        std::vector<float> meanVar, A, pi;   // [R][2 P], [R][K][K], [R][K]
+        uint64_t n = 0;
+    };
+    struct ManyResult {
+        std::vector<Result> members;         // every member's trace (steps + 1 values), steps, kept, reason
+        std::vector<double> objective;       // a member's last trace entry
+        Starts fitted;                       // every member's fitted parameters
+        int64_t best = -1;                   // -1: no member is a candidate, the chain's parameters were left alone
+        // the winner's trace as fit() would have returned it (best >= 0)
+        const Result& winner() const { return members.at((size_t)best); }
+    };
+    // member 0 the current parameters, the others drawn around the current means (spread: finite, positive)
+    Starts starts(uint64_t n, uint64_t seed, double spread = 1.0) const {
+        int D = 1, P = 0, K = 0;
+        shape(&D, &P, &K);
+        Starts s;
+        s.n = n;
+        s.meanVar.resize(n * 2 * P); s.A.resize(n * K * K); s.pi.resize(n * K);
+        check(hml_em_starts(mCtx, n, seed, spread, s.meanVar.data(), s.A.data(), s.pi.data()));
+        return s;
+    }
+    ManyResult fitMany(const Starts& s, uint64_t maxSteps, double relTol = 0.0, bool usePrior = false, bool install = true) {
+        int D = 1, P = 0, K = 0;
+        shape(&D, &P, &K);
+        const uint64_t R = s.n;
+        ManyResult m;
+        m.fitted.n = R;
+        m.fitted.meanVar.resize(R * 2 * P); m.fitted.A.resize(R * K * K); m.fitted.pi.resize(R * K);
+        m.objective.resize(R);
+        std::vector<double> trace(R * (maxSteps + 1));
+        std::vector<uint64_t> steps(R), kept(R);
+        std::vector<int> reason(R);
+        check(hml_em_fit_many(mCtx, R, s.meanVar.data(), s.A.data(), s.pi.data(), usePrior ? 1 : 0, maxSteps, relTol, install ? 1 : 0, trace.data(), steps.data(),
+                              reason.data(), kept.data(), m.fitted.meanVar.data(), m.fitted.A.data(), m.fitted.pi.data(), m.objective.data(), &m.best));
+        m.members.resize(R);
+        for (uint64_t r = 0; r < R; ++r) {
+            m.members[r].trace.assign(trace.begin() + r * (maxSteps + 1), trace.begin() + r * (maxSteps + 1) + steps[r] + 1);
+            m.members[r].steps = steps[r]; m.members[r].kept = kept[r]; m.members[r].reason = reason[r];
+        }
+        return m;
+    }
+    // `-O EMS`: one line per member - index, objective (%.17g), steps, reason, kept, then the fitted means and the fitted
+    // variances (%.9g) -, a "*" as the last field of the winner's line
+    void writeStartsFile(const std::string& fn, const ManyResult& m) const {
+        int D = 1, P = 0, K = 0;
+        shape(&D, &P, &K);
+        FILE* out = fopen(fn.c_str(), "w");
+        if (!out) throw std::runtime_error("Cannot write to file " + fn + "!");
+        for (size_t r = 0; r < m.members.size(); ++r) {
+            const Result& f = m.members[r];
+            fprintf(out, "%llu\t%.17g\t%llu\t%s\t%llu", (unsigned long long)r, m.objective[r], (unsigned long long)f.steps, reasonName(f.reason), (unsigned long long)f.kept);
+            for (int p = 0; p < P; ++p) fprintf(out, "\t%.9g", (double)m.fitted.meanVar[r * 2 * P + 2 * p]);
+            for (int p = 0; p < P; ++p) fprintf(out, "\t%.9g", (double)m.fitted.meanVar[r * 2 * P + 2 * p + 1]);
+            fprintf(out, (int64_t)r == m.best ? "\t*\n" : "\n");
+        }
+        if (fclose(out) != 0) throw std::runtime_error("Cannot write to file " + fn + "!");
     }
 
     // the fit's trace and the context's parameters as they are now

@@ -591,6 +591,40 @@ int hml_expected_counts(hml_ctx* ctx, double* xi /*K*K*/, double* first /*K*/, d
 int hml_em_step(hml_ctx* ctx, int use_prior, double* objective_before, uint64_t* kept);
 int hml_em_fit(hml_ctx* ctx, int use_prior, uint64_t max_steps, double rel_tol, double* trace /*max_steps+1, may be NULL*/, uint64_t* steps, int* reason, uint64_t* kept);
 
+/* ---- EM from many starts: a batch of fits smoothed together, the best kept.  No counterpart in the reference. ----
+ * hml_em_fit is deterministic and climbs to the local optimum its start leads to.  hml_em_fit_many runs R fits over the same
+ * blocks from R starts.  MEMBER r IS EXACTLY hml_set_parameters(start_r) FOLLOWED BY hml_em_fit(use_prior, max_steps, rel_tol)
+ * ON THIS CONTEXT: its trace, steps, reason, kept and fitted floats are those, word for word, whatever R is, whoever else is in
+ * the batch and however the batch is cut.  On the device the members still running share one set of launches per E-step (the
+ * member is a grid dimension); the stopping rule, the objective and the M-step run per member on the host, as in hml_em_fit.
+ *   R             1 ... 4096 members; start r is mean_var[r], A[r], pi[r].  Every start is checked as hml_set_parameters checks
+ *                 it before anything is launched; a bad one is refused with that function's message and the member's index,
+ *                 and nothing is changed.  The other refusals are hml_posterior's.
+ *   outputs       any may be NULL.  trace[r] holds max_steps + 1 entries, those past the member's last are NaN; objective[r] is
+ *                 the member's last trace entry.
+ *   best          the candidates are the members whose reason is not HML_EM_DEGENERATE and whose objective is finite; best is
+ *                 the candidate with the greatest objective, the smallest index among equals, and -1 without a candidate (the
+ *                 call still returns 0).  hammlet_amd/csrc/hml_em_many_ref.h holds the rule the library calls.
+ *   install       The context's parameters are not touched while the batch runs.  install != 0 and best >= 0: the winner's
+ *                 floats are installed through hml_set_parameters at the end, which leaves the context as a single hml_em_fit
+ *                 from that start would have.  Otherwise the chain is only read.
+ * Device memory is local to the call and bounded: the members run in groups of as many as fit hml_set_em_batch_bytes' budget
+ * (0: the default, 4 GiB; a member needs about 2 B K 8 bytes for alpha and beta and little else; at least one member a group).
+ * hml_em_starts fills R starts: member 0 is the context's current parameters; for r >= 1 the means are drawn uniformly over
+ * the current means' range widened by `spread` (finite, positive; 1 is a fair default) and sorted ascending, the variances
+ * between a quarter and twice the current mean variance, from Philox words addressed by (seed, r, parameter) - the header above
+ * states every operation; A and pi (either may be NULL) are the current ones for every member.
+ * hml_em_many_info, of the last hml_em_fit_many: members = R; groups and group_size of the first E-step; esteps = E-steps of
+ * the longest member; launch_sets = first-pass launches of the forward direction, one per group and E-step (groups x esteps
+ * while every member runs); stale_fwd, stale_bwd and serial_chunks summed over members and E-steps, rounds the maximum. */
+int hml_em_fit_many(hml_ctx* ctx, uint64_t R, const float* mean_var /*R*2P*/, const float* A /*R*K*K*/, const float* pi /*R*K*/, int use_prior, uint64_t max_steps,
+                    double rel_tol, int install, double* trace /*R*(max_steps+1)*/, uint64_t* steps /*R*/, int* reason /*R*/, uint64_t* kept /*R*/,
+                    float* fit_mean_var /*R*2P*/, float* fit_A /*R*K*K*/, float* fit_pi /*R*K*/, double* objective /*R*/, int64_t* best);
+int hml_em_starts(hml_ctx* ctx, uint64_t R, uint64_t seed, double spread, float* mean_var /*R*2P*/, float* A /*R*K*K*/, float* pi /*R*K*/);
+int hml_em_many_info(hml_ctx* ctx, uint64_t* members, uint64_t* groups, uint64_t* group_size, uint64_t* esteps, uint64_t* launch_sets, uint64_t* stale_fwd,
+                     uint64_t* stale_bwd, uint64_t* rounds, uint64_t* serial_chunks);
+int hml_set_em_batch_bytes(hml_ctx* ctx, uint64_t bytes /*0: the default*/);
+
 /* ---- pairwise read-outs of the smoothing: breakpoint and region posteriors under the current parameters.  No counterpart in
  * the reference. ----
  * The joint questions of "joint posteriors over regions" above, asked of a fitted model instead of recorded sweeps: where the
