@@ -1,12 +1,17 @@
-// Shared by the three kinds of translation unit of libhammlet_hip.so's chain code (hammlet_amd/build.py):
+// Shared by the four kinds of translation unit of libhammlet_hip.so's chain code (hammlet_amd/build.py):
 //   hml_capi.hip  - the C ABI (include/hml.h) and everything that does not depend on the number of states K: one object.  It
 //                   includes hml_rtk_sweep.hpp, the sweeps of the two paths that take K at run time (the reference-compatible mode,
 //                   more than 16 states) behind tables of their own (hml_ktab_compat, hml_ktab_wide): their kernels stay in this object;
-//   hml_readout.hip - the C ABI's read-outs of what the recorded sweeps accumulated (marginals, levels, breaks, bands, regions): one object;
+//   hml_readout.hip - the C ABI's read-outs of what the recorded sweeps accumulated (marginals, levels, agreement, breaks, bands,
+//                   regions, payloads, history): one object;
+//   hml_infer.hip - exact inference under the current parameters (Viterbi, smoothing, EM, EM from many starts, the exact breakpoint
+//                   and region posteriors): one object, whose kernels (hml_k_viterbi.h, hml_k_posterior.h, hml_k_em.h, hml_k_em_many.h,
+//                   hml_k_pairs.h) no other object holds.  The host helpers the two share are hml_readout_shared.hpp's;
 //   hml_sweep.hip - the sweep for K states: the kernels templated on K and the host code that launches them, behind a table
 //                   of function pointers (hml_ktab): fifteen objects, -DHML_TU_K=2 ... 16, compiled in parallel.
 // Every object carries its own code object, and the HIP runtime loads a code object when the first kernel of it is launched:
-// a run with K states loads the core's (construction, block scan, marginals) and the one of its K (1-2 MB each) instead of
+// a run with K states loads the core's (construction, block scan, marginals) and the one of its K (1-2 MB each), the read-outs'
+// and the inference's only if it calls one of them, instead of
 // one 19 MB object with every kernel for 2 ... 16 states - 45 ms of a short run's start-up - and the library
 // builds in a fifth of the time.  Kernels that are not templates have internal linkage (HML_KERNEL) so that the objects may
 // each hold the ones they launch.  (Round 4: this header and the two files were one file sliced by the preprocessor.)
@@ -14,7 +19,7 @@
 // (hml_ctx::kt) and never asks which path it is.  What a sweep launches is decided by a pure function per family of paths
 // (hml_sweep_plan.h, hml_rtk_plan.h), where the arrays of a carved buffer lie by one layout function per buffer
 // (hml_layouts.h); neither header needs HIP, and the CPU tests hold them to their rules.
-// Development builds for one K (tools/dev_build.py): both files with -DHML_ONLY_K=k.
+// Development builds for one K (tools/dev_build.py): every csrc/*.hip with -DHML_ONLY_K=k.
 #ifndef HML_CAPI_SHARED_HPP
 #define HML_CAPI_SHARED_HPP
 

@@ -205,22 +205,19 @@ struct hml_ctx {
     uint32_t prof_tick = 0;
     std::map<std::string, ProfAcc> prof;
     std::vector<hipEvent_t> ev_pool;
-    // The Viterbi decode (hml_viterbi; hml_k_viterbi.h).  Launch geometry only - options "viterbi_W", "viterbi_L",
-    // "viterbi_rounds" - and what the last decode did (hml_viterbi_info).  Its device memory lives for the length of a call.
-    struct {
+    // A chunked pass over the blocks under the current parameters (hml_infer.hip).  Launch geometry only, and what the last
+    // call did.  Its device memory lives for the length of a call.
+    struct chunked_pass {
         uint32_t W = 0, L = 0;         // warm-up and chunk length in blocks (0: the defaults)
         uint32_t rounds = 8;           // parallel repair rounds before the single lane
-        bool decoded = false;
-        uint64_t chunks = 0, used_L = 0, used_W = 0, stale = 0, rounds_run = 0, walked = 0;
-    } vit;
-    // Smoothing (hml_posterior; hml_k_posterior.h): the same - options "posterior_W", "posterior_L", "posterior_rounds" and
-    // what the last call did (hml_posterior_info).
-    struct {
-        uint32_t W = 0, L = 0;
-        uint32_t rounds = 8;
-        bool computed = false;
-        uint64_t chunks = 0, used_L = 0, used_W = 0, stale_fwd = 0, stale_bwd = 0, rounds_run = 0, walked = 0;
-    } post;
+        bool done = false;             // a call has run: the numbers below are its
+        uint64_t chunks = 0, used_L = 0, used_W = 0, stale[2] = {0, 0}, rounds_run = 0, walked = 0;   // stale: forward, backward
+    };
+    // The Viterbi decode (hml_viterbi; hml_k_viterbi.h): options "viterbi_W", "viterbi_L", "viterbi_rounds"; hml_viterbi_info.
+    // It has one direction: stale[0].
+    chunked_pass vit;
+    // Smoothing (hml_posterior; hml_k_posterior.h): options "posterior_W", "posterior_L", "posterior_rounds"; hml_posterior_info.
+    chunked_pass post;
     // EM from many starts (hml_em_fit_many; hml_k_em_many.h): the byte budget of a group's device memory (0: the default) and what
     // the last call did (hml_em_many_info).
     struct {
@@ -238,7 +235,7 @@ int hml_ctx_bind(hml_ctx* c);                         // hipSetDevice(ctx's devi
 int hml_ctx_fetch_model(hml_ctx* c, hml_model* out);  // synchronising copy of the device-resident model
 int hml_ctx_ensure_marginal_buffers(hml_ctx* c);
 int hml_settle(hml_ctx* c);                           // stream idle, no halted sweep left behind (block capacity, above)
-// hml_readout.hip
+// hml_readout.hip (hml_infer.hip, the library's other read-out object, declares nothing here: it is reached through the C ABI alone)
 // marginal segments on the device: starts d_seg[M] and count differences at the starts d_g[M * K]
 int hml_ctx_gather_marginal_segments(hml_ctx* c, uint64_t* M, DevBuf& d_seg, DevBuf& d_g);
 

@@ -1,9 +1,10 @@
 // libhammlet_hip.so - the read-outs of the C ABI (include/hml.h): what the recorded sweeps accumulated per position - state
 // marginals, emission levels, breakpoints, level bands - brought into the forms the callers ask for, and the merges of one
 // chain's recording into another's: on one device from recorder to recorder, across devices through the sparse payload of
-// hml_k_rec_payload.h.  Nothing here runs inside a sweep; hml_capi.hip holds the chain itself.
+// hml_k_rec_payload.h - and the chain's history.  Nothing here runs inside a sweep; hml_capi.hip holds the chain itself, and
+// hml_infer.hip what is computed exactly under the current parameters and reads nothing a recorder wrote (Viterbi, smoothing, EM).
 #define HML_REGIONS_KERNELS   // (hml_k_regions.h: this object holds the regions' kernels)
-#include "hml_capi_shared.hpp"
+#include "hml_readout_shared.hpp"   // (the helpers hml_infer.hip needs too; it brings hml_capi_shared.hpp)
 #include "hml_k_agree.h"   // (launched from this object alone)
 #include "hml_k_rec_payload.h"
 
@@ -26,33 +27,6 @@ static int compact_boundaries(hipStream_t s, const uint32_t* d_boundary, uint32_
     HIPCHK(hipStreamSynchronize(s));   // (d_cnt and d_off go with this frame)
     *M_out = M;
     return 0;
-}
-
-// The fixed-shape scan of hml_k_scan.h over `rows` rows of M entries on stream `s`: inclusive into d_out[rows][M] (d_out may
-// be d_in), or exclusive into d_out[rows][M + 1] with the totals last.
-template <typename In, typename Acc, bool Exclusive>
-static int scan_rows(hipStream_t s, const In* d_in, uint64_t M, int rows, Acc* d_out) {
-    DevBuf d_cs;
-    const uint32_t n_chunks = (uint32_t)((M + HML_SCAN_CHUNK - 1) / HML_SCAN_CHUNK);
-    HIPCHK(d_cs.alloc(((uint64_t)n_chunks * rows + 1) * sizeof(Acc)));
-    const dim3 grid((unsigned)grid_for(n_chunks, 1, 1, 4096), (unsigned)rows);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_scan_partial<In, Acc>), grid, dim3(256), 0, s, d_in, (uint32_t)M, n_chunks, d_cs.as<Acc>());
-    hipLaunchKernelGGL(hml_k_scan_chunks<Acc>, dim3(rows), dim3(1024), 0, s, d_cs.as<Acc>(), n_chunks);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_scan_final<In, Acc, Exclusive>), grid, dim3(256), 0, s, d_in, (uint32_t)M, n_chunks, (const Acc*)d_cs.as<Acc>(), d_out);
-    KLAUNCH_CHECK();
-    HIPCHK(hipStreamSynchronize(s));   // (d_cs goes with this frame)
-    return 0;
-}
-
-static int model_fault(const hml_model& m) {   // the device error a sweep left in the model, if any
-    if (!m.err_code) return 0;
-    char buf[256];
-    return set_err(HML_ERR_MODEL, deverr_text(m.err_code, m.err_value, buf, sizeof buf));
-}
-
-// M ascending starts (the first is position 0) and T into the M lengths
-static void lengths_of(const uint32_t* start, uint64_t M, uint32_t T, uint64_t* len) {
-    for (uint64_t i = 0; i < M; ++i) len[i] = (uint64_t)((i + 1 < M ? start[i + 1] : T) - start[i]);
 }
 
 // ---------------------------------------------------------------------------------------- count tables
@@ -122,38 +96,21 @@ template <class Pick>
 static int table_runs(hml_ctx* c, const hml_count_table& tab, Pick pick, uint64_t* n_runs, uint64_t* run_len, std::vector<int16_t>& run_key) {
     const int ncol = tab.ncol;
     uint64_t M = 0;
-    DevBuf b_seg, b_g, b_cs, b_rc, b_key;
+    DevBuf b_seg, b_g, b_cs, b_key;
     if (int r = table_segments(c, tab, &M, b_seg, b_g)) return r;
     const uint32_t n_chunks = (uint32_t)((M + 255) / 256);
     HIPCHK(b_cs.alloc((uint64_t)ncol * n_chunks * sizeof(int32_t)));
-    HIPCHK(b_rc.alloc(((uint64_t)n_chunks + 1) * sizeof(int32_t)));
     HIPCHK(b_key.alloc(M * sizeof(int16_t)));
-    int32_t *const d_cs = b_cs.as<int32_t>(), *const d_rc = b_rc.as<int32_t>();
+    int32_t* const d_cs = b_cs.as<int32_t>();
     int16_t* const d_key = b_key.as<int16_t>();
-    HIPCHK(hipMemsetAsync(d_rc + n_chunks, 0, sizeof(int32_t), c->stream));
     hipLaunchKernelGGL(hml_k_seg_partial, dim3(n_chunks), dim3(256), 0, c->stream, b_g.as<int32_t>(), (uint32_t)M, ncol, d_cs, n_chunks);
     hipLaunchKernelGGL(hml_k_scan_chunks<int32_t>, dim3(ncol), dim3(1024), 0, c->stream, d_cs, n_chunks);
     pick(b_g.as<int32_t>(), (uint32_t)M, d_cs, n_chunks, d_key);
-    hipLaunchKernelGGL(hml_k_seg_run_count, dim3(n_chunks), dim3(256), 0, c->stream, d_key, (uint32_t)M, d_rc);
-    hipLaunchKernelGGL(hml_k_scan_chunks<int32_t>, dim3(1), dim3(1024), 0, c->stream, d_rc, n_chunks + 1u);   // d_rc[n_chunks] = total
-    KLAUNCH_CHECK();
-    int32_t R = 0;
-    HIPCHK(hipMemcpyAsync(&R, d_rc + n_chunks, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    *n_runs = (uint64_t)R;
-    if (!run_len) return 0;
-    DevBuf b_rs, b_rq;
-    HIPCHK(b_rs.alloc((uint64_t)R * sizeof(uint32_t)));
-    HIPCHK(b_rq.alloc((uint64_t)R * sizeof(int16_t)));
-    hipLaunchKernelGGL(hml_k_seg_run_scatter, dim3(n_chunks), dim3(256), 0, c->stream, d_key, b_seg.as<uint32_t>(), (uint32_t)M, d_rc, b_rs.as<uint32_t>(), b_rq.as<int16_t>());
-    KLAUNCH_CHECK();
-    std::vector<uint32_t> h_rs(R);
-    run_key.resize(R);
-    HIPCHK(hipMemcpyAsync(h_rs.data(), b_rs.get(), (uint64_t)R * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(run_key.data(), b_rq.get(), (uint64_t)R * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    lengths_of(h_rs.data(), (uint64_t)R, (uint32_t)c->T, run_len);
-    return 0;
+    auto scatter = [&](uint32_t n_run_chunks, const int32_t* d_rc, uint64_t, uint32_t* d_rs, int16_t* d_rq) {
+        hipLaunchKernelGGL(hml_k_seg_run_scatter, dim3(n_run_chunks), dim3(256), 0, c->stream, d_key, b_seg.as<uint32_t>(), (uint32_t)M, d_rc, d_rs, d_rq);
+        return 0;
+    };
+    return merge_runs(c->stream, d_key, (uint32_t)M, (uint32_t)c->T, scatter, n_runs, run_len, run_key);
 }
 
 extern "C" {
@@ -1218,1089 +1175,6 @@ int hml_history_summary(hml_ctx* const* ctxs, int n, int col, uint64_t skip_swee
     std::vector<double> x((size_t)n * used);
     for (int k = 0; k < n; ++k) std::copy(series[k].end() - (ptrdiff_t)used, series[k].end(), x.begin() + (ptrdiff_t)((uint64_t)k * used));
     return hml_history_stats(x.data(), n, used, rhat, ess, chain_mean, chain_sd, n_nonfinite);
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------- Viterbi decode (hml_k_viterbi.h)
-// The jointly most probable state path over the current blocks under the current parameters.  Everything a decode allocates
-// is local to the call: it goes on every path out, and the context keeps only the numbers of hml_viterbi_info.
-#include "hml_k_viterbi.h"   // (launched from this object alone)
-
-struct vit_tables { DevBuf par, trans, init; };
-struct vit_path { DevBuf q; long long score = 0; uint32_t B = 0; };
-
-// the launches templated on the states the recursion's vector is kept for
-template <int KM>
-static void vit_launch_forward(hml_ctx* c, const vit_tables& t, uint32_t L, uint32_t W, uint32_t n_chunks, long long* entry, long long* exitv, uint8_t* psi) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_vit_forward<KM>), dim3((n_chunks + 63u) / 64u), dim3(64), 0, c->stream, t.par.as<hml_vit_par>(), t.trans.as<long long>(),
-                       t.init.as<long long>(), c->d_ia, c->d_starts.get(), L, W, n_chunks, entry, exitv, psi);
-}
-template <int KM>
-static void vit_launch_rerun(hml_ctx* c, const vit_tables& t, uint32_t L, uint32_t n_chunks, const uint32_t* heads, uint32_t n_heads, const uint8_t* match, long long* entry,
-                             long long* exitv, uint8_t* psi) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_vit_rerun<KM>), dim3((n_heads + 63u) / 64u), dim3(64), 0, c->stream, t.par.as<hml_vit_par>(), t.trans.as<long long>(),
-                       t.init.as<long long>(), c->d_ia, c->d_starts.get(), L, n_chunks, heads, n_heads, match, entry, exitv, psi);
-}
-template <int KM>
-static void vit_launch_finish(hml_ctx* c, const vit_tables& t, uint32_t L, uint32_t n_chunks, const uint8_t* match, long long* entry, long long* exitv, uint8_t* psi,
-                              unsigned long long* walked) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_vit_finish<KM>), dim3(1), dim3(64), 0, c->stream, t.par.as<hml_vit_par>(), t.trans.as<long long>(), t.init.as<long long>(),
-                       c->d_ia, c->d_starts.get(), L, n_chunks, match, entry, exitv, psi, walked);
-}
-#define VIT_BY_K(K, fn, ...) do { if ((K) <= 8) fn<8>(__VA_ARGS__); else if ((K) <= 16) fn<16>(__VA_ARGS__); else fn<HML_CAP_K>(__VA_ARGS__); } while (0)
-
-// how a decode begins: a settled chain with blocks, and the tables (parameters, trans, init) on the device
-static int vit_begin(hml_ctx* c, vit_tables& t, uint32_t* B_out) {
-    hml_model m; if (int r = fetch_model(c, &m)) return r;
-    if (int r = model_fault(m)) return r;
-    if (m.halted) return set_err(HML_ERR_ARG, "hml_viterbi: the chain is halted; settle it with hml_sync first");
-    if (m.B == 0) return set_err(HML_ERR_ARG, "hml_viterbi: no blocks yet: run a sweep or hml_create_blocks first");
-    const int K = c->K;
-    HIPCHK(t.par.alloc(sizeof(hml_vit_par)));
-    HIPCHK(t.trans.alloc((uint64_t)K * K * sizeof(long long)));
-    HIPCHK(t.init.alloc((uint64_t)K * sizeof(long long)));
-    hipLaunchKernelGGL(hml_k_vit_tables, dim3(1), dim3(256), 0, c->stream, c->d_mdl.get(), t.par.as<hml_vit_par>(), t.trans.as<long long>(), t.init.as<long long>());
-    KLAUNCH_CHECK();
-    *B_out = m.B;
-    return 0;
-}
-
-// the decode: path (device, int16 per block) and score
-static int vit_decode(hml_ctx* c, vit_path& out) {
-    vit_tables t;
-    uint32_t B = 0;
-    if (int r = vit_begin(c, t, &B)) return r;
-    const int K = c->K;
-    const uint32_t L = c->vit.L ? c->vit.L : HML_VIT_DEFAULT_L;
-    const uint32_t W = c->vit.W ? c->vit.W : HML_VIT_DEFAULT_W;
-    const uint32_t n_chunks = (uint32_t)(((uint64_t)B + L - 1u) / L);
-    const uint32_t S = std::max<uint32_t>(1u, (uint32_t)std::ceil(std::sqrt((double)n_chunks)));   // chunks per group of the back-track
-    const uint32_t n_groups = (n_chunks + S - 1u) / S;
-    DevBuf b_entry, b_exit, b_psi, b_match, b_list, b_words, b_maps, b_gmaps, b_gend, b_cend;
-    HIPCHK(b_entry.alloc((uint64_t)n_chunks * K * sizeof(long long)));
-    HIPCHK(b_exit.alloc((uint64_t)n_chunks * K * sizeof(long long)));
-    HIPCHK(b_psi.alloc((uint64_t)B * K));
-    HIPCHK(b_match.alloc(n_chunks));
-    HIPCHK(b_list.alloc((uint64_t)n_chunks * sizeof(uint32_t)));
-    HIPCHK(b_words.alloc(4 * sizeof(unsigned long long)));   // [0] stale chunks and heads of their runs (32 bits each), [1] chunks the single lane ran, [2] the score
-    HIPCHK(b_maps.alloc((uint64_t)n_chunks * K));
-    HIPCHK(b_gmaps.alloc((uint64_t)n_groups * K));
-    HIPCHK(b_gend.alloc(n_groups));
-    HIPCHK(b_cend.alloc(n_chunks));
-    HIPCHK(out.q.alloc((uint64_t)B * sizeof(int16_t)));
-    long long *const entry = b_entry.as<long long>(), *const exitv = b_exit.as<long long>();
-    uint8_t *const psi = b_psi.as<uint8_t>(), *const match = b_match.as<uint8_t>();
-    uint32_t* const list = b_list.as<uint32_t>();
-    unsigned long long* const words = b_words.as<unsigned long long>();
-    HIPCHK(hipMemsetAsync(words, 0, 4 * sizeof(unsigned long long), c->stream));
-
-    VIT_BY_K(K, vit_launch_forward, c, t, L, W, n_chunks, entry, exitv, psi);
-    KLAUNCH_CHECK();
-    // verify; repair in rounds while chunks are stale; the single lane for what the rounds leave
-    uint32_t n_stale = 0, stale_first = 0, rounds_run = 0;
-    unsigned long long walked = 0;
-    for (uint32_t round = 0;; ++round) {
-        uint32_t h_cnt[2] = {0, 0};   // stale chunks, heads of their runs
-        HIPCHK(hipMemsetAsync(words, 0, sizeof h_cnt, c->stream));
-        hipLaunchKernelGGL(hml_k_vit_verify, dim3(grid_for(n_chunks, 256, 1, 4096)), dim3(256), 0, c->stream, entry, exitv, K, n_chunks, match, list, (uint32_t*)words,
-                           (uint32_t*)words + 1);
-        KLAUNCH_CHECK();
-        HIPCHK(hipMemcpyAsync(h_cnt, words, sizeof h_cnt, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        n_stale = h_cnt[0];
-        if (round == 0) stale_first = n_stale;
-        if (n_stale == 0 || round >= c->vit.rounds) break;
-        VIT_BY_K(K, vit_launch_rerun, c, t, L, n_chunks, list, h_cnt[1], match, entry, exitv, psi);
-        KLAUNCH_CHECK();
-        rounds_run = round + 1u;
-    }
-    if (n_stale) {
-        VIT_BY_K(K, vit_launch_finish, c, t, L, n_chunks, match, entry, exitv, psi, words + 1);
-        KLAUNCH_CHECK();
-    }
-    // back-track
-    const dim3 cgrid((n_chunks + 63u) / 64u), ggrid((n_groups + 63u) / 64u);
-    hipLaunchKernelGGL(hml_k_vit_chunk_maps, cgrid, dim3(64), 0, c->stream, psi, K, B, L, n_chunks, b_maps.as<uint8_t>());
-    hipLaunchKernelGGL(hml_k_vit_group_maps, ggrid, dim3(64), 0, c->stream, b_maps.as<uint8_t>(), K, n_chunks, S, n_groups, b_gmaps.as<uint8_t>());
-    hipLaunchKernelGGL(hml_k_vit_group_ends, dim3(1), dim3(64), 0, c->stream, exitv, b_gmaps.as<uint8_t>(), K, n_chunks, n_groups, b_gend.as<uint8_t>());
-    hipLaunchKernelGGL(hml_k_vit_chunk_ends, ggrid, dim3(64), 0, c->stream, b_maps.as<uint8_t>(), b_gend.as<uint8_t>(), K, n_chunks, S, n_groups, b_cend.as<uint8_t>());
-    hipLaunchKernelGGL(hml_k_vit_walk, cgrid, dim3(64), 0, c->stream, psi, b_cend.as<uint8_t>(), K, B, L, n_chunks, out.q.as<int16_t>());
-    hipLaunchKernelGGL(hml_k_vit_score, dim3(grid_for(B, 256, 1, 4096)), dim3(256), 0, c->stream, t.par.as<hml_vit_par>(), t.trans.as<long long>(), t.init.as<long long>(),
-                       c->d_ia, c->d_starts.get(), out.q.as<int16_t>(), words + 2);
-    KLAUNCH_CHECK();
-    unsigned long long h_words[4];
-    HIPCHK(hipMemcpyAsync(h_words, words, sizeof h_words, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));   // (the scratch goes with this frame)
-    walked = h_words[1];
-    out.score = (long long)h_words[2];
-    out.B = B;
-    c->vit.decoded = true;
-    c->vit.chunks = n_chunks; c->vit.used_L = L; c->vit.used_W = W; c->vit.stale = stale_first; c->vit.rounds_run = rounds_run; c->vit.walked = walked;
-    return 0;
-}
-
-extern "C" {
-
-int hml_viterbi(hml_ctx* c, uint64_t* n_runs, uint64_t* run_len, int32_t* run_state, int64_t* score_fixed, double* score) {
-    NEED_MODEL();
-    if (!n_runs) return set_err(HML_ERR_ARG, "null argument");
-    vit_path p;
-    if (int r = vit_decode(c, p)) return r;
-    if (score_fixed) *score_fixed = (int64_t)p.score;
-    if (score) *score = (double)p.score / 1048576.0;
-    // runs of equal state over the blocks: the flag / count / scatter steps of the segmentation read-out, on block starts
-    const uint32_t M = p.B;
-    const uint32_t n_chunks = (M + 255u) / 256u;
-    DevBuf b_rc, b_rs, b_rq;
-    HIPCHK(b_rc.alloc(((uint64_t)n_chunks + 1) * sizeof(int32_t)));
-    int32_t* const d_rc = b_rc.as<int32_t>();
-    HIPCHK(hipMemsetAsync(d_rc + n_chunks, 0, sizeof(int32_t), c->stream));
-    hipLaunchKernelGGL(hml_k_seg_run_count, dim3(n_chunks), dim3(256), 0, c->stream, p.q.as<int16_t>(), M, d_rc);
-    hipLaunchKernelGGL(hml_k_scan_chunks<int32_t>, dim3(1), dim3(1024), 0, c->stream, d_rc, n_chunks + 1u);   // d_rc[n_chunks] = total
-    KLAUNCH_CHECK();
-    int32_t R = 0;
-    HIPCHK(hipMemcpyAsync(&R, d_rc + n_chunks, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    *n_runs = (uint64_t)R;
-    if (!run_len) return 0;
-    HIPCHK(b_rs.alloc((uint64_t)R * sizeof(uint32_t)));
-    HIPCHK(b_rq.alloc((uint64_t)R * sizeof(int16_t)));
-    hipLaunchKernelGGL(hml_k_seg_run_scatter, dim3(n_chunks), dim3(256), 0, c->stream, p.q.as<int16_t>(), c->d_starts.get(), M, d_rc, b_rs.as<uint32_t>(), b_rq.as<int16_t>());
-    KLAUNCH_CHECK();
-    std::vector<uint32_t> h_rs(R);
-    std::vector<int16_t> h_rq(R);
-    HIPCHK(hipMemcpyAsync(h_rs.data(), b_rs.get(), (uint64_t)R * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(h_rq.data(), b_rq.get(), (uint64_t)R * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    lengths_of(h_rs.data(), (uint64_t)R, (uint32_t)c->T, run_len);
-    if (run_state) std::copy(h_rq.begin(), h_rq.end(), run_state);
-    return 0;
-}
-
-int hml_viterbi_states(hml_ctx* c, int16_t* q) {
-    NEED_MODEL();
-    if (!q) return set_err(HML_ERR_ARG, "null argument");
-    vit_path p;
-    if (int r = vit_decode(c, p)) return r;
-    HIPCHK(hipMemcpyAsync(q, p.q.get(), (uint64_t)p.B * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-int hml_viterbi_scores(hml_ctx* c, int64_t* emit, int64_t* trans, int64_t* init) {
-    NEED_MODEL();
-    vit_tables t;
-    uint32_t B = 0;
-    if (int r = vit_begin(c, t, &B)) return r;
-    const int K = c->K;
-    DevBuf b_emit;
-    if (emit) {
-        HIPCHK(b_emit.alloc((uint64_t)B * K * sizeof(long long)));
-        hipLaunchKernelGGL(hml_k_vit_emit_table, dim3(grid_for(B, 256, 1, 16384)), dim3(256), 0, c->stream, t.par.as<hml_vit_par>(), c->d_ia, c->d_starts.get(), b_emit.as<long long>());
-        KLAUNCH_CHECK();
-        HIPCHK(hipMemcpyAsync(emit, b_emit.get(), (uint64_t)B * K * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
-    }
-    if (trans) HIPCHK(hipMemcpyAsync(trans, t.trans.get(), (uint64_t)K * K * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
-    if (init) HIPCHK(hipMemcpyAsync(init, t.init.get(), (uint64_t)K * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-int hml_viterbi_info(hml_ctx* c, uint64_t* chunks, uint64_t* L, uint64_t* W, uint64_t* stale_chunks, uint64_t* rounds, uint64_t* serial_chunks) {
-    if (!c) return set_err(HML_ERR_ARG, "null context");
-    if (!c->vit.decoded) return set_err(HML_ERR_ARG, "hml_viterbi_info: nothing was decoded yet");
-    if (chunks) *chunks = c->vit.chunks;
-    if (L) *L = c->vit.used_L;
-    if (W) *W = c->vit.used_W;
-    if (stale_chunks) *stale_chunks = c->vit.stale;
-    if (rounds) *rounds = c->vit.rounds_run;
-    if (serial_chunks) *serial_chunks = c->vit.walked;
-    return 0;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------- smoothing (hml_k_posterior.h)
-// State posteriors per block, log p(y | theta) and the call with a confidence per run: the sum-product sibling of the decode
-// above, with the same relation to the chain (read only) and to device memory (all of it local to the call).
-#include "hml_k_posterior.h"   // (launched from this object alone)
-
-struct post_tables { DevBuf par, A, pi; };
-struct post_result {
-    DevBuf gamma, q, conf, alpha, cval, beta;   // gamma only if asked for
-    double loglik = 0.0;
-    uint64_t degenerate = 0;
-    uint32_t B = 0;
-};
-
-template <int KM, int DIR>
-static void post_launch_first(hml_ctx* c, const hml_post_args& a, size_t lds) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_post_first<KM, DIR>), dim3((a.n_chunks + 63u) / 64u), dim3(64), lds, c->stream, a);
-}
-template <int KM, int DIR>
-static void post_launch_rerun(hml_ctx* c, const hml_post_args& a, size_t lds, const uint32_t* heads, uint32_t n_heads, const uint8_t* match) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_post_rerun<KM, DIR>), dim3((n_heads + 63u) / 64u), dim3(64), lds, c->stream, a, heads, n_heads, match);
-}
-template <int KM, int DIR>
-static void post_launch_finish(hml_ctx* c, const hml_post_args& a, size_t lds, const uint8_t* match, unsigned long long* walked) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_post_finish<KM, DIR>), dim3(1), dim3(64), lds, c->stream, a, match, walked);
-}
-#define POST_BY_K(K, DIR, fn, ...) do { if ((K) <= 8) fn<8, DIR>(__VA_ARGS__); else if ((K) <= 16) fn<16, DIR>(__VA_ARGS__); else fn<HML_CAP_K, DIR>(__VA_ARGS__); } while (0)
-
-// how a call begins: a settled chain with blocks, and the tables (parameters, A and pi in double) on the device
-static int post_ready(const hml_model& m) {
-    if (int r = model_fault(m)) return r;
-    if (m.halted) return set_err(HML_ERR_ARG, "hml_posterior: the chain is halted; settle it with hml_sync first");
-    if (m.B == 0) return set_err(HML_ERR_ARG, "hml_posterior: no blocks yet: run a sweep or hml_create_blocks first");
-    return 0;
-}
-static int post_begin(hml_ctx* c, post_tables& t, uint32_t* B_out) {
-    hml_model m; if (int r = fetch_model(c, &m)) return r;
-    if (int r = post_ready(m)) return r;
-    const int K = c->K;
-    HIPCHK(t.par.alloc(sizeof(hml_vit_par)));
-    HIPCHK(t.A.alloc((uint64_t)K * K * sizeof(double)));
-    HIPCHK(t.pi.alloc((uint64_t)K * sizeof(double)));
-    hipLaunchKernelGGL(hml_k_post_tables, dim3(1), dim3(256), 0, c->stream, c->d_mdl.get(), t.par.as<hml_vit_par>(), t.A.as<double>(), t.pi.as<double>());
-    KLAUNCH_CHECK();
-    *B_out = m.B;
-    return 0;
-}
-
-// one direction: first run, then verify / repair in rounds / the single lane, as vit_decode does it
-template <int DIR>
-static int post_direction(hml_ctx* c, const hml_post_args& a, int K, uint8_t* match, uint32_t* list, unsigned long long* words, uint64_t* stale_first_out,
-                          uint64_t* rounds_out, bool* finished_out) {
-    const size_t lds = ((size_t)K * K + K) * sizeof(double);
-    POST_BY_K(K, DIR, post_launch_first, c, a, lds);
-    KLAUNCH_CHECK();
-    uint32_t n_stale = 0;
-    uint64_t rounds_run = 0;
-    for (uint32_t round = 0;; ++round) {
-        uint32_t h_cnt[2] = {0, 0};   // stale chunks, heads of their runs
-        HIPCHK(hipMemsetAsync(words, 0, sizeof h_cnt, c->stream));
-        hipLaunchKernelGGL(hml_k_vit_verify, dim3(grid_for(a.n_chunks, 256, 1, 4096)), dim3(256), 0, c->stream, reinterpret_cast<const long long*>(a.entry),
-                           reinterpret_cast<const long long*>(a.exitv), K, a.n_chunks, match, list, (uint32_t*)words, (uint32_t*)words + 1);
-        KLAUNCH_CHECK();
-        HIPCHK(hipMemcpyAsync(h_cnt, words, sizeof h_cnt, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        n_stale = h_cnt[0];
-        if (round == 0) *stale_first_out = n_stale;
-        if (n_stale == 0 || round >= c->post.rounds) break;
-        POST_BY_K(K, DIR, post_launch_rerun, c, a, lds, list, h_cnt[1], match);
-        KLAUNCH_CHECK();
-        rounds_run = round + 1u;
-    }
-    if (n_stale) {
-        POST_BY_K(K, DIR, post_launch_finish, c, a, lds, match, words + 1);
-        KLAUNCH_CHECK();
-    }
-    *rounds_out = rounds_run;
-    *finished_out = n_stale != 0;
-    return 0;
-}
-
-// the whole computation; the rows alpha, c and beta stay in `out` for the probe, the tables in `t` for the E-step
-static int post_compute(hml_ctx* c, bool want_gamma, post_result& out, post_tables& t) {
-    uint32_t B = 0;
-    if (int r = post_begin(c, t, &B)) return r;
-    const int K = c->K;
-    const uint32_t L = c->post.L ? c->post.L : HML_POST_DEFAULT_L;
-    const uint32_t W = c->post.W ? c->post.W : HML_POST_DEFAULT_W;
-    const uint32_t n_chunks = (uint32_t)(((uint64_t)B + L - 1u) / L);
-    const uint64_t n1 = ((uint64_t)B + 63u) / 64u, n2 = (n1 + 63u) / 64u;   // the first two levels of the tree
-    DevBuf b_entry, b_exit, b_match, b_list, b_words, b_ell, b_t1, b_t2;
-    HIPCHK(out.alpha.alloc((uint64_t)B * K * sizeof(double)));
-    HIPCHK(out.beta.alloc((uint64_t)B * K * sizeof(double)));
-    HIPCHK(out.cval.alloc((uint64_t)B * sizeof(double)));
-    HIPCHK(b_ell.alloc((uint64_t)B * sizeof(double)));
-    HIPCHK(b_entry.alloc((uint64_t)n_chunks * K * sizeof(double)));
-    HIPCHK(b_exit.alloc((uint64_t)n_chunks * K * sizeof(double)));
-    HIPCHK(b_match.alloc(n_chunks));
-    HIPCHK(b_list.alloc((uint64_t)n_chunks * sizeof(uint32_t)));
-    HIPCHK(b_words.alloc(4 * sizeof(unsigned long long)));   // [0] stale chunks and heads (32 bits each), [1] chunks the single lane ran, [2] degenerate blocks, [3] log-likelihood
-    HIPCHK(b_t1.alloc(n1 * sizeof(double)));
-    HIPCHK(b_t2.alloc(n2 * sizeof(double)));
-    HIPCHK(out.q.alloc((uint64_t)B * sizeof(int16_t)));
-    HIPCHK(out.conf.alloc((uint64_t)B * sizeof(double)));
-    if (want_gamma) HIPCHK(out.gamma.alloc((uint64_t)B * K * sizeof(double)));
-    unsigned long long* const words = b_words.as<unsigned long long>();
-    HIPCHK(hipMemsetAsync(words, 0, 4 * sizeof(unsigned long long), c->stream));
-
-    hml_post_args a;
-    a.par = t.par.as<hml_vit_par>(); a.A = t.A.as<double>(); a.pi = t.pi.as<double>();
-    a.ia = c->d_ia; a.starts = c->d_starts.get();
-    a.L = L; a.W = W; a.n_chunks = n_chunks;
-    a.entry = b_entry.as<double>(); a.exitv = b_exit.as<double>();
-    uint64_t stale[2] = {0, 0}, rounds[2] = {0, 0};
-    bool finished[2] = {false, false};
-    a.rows = out.alpha.as<double>(); a.cval = out.cval.as<double>(); a.ell = b_ell.as<double>();
-    if (int r = post_direction<0>(c, a, K, b_match.as<uint8_t>(), b_list.as<uint32_t>(), words, &stale[0], &rounds[0], &finished[0])) return r;
-    a.rows = out.beta.as<double>(); a.cval = nullptr; a.ell = nullptr;   // (entry, exit, match and list are used again)
-    if (int r = post_direction<1>(c, a, K, b_match.as<uint8_t>(), b_list.as<uint32_t>(), words, &stale[1], &rounds[1], &finished[1])) return r;
-
-    hipLaunchKernelGGL(hml_k_post_combine, dim3(grid_for(B, 256, 1, 16384)), dim3(256), 0, c->stream, out.alpha.as<double>(), out.beta.as<double>(), out.cval.as<double>(), K, B,
-                       want_gamma ? out.gamma.as<double>() : nullptr, out.q.as<int16_t>(), out.conf.as<double>(), words + 2);
-    // the tree over l_b: levels until one value is left
-    const double* level = b_ell.as<double>();
-    uint64_t n = B;
-    double* bufs[2] = {b_t1.as<double>(), b_t2.as<double>()};
-    for (int k = 0; n > 1; ++k) {
-        double* const dst = bufs[k & 1];
-        hipLaunchKernelGGL(hml_k_post_tree, dim3(grid_for((n + 63u) / 64u, 256, 1, 4096)), dim3(256), 0, c->stream, level, n, dst);
-        level = dst;
-        n = (n + 63u) / 64u;
-    }
-    KLAUNCH_CHECK();
-    unsigned long long h_words[4];
-    HIPCHK(hipMemcpyAsync(h_words, words, sizeof h_words, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(&out.loglik, level, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));   // (the scratch goes with this frame)
-    out.degenerate = h_words[2];
-    out.B = B;
-    c->post.computed = true;
-    c->post.chunks = n_chunks; c->post.used_L = L; c->post.used_W = W; c->post.stale_fwd = stale[0]; c->post.stale_bwd = stale[1];
-    c->post.rounds_run = std::max(rounds[0], rounds[1]); c->post.walked = (finished[0] || finished[1]) ? h_words[1] : 0;
-    return 0;
-}
-
-static int post_compute(hml_ctx* c, bool want_gamma, post_result& out) {
-    post_tables t;
-    return post_compute(c, want_gamma, out, t);
-}
-
-extern "C" {
-
-int hml_posterior(hml_ctx* c, double* gamma, double* loglik, uint64_t* degenerate) {
-    NEED_MODEL();
-    post_result p;
-    if (int r = post_compute(c, gamma != nullptr, p)) return r;
-    if (gamma) {
-        HIPCHK(hipMemcpyAsync(gamma, p.gamma.get(), (uint64_t)p.B * c->K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    if (loglik) *loglik = p.loglik;
-    if (degenerate) *degenerate = p.degenerate;
-    return 0;
-}
-
-int hml_posterior_rle(hml_ctx* c, uint64_t* n_runs, uint64_t* run_len, int32_t* run_state, double* run_conf) {
-    NEED_MODEL();
-    if (!n_runs) return set_err(HML_ERR_ARG, "null argument");
-    post_result p;
-    if (int r = post_compute(c, false, p)) return r;
-    // runs of equal state over the blocks, as hml_viterbi forms them, each with the minimum of its blocks' posteriors
-    const uint32_t M = p.B;
-    const uint32_t n_chunks = (M + 255u) / 256u;
-    DevBuf b_rc, b_rs, b_rq, b_rconf;
-    HIPCHK(b_rc.alloc(((uint64_t)n_chunks + 1) * sizeof(int32_t)));
-    int32_t* const d_rc = b_rc.as<int32_t>();
-    HIPCHK(hipMemsetAsync(d_rc + n_chunks, 0, sizeof(int32_t), c->stream));
-    hipLaunchKernelGGL(hml_k_seg_run_count, dim3(n_chunks), dim3(256), 0, c->stream, p.q.as<int16_t>(), M, d_rc);
-    hipLaunchKernelGGL(hml_k_scan_chunks<int32_t>, dim3(1), dim3(1024), 0, c->stream, d_rc, n_chunks + 1u);   // d_rc[n_chunks] = total
-    KLAUNCH_CHECK();
-    int32_t R = 0;
-    HIPCHK(hipMemcpyAsync(&R, d_rc + n_chunks, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    *n_runs = (uint64_t)R;
-    if (!run_len) return 0;
-    HIPCHK(b_rs.alloc((uint64_t)R * sizeof(uint32_t)));
-    HIPCHK(b_rq.alloc((uint64_t)R * sizeof(int16_t)));
-    HIPCHK(b_rconf.alloc((uint64_t)R * sizeof(double)));
-    HIPCHK(hipMemsetAsync(b_rconf.get(), 0xff, (uint64_t)R * sizeof(double), c->stream));
-    hipLaunchKernelGGL(hml_k_post_run_scatter, dim3(n_chunks), dim3(256), 0, c->stream, p.q.as<int16_t>(), p.conf.as<double>(), c->d_starts.get(), M, d_rc, b_rs.as<uint32_t>(),
-                       b_rq.as<int16_t>(), b_rconf.as<unsigned long long>());
-    KLAUNCH_CHECK();
-    std::vector<uint32_t> h_rs(R);
-    std::vector<int16_t> h_rq(R);
-    HIPCHK(hipMemcpyAsync(h_rs.data(), b_rs.get(), (uint64_t)R * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(h_rq.data(), b_rq.get(), (uint64_t)R * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
-    if (run_conf) HIPCHK(hipMemcpyAsync(run_conf, b_rconf.get(), (uint64_t)R * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    lengths_of(h_rs.data(), (uint64_t)R, (uint32_t)c->T, run_len);
-    if (run_state) std::copy(h_rq.begin(), h_rq.end(), run_state);
-    return 0;
-}
-
-int hml_posterior_terms(hml_ctx* c, float* e, float* m, double* alpha, double* cval, double* beta) {
-    NEED_MODEL();
-    const int K = c->K;
-    if (e || m) {
-        post_tables t;
-        uint32_t B = 0;
-        if (int r = post_begin(c, t, &B)) return r;
-        DevBuf b_e, b_m;
-        if (e) HIPCHK(b_e.alloc((uint64_t)B * K * sizeof(float)));
-        if (m) HIPCHK(b_m.alloc((uint64_t)B * sizeof(float)));
-        hipLaunchKernelGGL(hml_k_post_term_table, dim3(grid_for(B, 256, 1, 16384)), dim3(256), 0, c->stream, t.par.as<hml_vit_par>(), c->d_ia, c->d_starts.get(), b_e.as<float>(),
-                           b_m.as<float>());
-        KLAUNCH_CHECK();
-        if (e) HIPCHK(hipMemcpyAsync(e, b_e.get(), (uint64_t)B * K * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        if (m) HIPCHK(hipMemcpyAsync(m, b_m.get(), (uint64_t)B * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    if (alpha || cval || beta || !(e || m)) {
-        post_result p;
-        if (int r = post_compute(c, false, p)) return r;
-        if (alpha) HIPCHK(hipMemcpyAsync(alpha, p.alpha.get(), (uint64_t)p.B * K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (cval) HIPCHK(hipMemcpyAsync(cval, p.cval.get(), (uint64_t)p.B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (beta) HIPCHK(hipMemcpyAsync(beta, p.beta.get(), (uint64_t)p.B * K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    return 0;
-}
-
-int hml_posterior_info(hml_ctx* c, uint64_t* chunks, uint64_t* L, uint64_t* W, uint64_t* stale_fwd, uint64_t* stale_bwd, uint64_t* rounds, uint64_t* serial_chunks) {
-    if (!c) return set_err(HML_ERR_ARG, "null context");
-    if (!c->post.computed) return set_err(HML_ERR_ARG, "hml_posterior_info: nothing was computed yet");
-    if (chunks) *chunks = c->post.chunks;
-    if (L) *L = c->post.used_L;
-    if (W) *W = c->post.used_W;
-    if (stale_fwd) *stale_fwd = c->post.stale_fwd;
-    if (stale_bwd) *stale_bwd = c->post.stale_bwd;
-    if (rounds) *rounds = c->post.rounds_run;
-    if (serial_chunks) *serial_chunks = c->post.walked;
-    return 0;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------- expectation-maximisation (hml_k_em.h)
-// The E-step's expected counts behind a smoothing pass, the M-step of hml_em_ref.h on the host, and the fit.  Device memory is
-// local to a call, as the smoothing's is.
-#include "hml_em_ref.h"
-#include "hml_k_em.h"   // (launched from this object alone)
-
-template <int KM>
-static void em_launch_norm(hml_ctx* c, const hml_post_args& a, size_t lds, uint32_t B, const double* alpha, const double* beta, double* X, unsigned long long* n_bad) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_em_norm<KM>), dim3((B - 1u + 63u) / 64u), dim3(64), lds, c->stream, a, alpha, beta, X, n_bad);
-}
-#define EM_BY_K(K, fn, ...) do { if ((K) <= 8) fn<8>(__VA_ARGS__); else if ((K) <= 16) fn<16>(__VA_ARGS__); else fn<HML_CAP_K>(__VA_ARGS__); } while (0)
-
-// the E-step: a smoothing pass, then the counts
-static int em_estep(hml_ctx* c, hml_em_counts& out) {
-    post_tables t;
-    post_result p;
-    if (int r = post_compute(c, false, p, t)) return r;
-    const int K = c->K, D = c->D, KK = K * K;
-    const uint32_t B = p.B;
-    const uint32_t ncols = (uint32_t)(KK + K * (2 + 2 * D));
-    const uint64_t n1 = ((uint64_t)B + 63u) / 64u, n2 = (n1 + 63u) / 64u;
-    DevBuf b_X, b_p1, b_p2, b_first, b_bad;
-    const bool small = K <= 16;   // one wavefront per group, X_b computed where it is used (hml_k_em_reduce_small)
-    if (!small) HIPCHK(b_X.alloc((uint64_t)B * sizeof(double)));
-    HIPCHK(b_p1.alloc(n1 * ncols * sizeof(double)));
-    HIPCHK(b_p2.alloc(n2 * ncols * sizeof(double)));
-    HIPCHK(b_first.alloc((uint64_t)K * sizeof(double)));
-    HIPCHK(b_bad.alloc(sizeof(unsigned long long)));
-    HIPCHK(hipMemsetAsync(b_bad.get(), 0, sizeof(unsigned long long), c->stream));
-    if (B > 1u && !small) {
-        hml_post_args a;
-        a.par = t.par.as<hml_vit_par>(); a.A = t.A.as<double>(); a.pi = t.pi.as<double>();
-        a.ia = c->d_ia; a.starts = c->d_starts.get();
-        a.L = 0; a.W = 0; a.n_chunks = 0; a.entry = nullptr; a.exitv = nullptr; a.rows = nullptr; a.cval = nullptr; a.ell = nullptr;
-        EM_BY_K(K, em_launch_norm, c, a, ((size_t)KK + K) * sizeof(double), B, p.alpha.as<double>(), p.beta.as<double>(), b_X.as<double>(), b_bad.as<unsigned long long>());
-        KLAUNCH_CHECK();
-    }
-    hml_em_args e;
-    e.par = t.par.as<hml_vit_par>(); e.A = t.A.as<double>(); e.ia = c->d_ia; e.starts = c->d_starts.get();
-    e.alpha = p.alpha.as<double>(); e.beta = p.beta.as<double>(); e.X = b_X.as<double>();
-    e.part = b_p1.as<double>(); e.first = b_first.as<double>();
-    if (K <= 8) hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_em_reduce_small<8>), dim3((uint32_t)n1), dim3(64), 0, c->stream, e, b_bad.as<unsigned long long>());
-    else if (small) hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_em_reduce_small<16>), dim3((uint32_t)n1), dim3(64), 0, c->stream, e, b_bad.as<unsigned long long>());
-    else hipLaunchKernelGGL(hml_k_em_reduce, dim3((uint32_t)n1), dim3(256), 0, c->stream, e);
-    // the upper levels of the trees: xi's has B - 1 leaves, the others' B
-    const double* level = b_p1.as<double>();
-    uint64_t n_x = ((uint64_t)B - 1u + 63u) / 64u, n_o = n1;
-    double* bufs[2] = {b_p2.as<double>(), b_p1.as<double>()};
-    for (int k = 0; n_o > 1; ++k) {
-        double* const dst = bufs[k & 1];
-        hipLaunchKernelGGL(hml_k_em_tree, dim3(grid_for(((n_o + 63u) / 64u) * ncols, 256, 1, 4096)), dim3(256), 0, c->stream, level, n_x, n_o, ncols, (uint32_t)KK, dst);
-        level = dst;
-        n_x = (n_x + 63u) / 64u; n_o = (n_o + 63u) / 64u;
-    }
-    KLAUNCH_CHECK();
-    std::vector<double> cols(ncols);
-    unsigned long long n_bad = 0;
-    out.first.resize(K);
-    HIPCHK(hipMemcpyAsync(cols.data(), level, (uint64_t)ncols * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(out.first.data(), b_first.get(), (uint64_t)K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(&n_bad, b_bad.get(), sizeof n_bad, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));   // (the scratch goes with this frame)
-    out.xi.assign(cols.begin(), cols.begin() + KK);
-    if (B == 1u) out.xi.assign((size_t)KK, 0.0);
-    out.occ.assign(cols.begin() + KK, cols.begin() + KK + K);
-    out.stay.assign(cols.begin() + KK + K, cols.begin() + KK + 2 * K);
-    out.sx.resize((size_t)K * D); out.sxx.resize((size_t)K * D);
-    for (int j = 0; j < K; ++j)
-        for (int d = 0; d < D; ++d) {
-            out.sx[j * D + d] = cols[KK + (2 + d) * K + j];
-            out.sxx[j * D + d] = cols[KK + (2 + D + d) * K + j];
-        }
-    out.loglik = p.loglik;
-    out.degenerate = p.degenerate;
-    out.xi_degenerate = n_bad;
-    return 0;
-}
-
-// the context's float parameters and priors, as the M-step and the objective take them
-struct em_params {
-    std::vector<float> mv, A, pi;
-    hml_em_prior pr;
-    int P = 0, self_trans = 1;
-};
-static void em_params_of(const hml_model& m, int K, em_params& q);
-static int em_fetch(hml_ctx* c, em_params& q) {
-    hml_model m; if (int r = fetch_model(c, &m)) return r;
-    em_params_of(m, c->K, q);
-    return 0;
-}
-static void em_params_of(const hml_model& m, int K, em_params& q) {
-    q.P = m.P; q.self_trans = m.self_trans != 0;
-    q.mv.resize(2 * (size_t)m.P);
-    for (int k = 0; k < m.P; ++k) { q.mv[2 * k] = m.mu[k]; q.mv[2 * k + 1] = m.var[k]; }
-    q.A.assign(m.A, m.A + K * K);
-    q.pi.assign(m.pi, m.pi + K);
-    q.pr.alpha = (double)m.nig_prior[0]; q.pr.beta = (double)m.nig_prior[1]; q.pr.mu0 = (double)m.nig_prior[2]; q.pr.nu = (double)m.nig_prior[3];
-    q.pr.a_off = (double)m.a_off; q.pr.a_diag = (double)m.a_diag; q.pr.pi_alpha = (double)m.pi_alpha;
-}
-
-// one E-step, the objective of the current parameters, and whether the E-step was degenerate
-static int em_expect(hml_ctx* c, int use_prior, em_params& q, hml_em_counts& n, double* objective) {
-    if (int r = em_estep(c, n)) return r;
-    if (int r = em_fetch(c, q)) return r;
-    *objective = hml_em_objective(c->K, q.P, use_prior, q.pr, n.loglik, q.mv.data(), q.A.data(), q.pi.data());
-    return 0;
-}
-// the M-step and the installation of its result
-static int em_maximise(hml_ctx* c, int use_prior, em_params& q, const hml_em_counts& n, uint64_t* kept) {
-    *kept += hml_em_mstep(c->K, c->D, q.P, q.self_trans, use_prior, q.pr, n, q.mv.data(), q.A.data(), q.pi.data());
-    return hml_set_parameters(c, q.mv.data(), q.A.data(), q.pi.data());
-}
-
-extern "C" {
-
-int hml_expected_counts(hml_ctx* c, double* xi, double* first, double* stay, double* occ, double* sum, double* sum_sq, double* loglik, uint64_t* degenerate,
-                        uint64_t* xi_degenerate) {
-    NEED_MODEL();
-    hml_em_counts n;
-    if (int r = em_estep(c, n)) return r;
-    if (xi) std::copy(n.xi.begin(), n.xi.end(), xi);
-    if (first) std::copy(n.first.begin(), n.first.end(), first);
-    if (stay) std::copy(n.stay.begin(), n.stay.end(), stay);
-    if (occ) std::copy(n.occ.begin(), n.occ.end(), occ);
-    if (sum) std::copy(n.sx.begin(), n.sx.end(), sum);
-    if (sum_sq) std::copy(n.sxx.begin(), n.sxx.end(), sum_sq);
-    if (loglik) *loglik = n.loglik;
-    if (degenerate) *degenerate = n.degenerate;
-    if (xi_degenerate) *xi_degenerate = n.xi_degenerate;
-    return 0;
-}
-
-int hml_em_step(hml_ctx* c, int use_prior, double* objective_before, uint64_t* kept) {
-    NEED_MODEL();
-    em_params q;
-    hml_em_counts n;
-    double obj = 0.0;
-    uint64_t k = 0;
-    if (int r = em_expect(c, use_prior, q, n, &obj)) return r;
-    if (int r = em_maximise(c, use_prior, q, n, &k)) return r;
-    if (objective_before) *objective_before = obj;
-    if (kept) *kept = k;
-    return 0;
-}
-
-int hml_em_fit(hml_ctx* c, int use_prior, uint64_t max_steps, double rel_tol, double* trace, uint64_t* steps, int* reason, uint64_t* kept) {
-    NEED_MODEL();
-    uint64_t k_total = 0, k = 0;
-    int why = HML_EM_MAX_STEPS;
-    double last[2] = {0.0, 0.0};   // trace[k - 1], trace[k]
-    for (;; ++k) {
-        em_params q;
-        hml_em_counts n;
-        last[0] = last[1];
-        if (int r = em_expect(c, use_prior, q, n, &last[1])) return r;
-        if (trace) trace[k] = last[1];
-        if (hml_em_stops(last[0], last[1], k, max_steps, rel_tol, n.degenerate + n.xi_degenerate, &why)) break;
-        if (int r = em_maximise(c, use_prior, q, n, &k_total)) return r;
-    }
-    if (steps) *steps = k;
-    if (reason) *reason = why;
-    if (kept) *kept = k_total;
-    return 0;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------- EM from many starts (hml_k_em_many.h)
-// A batch of fits over the same blocks, each hml_set_parameters(start) + hml_em_fit word for word: the E-steps of the members
-// still running go through one set of launches per group, the member being grid dimension y; objective, stopping rule and
-// M-step are the header's functions per member on the host, as in hml_em_fit.  The context's parameters are not touched before
-// the winner is installed.  Device memory is local to the call.
-#include <limits>
-
-#include "hml_em_many_ref.h"
-#include "hml_k_em_many.h"   // (launched from this object alone)
-
-#define HML_EM_MANY_DEFAULT_BYTES (4ull << 30)   // of a group's device memory (hml_set_em_batch_bytes)
-
-struct em_many_geom {
-    int K = 0, D = 0, P = 0;
-    uint32_t B = 0, L = 0, W = 0, n_chunks = 0, ncols = 0;
-    uint64_t n1 = 0, n2 = 0, nfloats = 0, nresult = 0;
-    bool small = false;
-};
-struct em_many_bufs {
-    DevBuf alpha, beta, cval, ell, entry, exitv, match, heads, cnt, words, lt1, lt2, X, p1, p2, first, par, A, pi, mdl, floats, result, recs;
-};
-struct em_many_stats { uint64_t launch_sets = 0, stale[2] = {0, 0}, rounds = 0, walked = 0; };
-
-// (array, bytes per member) in the order they are allocated
-static std::vector<std::pair<DevBuf*, uint64_t>> em_many_layout(em_many_bufs& b, const em_many_geom& g) {
-    const uint64_t B = g.B, K = g.K, dbl = sizeof(double);
-    std::vector<std::pair<DevBuf*, uint64_t>> v = {
-        {&b.alpha, B * K * dbl}, {&b.beta, B * K * dbl}, {&b.cval, B * dbl}, {&b.ell, B * dbl}, {&b.entry, (uint64_t)g.n_chunks * K * dbl},
-        {&b.exitv, (uint64_t)g.n_chunks * K * dbl}, {&b.match, g.n_chunks}, {&b.heads, (uint64_t)g.n_chunks * sizeof(uint32_t)}, {&b.cnt, 2 * sizeof(uint32_t)},
-        {&b.words, HML_EMM_WORDS * sizeof(unsigned long long)}, {&b.lt1, g.n1 * dbl}, {&b.lt2, g.n2 * dbl}, {&b.p1, g.n1 * g.ncols * dbl},
-        {&b.p2, g.n2 * g.ncols * dbl}, {&b.first, K * dbl}, {&b.par, sizeof(hml_vit_par)}, {&b.A, K * K * dbl}, {&b.pi, K * dbl}, {&b.mdl, sizeof(hml_model)},
-        {&b.floats, g.nfloats * sizeof(float)}, {&b.result, g.nresult * dbl}, {&b.recs, sizeof(hml_em_many_rec)}};
-    if (!g.small) v.push_back({&b.X, B * dbl});
-    return v;
-}
-
-template <int KM, int DIR>
-static void em_many_launch_first(hml_ctx* c, const hml_em_many_rec* recs, const em_many_geom& g, uint32_t n, size_t lds) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_em_many_first<KM, DIR>), dim3((g.n_chunks + 63u) / 64u, n), dim3(64), lds, c->stream, recs);
-}
-template <int KM, int DIR>
-static void em_many_launch_rerun(hml_ctx* c, const hml_em_many_rec* recs, uint32_t max_heads, uint32_t n, size_t lds) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_em_many_rerun<KM, DIR>), dim3((max_heads + 63u) / 64u, n), dim3(64), lds, c->stream, recs);
-}
-template <int KM, int DIR>
-static void em_many_launch_finish(hml_ctx* c, const hml_em_many_rec* recs, uint32_t n, size_t lds) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_em_many_finish<KM, DIR>), dim3(1, n), dim3(64), lds, c->stream, recs);
-}
-template <int KM>
-static void em_many_launch_norm(hml_ctx* c, const hml_em_many_rec* recs, const em_many_geom& g, uint32_t n, size_t lds) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_em_many_norm<KM>), dim3((g.B - 1u + 63u) / 64u, n), dim3(64), lds, c->stream, recs);
-}
-
-// one direction of the smoothing for the first n records: post_direction's rounds, the counts of all members in one copy each
-template <int DIR>
-static int em_many_direction(hml_ctx* c, const em_many_geom& g, em_many_bufs& b, uint32_t n, em_many_stats& st) {
-    const hml_em_many_rec* const recs = b.recs.as<hml_em_many_rec>();
-    const size_t lds = ((size_t)g.K * g.K + g.K) * sizeof(double);
-    POST_BY_K(g.K, DIR, em_many_launch_first, c, recs, g, n, lds);
-    KLAUNCH_CHECK();
-    std::vector<uint32_t> h_cnt(2 * (size_t)n);
-    bool any = false;
-    for (uint32_t round = 0;; ++round) {
-        HIPCHK(hipMemsetAsync(b.cnt.get(), 0, h_cnt.size() * sizeof(uint32_t), c->stream));
-        hipLaunchKernelGGL(hml_k_em_many_verify, dim3(grid_for(g.n_chunks, 256, 1, 4096), n), dim3(256), 0, c->stream, recs, DIR, g.K);
-        KLAUNCH_CHECK();
-        HIPCHK(hipMemcpyAsync(h_cnt.data(), b.cnt.get(), h_cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        uint64_t stale = 0;
-        uint32_t max_heads = 0;
-        for (uint32_t i = 0; i < n; ++i) { stale += h_cnt[2 * i]; max_heads = std::max(max_heads, h_cnt[2 * i + 1]); }
-        if (round == 0) st.stale[DIR] += stale;
-        any = stale != 0;
-        if (!any || round >= c->post.rounds) break;
-        POST_BY_K(g.K, DIR, em_many_launch_rerun, c, recs, max_heads, n, lds);
-        KLAUNCH_CHECK();
-        st.rounds = std::max<uint64_t>(st.rounds, round + 1u);
-    }
-    if (any) {
-        POST_BY_K(g.K, DIR, em_many_launch_finish, c, recs, n, lds);
-        KLAUNCH_CHECK();
-    }
-    return 0;
-}
-
-// The E-step of n members, whose floats (mean_var, A, pi per member) are h_floats: their result rows into h_result.
-static int em_many_estep(hml_ctx* c, const em_many_geom& g, em_many_bufs& b, uint32_t n, const float* h_floats, double* h_result, em_many_stats& st) {
-    const hml_em_many_rec* const recs = b.recs.as<hml_em_many_rec>();
-    const int K = g.K;
-    HIPCHK(hipMemcpyAsync(b.floats.get(), h_floats, (uint64_t)n * g.nfloats * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemsetAsync(b.words.get(), 0, (uint64_t)n * HML_EMM_WORDS * sizeof(unsigned long long), c->stream));
-    hipLaunchKernelGGL(hml_k_em_many_model, dim3(1, n), dim3(256), 0, c->stream, c->d_mdl.get(), recs);
-    hipLaunchKernelGGL(hml_k_em_many_tables, dim3(1, n), dim3(256), 0, c->stream, recs);
-    KLAUNCH_CHECK();
-    ++st.launch_sets;
-    if (int r = em_many_direction<0>(c, g, b, n, st)) return r;
-    if (int r = em_many_direction<1>(c, g, b, n, st)) return r;
-    hipLaunchKernelGGL(hml_k_em_many_degenerate, dim3(grid_for(g.B, 256, 1, 16384), n), dim3(256), 0, c->stream, recs, g.B);
-    int l_levels = 0, p_levels = 0;
-    for (uint64_t m = g.B; m > 1; m = (m + 63u) / 64u, ++l_levels)
-        hipLaunchKernelGGL(hml_k_em_many_ltree, dim3(grid_for((m + 63u) / 64u, 256, 1, 4096), n), dim3(256), 0, c->stream, recs, l_levels, m);
-    KLAUNCH_CHECK();
-    if (g.B > 1u && !g.small) {
-        EM_BY_K(K, em_many_launch_norm, c, recs, g, n, ((size_t)K * K + K) * sizeof(double));
-        KLAUNCH_CHECK();
-    }
-    if (K <= 8) hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_em_many_reduce_small<8>), dim3((uint32_t)g.n1, n), dim3(64), 0, c->stream, recs);
-    else if (g.small) hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_em_many_reduce_small<16>), dim3((uint32_t)g.n1, n), dim3(64), 0, c->stream, recs);
-    else hipLaunchKernelGGL(hml_k_em_many_reduce, dim3((uint32_t)g.n1, n), dim3(256), 0, c->stream, recs);
-    uint64_t n_x = ((uint64_t)g.B - 1u + 63u) / 64u, n_o = g.n1;
-    for (; n_o > 1; ++p_levels) {
-        hipLaunchKernelGGL(hml_k_em_many_tree, dim3(grid_for(((n_o + 63u) / 64u) * g.ncols, 256, 1, 4096), n), dim3(256), 0, c->stream, recs, p_levels, n_x, n_o, g.ncols,
-                           (uint32_t)(K * K));
-        n_x = (n_x + 63u) / 64u; n_o = (n_o + 63u) / 64u;
-    }
-    hipLaunchKernelGGL(hml_k_em_many_gather, dim3(1, n), dim3(256), 0, c->stream, recs, l_levels, p_levels, g.ncols, K);
-    KLAUNCH_CHECK();
-    HIPCHK(hipMemcpyAsync(h_result, b.result.get(), (uint64_t)n * g.nresult * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-// a member's result row as the counts em_estep returns
-static void em_many_counts(const em_many_geom& g, const double* row, hml_em_counts& out, uint64_t* walked) {
-    const int K = g.K, D = g.D, KK = K * K;
-    out.xi.assign(row, row + KK);
-    if (g.B == 1u) out.xi.assign((size_t)KK, 0.0);
-    out.occ.assign(row + KK, row + KK + K);
-    out.stay.assign(row + KK + K, row + KK + 2 * K);
-    out.sx.resize((size_t)K * D); out.sxx.resize((size_t)K * D);
-    for (int j = 0; j < K; ++j)
-        for (int d = 0; d < D; ++d) {
-            out.sx[j * D + d] = row[KK + (2 + d) * K + j];
-            out.sxx[j * D + d] = row[KK + (2 + D + d) * K + j];
-        }
-    const double* const tail = row + g.ncols;
-    out.first.assign(tail, tail + K);
-    out.loglik = tail[K];
-    uint64_t w[HML_EMM_WORDS];
-    memcpy(w, tail + K + 1, sizeof w);
-    *walked = w[HML_EMM_W_WALKED];
-    out.degenerate = w[HML_EMM_W_DEGENERATE];
-    out.xi_degenerate = w[HML_EMM_W_XI_BAD];
-}
-
-// hml_set_parameters' refusal of a start, or "" if it takes it
-static std::string em_many_refusal(int P, const float* mean_var) {
-    for (int k = 0; k < P; ++k) {
-        const float mean = mean_var[2 * k], var = mean_var[2 * k + 1];
-        if (!std::isfinite(mean)) return "Mean (" + std::to_string(mean) + ") must be set to a finite value!";
-        if (!std::isfinite(var)) return "Variance(" + std::to_string(var) + ") must be set to a finite value!";
-        if (var <= 0) return "Variance (" + std::to_string(var) + ") must be positive!";
-    }
-    return "";
-}
-
-extern "C" {
-
-int hml_em_fit_many(hml_ctx* c, uint64_t R, const float* mean_var, const float* A, const float* pi, int use_prior, uint64_t max_steps, double rel_tol, int install,
-                    double* trace, uint64_t* steps, int* reason, uint64_t* kept, float* fit_mean_var, float* fit_A, float* fit_pi, double* objective, int64_t* best) {
-    NEED_MODEL();
-    if (R < 1u || R > HML_EM_MANY_MAX_R) return set_err(HML_ERR_ARG, "hml_em_fit_many: the number of members must be 1 ... " + std::to_string(HML_EM_MANY_MAX_R));
-    if (!mean_var || !A || !pi) return set_err(HML_ERR_ARG, "null argument");
-    hml_model m; if (int r = fetch_model(c, &m)) return r;
-    if (int r = post_ready(m)) return r;
-    em_many_geom g;
-    g.K = c->K; g.D = c->D; g.P = m.P; g.B = m.B;
-    const int K = g.K, KK = K * K, P = g.P;
-    for (uint64_t r = 0; r < R; ++r) {
-        const std::string why = em_many_refusal(P, mean_var + r * 2u * P);
-        if (!why.empty()) return set_err(HML_ERR_MODEL, why + " (start " + std::to_string(r) + ")");
-    }
-    em_params q0;
-    em_params_of(m, K, q0);
-    g.L = c->post.L ? c->post.L : HML_POST_DEFAULT_L;
-    g.W = c->post.W ? c->post.W : HML_POST_DEFAULT_W;
-    g.n_chunks = (uint32_t)(((uint64_t)g.B + g.L - 1u) / g.L);
-    g.ncols = (uint32_t)(KK + K * (2 + 2 * g.D));
-    g.n1 = ((uint64_t)g.B + 63u) / 64u; g.n2 = (g.n1 + 63u) / 64u;
-    g.nfloats = 2u * P + KK + K;
-    g.nresult = (uint64_t)g.ncols + K + 1u + HML_EMM_WORDS;
-    g.small = K <= 16;
-
-    // the group: as many members as the byte budget holds
-    em_many_bufs b;
-    const auto layout = em_many_layout(b, g);
-    uint64_t member_bytes = 0;
-    for (const auto& e : layout) member_bytes += e.second;
-    const uint64_t budget = c->em_many.batch_bytes ? c->em_many.batch_bytes : HML_EM_MANY_DEFAULT_BYTES;
-    const uint64_t G0 = std::min<uint64_t>(std::max<uint64_t>(budget / member_bytes, 1u), R);
-    for (const auto& e : layout) HIPCHK(e.first->alloc(G0 * e.second));
-    {
-        std::vector<hml_em_many_rec> recs(G0);
-        for (uint64_t i = 0; i < G0; ++i) {
-            hml_em_many_rec& r = recs[i];
-            const uint64_t BK = (uint64_t)g.B * K, CK = (uint64_t)g.n_chunks * K;
-            r.floats = b.floats.as<float>() + i * g.nfloats;
-            r.mdl = b.mdl.as<hml_model>() + i;
-            r.par = b.par.as<hml_vit_par>() + i;
-            r.A = b.A.as<double>() + i * KK; r.pi = b.pi.as<double>() + i * K;
-            r.match = b.match.as<uint8_t>() + i * g.n_chunks;
-            r.heads = b.heads.as<uint32_t>() + i * g.n_chunks;
-            r.cnt = b.cnt.as<uint32_t>() + 2 * i;
-            r.words = b.words.as<unsigned long long>() + i * HML_EMM_WORDS;
-            r.lt[0] = b.lt1.as<double>() + i * g.n1; r.lt[1] = b.lt2.as<double>() + i * g.n2;
-            r.pt[0] = b.p1.as<double>() + i * g.n1 * g.ncols; r.pt[1] = b.p2.as<double>() + i * g.n2 * g.ncols;
-            r.X = g.small ? nullptr : b.X.as<double>() + i * g.B;
-            r.result = b.result.as<double>() + i * g.nresult;
-            hml_post_args& f = r.dir[0];
-            f.par = r.par; f.A = r.A; f.pi = r.pi; f.ia = c->d_ia; f.starts = c->d_starts.get();
-            f.L = g.L; f.W = g.W; f.n_chunks = g.n_chunks;
-            f.entry = b.entry.as<double>() + i * CK; f.exitv = b.exitv.as<double>() + i * CK;
-            f.rows = b.alpha.as<double>() + i * BK; f.cval = b.cval.as<double>() + i * g.B; f.ell = b.ell.as<double>() + i * g.B;
-            r.dir[1] = f;
-            r.dir[1].rows = b.beta.as<double>() + i * BK; r.dir[1].cval = nullptr; r.dir[1].ell = nullptr;   // (entry, exit, match and heads are used again)
-            hml_em_args& e = r.em;
-            e.par = r.par; e.A = r.A; e.ia = c->d_ia; e.starts = c->d_starts.get();
-            e.alpha = f.rows; e.beta = r.dir[1].rows; e.X = r.X; e.part = r.pt[0]; e.first = b.first.as<double>() + i * K;
-        }
-        HIPCHK(hipMemcpyAsync(b.recs.get(), recs.data(), G0 * sizeof(hml_em_many_rec), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));   // (the records leave this frame)
-    }
-
-    // the members: their floats, the last two trace entries, and who still runs
-    std::vector<float> mv(mean_var, mean_var + R * 2u * P), tA(A, A + R * (uint64_t)KK), tpi(pi, pi + R * (uint64_t)K);
-    std::vector<double> prev(R, 0.0), cur(R, 0.0);
-    std::vector<uint64_t> n_steps(R, 0), n_kept(R, 0);
-    std::vector<int> why(R, HML_EM_MAX_STEPS);
-    std::vector<uint64_t> active(R), next;
-    for (uint64_t r = 0; r < R; ++r) active[r] = r;
-    if (trace) std::fill(trace, trace + R * (max_steps + 1u), std::numeric_limits<double>::quiet_NaN());
-    std::vector<float> h_floats(G0 * g.nfloats);
-    std::vector<double> h_result(G0 * g.nresult);
-    em_many_stats st;
-    uint64_t esteps = 0, first_groups = 0;
-    for (uint64_t k = 0; !active.empty(); ++k, ++esteps) {
-        next.clear();
-        const uint64_t G = std::min<uint64_t>(G0, active.size());
-        if (k == 0) first_groups = (active.size() + G - 1u) / G;
-        for (uint64_t off = 0; off < active.size(); off += G) {
-            const uint32_t n = (uint32_t)std::min<uint64_t>(G, active.size() - off);
-            for (uint32_t i = 0; i < n; ++i) {
-                const uint64_t r = active[off + i];
-                float* const f = h_floats.data() + i * g.nfloats;
-                std::copy(mv.begin() + r * 2u * P, mv.begin() + (r + 1u) * 2u * P, f);
-                std::copy(tA.begin() + r * KK, tA.begin() + (r + 1u) * KK, f + 2 * P);
-                std::copy(tpi.begin() + r * K, tpi.begin() + (r + 1u) * K, f + 2 * P + KK);
-            }
-            if (int r = em_many_estep(c, g, b, n, h_floats.data(), h_result.data(), st)) return r;
-            for (uint32_t i = 0; i < n; ++i) {
-                const uint64_t r = active[off + i];
-                hml_em_counts cnt;
-                uint64_t walked = 0;
-                em_many_counts(g, h_result.data() + i * g.nresult, cnt, &walked);
-                st.walked += walked;
-                float* const rmv = mv.data() + r * 2u * P;
-                float* const rA = tA.data() + r * KK;
-                float* const rpi = tpi.data() + r * K;
-                prev[r] = cur[r];
-                cur[r] = hml_em_objective(K, P, use_prior, q0.pr, cnt.loglik, rmv, rA, rpi);
-                if (trace) trace[r * (max_steps + 1u) + k] = cur[r];
-                if (hml_em_stops(prev[r], cur[r], k, max_steps, rel_tol, cnt.degenerate + cnt.xi_degenerate, &why[r])) { n_steps[r] = k; continue; }
-                n_kept[r] += hml_em_mstep(K, g.D, P, q0.self_trans, use_prior, q0.pr, cnt, rmv, rA, rpi);
-                next.push_back(r);
-            }
-        }
-        active.swap(next);
-    }
-    const int64_t win = hml_em_many_best(R, why.data(), cur.data());
-    if (install && win >= 0)
-        if (int r = hml_set_parameters(c, mv.data() + (uint64_t)win * 2u * P, tA.data() + (uint64_t)win * KK, tpi.data() + (uint64_t)win * K)) return r;
-    if (steps) std::copy(n_steps.begin(), n_steps.end(), steps);
-    if (reason) std::copy(why.begin(), why.end(), reason);
-    if (kept) std::copy(n_kept.begin(), n_kept.end(), kept);
-    if (fit_mean_var) std::copy(mv.begin(), mv.end(), fit_mean_var);
-    if (fit_A) std::copy(tA.begin(), tA.end(), fit_A);
-    if (fit_pi) std::copy(tpi.begin(), tpi.end(), fit_pi);
-    if (objective) std::copy(cur.begin(), cur.end(), objective);
-    if (best) *best = win;
-    c->em_many.computed = true;
-    c->em_many.members = R; c->em_many.groups = first_groups; c->em_many.group_size = G0; c->em_many.esteps = esteps; c->em_many.launch_sets = st.launch_sets;
-    c->em_many.stale_fwd = st.stale[0]; c->em_many.stale_bwd = st.stale[1]; c->em_many.rounds_run = st.rounds; c->em_many.walked = st.walked;
-    return 0;
-}
-
-int hml_em_starts(hml_ctx* c, uint64_t R, uint64_t seed, double spread, float* mean_var, float* A, float* pi) {
-    NEED_MODEL();
-    if (R < 1u || R > HML_EM_MANY_MAX_R) return set_err(HML_ERR_ARG, "hml_em_starts: the number of members must be 1 ... " + std::to_string(HML_EM_MANY_MAX_R));
-    if (!mean_var) return set_err(HML_ERR_ARG, "null argument");
-    em_params q;
-    if (int r = em_fetch(c, q)) return r;
-    if (!hml_em_many_starts(c->K, q.P, R, seed, spread, q.mv.data(), q.A.data(), q.pi.data(), mean_var, A, pi))
-        return set_err(HML_ERR_ARG, "hml_em_starts: spread must be finite and positive");
-    return 0;
-}
-
-int hml_em_many_info(hml_ctx* c, uint64_t* members, uint64_t* groups, uint64_t* group_size, uint64_t* esteps, uint64_t* launch_sets, uint64_t* stale_fwd,
-                     uint64_t* stale_bwd, uint64_t* rounds, uint64_t* serial_chunks) {
-    if (!c) return set_err(HML_ERR_ARG, "null context");
-    if (!c->em_many.computed) return set_err(HML_ERR_ARG, "hml_em_many_info: nothing was computed yet");
-    if (members) *members = c->em_many.members;
-    if (groups) *groups = c->em_many.groups;
-    if (group_size) *group_size = c->em_many.group_size;
-    if (esteps) *esteps = c->em_many.esteps;
-    if (launch_sets) *launch_sets = c->em_many.launch_sets;
-    if (stale_fwd) *stale_fwd = c->em_many.stale_fwd;
-    if (stale_bwd) *stale_bwd = c->em_many.stale_bwd;
-    if (rounds) *rounds = c->em_many.rounds_run;
-    if (serial_chunks) *serial_chunks = c->em_many.walked;
-    return 0;
-}
-
-int hml_set_em_batch_bytes(hml_ctx* c, uint64_t bytes) {
-    if (!c) return set_err(HML_ERR_ARG, "null context");
-    c->em_many.batch_bytes = bytes;
-    return 0;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------- pairwise read-outs (hml_k_pairs.h)
-// Breakpoint and region posteriors under the current parameters: exact functions of the rows alpha and beta a smoothing pass
-// leaves behind.  The chain is only read; device memory is local to a call, as the smoothing's is.
-#include "hml_k_pairs.h"   // (launched from this object alone; it brings hml_pairs_ref.h)
-
-struct pairs_result {
-    post_result post;   // alpha and beta (c_b, the calls and their confidences are released)
-    DevBuf col, p, r;   // [2 K + 1][B] words: the terms, then their inclusive prefix sums; p[B]; r[B][K] for the probe alone
-    uint64_t bad = 0;
-    uint32_t B = 0;
-};
-
-template <int KM>
-static void pairs_launch_terms(hml_ctx* c, const hml_post_args& a, size_t lds, uint32_t B, const double* alpha, const double* beta, unsigned long long* col, double* p,
-                               double* r, unsigned long long* n_bad) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_pair_terms<KM>), dim3((B + 63u) / 64u), dim3(64), lds, c->stream, a, alpha, beta, col, p, r, n_bad);
-}
-
-// a smoothing pass, then the terms per block; the prefix sums only if asked (the probe reads the terms themselves)
-static int pairs_compute(hml_ctx* c, bool want_r, bool scan, pairs_result& out) {
-    post_tables t;
-    if (int r = post_compute(c, false, out.post, t)) return r;
-    out.post.cval.free(); out.post.conf.free(); out.post.q.free();
-    const int K = c->K;
-    const uint32_t B = out.post.B;
-    const int rows = 2 * K + 1;
-    DevBuf b_bad;
-    HIPCHK(out.col.alloc((uint64_t)rows * B * sizeof(unsigned long long)));
-    HIPCHK(out.p.alloc((uint64_t)B * sizeof(double)));
-    if (want_r) HIPCHK(out.r.alloc((uint64_t)B * K * sizeof(double)));
-    HIPCHK(b_bad.alloc(sizeof(unsigned long long)));
-    HIPCHK(hipMemsetAsync(b_bad.get(), 0, sizeof(unsigned long long), c->stream));
-    hml_post_args a;
-    a.par = t.par.as<hml_vit_par>(); a.A = t.A.as<double>(); a.pi = t.pi.as<double>();
-    a.ia = c->d_ia; a.starts = c->d_starts.get();
-    a.L = 0; a.W = 0; a.n_chunks = 0; a.entry = nullptr; a.exitv = nullptr; a.rows = nullptr; a.cval = nullptr; a.ell = nullptr;
-    EM_BY_K(K, pairs_launch_terms, c, a, ((size_t)K * K + K) * sizeof(double), B, out.post.alpha.as<double>(), out.post.beta.as<double>(), out.col.as<unsigned long long>(),
-            out.p.as<double>(), out.r.as<double>(), b_bad.as<unsigned long long>());
-    KLAUNCH_CHECK();
-    unsigned long long n_bad = 0;
-    HIPCHK(hipMemcpyAsync(&n_bad, b_bad.get(), sizeof n_bad, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));   // (the tables go with this frame)
-    if (scan)
-        if (int r = scan_rows<unsigned long long, unsigned long long, false>(c->stream, out.col.as<unsigned long long>(), B, rows, out.col.as<unsigned long long>())) return r;
-    out.bad = n_bad;
-    out.B = B;
-    return 0;
-}
-
-extern "C" {
-
-int hml_posterior_breaks(hml_ctx* c, double min_prob, uint64_t* n, uint32_t* pos, double* prob, double* expected_breaks, uint64_t* pair_degenerate) {
-    NEED_MODEL();
-    if (!n) return set_err(HML_ERR_ARG, "null argument");
-    if (min_prob != min_prob) return set_err(HML_ERR_ARG, "hml_posterior_breaks: min_prob is not a number");
-    pairs_result pr;
-    if (int r = pairs_compute(c, false, true, pr)) return r;
-    const uint32_t B = pr.B;
-    if (B > 0x7fffffffu) return set_err(HML_ERR_ARG, "hml_posterior_breaks: more than 2^31 - 1 blocks: the list's counts are 32-bit");
-    const uint32_t n_chunks = (uint32_t)(((uint64_t)B + 255u) / 256u);
-    DevBuf b_cnt, b_pos, b_prob;
-    HIPCHK(b_cnt.alloc(((uint64_t)n_chunks + 1) * sizeof(int32_t)));
-    int32_t* const d_cnt = b_cnt.as<int32_t>();
-    HIPCHK(hipMemsetAsync(d_cnt + n_chunks, 0, sizeof(int32_t), c->stream));
-    hipLaunchKernelGGL(hml_k_pair_break_count, dim3(n_chunks), dim3(256), 0, c->stream, pr.p.as<double>(), B, min_prob, d_cnt);
-    hipLaunchKernelGGL(hml_k_scan_chunks<int32_t>, dim3(1), dim3(1024), 0, c->stream, d_cnt, n_chunks + 1u);   // d_cnt[n_chunks] = total
-    KLAUNCH_CHECK();
-    int32_t M = 0;
-    unsigned long long units = 0;
-    HIPCHK(hipMemcpyAsync(&M, d_cnt + n_chunks, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(&units, pr.col.as<unsigned long long>() + (B - 1u), sizeof units, hipMemcpyDeviceToHost, c->stream));   // N[B - 1]
-    HIPCHK(hipStreamSynchronize(c->stream));
-    *n = (uint64_t)M;
-    if (expected_breaks) *expected_breaks = (double)units * (1.0 / 4294967296.0);
-    if (pair_degenerate) *pair_degenerate = pr.bad;
-    if (!pos || M == 0) return 0;
-    HIPCHK(b_pos.alloc((uint64_t)M * sizeof(uint32_t)));
-    HIPCHK(b_prob.alloc((uint64_t)M * sizeof(double)));
-    hipLaunchKernelGGL(hml_k_pair_break_scatter, dim3(n_chunks), dim3(256), 0, c->stream, pr.p.as<double>(), c->d_starts.get(), B, min_prob, d_cnt, b_pos.as<uint32_t>(),
-                       b_prob.as<double>());
-    KLAUNCH_CHECK();
-    HIPCHK(hipMemcpyAsync(pos, b_pos.get(), (uint64_t)M * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    if (prob) HIPCHK(hipMemcpyAsync(prob, b_prob.get(), (uint64_t)M * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-int hml_posterior_regions(hml_ctx* c, uint64_t n, const uint32_t* start, const uint32_t* end, double* whole, double* whole_state, double* expected_breaks, double* share,
-                          uint64_t* raw, uint64_t* pair_degenerate) {
-    NEED_MODEL();
-    if (n && (!start || !end)) return set_err(HML_ERR_ARG, "null argument");
-    for (uint64_t i = 0; i < n; ++i)
-        if (!hml_pairs_region_ok(start[i], end[i], c->T)) {
-            char buf[160];
-            snprintf(buf, sizeof buf, "hml_posterior_regions: region %llu is [%u, %u): it must hold a position and end at or before T = %llu", (unsigned long long)i, start[i],
-                     end[i], (unsigned long long)c->T);
-            return set_err(HML_ERR_ARG, buf);
-        }
-    pairs_result pr;
-    if (int r = pairs_compute(c, false, true, pr)) return r;
-    if (pair_degenerate) *pair_degenerate = pr.bad;
-    if (n == 0) return 0;
-    const int K = c->K;
-    const uint64_t nk = n * (uint64_t)K, nraw = n * (uint64_t)(2 * K + 1);
-    DevBuf b_st, b_en, b_whole, b_ws, b_eb, b_share, b_raw;
-    HIPCHK(b_st.alloc(n * sizeof(uint32_t)));
-    HIPCHK(b_en.alloc(n * sizeof(uint32_t)));
-    HIPCHK(b_whole.alloc(n * sizeof(double)));
-    HIPCHK(b_ws.alloc(nk * sizeof(double)));
-    HIPCHK(b_eb.alloc(n * sizeof(double)));
-    HIPCHK(b_share.alloc(nk * sizeof(double)));
-    HIPCHK(b_raw.alloc(nraw * sizeof(unsigned long long)));
-    HIPCHK(hipMemcpyAsync(b_st.get(), start, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(b_en.get(), end, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    hml_pair_regions_out o;
-    o.whole = b_whole.as<double>(); o.whole_state = b_ws.as<double>(); o.expected_breaks = b_eb.as<double>(); o.share = b_share.as<double>();
-    o.raw = b_raw.as<unsigned long long>();
-    hipLaunchKernelGGL(hml_k_pair_regions, dim3(grid_for(n, 256, 1, 4096)), dim3(256), 0, c->stream, c->d_starts.get(), pr.B, K, pr.post.alpha.as<double>(),
-                       pr.post.beta.as<double>(), pr.col.as<unsigned long long>(), b_st.as<uint32_t>(), b_en.as<uint32_t>(), n, o);
-    KLAUNCH_CHECK();
-    if (whole) HIPCHK(hipMemcpyAsync(whole, b_whole.get(), n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (whole_state) HIPCHK(hipMemcpyAsync(whole_state, b_ws.get(), nk * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (expected_breaks) HIPCHK(hipMemcpyAsync(expected_breaks, b_eb.get(), n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (share) HIPCHK(hipMemcpyAsync(share, b_share.get(), nk * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (raw) HIPCHK(hipMemcpyAsync(raw, b_raw.get(), nraw * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));   // (the scratch goes with this frame)
-    return 0;
-}
-
-int hml_posterior_pair_terms(hml_ctx* c, double* p, double* r, uint64_t* pfx, uint64_t* cost, uint64_t* mass) {
-    NEED_MODEL();
-    pairs_result pr;
-    if (int rc = pairs_compute(c, r != nullptr, false, pr)) return rc;
-    const int K = c->K;
-    const uint64_t B = pr.B;
-    std::vector<uint64_t> cols;
-    if (cost || mass) cols.resize((uint64_t)(2 * K + 1) * B);
-    if (p) HIPCHK(hipMemcpyAsync(p, pr.p.get(), B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (r) HIPCHK(hipMemcpyAsync(r, pr.r.get(), B * K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (pfx) HIPCHK(hipMemcpyAsync(pfx, pr.col.get(), B * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if (!cols.empty()) HIPCHK(hipMemcpyAsync(cols.data(), pr.col.get(), cols.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    for (uint64_t b = 0; b < B && !cols.empty(); ++b)   // the columns, by block
-        for (int j = 0; j < K; ++j) {
-            if (cost) cost[b * K + j] = cols[(uint64_t)(1 + j) * B + b];
-            if (mass) mass[b * K + j] = cols[(uint64_t)(1 + K + j) * B + b];
-        }
-    return 0;
 }
 
 }  // extern "C"
