@@ -496,25 +496,84 @@ __device__ __forceinline__ bool hml_fwd_step(const hml_fwd_ctx<K>& cx, float (&a
     return false;
 }
 
+// s_waitcnt vmcnt(0) - every vector-memory operation of the wavefront issued so far has completed - with the other
+// counters left alone.  The instruction's 16-bit immediate on gfx9 / CDNA: vmcnt in bits 3:0 and 15:14 (six bits),
+// expcnt in bits 6:4, lgkmcnt in bits 11:8; a field at its maximum waits for nothing.
+#define HML_WAITCNT_FIELDS(vm, exp, lgkm) ((((vm) & 0xfu) | (((vm) >> 4) << 14)) | ((exp) << 4) | ((lgkm) << 8))
+__device__ __forceinline__ void hml_wait_vector_memory() { __builtin_amdgcn_s_waitcnt(HML_WAITCNT_FIELDS(0u, 7u, 15u)); }
+static_assert(HML_WAITCNT_FIELDS(0u, 7u, 15u) == 0x0f70u && HML_WAITCNT_FIELDS(63u, 7u, 15u) == 0xcf7fu, "s_waitcnt immediate");
+
+// largest number of states whose full batches are addressed by plane (hml_fwd_run; DESIGN 6e: measured per number of states)
+#define HML_FWD_PLANES_MAX_K HML_A_REGISTERS_MAX_K
+
+// the loads of a full batch (hml_fwd_run): BATCH K consecutive planes from byte offset `plane` on, the lane's column at
+// byte offset lane_off.  WITH_G: the rescale factors too, through the same planes.
+template <int K, int BATCH, bool WITH_G>
+__device__ __forceinline__ void hml_fwd_load_planes(const float* __restrict__ em, const float* __restrict__ gsc, uint64_t plane,
+                                                    uint64_t pstride, uint32_t lane_off, float (&e)[BATCH][K], float (&g)[BATCH][K]) {
+#pragma unroll
+    for (int i = 0; i < BATCH; ++i) {
+#pragma unroll
+        for (int s = 0; s < K; ++s) {
+            e[i][s] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(em) + plane + lane_off);
+            g[i][s] = WITH_G ? *reinterpret_cast<const float*>(reinterpret_cast<const char*>(gsc) + plane + lane_off) : 1.0f;
+            plane += pstride;
+        }
+    }
+}
+
 // Runs the recursion over blocks [b0, b1) in batches so that the (recursion-independent) loads of the
 // emission terms are in flight together instead of one cache round trip per step.
+//
+// A FULL batch is addressed by plane (up to HML_FWD_PLANES_MAX_K states).  Element (block, state) lies in plane
+// (block % L) K + state at column block / L (hml_bk): the BATCH blocks of a batch that stays inside its chunk's column
+// are BATCH K CONSECUTIVE planes at ONE column.  The form is taken when, in every lane still in the loop (the vote), the
+// batch is full (b + BATCH <= b1), stays in one column, and starts at the same row of its chunk - the lanes hold chunks
+// of one geometry, so they agree unless a warm-up window is clipped at block 0.  Then: one address per lane and batch,
+// one wave-uniform stride from plane to plane, the loads back to back without a predicate or a 64-bit hml_bk each, the
+// rows stored through the same planes.  Same loads in the same order, same arithmetic, same stores.  Everything else -
+// the tail of a chunk, a clipped window, a warm-up that is no multiple of the batch, chunks shorter than a batch -
+// takes the general form.  The steps are ONE copy of code behind either form of the loads; the general form ends in a
+// wait for its loads, so that at the join the compiler knows how many loads of a full batch are outstanding and lets
+// step i wait for the first (i + 1) K of them only (DESIGN 6e has the figures and what the general form pays).
 template <int K, bool STORE>
 __device__ __forceinline__ void hml_fwd_run(const hml_fwd_ctx<K>& cx, float (&alpha)[K], const float* __restrict__ em,
                                             const float* __restrict__ gsc, float* __restrict__ rows,
                                             float* __restrict__ aprobe, uint32_t b0, uint32_t b1, uint32_t& nfb,
                                             const hml_layout lay) {
     constexpr int BATCH = (K <= 6) ? 4 : 2;
+    constexpr bool PLANES = K <= HML_FWD_PLANES_MAX_K;
+    const uint32_t Lm = (1u << lay.lshift) - 1u;
+    const uint64_t pstride = (uint64_t)lay.cstride * sizeof(float);   // bytes from one (row, state) plane to the next
     for (uint32_t b = b0; b < b1; b += BATCH) {
         float e[BATCH][K], g[BATCH][K];
+        bool planes = false;            // wave-uniform: this batch is full in every lane still in the loop
+        uint64_t first_plane = 0;       // byte offset of plane (b % L) K (wave-uniform where `planes`)
+        uint32_t lane_off = 0;          // byte offset of the lane's column
+        if constexpr (PLANES) {
+            const uint32_t r0 = b & Lm, col = b >> lay.lshift;
+            const uint32_t r0u = (uint32_t)__builtin_amdgcn_readfirstlane((int)r0);
+            // (col < 2^30: the column's byte offset fits 32 bits)
+            const bool full = (b1 - b >= (uint32_t)BATCH) && (r0 + (uint32_t)BATCH <= Lm + 1u) && (r0 == r0u) && (col < (1u << 30));
+            planes = __builtin_amdgcn_ballot_w64(!full) == 0ull;
+            first_plane = (uint64_t)(r0u * (uint32_t)K) * pstride;
+            lane_off = col << 2;
+        }
+        if (PLANES && planes) {
+            if (STORE && cx.self && gsc) hml_fwd_load_planes<K, BATCH, true>(em, gsc, first_plane, pstride, lane_off, e, g);
+            else hml_fwd_load_planes<K, BATCH, false>(em, gsc, first_plane, pstride, lane_off, e, g);
+        } else {
 #pragma unroll
-        for (int i = 0; i < BATCH; ++i) {
-            const uint32_t bi = b + (uint32_t)i;
-            const bool ok = bi < b1;
+            for (int i = 0; i < BATCH; ++i) {
+                const uint32_t bi = b + (uint32_t)i;
+                const bool ok = bi < b1;
 #pragma unroll
-            for (int s = 0; s < K; ++s) {
-                e[i][s] = ok ? em[hml_bk(lay, bi, K, s)] : 0.0f;
-                g[i][s] = (STORE && ok && cx.self && gsc) ? gsc[hml_bk(lay, bi, K, s)] : 1.0f;   // (no plane: the rows stay unscaled)
+                for (int s = 0; s < K; ++s) {
+                    e[i][s] = ok ? em[hml_bk(lay, bi, K, s)] : 0.0f;
+                    g[i][s] = (STORE && ok && cx.self && gsc) ? gsc[hml_bk(lay, bi, K, s)] : 1.0f;   // (no plane: the rows stay unscaled)
+                }
             }
+            if constexpr (PLANES) hml_wait_vector_memory();
         }
 #pragma unroll
         for (int i = 0; i < BATCH; ++i) {
@@ -524,10 +583,20 @@ __device__ __forceinline__ void hml_fwd_run(const hml_fwd_ctx<K>& cx, float (&al
                 if (STORE) {
                     if (fb) nfb++;
                     const uint32_t t = bi + 1u;
+                    if (PLANES && planes) {
+                        uint64_t plane = first_plane + (uint64_t)(i * K) * pstride;
 #pragma unroll
-                    for (int s = 0; s < K; ++s) {
-                        rows[hml_bk(lay, bi, K, s)] = (cx.self && t < cx.B) ? alpha[s] * g[i][s] : alpha[s];
-                        if (aprobe) aprobe[(uint64_t)t * K + s] = alpha[s];
+                        for (int s = 0; s < K; ++s) {
+                            *reinterpret_cast<float*>(reinterpret_cast<char*>(rows) + plane + lane_off) = (cx.self && t < cx.B) ? alpha[s] * g[i][s] : alpha[s];
+                            plane += pstride;
+                            if (aprobe) aprobe[(uint64_t)t * K + s] = alpha[s];
+                        }
+                    } else {
+#pragma unroll
+                        for (int s = 0; s < K; ++s) {
+                            rows[hml_bk(lay, bi, K, s)] = (cx.self && t < cx.B) ? alpha[s] * g[i][s] : alpha[s];
+                            if (aprobe) aprobe[(uint64_t)t * K + s] = alpha[s];
+                        }
                     }
                 }
             }

@@ -1,4 +1,5 @@
-"""Time plain sweeps (no event brackets) of the bench workload: python tools/time_sweeps.py [workload] [sweeps]"""
+"""Time plain sweeps (no event brackets) of the bench workload: python tools/time_sweeps.py [workload] [sweeps] [states]
+(states: a model of that many states on the workload's trace instead of the workload's own number)"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench, hammlet_amd
@@ -8,7 +9,8 @@ T, K, levels, sigma, dwell, data_seed = bench.WORKLOADS[wl]
 x = hammlet_amd.synth_depth(T, depth=dwell, ln_sigma=sigma, seed=data_seed, nthreads=8) if levels is None else hammlet_amd.synth_gauss(T, K, levels, sigma, dwell, data_seed, nthreads=8)
 ch = hammlet_amd.Chain(device=0, seed=1)
 ch.load(x)
-ch.set_model(K, ch.autoprior(0.2, 0.9))
+KM = int(sys.argv[3]) if len(sys.argv) > 3 else K
+ch.set_model(KM, ch.autoprior(0.2, 0.9))
 ch.sample_prior()
 ch.set_recording(marginals=False)
 ch.iterate("F", 40, 0); ch.sync()
