@@ -12,12 +12,12 @@
 #ifndef HAMMLET_FIT_HPP
 #define HAMMLET_FIT_HPP
 
-#include <cstdio>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "../hml.h"
+#include "TextFile.hpp"
 
 namespace hammlet {
 
@@ -119,16 +119,15 @@ public:
     void writeStartsFile(const std::string& fn, const ManyResult& m) const {
         int D = 1, P = 0, K = 0;
         shape(&D, &P, &K);
-        FILE* out = fopen(fn.c_str(), "w");
-        if (!out) throw std::runtime_error("Cannot write to file " + fn + "!");
+        TextFile out(fn);
         for (size_t r = 0; r < m.members.size(); ++r) {
             const Result& f = m.members[r];
-            fprintf(out, "%llu\t%.17g\t%llu\t%s\t%llu", (unsigned long long)r, m.objective[r], (unsigned long long)f.steps, reasonName(f.reason), (unsigned long long)f.kept);
-            for (int p = 0; p < P; ++p) fprintf(out, "\t%.9g", (double)m.fitted.meanVar[r * 2 * P + 2 * p]);
-            for (int p = 0; p < P; ++p) fprintf(out, "\t%.9g", (double)m.fitted.meanVar[r * 2 * P + 2 * p + 1]);
-            fprintf(out, (int64_t)r == m.best ? "\t*\n" : "\n");
+            out.printf("%llu\t%.17g\t%llu\t%s\t%llu", (unsigned long long)r, m.objective[r], (unsigned long long)f.steps, reasonName(f.reason), (unsigned long long)f.kept);
+            for (int p = 0; p < P; ++p) out.printf("\t%.9g", (double)m.fitted.meanVar[r * 2 * P + 2 * p]);
+            for (int p = 0; p < P; ++p) out.printf("\t%.9g", (double)m.fitted.meanVar[r * 2 * P + 2 * p + 1]);
+            out.printf((int64_t)r == m.best ? "\t*\n" : "\n");
         }
-        if (fclose(out) != 0) throw std::runtime_error("Cannot write to file " + fn + "!");
+        out.close();
     }
 
     // the fit's trace and the context's parameters as they are now
@@ -138,24 +137,23 @@ public:
         std::vector<float> mv(2 * (size_t)P), A((size_t)K * K), pi(K);
         check(hml_get_theta(mCtx, mv.data()));
         check(hml_get_transitions(mCtx, A.data(), pi.data()));
-        FILE* out = fopen(fn.c_str(), "w");
-        if (!out) throw std::runtime_error("Cannot write to file " + fn + "!");
-        for (size_t k = 0; k < r.trace.size(); ++k) fprintf(out, "%llu\t%.17g\n", (unsigned long long)k, r.trace[k]);
-        fprintf(out, "reason\t%s\nkept\t%llu\n", reasonName(r.reason), (unsigned long long)r.kept);
-        fprintf(out, "means");
-        for (int p = 0; p < P; ++p) fprintf(out, "\t%.9g", (double)mv[2 * p]);
-        fprintf(out, "\nvariances");
-        for (int p = 0; p < P; ++p) fprintf(out, "\t%.9g", (double)mv[2 * p + 1]);
-        fprintf(out, "\n");
+        TextFile out(fn);
+        for (size_t k = 0; k < r.trace.size(); ++k) out.printf("%llu\t%.17g\n", (unsigned long long)k, r.trace[k]);
+        out.printf("reason\t%s\nkept\t%llu\n", reasonName(r.reason), (unsigned long long)r.kept);
+        out.printf("means");
+        for (int p = 0; p < P; ++p) out.printf("\t%.9g", (double)mv[2 * p]);
+        out.printf("\nvariances");
+        for (int p = 0; p < P; ++p) out.printf("\t%.9g", (double)mv[2 * p + 1]);
+        out.printf("\n");
         for (int i = 0; i < K; ++i) {
-            fprintf(out, "A");
-            for (int j = 0; j < K; ++j) fprintf(out, "\t%.9g", (double)A[(size_t)i * K + j]);
-            fprintf(out, "\n");
+            out.printf("A");
+            for (int j = 0; j < K; ++j) out.printf("\t%.9g", (double)A[(size_t)i * K + j]);
+            out.printf("\n");
         }
-        fprintf(out, "pi");
-        for (int j = 0; j < K; ++j) fprintf(out, "\t%.9g", (double)pi[j]);
-        fprintf(out, "\n");
-        if (fclose(out) != 0) throw std::runtime_error("Cannot write to file " + fn + "!");
+        out.printf("pi");
+        for (int j = 0; j < K; ++j) out.printf("\t%.9g", (double)pi[j]);
+        out.printf("\n");
+        out.close();
     }
 };
 

@@ -10,12 +10,12 @@
 #ifndef HAMMLET_HISTORY_HPP
 #define HAMMLET_HISTORY_HPP
 
-#include <cstdio>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "../hml.h"
+#include "TextFile.hpp"
 
 namespace hammlet {
 
@@ -42,42 +42,36 @@ public:
 
     // PREFIXhistorySUFFIX of the chains, in order
     static void writeFile(const std::string& fn, const std::vector<hml_ctx*>& ctxs) {
-        FILE* out = fopen(fn.c_str(), "w");
-        if (!out) throw std::runtime_error("Cannot write to file " + fn + "!");
-        try {
-            for (int j = 0; j < HML_HISTORY_COLS; ++j) fprintf(out, "%s%s", j ? "\t" : "", hml_history_column(j));
-            fprintf(out, "\n");
-            for (hml_ctx* ctx : ctxs) {
-                const std::vector<double> r = History(ctx).rows();
-                for (size_t i = 0; i + HML_HISTORY_COLS <= r.size(); i += HML_HISTORY_COLS) {
-                    for (int j = 0; j < HML_HISTORY_COLS; ++j) {
-                        if (wholeNumberColumn(j)) fprintf(out, "%s%lld", j ? "\t" : "", (long long)r[i + (size_t)j]);
-                        else fprintf(out, "%s%.17g", j ? "\t" : "", r[i + (size_t)j]);
-                    }
-                    fprintf(out, "\n");
+        TextFile out(fn);
+        for (int j = 0; j < HML_HISTORY_COLS; ++j) out.printf("%s%s", j ? "\t" : "", hml_history_column(j));
+        out.printf("\n");
+        for (hml_ctx* ctx : ctxs) {
+            const std::vector<double> r = History(ctx).rows();
+            for (size_t i = 0; i + HML_HISTORY_COLS <= r.size(); i += HML_HISTORY_COLS) {
+                for (int j = 0; j < HML_HISTORY_COLS; ++j) {
+                    if (wholeNumberColumn(j)) out.printf("%s%lld", j ? "\t" : "", (long long)r[i + (size_t)j]);
+                    else out.printf("%s%.17g", j ? "\t" : "", r[i + (size_t)j]);
                 }
+                out.printf("\n");
             }
-        } catch (...) { fclose(out); throw; }
-        if (fclose(out) != 0) throw std::runtime_error("Cannot write to file " + fn + "!");
+        }
+        out.close();
     }
 
     // PREFIXhistorysummarySUFFIX of the chains: the rows with sweep <= skipSweeps are left out
     static void writeSummaryFile(const std::string& fn, const std::vector<hml_ctx*>& ctxs, uint64_t skipSweeps) {
-        FILE* out = fopen(fn.c_str(), "w");
-        if (!out) throw std::runtime_error("Cannot write to file " + fn + "!");
-        try {
-            const struct { const char* name; int col; } what[4] = {{"loglik", HML_HISTORY_LOGLIK}, {"logpost", HML_HISTORY_LOGPOST}, {"segments", 6}, {"blocks", 7}};
-            const int n = (int)ctxs.size();
-            std::vector<double> mean((size_t)n), sd((size_t)n);
-            for (const auto& w : what) {
-                double rhat = 0, ess = 0;
-                uint64_t used = 0, bad = 0;
-                check(hml_history_summary(ctxs.data(), n, w.col, skipSweeps, &rhat, &ess, mean.data(), sd.data(), &used, &bad));
-                fprintf(out, "%s\tall\t%.9g\t%.9g\t%llu\t%llu\n", w.name, rhat, ess, (unsigned long long)used, (unsigned long long)bad);
-                for (int k = 0; k < n; ++k) fprintf(out, "%s\t%d\t%.17g\t%.17g\n", w.name, k, mean[(size_t)k], sd[(size_t)k]);
-            }
-        } catch (...) { fclose(out); throw; }
-        if (fclose(out) != 0) throw std::runtime_error("Cannot write to file " + fn + "!");
+        TextFile out(fn);
+        const struct { const char* name; int col; } what[4] = {{"loglik", HML_HISTORY_LOGLIK}, {"logpost", HML_HISTORY_LOGPOST}, {"segments", 6}, {"blocks", 7}};
+        const int n = (int)ctxs.size();
+        std::vector<double> mean((size_t)n), sd((size_t)n);
+        for (const auto& w : what) {
+            double rhat = 0, ess = 0;
+            uint64_t used = 0, bad = 0;
+            check(hml_history_summary(ctxs.data(), n, w.col, skipSweeps, &rhat, &ess, mean.data(), sd.data(), &used, &bad));
+            out.printf("%s\tall\t%.9g\t%.9g\t%llu\t%llu\n", w.name, rhat, ess, (unsigned long long)used, (unsigned long long)bad);
+            for (int k = 0; k < n; ++k) out.printf("%s\t%d\t%.17g\t%.17g\n", w.name, k, mean[(size_t)k], sd[(size_t)k]);
+        }
+        out.close();
     }
 };
 

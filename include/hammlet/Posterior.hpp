@@ -14,12 +14,12 @@
 #ifndef HAMMLET_POSTERIOR_HPP
 #define HAMMLET_POSTERIOR_HPP
 
-#include <cstdio>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "../hml.h"
+#include "TextFile.hpp"
 
 namespace hammlet {
 
@@ -109,33 +109,30 @@ public:
         uint64_t degenerate = 0;
         const double l = loglik(&degenerate);
         const Runs r = runs();
-        FILE* out = fopen(fn.c_str(), "w");
-        if (!out) throw std::runtime_error("Cannot write to file " + fn + "!");
-        fprintf(out, "%.17g\t%llu\n", l, (unsigned long long)degenerate);
-        for (size_t i = 0; i < r.length.size(); ++i) fprintf(out, "%llu\t%d\t%.17g\n", (unsigned long long)r.length[i], (int)r.state[i], r.confidence[i]);
-        if (fclose(out) != 0) throw std::runtime_error("Cannot write to file " + fn + "!");
+        TextFile out(fn);
+        out.printf("%.17g\t%llu\n", l, (unsigned long long)degenerate);
+        for (size_t i = 0; i < r.length.size(); ++i) out.printf("%llu\t%d\t%.17g\n", (unsigned long long)r.length[i], (int)r.state[i], r.confidence[i]);
+        out.close();
     }
 
     void writeBreaksFile(const std::string& fn, double minProb) const {
         const Breaks b = breaks(minProb);
-        FILE* out = fopen(fn.c_str(), "w");
-        if (!out) throw std::runtime_error("Cannot write to file " + fn + "!");
-        fprintf(out, "%.17g\t%llu\t%.17g\n", b.expectedBreaks, (unsigned long long)b.pairDegenerate, minProb);
-        for (size_t i = 0; i < b.position.size(); ++i) fprintf(out, "%u\t%.17g\n", b.position[i], b.probability[i]);
-        if (fclose(out) != 0) throw std::runtime_error("Cannot write to file " + fn + "!");
+        TextFile out(fn);
+        out.printf("%.17g\t%llu\t%.17g\n", b.expectedBreaks, (unsigned long long)b.pairDegenerate, minProb);
+        for (size_t i = 0; i < b.position.size(); ++i) out.printf("%u\t%.17g\n", b.position[i], b.probability[i]);
+        out.close();
     }
 
     void writeRegionsFile(const std::string& fn, const std::vector<uint32_t>& start, const std::vector<uint32_t>& end, const std::vector<std::string>& label, int K) const {
         const Regions r = regions(start, end, K);
-        FILE* out = fopen(fn.c_str(), "w");
-        if (!out) throw std::runtime_error("Cannot write to file " + fn + "!");
+        TextFile out(fn);
         for (size_t i = 0; i < start.size(); ++i) {
-            fprintf(out, "%u\t%u\t%.17g\t%.17g", start[i], end[i], r.whole[i], r.expectedBreaks[i]);
-            for (int j = 0; j < K; ++j) fprintf(out, "\t%.17g", r.wholeState[i * (size_t)K + j]);
-            for (int j = 0; j < K; ++j) fprintf(out, "\t%.17g", r.share[i * (size_t)K + j]);
-            fprintf(out, "\t%s\n", i < label.size() ? label[i].c_str() : "");
+            out.printf("%u\t%u\t%.17g\t%.17g", start[i], end[i], r.whole[i], r.expectedBreaks[i]);
+            for (int j = 0; j < K; ++j) out.printf("\t%.17g", r.wholeState[i * (size_t)K + j]);
+            for (int j = 0; j < K; ++j) out.printf("\t%.17g", r.share[i * (size_t)K + j]);
+            out.printf("\t%s\n", i < label.size() ? label[i].c_str() : "");
         }
-        if (fclose(out) != 0) throw std::runtime_error("Cannot write to file " + fn + "!");
+        out.close();
     }
 };
 

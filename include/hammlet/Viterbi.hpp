@@ -7,12 +7,12 @@
 #ifndef HAMMLET_VITERBI_HPP
 #define HAMMLET_VITERBI_HPP
 
-#include <cstdio>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "../hml.h"
+#include "TextFile.hpp"
 
 namespace hammlet {
 
@@ -61,11 +61,10 @@ public:
 
     void writeFile(const std::string& fn) const {
         const Runs r = runs();
-        FILE* out = fopen(fn.c_str(), "w");
-        if (!out) throw std::runtime_error("Cannot write to file " + fn + "!");
-        if (!r.state.empty() && r.state[0] != 0) fprintf(out, "0\t0\n");
-        for (size_t i = 0; i < r.length.size(); ++i) fprintf(out, "%llu\t%d\n", (unsigned long long)r.length[i], (int)r.state[i]);
-        if (fclose(out) != 0) throw std::runtime_error("Cannot write to file " + fn + "!");
+        TextFile out(fn);
+        if (!r.state.empty() && r.state[0] != 0) out.printf("0\t0\n");
+        for (size_t i = 0; i < r.length.size(); ++i) out.printf("%llu\t%d\n", (unsigned long long)r.length[i], (int)r.state[i]);
+        out.close();
     }
 };
 

@@ -621,6 +621,7 @@ template <> inline char StateSequence<Mixture>::method() { return HML_METHOD_MIX
 #include "Viterbi.hpp"
 #include "Posterior.hpp"
 #include "Fit.hpp"
+#include "Recorded.hpp"
 
 namespace hammlet {
 

@@ -2,26 +2,20 @@
 taken before the chains are merged - against the C ABI on the same chains, and the levels file of the same run against the run
 without `-O rhat`."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import cli_util
 from tests import oracle_lib as ol
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(REPO, "hammlet_amd", "hammlet")
 T, K, SEED = 100000, 3, 4
 
 
 def run_cli(tmp, x, flags, outputs, prefix="g-", overwrite=True):
-    raw = os.path.join(tmp, "in.f32")
-    x.tofile(raw)
-    env = dict(os.environ)
-    env["HIP_VISIBLE_DEVICES"] = "0"
-    return subprocess.run([CLI, "-raw", raw, "-o", os.path.join(tmp, prefix), ".csv", "-a"] + (["-w"] if overwrite else []) + flags.split() + ["-O"] + outputs,
-                          capture_output=True, text=True, env=env)
+    """the chains of these runs share the first GPU"""
+    return cli_util.run_cli(tmp, x, flags, outputs, one_gpu=True, prefix=prefix, overwrite=overwrite)
 
 
 def api_chain(hml, x, chain=0, attach=None):

@@ -2,32 +2,20 @@
 compression): PREFIXbreakpointsSUFFIX and PREFIXconsensusSUFFIX against files written from tests/breaks_util.py on the CPU
 checker's chain."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import breaks_cases as bc
 from tests import breaks_util as bu
+from tests.cli_util import run_cli
 from tests import levels_util as lu
 from tests import oracle_lib as ol
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(REPO, "hammlet_amd", "hammlet")
 T, K, SEED = 100000, 3, 4
 SCHEME = [("F", 20, 0), ("F", 30, 2)]
 FLAGS = "-s %d -R %d -i F 20 0 F 30 2" % (K, SEED)
-
-
-def run_cli(tmp, x, flags, outputs, one_gpu=False):
-    raw = os.path.join(tmp, "in.f32")
-    x.tofile(raw)
-    env = dict(os.environ)
-    if one_gpu:
-        env["HIP_VISIBLE_DEVICES"] = "0"
-    return subprocess.run([CLI, "-raw", raw, "-o", os.path.join(tmp, "g-"), ".csv", "-a", "-w"] + flags.split() + ["-O"] + outputs,
-                          capture_output=True, text=True, env=env)
 
 
 def checker_sweeps(x, chain=0):

@@ -86,6 +86,44 @@ def test_cli_multivariate_files_equal_checker_files(P, D, T, flags):
     assert len(res["parameters"][0].splitlines()[0].split("\t")) == 2 * P
 
 
+# every name of -O, in the order the driver registers them ("mapping" is registered like the reference's and never written)
+ALL_OUTPUTS = ["marginals", "sequences", "parameters", "blocks", "compression", "mapping", "segments", "maxsegmentation", "viterbi", "posterior", "em",
+               "emstarts", "posteriorbreaks", "posteriorregions", "levels", "breakpoints", "consensus", "bands", "bandcalls", "rhat", "regions", "history",
+               "historysummary"]
+# the files of one chain, and what -chains 2 adds to them: R-hat, the relabel files of the pool and the second chain's own files
+ONE_CHAIN_FILES = ["bandcalls", "bands", "blocks", "breakpoints", "compression", "consensus", "em", "emstarts", "history", "historysummary", "levels",
+                   "marginals", "maxsegmentation", "parameters", "posterior", "posteriorbreaks", "posteriorregions", "regions", "segments", "sequences",
+                   "viterbi"]
+SECOND_CHAIN_FILES = ["rhat", "relabel"] + ["chain1." + n for n in ("blocks", "compression", "em", "emstarts", "parameters", "posterior", "posteriorbreaks",
+                                                                     "posteriorregions", "relabel", "segments", "sequences", "viterbi")]
+
+
+@pytest.mark.parametrize("chains", [1, 2])
+def test_cli_every_output_at_once(tmp_path, chains):
+    """Every output of -O in one run: the set of files written is the list above - every stem, and the infix "chainK." of every
+    file a chain has of its own -, and the same command once more, without -w, exits 1 and leaves every byte as it was.  One
+    chain cannot have R-hat (the driver refuses): that run asks for every name but that one; the two chains share one GPU.
+    -history-skip 0: the summary needs eight rows per chain, and the scheme has ten sweeps."""
+    from tests import cli_util
+    T = 20000
+    x = ol.trace(T, 3, 9)
+    tmp = str(tmp_path)
+    regions = os.path.join(tmp, "regions.txt")
+    with open(regions, "w") as f:
+        f.write("100 200 first\n5000 20000\n")
+    flags = "-s 3 -R 4 -i F 4 0 F 6 2 -bands -0.5 0.5 -regions %s -em 3 -em-starts 2 -history-skip 0 -chains %d" % (regions, chains)
+    outputs = [o for o in ALL_OUTPUTS if chains > 1 or o != "rhat"]
+    r = cli_util.run_cli(tmp, x, flags, outputs, one_gpu=True, overwrite=False, timeout=120)
+    assert r.returncode == 0, r.stderr
+    written = sorted(f for f in os.listdir(tmp) if f.startswith("g-"))
+    assert written == sorted("g-%s.csv" % n for n in ONE_CHAIN_FILES + (SECOND_CHAIN_FILES if chains > 1 else []))
+    before = {f: open(os.path.join(tmp, f), "rb").read() for f in written}
+    again = cli_util.run_cli(tmp, x, flags, outputs, one_gpu=True, overwrite=False, timeout=120)
+    assert again.returncode == 1 and "already exists! Use -w to allow overwrite!" in again.stderr
+    assert sorted(f for f in os.listdir(tmp) if f.startswith("g-")) == written
+    assert {f: open(os.path.join(tmp, f), "rb").read() for f in written} == before
+
+
 def test_cli_chains_pools_marginals_over_rccl(tmp_path):
     """`hammlet -chains 3` (extension): three independent chains (Philox sub-keys 0, 1, 2) in their own host threads, the
     recorded marginals pooled by hml_allreduce_marginals (RCCL) before PREFIXmarginalsSUFFIX is written.  Expected result

@@ -2,23 +2,15 @@
 outputs, so PREFIXviterbiSUFFIX and PREFIXposteriorSUFFIX are under the fitted parameters; PREFIXemSUFFIX holds the trace that
 Chain.em_fit gives for the chain of the same seed after the same scheme.  The shape is the baseline's config 1."""
 import os
-import subprocess
 
 import pytest
 
+from tests.cli_util import run_cli
 from tests import oracle_lib as ol
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(REPO, "hammlet_amd", "hammlet")
 T, K, SEED = 100000, 3, 1
 FLAGS = "-s %d -R %d -i F 100 1" % (K, SEED)
-
-
-def run_cli(tmp, x, flags, outputs):
-    raw = os.path.join(tmp, "in.f32")
-    x.tofile(raw)
-    return subprocess.run([CLI, "-raw", raw, "-o", os.path.join(tmp, "g-"), ".csv", "-a", "-w"] + flags.split() + ["-O"] + outputs, capture_output=True, text=True)
 
 
 def fitted_chain(hml, x, steps, use_prior):

@@ -6,7 +6,8 @@ import os
 import pytest
 
 from tests import oracle_lib as ol
-from tests.test_gpu_em_cli import FLAGS, K, SEED, run_cli
+from tests.cli_util import run_cli
+from tests.test_gpu_em_cli import FLAGS, K, SEED
 
 pytestmark = pytest.mark.gpu
 T, R, STARTS_SEED, STEPS = 30000, 5, 7, 6

@@ -8,23 +8,15 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.cli_util import CLI, run_cli
 from tests import history_util as hu
 from tests import oracle_lib as ol
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(REPO, "hammlet_amd", "hammlet")
 T, K, SEED, EVERY = 20000, 3, 4, 2
 SCHEME = [("M", 4, 0), ("F", 56, 0)]
 FLAGS = "-s %d -R %d -i M 4 0 F 56 0 -chains 2 -history-every %d" % (K, SEED, EVERY)
 ROWS = 60 // EVERY
-
-
-def run_cli(tmp, x, flags, outputs, overwrite=True):
-    raw = os.path.join(tmp, "in.f32")
-    x.tofile(raw)
-    return subprocess.run([CLI, "-raw", raw, "-o", os.path.join(tmp, "g-"), ".csv", "-a"] + (["-w"] if overwrite else []) + flags.split() + ["-O"] + outputs,
-                          capture_output=True, text=True)
 
 
 def chains_of(hml, x):

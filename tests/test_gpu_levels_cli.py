@@ -1,27 +1,15 @@
 """`hammlet -O L` (extension): PREFIXlevelsSUFFIX, the denoised trace - per segment its length and, per data dimension, the
 posterior mean and standard deviation of the emission level - against the Python API of the same chain."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests.cli_util import run_cli
 from tests import oracle_lib as ol
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(REPO, "hammlet_amd", "hammlet")
 T, K, SEED = 100000, 3, 4
-
-
-def run_cli(tmp, x, flags, outputs, one_gpu=False):
-    raw = os.path.join(tmp, "in.f32")
-    x.tofile(raw)
-    env = dict(os.environ)
-    if one_gpu:
-        env["HIP_VISIBLE_DEVICES"] = "0"
-    return subprocess.run([CLI, "-raw", raw, "-o", os.path.join(tmp, "g-"), ".csv", "-a", "-w"] + flags.split() + ["-O"] + outputs,
-                          capture_output=True, text=True, env=env)
 
 
 def read_levels(path):

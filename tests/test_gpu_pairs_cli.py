@@ -3,25 +3,17 @@ PREFIXposteriorregionsSUFFIX are written once the scheme (and a fit, with -em) h
 they hold what Chain.posterior_breaks and Chain.posterior_regions give for the chain of the same seed after the same scheme.
 The shape is the baseline's config 1."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests.cli_util import run_cli
 from tests import oracle_lib as ol
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(REPO, "hammlet_amd", "hammlet")
 T, K, SEED = 100000, 3, 1
 FLAGS = "-s %d -R %d -i F 100 1" % (K, SEED)
 REGIONS = [(0, T, "everything"), (0, 1, ""), (40000, 40500, "gene A"), (40000, 40500, "gene A again"), (99999, T, "last"), (123, 70000, "long one")]
-
-
-def run_cli(tmp, x, flags, outputs):
-    raw = os.path.join(tmp, "in.f32")
-    x.tofile(raw)
-    return subprocess.run([CLI, "-raw", raw, "-o", os.path.join(tmp, "g-"), ".csv", "-a", "-w"] + flags.split() + ["-O"] + outputs, capture_output=True, text=True)
 
 
 def regions_file(tmp):

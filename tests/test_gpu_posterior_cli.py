@@ -2,26 +2,17 @@
 length, state and confidence - what Chain.posterior() and Chain.posterior_rle() give for the chain of the same seed and chain
 number after the same scheme; with -chains 2 there is one file per chain."""
 import os
-import subprocess
 
 import pytest
 
+from tests.cli_util import run_cli
 from tests import oracle_lib as ol
 from tests import posterior_util as pu
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(REPO, "hammlet_amd", "hammlet")
 T, K, SEED = 30000, 3, 4
 SCHEME = [("M", 4, 0), ("F", 36, 0)]
 FLAGS = "-s %d -R %d -i M 4 0 F 36 0" % (K, SEED)
-
-
-def run_cli(tmp, x, flags, outputs, overwrite=True):
-    raw = os.path.join(tmp, "in.f32")
-    x.tofile(raw)
-    return subprocess.run([CLI, "-raw", raw, "-o", os.path.join(tmp, "g-"), ".csv", "-a"] + (["-w"] if overwrite else []) + flags.split() + ["-O"] + outputs,
-                          capture_output=True, text=True)
 
 
 def want_text(hml, x, chain_id):

@@ -1,27 +1,22 @@
 """`hammlet -chains N -merge-gpus` (extension): the levels, breakpoints, consensus, bands, bandcalls and rhat files of chains whose
 recordings are merged through sparse payloads (hml_recording_merge_across, shadow contexts for R-hat).  On one GPU the flag takes
 the payload path for every merge and every shadow, and the six files must be those of the run without it, byte for byte."""
-import os
 import subprocess
 
 import pytest
 
+from tests import cli_util
+from tests.cli_util import CLI
 from tests import oracle_lib as ol
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(REPO, "hammlet_amd", "hammlet")
 T, K, SEED = 100000, 3, 4
 FILES = ["levels", "breakpoints", "consensus", "bands", "bandcalls", "rhat"]
 
 
 def run_cli(tmp, x, flags, outputs, prefix):
-    raw = os.path.join(tmp, "in.f32")
-    x.tofile(raw)
-    env = dict(os.environ)
-    env["HIP_VISIBLE_DEVICES"] = "0"
-    return subprocess.run([CLI, "-raw", raw, "-o", os.path.join(tmp, prefix), ".csv", "-a", "-w"] + flags.split() + ["-O"] + outputs,
-                          capture_output=True, text=True, env=env)
+    """the chains of these runs share the first GPU"""
+    return cli_util.run_cli(tmp, x, flags, outputs, one_gpu=True, prefix=prefix)
 
 
 def test_cli_merge_gpus_writes_the_same_files_on_one_gpu(tmp_path):

@@ -15,26 +15,15 @@ import numpy as np
 import pytest
 
 from tests import bands_cases as bc
+from tests.cli_util import CLI, run_cli
 from tests import oracle_lib as ol
 from tests import regions_util as ru
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(REPO, "hammlet_amd", "hammlet")
 T, K, SEED = 50000, 3, 4
 SCHEME = [("F", 20, 0), ("F", 30, 2)]
 FLAGS = "-s %d -R %d -i F 20 0 F 30 2" % (K, SEED)
 EDGES = (-0.5, 0.5)
-
-
-def run_cli(tmp, x, flags, outputs, one_gpu=False, prefix="g-"):
-    raw = os.path.join(tmp, "in.f32")
-    x.tofile(raw)
-    env = dict(os.environ)
-    if one_gpu:
-        env["HIP_VISIBLE_DEVICES"] = "0"
-    return subprocess.run([CLI, "-raw", raw, "-o", os.path.join(tmp, prefix), ".csv", "-a", "-w"] + flags.split() + ["-O"] + outputs,
-                          capture_output=True, text=True, env=env)
 
 
 def checker_sweeps(x, chain=0):

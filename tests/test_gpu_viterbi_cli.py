@@ -2,16 +2,14 @@
 restatement for one host thread (tests/fixtures/viterbi_ref_main.cpp) decodes from the blocks, block statistics and final
 parameters of the chain of the same seed and chain number; with -chains 2 there is one file per chain."""
 import os
-import subprocess
 
 import pytest
 
+from tests.cli_util import run_cli
 from tests import oracle_lib as ol
 from tests import viterbi_util as vu
 
 pytestmark = pytest.mark.gpu
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(REPO, "hammlet_amd", "hammlet")
 T, K, SEED = 30000, 3, 4
 SCHEME = [("M", 4, 0), ("F", 36, 0)]
 FLAGS = "-s %d -R %d -i M 4 0 F 36 0" % (K, SEED)
@@ -20,13 +18,6 @@ FLAGS = "-s %d -R %d -i M 4 0 F 36 0" % (K, SEED)
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
     return vu.build_programs(tmp_path_factory.mktemp("viterbi_ref"), sanitized=False)["plain"]
-
-
-def run_cli(tmp, x, flags, outputs, overwrite=True):
-    raw = os.path.join(tmp, "in.f32")
-    x.tofile(raw)
-    return subprocess.run([CLI, "-raw", raw, "-o", os.path.join(tmp, "g-"), ".csv", "-a"] + (["-w"] if overwrite else []) + flags.split() + ["-O"] + outputs,
-                          capture_output=True, text=True)
 
 
 def want_text(hml, program, x, chain_id):

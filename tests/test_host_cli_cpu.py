@@ -67,3 +67,137 @@ def test_segments_rule_of_the_driver_on_the_reference_binarys_own_sequences(case
     r = subprocess.run([exe, os.path.join(GOLD, case, "sequences.csv")], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     assert r.stdout == open(os.path.join(GOLD, case, "segments.csv")).read()
+
+
+def test_text_file_and_mean_sd_on_the_host(tmp_path):
+    """hammlet/TextFile.hpp - what every writer of the extensions' files prints through - and meanSd / readRegions of
+    hammlet/Recorded.hpp, in a program of their own under the address and undefined-behaviour sanitizers: no device call"""
+    exe = str(tmp_path / "text_file")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-I", os.path.join(REPO, "include"), "-o", exe, os.path.join(REPO, "tests", "fixtures", "text_file_main.cpp")], check=True)
+    out = tmp_path / "out"
+    out.mkdir()
+    r = subprocess.run([exe, str(out)], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout == "ok\n", r.stdout + r.stderr
+
+
+# ---- the driver's refusals: every check that one fault reaches, raised before any device call and before any output file
+# exists.  `args` follows "-raw RAW -o PRE .csv" unless it names its own input; {tmp} is the test's directory, {regions} a good
+# regions file in it.  `values`: the float32 zeros in RAW.
+TAIL = "!\nTerminating HaMMLET. The rest is silence.\n"
+NEEDS_FB = " a model with transitions: the scheme has mixture sweeps only"
+RHAT_CHAINS = "The output rhat (R) compares the chains of one run: give -chains N with N between 2 and 64"
+EVERY = "The argument of -history-every must be a whole number of sweeps, at least 1"
+EM_STEPS = "The first argument of -em must be a whole number of steps, at most 1000000"
+EM_STARTS = "The first argument of -em-starts must be a whole number of starts, 1 to 4096"
+
+REFUSALS = [
+    # general
+    ("-a -chains 0", "Number of chains must be positive", 2000),
+    ("-a -s X 2 2", "Unknown mapping type X", 2000),
+    ("", "Manual theta priors not implemented, use -a", 2000),
+    ("-a -s C 2 2", "Input stream did not contain enough values to fill all dimensions at last position", 2001),
+    ("-a", "Cannot compute Haar breakpoint weights, vector is empty", 0),
+    ("-a -i F 10 1 M 5", "Parameters for -i, excluding \"P\", \"S\" and \"D\", must be multiples of 3", 2000),
+    # per output
+    ("-a -O R", RHAT_CHAINS, 2000),
+    ("-a -chains 65 -O R", RHAT_CHAINS, 2000),
+    ("-a -O LB", "The outputs bands (LB) and bandcalls (LC) need the edges of the bands: give them with -bands E0 [E1 ...]", 2000),
+    ("-a -O LB -bands " + " ".join(str(e) for e in range(32)), "Too many edges for -bands: at most 31", 2000),
+    ("-a -O LB -bands inf", "The edges of -bands must be finite", 2000),
+    ("-a -O LB -bands 1 1", "The edges of -bands must be strictly ascending", 2000),
+    ("-a -O LB -bands x", "Conversion failed for string \"x\"", 2000),
+    # (two dimensions reach the bound of 64 columns at 31 edges, the most -bands takes, and pass; three cross it at 21)
+    ("-a -s C 2 3 -O LB -bands " + " ".join(str(e) for e in range(21)), "Too many bands: data dimensions times (edges + 1) may not exceed 64", 1998),
+    ("-a -O LC -bands -0.5 0.5 -bandcall 1.5", "The quantile of -bandcall must lie in [0, 1]", 2000),
+    ("-a -O RG", "The output regions (RG) needs the regions: give them with -regions FILE", 2000),
+    ("-a -O PR", "The output posteriorregions (PR) needs the regions: give them with -regions FILE", 2000),
+    ("-a -O H -history-every 0", EVERY, 2000),
+    ("-a -O H -history-every 1.5", EVERY, 2000),
+    ("-a -O HS -history-skip -1", "The argument of -history-skip must be a whole number of sweeps", 2000),
+    ("-a -i M 5 1 -O PD", "The output posterior (PD) needs" + NEEDS_FB, 2000),
+    ("-a -i M 5 1 -O PB", "The outputs posteriorbreaks (PB) and posteriorregions (PR) need" + NEEDS_FB, 2000),
+    ("-a -i M 5 1 -em 3", "The fit (-em) needs" + NEEDS_FB, 2000),
+    ("-a -O EM", "The output em (EM) needs a fit: ask for one with -em STEPS [TOL]", 2000),
+    ("-a -em 1 2 3", "Too many arguments for flag -em: STEPS and, optionally, TOL", 2000),
+    ("-a -em 1.5", EM_STEPS, 2000),
+    ("-a -em 2e6", EM_STEPS, 2000),
+    ("-a -em 3 -O EMS", "The output emstarts (EMS) needs a batch: ask for one with -em-starts R [SEED [SPREAD]]", 2000),
+    ("-a -em-starts 4", "The flag -em-starts needs a fit: ask for one with -em STEPS [TOL]", 2000),
+    ("-a -em 3 -em-starts 1 2 3 4", "Too many arguments for flag -em-starts: R and, optionally, SEED and SPREAD", 2000),
+    ("-a -em 3 -em-starts 0", EM_STARTS, 2000),
+    ("-a -em 3 -em-starts 4097", EM_STARTS, 2000),
+    ("-a -em 3 -em-starts 2 -1", "The seed of -em-starts must be a whole number, 0 to 2^53", 2000),
+    ("-a -em 3 -em-starts 2 0 0", "The spread of -em-starts must be a positive number", 2000),
+    ("-a -O CS -consensus -1 0.5", "The window of -consensus must be a number of positions", 2000),
+    ("-a -O CS -consensus 16 2", "The share of -consensus must lie in [0, 1]", 2000),
+]
+
+
+def run_refusal(cli, tmp_path, args, values=2000, own_input=False):
+    import numpy as np
+    raw = str(tmp_path / "in.f32")
+    np.zeros(values, np.float32).tofile(raw)
+    regions = str(tmp_path / "regions.txt")
+    with open(regions, "w") as f:
+        f.write("0 10 a\n5 2000\n")
+    pre = str(tmp_path / "g-")
+    line = ([] if own_input else ["-raw", raw]) + ["-o", pre, ".csv"] + args.format(tmp=str(tmp_path), regions=regions).split()
+    return subprocess.run([cli] + line, capture_output=True, text=True, stdin=subprocess.DEVNULL), pre
+
+
+@pytest.mark.parametrize("args,message,values", REFUSALS, ids=[r[0] or "no -a" for r in REFUSALS])
+def test_driver_refusals(cli, tmp_path, args, message, values):
+    r, pre = run_refusal(cli, tmp_path, args, values)
+    assert r.returncode == 1
+    assert r.stderr == "\n[ERROR] " + message + TAIL
+    assert [f for f in os.listdir(str(tmp_path)) if f.startswith("g-")] == []
+
+
+def test_driver_refuses_an_unreadable_input_file(cli, tmp_path):
+    r, pre = run_refusal(cli, tmp_path, "-a -f {tmp}/missing.txt", own_input=True)
+    assert r.returncode == 1
+    assert r.stderr == "\n[ERROR] Cannot read from input file " + str(tmp_path / "missing.txt") + TAIL
+    assert [f for f in os.listdir(str(tmp_path)) if f.startswith("g-")] == []
+
+
+# the outputs the driver itself guards against overwriting (those of the reference are guarded where they are opened, once
+# a device exists): the flags that reach the guard, the file's stem, and whether it is one file per chain
+GUARDED = [
+    ("-O L", "levels", False),
+    ("-O R -chains 2", "rhat", False),
+    ("-O BP", "breakpoints", False),
+    ("-O CS", "consensus", False),
+    ("-O LB -bands 0", "bands", False),
+    ("-O LC -bands 0", "bandcalls", False),
+    ("-O RG -regions {regions}", "regions", False),
+    ("-O H", "history", False),
+    ("-O HS", "historysummary", False),
+    ("-O V", "viterbi", True),
+    ("-O PD", "posterior", True),
+    ("-O PB", "posteriorbreaks", True),
+    ("-O PR -regions {regions}", "posteriorregions", True),
+    ("-O EM -em 3", "em", True),
+    ("-O EMS -em 3 -em-starts 2", "emstarts", True),
+]
+
+
+def check_existing_file_refusal(cli, tmp_path, args, name):
+    fn = str(tmp_path / name)
+    with open(fn, "w") as f:
+        f.write("kept\n")
+    r, pre = run_refusal(cli, tmp_path, "-a " + args)
+    assert r.returncode == 1
+    assert r.stderr == "\n[ERROR] File " + fn + " already exists! Use -w to allow overwrite" + TAIL
+    assert [f for f in os.listdir(str(tmp_path)) if f.startswith("g-")] == [name] and open(fn).read() == "kept\n"
+
+
+@pytest.mark.parametrize("args,stem,per_chain", GUARDED, ids=[g[1] for g in GUARDED])
+def test_driver_refuses_an_existing_file(cli, tmp_path, args, stem, per_chain):
+    check_existing_file_refusal(cli, tmp_path, args, "g-%s.csv" % stem)
+
+
+@pytest.mark.parametrize("args,stem", [g[:2] for g in GUARDED if g[2]], ids=[g[1] for g in GUARDED if g[2]])
+def test_driver_refuses_an_existing_file_of_the_second_chain(cli, tmp_path, args, stem):
+    """-chains 2, and only the second chain's file is there: the infix and the loop over the chains"""
+    check_existing_file_refusal(cli, tmp_path, args + " -chains 2", "g-chain1.%s.csv" % stem)
