@@ -159,6 +159,9 @@ SIGNATURES = {
     "hml_debug_eval": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, C.c_uint64, C.c_uint64]),
     "hml_device_memory_live": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "hml_debug_fail_allocation": (C.c_int, [C.c_int64]),
+    "hml_debug_guard_allocations": (C.c_int, [C.c_uint64, C.c_int]),
+    "hml_debug_check_guards": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
+    "hml_debug_guard_selftest": (C.c_int, []),
     "hml_synth_depth": (C.c_int, [_P, _P, C.c_uint64, C.c_double, C.c_double, C.c_uint64, C.c_int]),
     "hml_synth_gauss": (C.c_int, [_P, _P, C.c_uint64, C.c_int, _P, C.c_float, C.c_double, C.c_uint64, C.c_int]),
 }
@@ -274,6 +277,31 @@ def debug_fail_allocation(nth):
     """Test hook: the nth device allocation from now (1: the next) fails once, as if out of memory; 0 turns it off.
     Returns the number of allocations made since the hook was last set."""
     return load_library().hml_debug_fail_allocation(nth)
+
+
+GUARD_TAG = "hml-guard:"   # HML_GUARD_TAG: what a damaged guard's line on stderr starts with
+
+
+def debug_guard_allocations(guard_bytes, poison=False):
+    """Test mode: from the next device allocation on, guard bands of guard_bytes (rounded up to a multiple of 256) on both
+    sides of every allocation and, with poison, a body of 0xFF bytes; 0 turns it off."""
+    _check(load_library().hml_debug_guard_allocations(int(guard_bytes), 1 if poison else 0))
+
+
+def debug_check_guards(reset=True):
+    """Waits for the device and checks the guards of every registered allocation.  Returns a dict: damaged (allocations with a
+    damaged guard since the last reset, at a check or when freed) and, of the first of them, ordinal (among the allocations
+    since the mode was armed), bytes, side ("front" / "back") and offset (of the first damaged byte in that guard)."""
+    n, o, b, s, at = C.c_uint64(), C.c_int64(), C.c_uint64(), C.c_int(), C.c_uint64()
+    _check(load_library().hml_debug_check_guards(1 if reset else 0, C.byref(n), C.byref(o), C.byref(b), C.byref(s), C.byref(at)))
+    if not n.value:
+        return {"damaged": 0}
+    return {"damaged": n.value, "ordinal": o.value, "bytes": b.value, "side": "back" if s.value else "front", "offset": at.value}
+
+
+def debug_guard_selftest():
+    """The mode's own proof that it detects (hml_debug_guard_selftest): raises HmlError if it does not, or without a GPU."""
+    _check(load_library().hml_debug_guard_selftest())
 
 
 class Chain:

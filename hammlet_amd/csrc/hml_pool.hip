@@ -182,8 +182,7 @@ struct hml_pool {
     ncclComm_t comm = nullptr;
     int device = 0, rank = 0, n_ranks = 1;
     hipStream_t stream = nullptr;
-    int32_t* d_payload = nullptr;
-    int32_t* d_handshake = nullptr;
+    DevArr<int32_t> d_payload, d_handshake;   // freed with the communicator (DevBuf, hml_host_common.hpp)
     uint64_t capacity = 0;       // int32 elements
     double last_ms = 0;
     uint64_t last_bytes = 0;
@@ -215,7 +214,7 @@ int hml_pool_create(hml_pool** out, int device, int rank, int n_ranks, const voi
     memcpy(&u, id, sizeof u);
     ncclResult_t rc = rccl().CommInitRank(&p->comm, n_ranks, u, rank);
     if (rc != ncclSuccess) { delete p; return set_err(HML_ERR_HIP, std::string("ncclCommInitRank: ") + rccl().GetErrorString(rc)); }
-    if (hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess || hipMalloc(&p->d_handshake, 16 * sizeof(int32_t)) != hipSuccess) {
+    if (hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess || p->d_handshake.alloc(16) != hipSuccess) {
         (void)hipGetLastError();
         if (p->stream) (void)hipStreamDestroy(p->stream);
         rccl().CommDestroy(p->comm);
@@ -232,8 +231,8 @@ void hml_pool_destroy(hml_pool* p) {
     hipSetDevice(p->device);
     if (p->stream) hipStreamSynchronize(p->stream);
     if (p->comm) rccl().CommDestroy(p->comm);
-    if (p->d_payload) hipFree(p->d_payload);
-    if (p->d_handshake) hipFree(p->d_handshake);
+    p->d_payload.free();
+    p->d_handshake.free();
     if (p->stream) hipStreamDestroy(p->stream);
     delete p;
 }
@@ -290,9 +289,9 @@ int hml_pool_marginals(hml_pool* p, hml_ctx* c, int32_t* perm_out) {
     const bool lists = p->form == 2 || (p->form == 0 && slot * (uint64_t)p->n_ranks * 8u <= n);
     const uint64_t need = lists ? slot * (uint64_t)p->n_ranks : n;
     if (p->capacity < need) {
-        if (p->d_payload) (void)hipFree(p->d_payload);
-        p->d_payload = nullptr; p->capacity = 0;
-        if (hipMalloc(&p->d_payload, need * sizeof(int32_t)) != hipSuccess) { (void)hipGetLastError(); rc = set_err(HML_ERR_HIP, "out of device memory for the pooling payload"); }
+        p->d_payload.free();
+        p->capacity = 0;
+        if (p->d_payload.alloc(need) != hipSuccess) { (void)hipGetLastError(); rc = set_err(HML_ERR_HIP, "out of device memory for the pooling payload"); }
         else p->capacity = need;
     }
     EventPair ev;
@@ -392,26 +391,27 @@ int hml_allreduce_marginals_perm(hml_ctx* const* ctxs, int n, int32_t* perms) {
     const bool one_device = by_dev.size() == 1;
     if (!one_device) { if (int r = need_rccl()) return r; }
     std::vector<int> devs;
-    std::vector<int32_t*> bufs;
+    std::vector<DevArr<int32_t>> bufs(by_dev.size());   // one per device, freed on every path out
     int rc = 0;
-    auto cleanup = [&]() { for (size_t k = 0; k < bufs.size(); ++k) { hipSetDevice(devs[k]); hipFree(bufs[k]); } };
+    auto cleanup = [&]() { for (size_t k = 0; k < devs.size(); ++k) { hipSetDevice(devs[k]); bufs[k].free(); } };
     for (auto& kv : by_dev) {
         HIPCHK(hipSetDevice(kv.first));
-        int32_t *acc = nullptr, *tmp = nullptr;
-        if (hipMalloc(&acc, cnt * sizeof(int32_t)) != hipSuccess) { cleanup(); return set_err(HML_ERR_HIP, "out of device memory for the pooling payload"); }
-        devs.push_back(kv.first); bufs.push_back(acc);
+        DevArr<int32_t>& acc = bufs[devs.size()];
+        DevArr<int32_t> tmp;
+        if (acc.alloc(cnt) != hipSuccess) { (void)hipGetLastError(); cleanup(); return set_err(HML_ERR_HIP, "out of device memory for the pooling payload"); }
+        devs.push_back(kv.first);
         for (size_t j = 0; j < kv.second.size() && !rc; ++j) {
             hml_ctx* c = ctxs[kv.second[j]];
             int32_t* const perm_j = perms ? perms + (size_t)kv.second[j] * K : nullptr;
             if (j == 0) { rc = export_payload(c, acc, perm_j); continue; }
-            if (!tmp && hipMalloc(&tmp, cnt * sizeof(int32_t)) != hipSuccess) { rc = set_err(HML_ERR_HIP, "out of device memory for the pooling payload"); break; }
+            if (!tmp && tmp.alloc(cnt) != hipSuccess) { (void)hipGetLastError(); rc = set_err(HML_ERR_HIP, "out of device memory for the pooling payload"); break; }
             rc = export_payload(c, tmp, perm_j);
             if (!rc) {
                 hipLaunchKernelGGL(hml_k_pool_add, dim3(grid_for(cnt, 256, 1 << 16)), dim3(256), 0, c->stream, acc, tmp, cnt);
                 if (hipStreamSynchronize(c->stream) != hipSuccess) rc = set_err(HML_ERR_HIP, "pooling kernel failed");
             }
         }
-        if (tmp) hipFree(tmp);
+        tmp.free();
         if (rc) { cleanup(); return rc; }
     }
     const int nd = (int)devs.size();

@@ -31,11 +31,11 @@ struct hml_text {
     uint64_t chunk = 0;                 // staging capacity in bytes
     char* h_in[2] = {nullptr, nullptr}; // pinned staging buffers
     hml_text_meta* h_meta = nullptr;    // pinned, 2 entries
-    uint8_t* d_text[2] = {nullptr, nullptr};
-    float* d_vals[2] = {nullptr, nullptr};
-    hml_text_meta* d_meta = nullptr;    // 2 entries
-    hml_text_irr* d_irr[2] = {nullptr, nullptr};
-    uint32_t *d_tile_count = nullptr, *d_tile_base = nullptr;
+    DevArr<uint8_t> d_text[2];          // device memory: freed with the reader (DevBuf, hml_host_common.hpp)
+    DevArr<float> d_vals[2];
+    DevArr<hml_text_meta> d_meta;       // 2 entries
+    DevArr<hml_text_irr> d_irr[2];
+    DevArr<uint32_t> d_tile_count, d_tile_base;
     hipEvent_t done[2] = {nullptr, nullptr};
     bool in_flight[2] = {false, false};
     uint64_t sub_len[2] = {0, 0};       // bytes of the submitted chunk in each slot
@@ -71,15 +71,15 @@ bool hml_text_host_extract(const char* b, const char* e, Vec& out) {
 void hml_text_free(hml_text* p) {
     for (int j = 0; j < 2; ++j) {
         if (p->h_in[j]) hipHostFree(p->h_in[j]);
-        if (p->d_text[j]) hipFree(p->d_text[j]);
-        if (p->d_vals[j]) hipFree(p->d_vals[j]);
-        if (p->d_irr[j]) hipFree(p->d_irr[j]);
+        p->d_text[j].free();
+        p->d_vals[j].free();
+        p->d_irr[j].free();
         if (p->done[j]) hipEventDestroy(p->done[j]);
     }
     if (p->h_meta) hipHostFree(p->h_meta);
-    if (p->d_meta) hipFree(p->d_meta);
-    if (p->d_tile_count) hipFree(p->d_tile_count);
-    if (p->d_tile_base) hipFree(p->d_tile_base);
+    p->d_meta.free();
+    p->d_tile_count.free();
+    p->d_tile_base.free();
     if (p->stream) hipStreamDestroy(p->stream);
 }
 
@@ -195,14 +195,14 @@ int hml_text_open(hml_text** out, int device, uint64_t chunk_bytes) {
     int rc = [&]() -> int {
         HIPCHK(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
         HIPCHK(hipHostMalloc(&p->h_meta, 2 * sizeof(hml_text_meta), hipHostMallocDefault));
-        HIPCHK(hipMalloc(&p->d_meta, 2 * sizeof(hml_text_meta)));
-        HIPCHK(hipMalloc(&p->d_tile_count, tiles * sizeof(uint32_t)));
-        HIPCHK(hipMalloc(&p->d_tile_base, tiles * sizeof(uint32_t)));
+        HIPCHK(p->d_meta.alloc(2));
+        HIPCHK(p->d_tile_count.alloc(tiles));
+        HIPCHK(p->d_tile_base.alloc(tiles));
         for (int j = 0; j < 2; ++j) {
             HIPCHK(hipHostMalloc(&p->h_in[j], chunk_bytes, hipHostMallocDefault));
-            HIPCHK(hipMalloc(&p->d_text[j], (tiles + 1) * HML_TEXT_TILE));
-            HIPCHK(hipMalloc(&p->d_vals[j], (chunk_bytes / 2 + 1) * sizeof(float)));
-            HIPCHK(hipMalloc(&p->d_irr[j], HML_TEXT_IRR_CAP * sizeof(hml_text_irr)));
+            HIPCHK(p->d_text[j].alloc((tiles + 1) * HML_TEXT_TILE));
+            HIPCHK(p->d_vals[j].alloc(chunk_bytes / 2 + 1));
+            HIPCHK(p->d_irr[j].alloc(HML_TEXT_IRR_CAP));
             HIPCHK(hipEventCreateWithFlags(&p->done[j], hipEventDisableTiming));
         }
         return 0;

@@ -788,14 +788,40 @@ int hml_profile_get(hml_ctx* ctx, const char* name, double* total_ms, uint64_t* 
 int hml_debug_eval(int device, int fn, const float* a, const float* b_or_null, float* out, uint64_t n, uint64_t seed);
 
 /* Device memory the library's contexts and read-outs hold at this moment, over the whole process: bytes and number of
- * allocations.  Both are 0 once every context is destroyed (and without a GPU).  The pooling object (hml_pool_create) and the
- * text reader keep their own and are not counted. */
+ * allocations.  Both are 0 once every context, pooling object (hml_pool_create) and text reader is destroyed (and without a
+ * GPU). */
 int hml_device_memory_live(uint64_t* bytes, uint64_t* allocations);
 
 /* Test hook for the out-of-memory paths: the `nth` device allocation from now (1: the next) fails once with
  * hipErrorOutOfMemory - the call that made it returns HML_ERR_HIP - without the runtime being asked, then the hook is off again;
  * 0 turns it off.  Returns the number of allocations made since the hook was last set.  Process-wide, like the totals above. */
 int hml_debug_fail_allocation(int64_t nth);
+
+/* Test mode for stores outside an array and reads of memory nobody wrote.  From the next allocation on
+ * every device allocation of the library is guard + bytes + guard: both guards hold a fixed byte pattern, and with `poison`
+ * the body is filled with 0xFF bytes (NaN as float or double, -1 or the maximum as an integer) before the allocation is
+ * handed out.  `guard_bytes` is rounded up to a multiple of 256; 0 turns the mode off (allocations made under it stay
+ * registered until they are freed).  Arming it restarts the count of allocations hml_debug_fail_allocation returns.
+ * HML_GUARD_BYTES / HML_POISON in the environment arm it when the library is loaded.  Off by default; needs no device. */
+int hml_debug_guard_allocations(uint64_t guard_bytes, int poison);
+
+/* Waits for the devices of the registered allocations and reads their guards back.  *damaged: allocations found with a
+ * damaged guard since the last reset, here or when they were freed (a free checks the buffer it frees).  For the first of
+ * them: its ordinal among the allocations since the mode was armed (1: the first), the bytes its owner asked for, the side
+ * (0: the guard before the body, 1: the one behind it) and the offset of the first damaged byte from that guard's start.
+ * Any output may be null.  reset != 0 empties the report.  Each damaged allocation also prints one line to stderr that starts
+ * with HML_GUARD_TAG.  Answers 0 damaged without a device. */
+#define HML_GUARD_TAG "hml-guard:"
+int hml_debug_check_guards(int reset, uint64_t* damaged, int64_t* ordinal, uint64_t* bytes, int* side, uint64_t* offset);
+
+/* Proves from the host that the mode detects: a guarded, poisoned allocation reads back as 0xFF; one byte set just behind it
+ * is reported by the check (side 1, offset 0, its size), one byte set just before it by the free of the buffer (side 0, the
+ * guard's last byte).  Touches only memory the library owns; leaves the mode and the report as they were.  HML_ERR_HIP without
+ * a device, HML_ERR_ARG with a message if the mode missed something or the report was not empty.  A test hook like the two
+ * above: it sets and restores the mode's switches and the allocation count one after the other, so it must not run while another
+ * thread allocates or frees device memory, and - like arming the mode - it makes a pending hml_debug_fail_allocation(nth) refer
+ * to another allocation: set that hook afterwards. */
+int hml_debug_guard_selftest(void);
 
 /* synthetic piecewise-constant Gaussian trace, host buffer */
 int hml_synth_gauss(float* x, int16_t* states_or_null, uint64_t T, int K, const float* mu, float sigma,

@@ -69,6 +69,28 @@ def test_memory_diagnostics_answer_without_a_gpu():
     assert (live[0] == 0) == (live[1] == 0)
 
 
+def test_guard_mode_answers_without_a_gpu():
+    """hml_debug_guard_allocations and hml_debug_check_guards need no device: arming rounds the guard, registers nothing and
+    restarts the allocation count; a check with nothing registered is clean.  The self-test needs device memory: without a
+    GPU it is an error with a message, not a crash."""
+    import torch
+    import hammlet_amd
+    hammlet_amd.debug_guard_allocations(1, poison=True)
+    try:
+        assert hammlet_amd.debug_check_guards(reset=False) == {"damaged": 0}
+        assert hammlet_amd.debug_fail_allocation(0) == 0    # nothing was allocated since the mode was armed
+    finally:
+        hammlet_amd.debug_guard_allocations(0)
+    assert hammlet_amd.debug_check_guards() == {"damaged": 0}
+    with pytest.raises(hammlet_amd.HmlError):
+        hammlet_amd.debug_guard_allocations(1 << 40)
+    if not torch.cuda.is_available():
+        with pytest.raises(hammlet_amd.HmlError) as e:
+            hammlet_amd.debug_guard_selftest()
+        assert e.value.code == 2 and "no HIP device" in str(e.value)    # HML_ERR_HIP
+        assert hammlet_amd.device_memory_live() == (0, 0)
+
+
 def test_product_never_references_the_oracle():
     """Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may touch oracle/."""
     for root in ("hammlet_amd", "include"):

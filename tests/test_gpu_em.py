@@ -2,6 +2,7 @@
 for one host thread, tests/fixtures/em_ref_main.cpp over hammlet_amd/csrc/hml_em_ref.h, which is fed the GPU's own
 block_stats(), blocks(), theta() and transitions().  Every double is compared as its 64-bit word, every float as its 32-bit
 word: there is no tolerance anywhere in this file."""
+import gc
 import numpy as np
 import pytest
 
@@ -232,6 +233,7 @@ def test_calls_keep_no_device_memory_and_survive_failed_allocations(hml):
     g = chain(hml, ol.trace(5000, 3, 3), 3, every_position=True)
     g.set_option("posterior_W", 1)      # (stale chunks: the repair kernels run too)
     mv, (A, pi) = g.theta(), g.transitions()
+    gc.collect()      # (chains that earlier tests dropped without closing go first: the totals below are this test's alone)
     before = hml.device_memory_live()
     flat = lambda r: [np.asarray(v).tobytes() for v in (r.values() if isinstance(r, dict) else r)]
     for name, call in {"expected_counts": g.expected_counts, "em_fit": lambda: g.em_fit(1)}.items():

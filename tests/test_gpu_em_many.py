@@ -3,6 +3,7 @@ Member r of a batch is set_parameters(start r) + em_fit on the same chain, word 
 compares the trace's 64-bit words, steps, reason, kept and the fitted floats' 32-bit words; for some members the restatement
 for one host thread (tests/fixtures/em_ref_main.cpp in fit mode, fed the GPU's own blocks, statistics and the start) gives the
 same.  There is no tolerance anywhere in this file."""
+import gc
 import numpy as np
 import pytest
 
@@ -293,6 +294,7 @@ def test_the_call_keeps_no_device_memory_and_survives_failed_allocations(hml):
     g = chain(hml, ol.trace(5000, 3, 3), 3, every_position=True)
     g.set_option("posterior_W", 1)      # (stale chunks: the repair kernels run too)
     starts = g.em_starts(3, 2)
+    gc.collect()      # (chains that earlier tests dropped without closing go first: the totals below are this test's alone)
     before, params = hml.device_memory_live(), parameters(g)
     flat = lambda r: [np.asarray(v).tobytes() for v in r.values()]
     call = lambda: g.em_fit_many(starts=starts, max_steps=1, install=False)

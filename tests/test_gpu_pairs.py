@@ -4,6 +4,7 @@ hammlet_amd/csrc/hml_pairs_ref.h, which is fed the GPU's own block_stats(), bloc
 is compared as its 64-bit word and every fixed-point value as an integer: p, r, pfx, cost, mass, the break list, and the
 regions' doubles and raw integers.  There is no tolerance anywhere in this file except in the consistency check with the
 E-step, which compares two different sums."""
+import gc
 import numpy as np
 import pytest
 
@@ -282,6 +283,7 @@ def test_calls_keep_no_device_memory_and_survive_failed_allocations(hml):
     g.set_option("posterior_W", 1)      # (stale chunks: the repair kernels run too)
     rng = np.random.default_rng(1)
     start, end = pz.edge_regions(g.blocks(), rng, 100)
+    gc.collect()      # (chains that earlier tests dropped without closing go first: the totals below are this test's alone)
     before = hml.device_memory_live()
     flat = lambda d: [np.asarray(v).tobytes() for v in d.values()]
     calls = {"posterior_breaks": lambda: g.posterior_breaks(0.25), "posterior_regions": lambda: g.posterior_regions(start, end, raw=True),

@@ -4,6 +4,7 @@ blocks(), theta() and transitions():
   (a) posterior_terms() equals its e, m, alpha, c and beta word for word;
   (b) posterior() equals its gamma, log-likelihood and degenerate count, posterior_rle() its runs and confidences.
 Floats are compared as their 32-bit, doubles as their 64-bit words: there is no tolerance anywhere in this file."""
+import gc
 import itertools
 import time
 
@@ -268,6 +269,7 @@ def test_twin_states(hml, program, every_position):
 def test_a_call_keeps_no_device_memory_and_survives_failed_allocations(hml):
     g = chain(hml, ol.trace(5000, 3, 3), 3, every_position=True)
     g.set_option("posterior_W", 1)      # (stale chunks: the repair kernels run too)
+    gc.collect()      # (chains that earlier tests dropped without closing go first: the totals below are this test's alone)
     before = hml.device_memory_live()
     calls = {"posterior": g.posterior, "posterior_rle": g.posterior_rle, "posterior_terms": g.posterior_terms}
     good = {}

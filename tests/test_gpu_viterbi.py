@@ -4,6 +4,7 @@ theta() and transitions():
   (a) viterbi_scores() equals its tables bit for bit;
   (b) viterbi_states(), the run-length form and score_fixed equal its decode of those tables exactly.
 Everything is an integer: there is no tolerance anywhere in this file."""
+import gc
 import itertools
 
 import numpy as np
@@ -221,6 +222,7 @@ def test_twin_states(hml, program, every_position):
 def test_a_decode_keeps_no_device_memory_and_survives_failed_allocations(hml):
     g = chain(hml, ol.trace(5000, 3, 3), 3, every_position=True)
     g.set_option("viterbi_W", 1)      # (stale chunks: the repair kernels run too)
+    gc.collect()      # (chains that earlier tests dropped without closing go first: the totals below are this test's alone)
     before = hml.device_memory_live()
     calls = {"viterbi": g.viterbi, "viterbi_states": g.viterbi_states, "viterbi_scores": g.viterbi_scores}
     good = {}
