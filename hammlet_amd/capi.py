@@ -134,6 +134,10 @@ SIGNATURES = {
     "hml_posterior_breaks": (C.c_int, [_P, C.c_double, C.POINTER(C.c_uint64), _P, _P, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "hml_posterior_regions": (C.c_int, [_P, C.c_uint64] + [_P] * 7 + [C.POINTER(C.c_uint64)]),
     "hml_posterior_pair_terms": (C.c_int, [_P] * 6),
+    "hml_posterior_sample": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_uint64] + [_P] * 5 + [C.POINTER(C.c_uint64)]),
+    "hml_posterior_sample_regions": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, _P, _P, C.c_uint32] + [_P] * 4),
+    "hml_posterior_sample_info": (C.c_int, [_P] + [C.POINTER(C.c_uint64)] * 9),
+    "hml_set_sample_batch_bytes": (C.c_int, [_P, C.c_uint64]),
     "hml_recording_payload_size": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64)]),
     "hml_recording_export": (C.c_int, [_P, C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "hml_recording_merge_payload": (C.c_int, [_P, C.c_int, _P, C.c_uint64]),
@@ -881,6 +885,54 @@ class Chain:
                    mass=np.empty((B, K), np.uint64))
         _check(self.lib.hml_posterior_pair_terms(self.h, *[out[k].ctypes.data for k in ("p", "r", "pfx", "cost", "mass")]))
         return out
+
+    # ---- sampled paths: independent draws from p(q | y, theta) under the current parameters ----
+    def posterior_sample(self, count, seed=0, first=0, paths=False, state_counts=False):
+        """dict(segments[count] uint64, score_fixed[count] int64, change_count[B] uint32, sample_degenerate, and with paths=True
+        paths[count, B] uint8, with state_counts=True state_count[B, K] uint32): draws first ... first + count - 1 of whole
+        state paths over the current blocks; draw r depends on (seed, r) alone (hml_posterior_sample)"""
+        count, B, K = int(count), self.num_blocks(), self.K
+        n = max(count, 0)
+        out = dict(segments=np.empty(n, np.uint64), score_fixed=np.empty(n, np.int64), change_count=np.empty(B, np.uint32))
+        q = np.empty((n, B), np.uint8) if paths else None
+        sc = np.empty((B, K), np.uint32) if state_counts else None
+        bad = C.c_uint64()
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        _check(self.lib.hml_posterior_sample(self.h, int(first), count, int(seed), ptr(q), ptr(out["segments"]), ptr(out["score_fixed"]), ptr(out["change_count"]),
+                                             ptr(sc), C.byref(bad)))
+        out["sample_degenerate"] = bad.value
+        if paths:
+            out["paths"] = q
+        if state_counts:
+            out["state_count"] = sc
+        return out
+
+    def posterior_sample_regions(self, start, end, count, seed=0, first=0, max_breaks=8):
+        """dict(hist[n, max_breaks + 1], whole_state[n, K] uint32, breaks_sum[n], breaks_sq[n] uint64): per region [start[r],
+        end[r]) over the draws first ... first + count - 1 the histogram of the number of breakpoints inside it (last bin: that
+        many or more), the draws with none and all of it in state j, and the sum and sum of squares of that number
+        (hml_posterior_sample_regions)"""
+        start, end = _region_positions(start, "start"), _region_positions(end, "end")
+        if start.shape != end.shape:
+            raise ValueError("start and end: two one-dimensional arrays of one length")
+        n, K, H = start.size, self.K, int(max_breaks)
+        out = dict(hist=np.zeros((n, max(H, 0) + 1), np.uint32), whole_state=np.zeros((n, K), np.uint32), breaks_sum=np.zeros(n, np.uint64),
+                   breaks_sq=np.zeros(n, np.uint64))
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        _check(self.lib.hml_posterior_sample_regions(self.h, int(first), int(count), int(seed), n, ptr(start), ptr(end), H, ptr(out["hist"]), ptr(out["whole_state"]),
+                                                     ptr(out["breaks_sum"]), ptr(out["breaks_sq"])))
+        return out
+
+    def posterior_sample_info(self):
+        """of the last posterior_sample / posterior_sample_regions: dict(draws, groups, group_size, chunks, L, W, stale_first,
+        rounds, serial_chunks) (hml_posterior_sample_info)"""
+        v = [C.c_uint64() for _ in range(9)]
+        _check(self.lib.hml_posterior_sample_info(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("draws", "groups", "group_size", "chunks", "L", "W", "stale_first", "rounds", "serial_chunks"), (x.value for x in v)))
+
+    def set_sample_batch_bytes(self, n_bytes=0):
+        """the device memory a group of posterior_sample's draws may take (0: the default) (hml_set_sample_batch_bytes)"""
+        _check(self.lib.hml_set_sample_batch_bytes(self.h, int(n_bytes)))
 
     # ---- sparse payloads of the levels, breakpoints and bands (across GPUs) -------------------
     def recording_payload_size(self, kind):

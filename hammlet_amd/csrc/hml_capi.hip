@@ -1173,6 +1173,17 @@ int hml_set_option(hml_ctx* c, const char* name, int value) {
         c->post.rounds = (uint32_t)value;
         return 0;
     }
+    // ... and the path sampler's (hml_k_sample.h)
+    if (std::string(name) == "sample_W" || std::string(name) == "sample_L") {
+        if (value < 0 || value > (1 << 20)) return set_err(HML_ERR_ARG, std::string(name) + ": a number of blocks up to 2^20, or 0 for the default");
+        (name[7] == 'W' ? c->samp.W : c->samp.L) = (uint32_t)value;
+        return 0;
+    }
+    if (std::string(name) == "sample_rounds") {
+        if (value < 0 || value > 16) return set_err(HML_ERR_ARG, "sample_rounds: 0 to 16 parallel repair rounds");
+        c->samp.rounds = (uint32_t)value;
+        return 0;
+    }
     return set_err(HML_ERR_ARG, std::string("unknown option ") + name);
 }
 

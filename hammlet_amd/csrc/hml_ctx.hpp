@@ -225,6 +225,12 @@ struct hml_ctx {
         bool computed = false;
         uint64_t members = 0, groups = 0, group_size = 0, esteps = 0, launch_sets = 0, stale_fwd = 0, stale_bwd = 0, rounds_run = 0, walked = 0;
     } em_many;
+    // Sampled paths (hml_posterior_sample; hml_k_sample.h): options "sample_W", "sample_L", "sample_rounds"; the byte budget of a
+    // group of draws (0: the default) and what the last call did (hml_posterior_sample_info).  stale[0] and walked: over all groups.
+    chunked_pass samp;
+    struct {
+        uint64_t batch_bytes = 0, draws = 0, groups = 0, group_size = 0;
+    } samp_batch;
     // Every d_* above that is not a plain pointer owns its buffer (DevBuf / DevArr, hml_host_common.hpp): deleting the context
     // frees them, whatever a call that failed half-way left allocated, and allocating one again replaces what it held.
     ~hml_ctx() { if (h_B) (void)hipHostFree(h_B); }

@@ -1,7 +1,7 @@
 // libhammlet_hip.so - exact inference under the chain's current parameters, over its current blocks (include/hml.h): the most
 // probable path (hml_viterbi*), the state posteriors and log p(y | theta) (hml_posterior*), the E-step's expected counts and
 // the fits built on them (hml_expected_counts, hml_em_*, hml_em_fit_many), and the exact breakpoint and region posteriors
-// (hml_posterior_breaks / _regions / _pair_terms).  Nothing here reads what a recorder wrote - those read-outs are
+// (hml_posterior_breaks / _regions / _pair_terms), and independent draws of whole paths (hml_posterior_sample*).  Nothing here reads what a recorder wrote - those read-outs are
 // hml_readout.hip's - and nothing runs inside a sweep: the chain is only read, every call owns its device memory for its own
 // length, and the context keeps the launch geometry and a few numbers about the last call (hml_ctx::vit, post, em_many).
 #include <limits>
@@ -16,6 +16,7 @@
 #include "hml_k_em.h"
 #include "hml_k_em_many.h"
 #include "hml_k_pairs.h"   // (it brings hml_pairs_ref.h)
+#include "hml_k_sample.h"   // (it brings hml_sample_ref.h)
 
 // ---------------------------------------------------------------------------------------- what the passes share
 // f(std::integral_constant<int, KM>()) for the number of states the kernels keep a recursion's vector for
@@ -282,37 +283,55 @@ static int post_direction(hml_ctx* c, const hml_post_args& a, int K, uint8_t* ma
     return repair_rounds(c->post.rounds, verify, rerun, finish, rep);
 }
 
-// the whole computation; the rows alpha, c and beta stay in `out` for the probe, the tables in `t` for the E-step
-static int post_compute(hml_ctx* c, bool want_gamma, post_result& out, infer_tables& t) {
+// The forward half: the tables, the rows alpha_b and c_b into `out`, l_b and the chunk scratch into `s` (the backward run uses
+// entry, exit, match and list again).  The path sampler needs no more than this.
+struct post_forward_scratch {
+    DevBuf entry, exitv, match, list, words, ell;   // words: [0] stale chunks and heads (32 bits each), [1] chunks the single lane ran, [2] degenerate blocks, [3] log-likelihood
+    uint32_t L = 0, W = 0, n_chunks = 0;
+    repair_outcome rep;
+};
+static int post_forward(hml_ctx* c, post_result& out, infer_tables& t, post_forward_scratch& s) {
     uint32_t B = 0;
     if (int r = post_begin(c, t, &B)) return r;
     const int K = c->K;
-    const uint32_t L = c->post.L ? c->post.L : HML_POST_DEFAULT_L;
-    const uint32_t W = c->post.W ? c->post.W : HML_POST_DEFAULT_W;
-    const uint32_t n_chunks = (uint32_t)(((uint64_t)B + L - 1u) / L);
-    const uint64_t n1 = ((uint64_t)B + 63u) / 64u, n2 = (n1 + 63u) / 64u;   // the first two levels of the tree
-    DevBuf b_entry, b_exit, b_match, b_list, b_words, b_ell, b_t1, b_t2;
+    s.L = c->post.L ? c->post.L : HML_POST_DEFAULT_L;
+    s.W = c->post.W ? c->post.W : HML_POST_DEFAULT_W;
+    s.n_chunks = (uint32_t)(((uint64_t)B + s.L - 1u) / s.L);
     HIPCHK(out.alpha.alloc((uint64_t)B * K * sizeof(double)));
-    HIPCHK(out.beta.alloc((uint64_t)B * K * sizeof(double)));
     HIPCHK(out.cval.alloc((uint64_t)B * sizeof(double)));
-    HIPCHK(b_ell.alloc((uint64_t)B * sizeof(double)));
-    HIPCHK(b_entry.alloc((uint64_t)n_chunks * K * sizeof(double)));
-    HIPCHK(b_exit.alloc((uint64_t)n_chunks * K * sizeof(double)));
-    HIPCHK(b_match.alloc(n_chunks));
-    HIPCHK(b_list.alloc((uint64_t)n_chunks * sizeof(uint32_t)));
-    HIPCHK(b_words.alloc(4 * sizeof(unsigned long long)));   // [0] stale chunks and heads (32 bits each), [1] chunks the single lane ran, [2] degenerate blocks, [3] log-likelihood
+    HIPCHK(s.ell.alloc((uint64_t)B * sizeof(double)));
+    HIPCHK(s.entry.alloc((uint64_t)s.n_chunks * K * sizeof(double)));
+    HIPCHK(s.exitv.alloc((uint64_t)s.n_chunks * K * sizeof(double)));
+    HIPCHK(s.match.alloc(s.n_chunks));
+    HIPCHK(s.list.alloc((uint64_t)s.n_chunks * sizeof(uint32_t)));
+    HIPCHK(s.words.alloc(4 * sizeof(unsigned long long)));
+    HIPCHK(hipMemsetAsync(s.words.get(), 0, 4 * sizeof(unsigned long long), c->stream));
+    hml_post_args a = post_args_of(c, t, s.L, s.W, s.n_chunks, s.entry.as<double>(), s.exitv.as<double>());
+    a.rows = out.alpha.as<double>(); a.cval = out.cval.as<double>(); a.ell = s.ell.as<double>();
+    out.B = B;
+    return post_direction<0>(c, a, K, s.match.as<uint8_t>(), s.list.as<uint32_t>(), s.words.as<unsigned long long>(), s.rep);
+}
+
+// the whole computation; the rows alpha, c and beta stay in `out` for the probe, the tables in `t` for the E-step
+static int post_compute(hml_ctx* c, bool want_gamma, post_result& out, infer_tables& t) {
+    post_forward_scratch s;
+    if (int r = post_forward(c, out, t, s)) return r;
+    const int K = c->K;
+    const uint32_t B = out.B, L = s.L, W = s.W, n_chunks = s.n_chunks;
+    const uint64_t n1 = ((uint64_t)B + 63u) / 64u, n2 = (n1 + 63u) / 64u;   // the first two levels of the tree
+    DevBuf b_t1, b_t2;
+    DevBuf &b_entry = s.entry, &b_exit = s.exitv, &b_match = s.match, &b_list = s.list, &b_ell = s.ell;
+    HIPCHK(out.beta.alloc((uint64_t)B * K * sizeof(double)));
     HIPCHK(b_t1.alloc(n1 * sizeof(double)));
     HIPCHK(b_t2.alloc(n2 * sizeof(double)));
     HIPCHK(out.q.alloc((uint64_t)B * sizeof(int16_t)));
     HIPCHK(out.conf.alloc((uint64_t)B * sizeof(double)));
     if (want_gamma) HIPCHK(out.gamma.alloc((uint64_t)B * K * sizeof(double)));
-    unsigned long long* const words = b_words.as<unsigned long long>();
-    HIPCHK(hipMemsetAsync(words, 0, 4 * sizeof(unsigned long long), c->stream));
+    unsigned long long* const words = s.words.as<unsigned long long>();
 
     hml_post_args a = post_args_of(c, t, L, W, n_chunks, b_entry.as<double>(), b_exit.as<double>());
     repair_outcome rep[2];
-    a.rows = out.alpha.as<double>(); a.cval = out.cval.as<double>(); a.ell = b_ell.as<double>();
-    if (int r = post_direction<0>(c, a, K, b_match.as<uint8_t>(), b_list.as<uint32_t>(), words, rep[0])) return r;
+    rep[0] = s.rep;
     a.rows = out.beta.as<double>(); a.cval = nullptr; a.ell = nullptr;   // (entry, exit, match and list are used again)
     if (int r = post_direction<1>(c, a, K, b_match.as<uint8_t>(), b_list.as<uint32_t>(), words, rep[1])) return r;
 
@@ -1014,6 +1033,244 @@ int hml_posterior_pair_terms(hml_ctx* c, double* p, double* r, uint64_t* pfx, ui
             if (cost) cost[b * K + j] = cols[(uint64_t)(1 + j) * B + b];
             if (mass) mass[b * K + j] = cols[(uint64_t)(1 + K + j) * B + b];
         }
+    return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------- sampled paths (hml_k_sample.h)
+// Independent draws of whole paths from p(q | y, theta): the forward half of a smoothing pass, then the draws in groups of as
+// many as the byte budget holds.  Every count is an integer sum that the groups add to, so no word depends on the grouping.
+// The chain is only read; device memory is local to the call.
+#define HML_SAMPLE_DEFAULT_BYTES (4ull << 30)   // of a group's device memory (hml_set_sample_batch_bytes)
+#define HML_SAMPLE_MAX_COUNT (1ull << 24)
+#define HML_SAMPLE_MAX_GROUP (1ull << 20)       // (grid dimension y of the first run: draws / 256)
+
+struct sample_request {
+    uint64_t first = 0, count = 0, seed = 0;
+    uint8_t* paths = nullptr;
+    uint64_t* segments = nullptr;
+    int64_t* score_fixed = nullptr;
+    uint32_t *change_count = nullptr, *state_count = nullptr;
+    uint64_t* sample_degenerate = nullptr;
+    uint64_t n_regions = 0;
+    const uint32_t *start = nullptr, *end = nullptr;
+    uint32_t H = 0;
+    uint32_t *hist = nullptr, *whole_state = nullptr;
+    uint64_t *breaks_sum = nullptr, *breaks_sq = nullptr;
+};
+
+static int sample_run(hml_ctx* c, const char* who, const sample_request& q) {
+    if (q.count < 1u || q.count > HML_SAMPLE_MAX_COUNT) return set_err(HML_ERR_ARG, std::string(who) + ": count must be 1 ... 2^24");
+    if (q.first > (1ull << 48) || q.first + q.count > (1ull << 48)) return set_err(HML_ERR_ARG, std::string(who) + ": first + count must not exceed 2^48");
+    const int K = c->K;
+    infer_tables t, ts;   // A and pi in double; the decode's fixed-point terms, for the scores
+    post_result post;
+    {
+        post_forward_scratch s;
+        if (int r = post_forward(c, post, t, s)) return r;
+        HIPCHK(hipStreamSynchronize(c->stream));   // (the scratch goes with this frame)
+    }
+    post.cval.free();
+    const uint32_t B = post.B;
+    const uint32_t L = c->samp.L ? c->samp.L : HML_SAMP_DEFAULT_L;
+    const uint32_t W = c->samp.W ? c->samp.W : HML_SAMP_DEFAULT_W;
+    const uint32_t n_chunks = (uint32_t)(((uint64_t)B + L - 1u) / L);
+    const bool want_regions = q.n_regions != 0;
+    const bool want_counts = q.change_count || q.state_count;
+
+    // what lives for the whole call
+    DevBuf b_guess, b_emit, b_cc, b_sc, b_st, b_en, b_hist, b_ws, b_bs, b_bq, b_words;
+    HIPCHK(b_guess.alloc(B));
+    hipLaunchKernelGGL(hml_k_samp_guess, dim3(grid_for(B, 256, 1, 16384)), dim3(256), 0, c->stream, post.alpha.as<double>(), K, B, b_guess.as<uint8_t>());
+    KLAUNCH_CHECK();
+    if (q.score_fixed) {
+        uint32_t B2 = 0;
+        if (int r = vit_begin(c, ts, &B2)) return r;
+        HIPCHK(b_emit.alloc((uint64_t)B * K * sizeof(long long)));
+        hipLaunchKernelGGL(hml_k_vit_emit_table, dim3(grid_for(B, 256, 1, 16384)), dim3(256), 0, c->stream, ts.par.as<hml_vit_par>(), c->d_ia, c->d_starts.get(), b_emit.as<long long>());
+        KLAUNCH_CHECK();
+    }
+    if (want_counts) {
+        HIPCHK(b_cc.alloc((uint64_t)B * sizeof(uint32_t)));
+        HIPCHK(hipMemsetAsync(b_cc.get(), 0, (uint64_t)B * sizeof(uint32_t), c->stream));
+        if (q.state_count) {
+            HIPCHK(b_sc.alloc((uint64_t)B * K * sizeof(uint32_t)));
+            HIPCHK(hipMemsetAsync(b_sc.get(), 0, (uint64_t)B * K * sizeof(uint32_t), c->stream));
+        }
+    }
+    const uint64_t n = q.n_regions, nh = n * (q.H + 1ull), nk = n * (uint64_t)K;
+    if (want_regions) {
+        HIPCHK(b_st.alloc(n * sizeof(uint32_t)));
+        HIPCHK(b_en.alloc(n * sizeof(uint32_t)));
+        HIPCHK(b_hist.alloc(nh * sizeof(uint32_t)));
+        HIPCHK(b_ws.alloc(nk * sizeof(uint32_t)));
+        HIPCHK(b_bs.alloc(n * sizeof(unsigned long long)));
+        HIPCHK(b_bq.alloc(n * sizeof(unsigned long long)));
+        HIPCHK(hipMemcpyAsync(b_st.get(), q.start, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(b_en.get(), q.end, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemsetAsync(b_hist.get(), 0, nh * sizeof(uint32_t), c->stream));
+        HIPCHK(hipMemsetAsync(b_ws.get(), 0, nk * sizeof(uint32_t), c->stream));
+        HIPCHK(hipMemsetAsync(b_bs.get(), 0, n * sizeof(unsigned long long), c->stream));
+        HIPCHK(hipMemsetAsync(b_bq.get(), 0, n * sizeof(unsigned long long), c->stream));
+    }
+    HIPCHK(b_words.alloc(4 * sizeof(unsigned long long)));   // [0] stale pairs and heads (32 bits each), [1] pairs the finishing lanes ran, [2] degenerate blocks
+    unsigned long long* const words = b_words.as<unsigned long long>();
+    HIPCHK(hipMemsetAsync(words, 0, 4 * sizeof(unsigned long long), c->stream));
+
+    // the group: a draw's bytes are its path (twice if the caller takes the paths: the transposed copy), the words of its chunks
+    // and its two sums; pair indices are 32-bit
+    const uint64_t draw_bytes = (uint64_t)B * (q.paths ? 2u : 1u) + (uint64_t)n_chunks * (2u + 2u * sizeof(uint32_t)) + 2u * sizeof(unsigned long long);
+    const uint64_t budget = c->samp_batch.batch_bytes ? c->samp_batch.batch_bytes : HML_SAMPLE_DEFAULT_BYTES;
+    uint64_t G0 = std::max<uint64_t>(budget / draw_bytes, 1u);
+    G0 = std::min<uint64_t>(G0, std::max<uint64_t>(0xffffffffull / n_chunks, 1u));
+    G0 = std::min<uint64_t>(std::min<uint64_t>(G0, HML_SAMPLE_MAX_GROUP), q.count);
+    const uint64_t pairs0 = G0 * n_chunks;
+    DevBuf b_path, b_out, b_entry, b_exit, b_deg, b_list, b_chg, b_score;
+    HIPCHK(b_path.alloc(G0 * B));
+    if (q.paths) HIPCHK(b_out.alloc(G0 * B));
+    HIPCHK(b_entry.alloc(pairs0));
+    HIPCHK(b_exit.alloc(pairs0));
+    HIPCHK(b_deg.alloc(pairs0 * sizeof(uint32_t)));
+    HIPCHK(b_list.alloc(pairs0 * sizeof(uint32_t)));
+    HIPCHK(b_chg.alloc(G0 * sizeof(unsigned long long)));
+    HIPCHK(b_score.alloc(G0 * sizeof(unsigned long long)));
+
+    hml_samp_args a;
+    a.alpha = post.alpha.as<double>(); a.A = t.trans.as<double>(); a.guess = b_guess.as<uint8_t>();
+    a.K = K; a.B = B; a.L = L; a.W = W; a.n_chunks = n_chunks; a.seed = q.seed;
+    a.path = b_path.as<uint8_t>(); a.entry = b_entry.as<uint8_t>(); a.exitv = b_exit.as<uint8_t>(); a.deg = b_deg.as<uint32_t>();
+    const size_t lds = (size_t)K * (K + 1) * sizeof(double);
+    std::vector<unsigned long long> h_chg(G0), h_score(G0);
+    uint64_t stale_first = 0, rounds_run = 0, n_groups = 0;
+    for (uint64_t off = 0; off < q.count; off += G0, ++n_groups) {
+        const uint32_t G = (uint32_t)std::min<uint64_t>(G0, q.count - off);
+        const uint64_t n_pairs = (uint64_t)G * n_chunks;
+        a.G = G; a.first = q.first + off;
+        HIPCHK(hipMemsetAsync(b_entry.get(), 0, n_pairs, c->stream));
+        HIPCHK(hipMemsetAsync(b_chg.get(), 0, (uint64_t)G * sizeof(unsigned long long), c->stream));
+        HIPCHK(hipMemsetAsync(b_score.get(), 0, (uint64_t)G * sizeof(unsigned long long), c->stream));
+        const dim3 grid(n_chunks, (G + HML_SAMP_LANES - 1u) / HML_SAMP_LANES);
+        by_states(K, [&](auto km) { hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_samp_first<km()>), grid, dim3(HML_SAMP_LANES), lds, c->stream, a); });
+        KLAUNCH_CHECK();
+        auto verify = [&](uint64_t* stale, uint32_t* heads) {
+            uint32_t h_cnt[2] = {0, 0};
+            if (n_chunks > 1u) {
+                HIPCHK(hipMemsetAsync(words, 0, sizeof h_cnt, c->stream));
+                hipLaunchKernelGGL(hml_k_samp_verify, dim3(grid_for(n_pairs - G, 256, 1, 4096)), dim3(256), 0, c->stream, a.entry, a.exitv, G, n_pairs, b_list.as<uint32_t>(),
+                                   (uint32_t*)words, (uint32_t*)words + 1);
+                KLAUNCH_CHECK();
+                HIPCHK(hipMemcpyAsync(h_cnt, words, sizeof h_cnt, hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(hipStreamSynchronize(c->stream));
+            }
+            *stale = h_cnt[0]; *heads = h_cnt[1];
+            return 0;
+        };
+        auto rerun = [&](uint32_t n_heads) {
+            by_states(K, [&](auto km) {
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_samp_rerun<km()>), dim3((n_heads + 63u) / 64u), dim3(64), lds, c->stream, a, b_list.as<uint32_t>(), n_heads);
+            });
+        };
+        auto finish = [&] {
+            by_states(K, [&](auto km) { hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_samp_finish<km()>), dim3((G + 63u) / 64u), dim3(64), lds, c->stream, a, words + 1); });
+        };
+        repair_outcome rep;
+        if (int r = repair_rounds(c->samp.rounds, verify, rerun, finish, rep)) return r;
+        stale_first += rep.stale_first;
+        rounds_run = std::max(rounds_run, rep.rounds);
+
+        // the paths of the group are final: what is read off them
+        hipLaunchKernelGGL(hml_k_samp_deg_sum, dim3(grid_for(n_pairs, 256, 1, 4096)), dim3(256), 0, c->stream, a.deg, n_pairs, words + 2);
+        if (q.segments || q.score_fixed)
+            hipLaunchKernelGGL(hml_k_samp_draw_stats, grid, dim3(HML_SAMP_LANES), 0, c->stream, a, q.score_fixed ? b_emit.as<long long>() : nullptr, ts.trans.as<long long>(),
+                               ts.init.as<long long>(), b_chg.as<unsigned long long>(), b_score.as<unsigned long long>());
+        if (want_counts)
+            hipLaunchKernelGGL(hml_k_samp_block_counts, dim3(grid_for(B, 1, 1, 65536)), dim3(64), 0, c->stream, a.path, K, B, G, b_cc.as<uint32_t>(), b_sc.as<uint32_t>());
+        if (want_regions) {
+            hml_samp_regions_out o;
+            o.hist = b_hist.as<uint32_t>(); o.whole_state = b_ws.as<uint32_t>(); o.breaks_sum = b_bs.as<unsigned long long>(); o.breaks_sq = b_bq.as<unsigned long long>();
+            hipLaunchKernelGGL(hml_k_samp_regions, dim3((G + 255u) / 256u, (unsigned)std::min<uint64_t>(n, 65535u)), dim3(256), 0, c->stream, a.path, c->d_starts.get(), K, B, G,
+                               b_st.as<uint32_t>(), b_en.as<uint32_t>(), n, q.H, o);
+        }
+        if (q.paths) hipLaunchKernelGGL(hml_k_samp_transpose, dim3((B + 63u) / 64u, (G + 63u) / 64u), dim3(256), 0, c->stream, a.path, B, G, b_out.as<uint8_t>());
+        KLAUNCH_CHECK();
+        if (q.paths) HIPCHK(hipMemcpyAsync(q.paths + off * B, b_out.get(), (uint64_t)G * B, hipMemcpyDeviceToHost, c->stream));
+        if (q.segments) HIPCHK(hipMemcpyAsync(h_chg.data(), b_chg.get(), (uint64_t)G * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        if (q.score_fixed) HIPCHK(hipMemcpyAsync(h_score.data(), b_score.get(), (uint64_t)G * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        for (uint32_t g = 0; g < G; ++g) {
+            if (q.segments) q.segments[off + g] = 1u + h_chg[g];
+            if (q.score_fixed) q.score_fixed[off + g] = (int64_t)h_score[g];
+        }
+    }
+    unsigned long long h_words[4];
+    HIPCHK(hipMemcpyAsync(h_words, words, sizeof h_words, hipMemcpyDeviceToHost, c->stream));
+    if (q.change_count) HIPCHK(hipMemcpyAsync(q.change_count, b_cc.get(), (uint64_t)B * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (q.state_count) HIPCHK(hipMemcpyAsync(q.state_count, b_sc.get(), (uint64_t)B * K * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (want_regions) {
+        if (q.hist) HIPCHK(hipMemcpyAsync(q.hist, b_hist.get(), nh * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        if (q.whole_state) HIPCHK(hipMemcpyAsync(q.whole_state, b_ws.get(), nk * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        if (q.breaks_sum) HIPCHK(hipMemcpyAsync(q.breaks_sum, b_bs.get(), n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        if (q.breaks_sq) HIPCHK(hipMemcpyAsync(q.breaks_sq, b_bq.get(), n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));   // (the scratch goes with this frame)
+    if (q.sample_degenerate) *q.sample_degenerate = h_words[2];
+    c->samp.done = true;
+    c->samp.chunks = n_chunks; c->samp.used_L = L; c->samp.used_W = W; c->samp.stale[0] = stale_first; c->samp.rounds_run = rounds_run; c->samp.walked = h_words[1];
+    c->samp_batch.draws = q.count; c->samp_batch.groups = n_groups; c->samp_batch.group_size = G0;
+    return 0;
+}
+
+extern "C" {
+
+int hml_posterior_sample(hml_ctx* c, uint64_t first, uint64_t count, uint64_t seed, uint8_t* paths, uint64_t* segments, int64_t* score_fixed, uint32_t* change_count,
+                         uint32_t* state_count, uint64_t* sample_degenerate) {
+    NEED_MODEL();
+    sample_request q;
+    q.first = first; q.count = count; q.seed = seed;
+    q.paths = paths; q.segments = segments; q.score_fixed = score_fixed; q.change_count = change_count; q.state_count = state_count;
+    q.sample_degenerate = sample_degenerate;
+    return sample_run(c, "hml_posterior_sample", q);
+}
+
+int hml_posterior_sample_regions(hml_ctx* c, uint64_t first, uint64_t count, uint64_t seed, uint64_t n, const uint32_t* start, const uint32_t* end, uint32_t max_breaks,
+                                 uint32_t* hist, uint32_t* whole_state, uint64_t* breaks_sum, uint64_t* breaks_sq) {
+    NEED_MODEL();
+    if (n && (!start || !end)) return set_err(HML_ERR_ARG, "null argument");
+    if (max_breaks < 1u) return set_err(HML_ERR_ARG, "hml_posterior_sample_regions: max_breaks must be at least 1");
+    for (uint64_t i = 0; i < n; ++i)
+        if (!hml_pairs_region_ok(start[i], end[i], c->T)) {
+            char buf[176];
+            snprintf(buf, sizeof buf, "hml_posterior_sample_regions: region %llu is [%u, %u): it must hold a position and end at or before T = %llu", (unsigned long long)i,
+                     start[i], end[i], (unsigned long long)c->T);
+            return set_err(HML_ERR_ARG, buf);
+        }
+    sample_request q;
+    q.first = first; q.count = count; q.seed = seed;
+    q.n_regions = n; q.start = start; q.end = end; q.H = max_breaks;
+    q.hist = hist; q.whole_state = whole_state; q.breaks_sum = breaks_sum; q.breaks_sq = breaks_sq;
+    return sample_run(c, "hml_posterior_sample_regions", q);
+}
+
+int hml_posterior_sample_info(hml_ctx* c, uint64_t* draws, uint64_t* groups, uint64_t* group_size, uint64_t* chunks, uint64_t* L, uint64_t* W, uint64_t* stale_first,
+                              uint64_t* rounds, uint64_t* serial_chunks) {
+    if (!c) return set_err(HML_ERR_ARG, "null context");
+    if (!c->samp.done) return set_err(HML_ERR_ARG, "hml_posterior_sample_info: nothing was sampled yet");
+    if (draws) *draws = c->samp_batch.draws;
+    if (groups) *groups = c->samp_batch.groups;
+    if (group_size) *group_size = c->samp_batch.group_size;
+    if (chunks) *chunks = c->samp.chunks;
+    if (L) *L = c->samp.used_L;
+    if (W) *W = c->samp.used_W;
+    if (stale_first) *stale_first = c->samp.stale[0];
+    if (rounds) *rounds = c->samp.rounds_run;
+    if (serial_chunks) *serial_chunks = c->samp.walked;
+    return 0;
+}
+
+int hml_set_sample_batch_bytes(hml_ctx* c, uint64_t bytes) {
+    if (!c) return set_err(HML_ERR_ARG, "null context");
+    c->samp_batch.batch_bytes = bytes;
     return 0;
 }
 

@@ -30,7 +30,8 @@ enum {
     HML_KIND_PI = 4,
     HML_KIND_TRANS = 5,
     HML_KIND_DATA = 6,
-    HML_KIND_HOST = 7    // draws made by the host on a chain's behalf (Trellis::sample of the C++ surface); index = call number
+    HML_KIND_HOST = 7,   // draws made by the host on a chain's behalf (Trellis::sample of the C++ surface); index = call number
+    HML_KIND_PSAMPLE = 8 // path draws under fixed parameters (hml_sample_ref.h); epoch = draw, index = block >> 1
 };
 
 typedef struct { uint32_t v[4]; } hml_u32x4;

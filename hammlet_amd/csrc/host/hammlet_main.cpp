@@ -69,6 +69,14 @@ static const char* kHelp =
     "                                 breakpoint inside, the expected number of breakpoints, per state the probability that\n"
     "                                 all of the region is in it, per state its expected share of the region, the label; exact\n"
     "                                 under the parameters of -O PD; with -chains N one file per chain (extension)\n"
+    "                    PS           posteriorsample: the R independent draws of -psample of whole state paths from the exact\n"
+    "                                 posterior p(q|y,theta) under the parameters of -O PD, one line per draw in the line format\n"
+    "                                 of the sequences file (tab-separated SIZE:STATE); with -chains N one file per chain\n"
+    "                                 (extension; needs -psample)\n"
+    "                    PSS          posteriorsamplesummary: first line R, the seed, the Viterbi score in nats and the expected\n"
+    "                                 number of breakpoints; then per draw: index, segments, score in nats; with -regions, then\n"
+    "                                 per region: start, end, the mean number of breakpoints inside it over the draws, the draws\n"
+    "                                 with 0, 1, ... 7 and with 8 or more of them, the label (extension; needs -psample)\n"
     "                    EM           em: the fit of -em - one line per step: step, objective; then the reason it stopped, the\n"
     "                                 parameters kept for want of support, and the fitted means, variances, A and pi; with\n"
     "                                 -chains N one file per chain (extension; needs -em); with -em-starts the winner's\n"
@@ -130,6 +138,9 @@ static const char* kHelp =
     "  -bandcall P                    the call of -O LC: 0 (default) the most probable band, 0 < P <= 1 the band of the\n"
     "                                 P-quantile of the recorded levels (0.5: the median) (extension)\n"
     "  -pbreak P                      the least probability of -O PB (default 0.5) (extension)\n"
+    "  -psample R [SEED]              R independent draws (1 to 2^24) of whole state paths from p(q|y,theta) under the chain's\n"
+    "                                 final (or -em fitted) parameters for -O PS and -O PSS; draw r depends on SEED (default: the\n"
+    "                                 seed of -R) and r alone (extension)\n"
     "  -regions FILE                  the regions of -O RG and -O PR, one per line: start end [label ...], positions counted from 0, the\n"
     "                                 end not included; lines that begin with # and blank lines are skipped.  Regions may\n"
     "                                 overlap, nest and repeat (extension)\n"
@@ -168,7 +179,7 @@ struct Step {
 // job wants, every file name and the refusal to overwrite.  The long flag is the file's stem: PREFIX[chainK.]nameSUFFIX.
 enum Output {
     oMarginals, oSequences, oParameters, oBlocks, oCompression, oMapping, oSegments, oMaxSegmentation, oViterbi, oPosterior, oEm, oEmStarts,
-    oPosteriorBreaks, oPosteriorRegions, oLevels, oBreakpoints, oConsensus, oBands, oBandCalls, oRhat, oRegions, oHistory, oHistorySummary, nrOutputs
+    oPosteriorBreaks, oPosteriorRegions, oPosteriorSample, oPosteriorSampleSummary, oLevels, oBreakpoints, oConsensus, oBands, oBandCalls, oRhat, oRegions, oHistory, oHistorySummary, nrOutputs
 };
 struct OutputSpec {
     Output id;
@@ -192,6 +203,8 @@ static constexpr OutputSpec kOutputs[nrOutputs] = {
     {oEmStarts, "EMS", "emstarts", true, true},
     {oPosteriorBreaks, "PB", "posteriorbreaks", true, true},
     {oPosteriorRegions, "PR", "posteriorregions", true, true},
+    {oPosteriorSample, "PS", "posteriorsample", true, true},
+    {oPosteriorSampleSummary, "PSS", "posteriorsamplesummary", true, true},
     {oLevels, "L", "levels", false, true},
     {oBreakpoints, "BP", "breakpoints", false, true},   // (B and C are the reference's blocks and compression)
     {oConsensus, "CS", "consensus", false, true},
@@ -220,6 +233,7 @@ struct Job {
     double consensusShare = 0.5;
     double bandCall = 0;             // -bandcall P
     double posteriorBreak = 0.5;     // -pbreak P (-O PB)
+    uint64_t sampleDraws = 0, sampleSeed = 0;   // -psample R [SEED] (-O PS, PSS); 0: none
     Regions regions;                 // -regions FILE (recorded when -O RG asks for them)
     vector<float> regionEdges;       // ... and their edges: those of -bands
     uint64_t historyEvery = 1;       // -history-every N (-O H, HS)
@@ -386,6 +400,10 @@ static void finishChain(const Job& job, int index, hml_ctx* ctx) {
     if (job.wants(oPosteriorBreaks)) posterior.writeBreaksFile(job.fileName(oPosteriorBreaks, index), job.posteriorBreak);
     if (job.wants(oPosteriorRegions))
         posterior.writeRegionsFile(job.fileName(oPosteriorRegions, index), job.regions.start, job.regions.end, job.regions.label, (int)job.nrStates);
+    if (job.wants(oPosteriorSample)) posterior.writeSampleFile(job.fileName(oPosteriorSample, index), job.sampleDraws, job.sampleSeed);
+    if (job.wants(oPosteriorSampleSummary))
+        posterior.writeSampleSummaryFile(job.fileName(oPosteriorSampleSummary, index), job.sampleDraws, job.sampleSeed, job.regions.start, job.regions.end, job.regions.label,
+                                         (int)job.nrStates);
 }
 
 // the chains' histories, in chain order (hammlet/History.hpp): read through the host, whichever GPUs the chains are on
@@ -751,6 +769,19 @@ static Job parseJob(Parser& args, vector<real_t>& inputValues) {
         if (job.wants(oPosteriorBreaks)) job.posteriorBreak = args.parse<double>("-pbreak", 0);
         if (job.wants(oPosteriorRegions) && !args.isSet("-regions")) throw std::runtime_error("The output posteriorregions (PR) needs the regions: give them with -regions FILE!");
     }
+    if (job.wants(oPosteriorSample) || job.wants(oPosteriorSampleSummary)) {
+        if (!anyFB)
+            throw std::runtime_error("The outputs posteriorsample (PS) and posteriorsamplesummary (PSS) need a model with transitions: the scheme has mixture sweeps only!");
+        if (!args.isSet("-psample")) throw std::runtime_error("The outputs posteriorsample (PS) and posteriorsamplesummary (PSS) need the draws: ask for them with -psample R [SEED]!");
+    }
+    if (args.isSet("-psample")) {
+        if (args.nrTokens("-psample") < 1) throw std::runtime_error("Not enough arguments for flag -psample!");
+        if (args.nrTokens("-psample") > 2) throw std::runtime_error("Too many arguments for flag -psample: R and, optionally, SEED!");
+        job.sampleDraws = wholeNumber(args.parse<double>("-psample", 0), 1, 16777216, "The first argument of -psample must be a whole number of draws, 1 to 16777216!");
+        job.sampleSeed = args.nrTokens("-psample") > 1
+                             ? wholeNumber(args.parse<double>("-psample", 1), 0, 9007199254740992.0, "The seed of -psample must be a whole number, 0 to 2^53!")
+                             : (uint64_t)job.seed;
+    }
     if (job.wants(oEm) && !args.isSet("-em")) throw std::runtime_error("The output em (EM) needs a fit: ask for one with -em STEPS [TOL]!");
     if (args.isSet("-em")) {
         if (!anyFB) throw std::runtime_error("The fit (-em) needs a model with transitions: the scheme has mixture sweeps only!");
@@ -915,6 +946,7 @@ int main(int argc, const char* argv[]) {
         args.registerFlags({"-bands"});
         args.registerFlags({"-bandcall"}, "0");
         args.registerFlags({"-pbreak"}, "0.5");
+        args.registerFlags({"-psample"});
         args.registerFlags({"-merge-gpus"});
         args.registerFlags({"-regions"});
         args.registerFlags({"-history-every"}, "1");

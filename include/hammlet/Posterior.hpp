@@ -9,6 +9,11 @@
 //                           state is at least `-pbreak P`, by ascending position (hml_posterior_breaks)
 //   PREFIXposteriorregionsSUFFIX  `-O PR`: per region of `-regions FILE`, tab-separated: start, end, whole, expected_breaks,
 //                           K whole_state, K share (%.17g), then the region's label (hml_posterior_regions)
+//   PREFIXposteriorsampleSUFFIX   `-O PS` with `-psample R [SEED]`: one line per independent draw of a whole path from
+//                           p(q | y, theta), tab-separated SIZE:STATE per run - the `sequences` file's line (hml_posterior_sample)
+//   PREFIXposteriorsamplesummarySUFFIX  `-O PSS`: "draws<TAB>seed<TAB>viterbi_score<TAB>expected_breaks", then per draw
+//                           "index<TAB>segments<TAB>score" (nats); with `-regions FILE`, then per region start, end, the mean number
+//                           of breakpoints inside it, its histogram over the draws and the label
 // A thin handle over a context that something else owns (the chain's rng_t), next to Viterbi.  Every call computes anew; the
 // chain is only read.
 #ifndef HAMMLET_POSTERIOR_HPP
@@ -45,6 +50,21 @@ public:
         uint64_t pairDegenerate = 0;
     };
     struct Info { uint64_t chunks = 0, L = 0, W = 0, staleForward = 0, staleBackward = 0, rounds = 0, serialChunks = 0; };
+    struct Sample {
+        uint64_t first = 0, blocks = 0;
+        std::vector<uint8_t> paths;          // [count][blocks], if asked for
+        std::vector<uint64_t> segments;      // [count]
+        std::vector<int64_t> scoreFixed;     // [count], units of 2^-20 nat
+        std::vector<uint32_t> changeCount;   // [blocks]
+        std::vector<uint32_t> stateCount;    // [blocks][K], if asked for
+        uint64_t degenerate = 0;
+    };
+    struct SampleRegions {
+        uint32_t maxBreaks = 0;
+        std::vector<uint32_t> hist, wholeState;      // [n][maxBreaks + 1], [n][K]
+        std::vector<uint64_t> breaksSum, breaksSq;   // [n]
+    };
+    struct SampleInfo { uint64_t draws = 0, groups = 0, groupSize = 0, chunks = 0, L = 0, W = 0, staleFirst = 0, rounds = 0, serialChunks = 0; };
 
     explicit Posterior(hml_ctx* ctx) : mCtx(ctx) {}
     // launch geometry only (0: the defaults): never part of the result
@@ -105,6 +125,55 @@ public:
         return i;
     }
 
+    // ---- sampled paths: independent draws from p(q | y, theta) (hml_posterior_sample) ----
+    // Draws first ... first + count - 1 under `seed`; draw r depends on (seed, r) alone.  With paths: the states per block,
+    // draw-major.
+    Sample sample(uint64_t first, uint64_t count, uint64_t seed, bool paths = false, bool stateCounts = false, int K = 0) const {
+        Sample s;
+        check(hml_get_num_blocks(mCtx, &s.blocks));
+        s.first = first;
+        s.segments.resize(count); s.scoreFixed.resize(count); s.changeCount.resize(s.blocks);
+        if (paths) s.paths.resize(count * s.blocks);
+        if (stateCounts) s.stateCount.resize(s.blocks * (uint64_t)K);
+        check(hml_posterior_sample(mCtx, first, count, seed, paths ? s.paths.data() : nullptr, s.segments.data(), s.scoreFixed.data(), s.changeCount.data(),
+                                   stateCounts ? s.stateCount.data() : nullptr, &s.degenerate));
+        return s;
+    }
+    // per region over the same draws: the histogram of the number of breakpoints inside it, and the draws that hold it whole
+    SampleRegions sampleRegions(const std::vector<uint32_t>& start, const std::vector<uint32_t>& end, uint64_t first, uint64_t count, uint64_t seed, uint32_t maxBreaks,
+                                int K) const {
+        if (start.size() != end.size()) throw std::runtime_error("Posterior::sampleRegions: as many starts as ends");
+        SampleRegions r;
+        const size_t n = start.size();
+        r.maxBreaks = maxBreaks;
+        r.hist.resize(n * ((size_t)maxBreaks + 1)); r.wholeState.resize(n * (size_t)K); r.breaksSum.resize(n); r.breaksSq.resize(n);
+        check(hml_posterior_sample_regions(mCtx, first, count, seed, n, start.data(), end.data(), maxBreaks, r.hist.data(), r.wholeState.data(), r.breaksSum.data(),
+                                           r.breaksSq.data()));
+        return r;
+    }
+    SampleInfo sampleInfo() const {
+        SampleInfo i;
+        check(hml_posterior_sample_info(mCtx, &i.draws, &i.groups, &i.groupSize, &i.chunks, &i.L, &i.W, &i.staleFirst, &i.rounds, &i.serialChunks));
+        return i;
+    }
+    // the run-length form of draw k of a sample with paths: adjacent blocks of equal state merged, lengths in positions
+    static void sampleRuns(const Sample& s, const std::vector<uint32_t>& starts, uint64_t k, std::vector<uint64_t>& length, std::vector<int32_t>& state) {
+        length.clear(); state.clear();
+        const uint8_t* const q = s.paths.data() + k * s.blocks;
+        for (uint64_t b = 0; b < s.blocks; ++b) {
+            const uint64_t n = starts[b + 1] - starts[b];
+            if (b > 0 && state.back() == (int32_t)q[b]) length.back() += n;
+            else { length.push_back(n); state.push_back(q[b]); }
+        }
+    }
+    // the draws of a window whose paths take at most hostBytes on the host (at least one)
+    uint64_t sampleWindow(uint64_t hostBytes) const {
+        uint64_t B = 0;
+        check(hml_get_num_blocks(mCtx, &B));
+        const uint64_t per = B + 16u;
+        return hostBytes / per > 0 ? hostBytes / per : 1u;
+    }
+
     void writeFile(const std::string& fn) const {
         uint64_t degenerate = 0;
         const double l = loglik(&degenerate);
@@ -112,6 +181,54 @@ public:
         TextFile out(fn);
         out.printf("%.17g\t%llu\n", l, (unsigned long long)degenerate);
         for (size_t i = 0; i < r.length.size(); ++i) out.printf("%llu\t%d\t%.17g\n", (unsigned long long)r.length[i], (int)r.state[i], r.confidence[i]);
+        out.close();
+    }
+
+    // `-O PS`: one line per draw, tab-separated SIZE:STATE per run of equal state - the line format of the `sequences` file.
+    // The draws are read in windows of at most hostBytes of paths.
+    void writeSampleFile(const std::string& fn, uint64_t count, uint64_t seed, uint64_t hostBytes = 256ull << 20) const {
+        uint64_t B = 0;
+        check(hml_get_num_blocks(mCtx, &B));
+        std::vector<uint32_t> starts(B + 1);
+        check(hml_get_blocks(mCtx, starts.data()));
+        const uint64_t window = sampleWindow(hostBytes);
+        std::vector<uint64_t> length;
+        std::vector<int32_t> state;
+        TextFile out(fn);
+        for (uint64_t first = 0; first < count; first += window) {
+            const uint64_t n = count - first < window ? count - first : window;
+            const Sample s = sample(first, n, seed, true);
+            for (uint64_t k = 0; k < n; ++k) {
+                sampleRuns(s, starts, k, length, state);
+                for (size_t i = 0; i < length.size(); ++i) out.printf("%s%llu:%d", i ? "\t" : "", (unsigned long long)length[i], (int)state[i]);
+                out.printf("\n");
+            }
+        }
+        out.close();
+    }
+
+    // `-O PSS`: first line "draws<TAB>seed<TAB>viterbi_score<TAB>expected_breaks" (integers, %.17g nats, %.17g), then per draw
+    // "index<TAB>segments<TAB>score" (%.17g nats); with regions, then per region "start<TAB>end<TAB>mean_breaks<TAB>hist[0 ...
+    // maxBreaks]<TAB>label", the histogram in draws (last bin: that many breakpoints or more)
+    void writeSampleSummaryFile(const std::string& fn, uint64_t count, uint64_t seed, const std::vector<uint32_t>& start, const std::vector<uint32_t>& end,
+                                const std::vector<std::string>& label, int K, uint32_t maxBreaks = 8) const {
+        uint64_t nRuns = 0;
+        double vitScore = 0;
+        check(hml_viterbi(mCtx, &nRuns, nullptr, nullptr, nullptr, &vitScore));
+        const Breaks b = breaks(2.0);   // (no boundary is listed: the expectation alone)
+        const Sample s = sample(0, count, seed);
+        TextFile out(fn);
+        out.printf("%llu\t%llu\t%.17g\t%.17g\n", (unsigned long long)count, (unsigned long long)seed, vitScore, b.expectedBreaks);
+        for (uint64_t k = 0; k < count; ++k)
+            out.printf("%llu\t%llu\t%.17g\n", (unsigned long long)k, (unsigned long long)s.segments[k], (double)s.scoreFixed[k] / 1048576.0);
+        if (!start.empty()) {
+            const SampleRegions r = sampleRegions(start, end, 0, count, seed, maxBreaks, K);
+            for (size_t i = 0; i < start.size(); ++i) {
+                out.printf("%u\t%u\t%.17g", start[i], end[i], (double)r.breaksSum[i] / (double)count);
+                for (uint32_t h = 0; h <= maxBreaks; ++h) out.printf("\t%u", r.hist[i * ((size_t)maxBreaks + 1) + h]);
+                out.printf("\t%s\n", i < label.size() ? label[i].c_str() : "");
+            }
+        }
         out.close();
     }
 

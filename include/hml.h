@@ -668,6 +668,47 @@ int hml_posterior_regions(hml_ctx* ctx, uint64_t n, const uint32_t* start /*n*/,
                           double* expected_breaks /*n*/, double* share /*n*K*/, uint64_t* raw /*n*(2K+1), may be NULL*/, uint64_t* pair_degenerate);
 int hml_posterior_pair_terms(hml_ctx* ctx, double* p /*B*/, double* r /*B*K*/, uint64_t* pfx /*B*/, uint64_t* cost /*B*K*/, uint64_t* mass /*B*K*/);
 
+/* ---- sampled paths: independent draws of whole state paths from p(q | y, theta) under the current parameters.  No counterpart
+ * in the reference (its `sequences` file holds the dependent paths of the sweeps, each under its own parameters). ----
+ * What has no closed form under a fitted model is read off such draws: the distribution of the number of breakpoints in a
+ * region, how far a breakpoint can move, whether two regions change together.  A sweep cannot serve: it redraws the parameters
+ * and yields one dependent path.  With alpha as smoothing defines it (forward rows, degenerate restarts included) and A widened
+ * exactly to double:
+ *   uniform of draw r at block b:  o = Philox4x32-10 words of hml_stream4(hml_make_key(seed, 0), HML_KIND_PSAMPLE = 8, epoch r,
+ *     index b >> 1, 0);  (hi, lo) = (o[0], o[1]) for even b, (o[2], o[3]) for odd b;  u = ((hi >> 5) 2^26 + (lo >> 6)) 2^-53.
+ *     Draw r depends on (seed, r) alone - never on count, first, the grouping or the launch geometry.
+ *   categorical rule over weights w(0 ... K - 1) in IEEE double: c_i the running sums from 0.0 in ascending i, S = c_{K-1},
+ *     t = u S; the smallest i with t < c_i, or, if there is none, the largest i with w(i) > 0.  Weight 0 is never drawn.
+ *   q_{B-1} from w = alpha_{B-1};  q_b, b = B - 2 ... 0, from w(i) = alpha_b(i) A[i][q_{b+1}].  If S is not a positive finite
+ *     number the block is degenerate for this draw - counted in sample_degenerate - and w = alpha_b is used; if that sum fails the
+ *     same test, q_b = 0.
+ *   per draw: segments = 1 + #{b >= 1: q_b != q_{b-1}};  score_fixed in the tables of hml_viterbi_scores (units of 2^-20 nat,
+ *     comparable with hml_viterbi's and never above it).
+ *   over the draws of a call: change_count[b] = #draws with q_b != q_{b-1} (0 at b = 0);  state_count[b][j] = #draws with q_b = j.
+ *   per region [start, end), ba and be as in hml_posterior_regions, n_r = #{b in (ba, be]: q_b != q_{b-1}} in draw r:
+ *     hist[h], h = 0 ... H = max_breaks, the draws with n_r = h (the last bin: n_r >= H);  whole_state[j] the draws with n_r = 0
+ *     and q_ba = j;  breaks_sum = sum_r n_r;  breaks_sq = sum_r n_r^2.
+ * hammlet_amd/csrc/hml_sample_ref.h restates all of it for one host thread; the device gives those very words.
+ * The call makes draws first ... first + count - 1; count is 1 ... 2^24 and first + count <= 2^48 (HML_ERR_ARG otherwise), so
+ * ranges of `first` split a sample over calls or processes exactly.  paths is draw-major, a byte per block.  Any output may be
+ * NULL.  A bad region is HML_ERR_ARG as in hml_posterior_regions, max_breaks = 0 too; n = 0 succeeds.  The refusals are
+ * hml_posterior's (a halted chain, no blocks, no model).  The chain is only read.  Device memory is local to a call and
+ * released before it returns: the alpha rows, and per draw of a group about B bytes (2 B with paths) plus 10 bytes per chunk;
+ * the draws run in groups of as many as fit hml_set_sample_batch_bytes (at least one), and no output word depends on the
+ * grouping.  Options "sample_W", "sample_L", "sample_rounds" (hml_set_option; ranges of the posterior_ ones) are launch geometry
+ * only.  hml_posterior_sample_info: of the last call - the draws, their groups and the size of a full one, the chunks of a draw,
+ * L, W, the (draw, chunk) pairs that were stale after the first run, the greatest number of repair rounds of a group, and the
+ * pairs the finishing lanes ran. */
+int hml_posterior_sample(hml_ctx* ctx, uint64_t first, uint64_t count, uint64_t seed, uint8_t* paths /*count*B, draw-major, may be NULL*/,
+                         uint64_t* segments /*count*/, int64_t* score_fixed /*count*/, uint32_t* change_count /*B*/, uint32_t* state_count /*B*K*/,
+                         uint64_t* sample_degenerate);
+int hml_posterior_sample_regions(hml_ctx* ctx, uint64_t first, uint64_t count, uint64_t seed, uint64_t n, const uint32_t* start /*n*/, const uint32_t* end /*n*/,
+                                 uint32_t max_breaks /*H >= 1*/, uint32_t* hist /*n*(H+1)*/, uint32_t* whole_state /*n*K*/, uint64_t* breaks_sum /*n*/,
+                                 uint64_t* breaks_sq /*n*/);
+int hml_posterior_sample_info(hml_ctx* ctx, uint64_t* draws, uint64_t* groups, uint64_t* group_size, uint64_t* chunks, uint64_t* L, uint64_t* W,
+                              uint64_t* stale_first, uint64_t* rounds, uint64_t* serial_chunks);
+int hml_set_sample_batch_bytes(hml_ctx* ctx, uint64_t bytes /*0: the default, 4 GiB*/);
+
 /* ---- sparse payloads: levels, breakpoints and bands across GPUs.  No counterpart in the reference. ----
  * The three recordings above keep a cell and a boundary bit per change of state, so what another GPU needs of one is a list:
  * the M positions with a cell and the cells there.  The PAYLOAD is one contiguous buffer in device memory, little endian,
