@@ -21,6 +21,7 @@ from tests.fuzz_util import fuzz
 from tests.readout_fuzz_util import fuzz_readouts
 from tests.test_gpu_forward_loads import SCHEME, check, set_up
 from tests.test_gpu_parity import compare_state, make_pair, run_both, setup_model
+from tests.words_util import DEVICE_NAN, HOST_NAN, same_words  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -461,21 +462,6 @@ def exact_chain(hml, T, K):
         g = te.chain(hml, ol.trace(max(T, 16), min(K, 5), 4)[:T].copy(), K, every_position=True)
     assert g.num_blocks() == T
     return g
-
-
-HOST_NAN = {64: 0xFFF8000000000000, 32: 0xFFC00000}      # the NaN an x86 operation makes (0 / 0, inf - inf): quiet, the sign set
-DEVICE_NAN = {64: 0x7FF8000000000000, 32: 0x7FC00000}    # ... and a gfx950 operation: quiet, the sign clear
-
-
-def same_words(got, want, bits=64):
-    """Words of floats against the restatement's, word for word - with one translation: where the restatement, run on the host,
-    holds exactly the NaN its processor makes, the GPU must hold exactly the NaN its own makes (a fit's objective is no number
-    on some of these tiny traces, on both sides; IEEE 754-2008, 6.3 leaves the sign of a made NaN to the processor).  Any other
-    NaN - the all-ones word of a poisoned body among them - is a difference."""
-    got, want = np.asarray(got).ravel(), np.asarray(want).ravel()
-    assert got.dtype == want.dtype == (np.uint64 if bits == 64 else np.uint32), (got.dtype, want.dtype)
-    expected = np.where(want == want.dtype.type(HOST_NAN[bits]), want.dtype.type(DEVICE_NAN[bits]), want)
-    return got.shape == want.shape and np.array_equal(got, expected)
 
 
 def same_trace(trace, want):
