@@ -1151,38 +1151,20 @@ int hml_set_option(hml_ctx* c, const char* name, int value) {
         c->tre_L = (uint32_t)value;
         return 0;
     }
-    // the Viterbi decode's launch geometry (hml_k_viterbi.h): never part of its result
-    if (std::string(name) == "viterbi_W" || std::string(name) == "viterbi_L") {
-        if (value < 0 || value > (1 << 20)) return set_err(HML_ERR_ARG, std::string(name) + ": a number of blocks up to 2^20, or 0 for the default");
-        (name[8] == 'W' ? c->vit.W : c->vit.L) = (uint32_t)value;
-        return 0;
-    }
-    if (std::string(name) == "viterbi_rounds") {
-        if (value < 0 || value > 16) return set_err(HML_ERR_ARG, "viterbi_rounds: 0 to 16 parallel repair rounds");
-        c->vit.rounds = (uint32_t)value;
-        return 0;
-    }
-    // ... and the smoothing read-out's (hml_k_posterior.h)
-    if (std::string(name) == "posterior_W" || std::string(name) == "posterior_L") {
-        if (value < 0 || value > (1 << 20)) return set_err(HML_ERR_ARG, std::string(name) + ": a number of blocks up to 2^20, or 0 for the default");
-        (name[10] == 'W' ? c->post.W : c->post.L) = (uint32_t)value;
-        return 0;
-    }
-    if (std::string(name) == "posterior_rounds") {
-        if (value < 0 || value > 16) return set_err(HML_ERR_ARG, "posterior_rounds: 0 to 16 parallel repair rounds");
-        c->post.rounds = (uint32_t)value;
-        return 0;
-    }
-    // ... and the path sampler's (hml_k_sample.h)
-    if (std::string(name) == "sample_W" || std::string(name) == "sample_L") {
-        if (value < 0 || value > (1 << 20)) return set_err(HML_ERR_ARG, std::string(name) + ": a number of blocks up to 2^20, or 0 for the default");
-        (name[7] == 'W' ? c->samp.W : c->samp.L) = (uint32_t)value;
-        return 0;
-    }
-    if (std::string(name) == "sample_rounds") {
-        if (value < 0 || value > 16) return set_err(HML_ERR_ARG, "sample_rounds: 0 to 16 parallel repair rounds");
-        c->samp.rounds = (uint32_t)value;
-        return 0;
+    // the launch geometry of the chunked passes of exact inference (hml_infer.hip): never part of a result
+    const struct { const char* pass; hml_ctx::chunked_pass* p; } passes[] = {{"viterbi", &c->vit}, {"posterior", &c->post}, {"sample", &c->samp}};
+    for (const auto& e : passes) {
+        const std::string pass(e.pass), opt(name);
+        if (opt == pass + "_W" || opt == pass + "_L") {
+            if (value < 0 || value > (1 << 20)) return set_err(HML_ERR_ARG, opt + ": a number of blocks up to 2^20, or 0 for the default");
+            (opt.back() == 'W' ? e.p->W : e.p->L) = (uint32_t)value;
+            return 0;
+        }
+        if (opt == pass + "_rounds") {
+            if (value < 0 || value > 16) return set_err(HML_ERR_ARG, opt + ": 0 to 16 parallel repair rounds");
+            e.p->rounds = (uint32_t)value;
+            return 0;
+        }
     }
     return set_err(HML_ERR_ARG, std::string("unknown option ") + name);
 }

@@ -27,6 +27,16 @@ static void by_states(int K, F f) {
     else f(std::integral_constant<int, HML_CAP_K>());
 }
 
+// a pass's geometry over B blocks: its options, 0 meaning the default
+struct chunk_geom { uint32_t L, W, n_chunks; };
+static chunk_geom chunk_geom_of(const hml_ctx::chunked_pass& p, uint32_t default_L, uint32_t default_W, uint32_t B) {
+    chunk_geom g;
+    g.L = p.L ? p.L : default_L;
+    g.W = p.W ? p.W : default_W;
+    g.n_chunks = (uint32_t)(((uint64_t)B + g.L - 1u) / g.L);
+    return g;
+}
+
 // The tables of a pass on the device: the parameters, and the transition and initial terms - fixed-point scores of 8 bytes for
 // the decode (hml_k_vit_tables), A and pi in double for the smoothing (hml_k_post_tables).
 struct infer_tables { DevBuf par, trans, init; };
@@ -77,13 +87,14 @@ static int repair_rounds(uint32_t rounds, Verify verify, Rerun rerun, Finish fin
     KLAUNCH_CHECK();
     return 0;
 }
-// verify of one pass: entry against exit rows (8-byte terms compared as words); the counters are the first two 32-bit words of `words`
-static int verify_chunks(hml_ctx* c, const void* entry, const void* exitv, int K, uint32_t n_chunks, uint8_t* match, uint32_t* list, unsigned long long* words,
-                         uint64_t* stale, uint32_t* heads) {
+// verify of one pass: entry against exit rows (long long or double, compared as words); the counters are the first two 32-bit words of `words`
+template <typename T>
+static int verify_chunks(hml_ctx* c, const T* entry, const T* exitv, int K, uint32_t n_chunks, uint8_t* match, uint32_t* list, unsigned long long* words, uint64_t* stale,
+                         uint32_t* heads) {
     uint32_t h_cnt[2] = {0, 0};   // stale chunks, heads of their runs
     HIPCHK(hipMemsetAsync(words, 0, sizeof h_cnt, c->stream));
-    hipLaunchKernelGGL(hml_k_vit_verify, dim3(grid_for(n_chunks, 256, 1, 4096)), dim3(256), 0, c->stream, (const long long*)entry, (const long long*)exitv, K, n_chunks, match,
-                       list, (uint32_t*)words, (uint32_t*)words + 1);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_chunk_verify<T>), dim3(grid_for(n_chunks, 256, 1, 4096)), dim3(256), 0, c->stream, entry, exitv, K, n_chunks, match, list,
+                       (uint32_t*)words, (uint32_t*)words + 1);
     KLAUNCH_CHECK();
     HIPCHK(hipMemcpyAsync(h_cnt, words, sizeof h_cnt, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -113,9 +124,8 @@ static int vit_decode(hml_ctx* c, vit_path& out) {
     uint32_t B = 0;
     if (int r = vit_begin(c, t, &B)) return r;
     const int K = c->K;
-    const uint32_t L = c->vit.L ? c->vit.L : HML_VIT_DEFAULT_L;
-    const uint32_t W = c->vit.W ? c->vit.W : HML_VIT_DEFAULT_W;
-    const uint32_t n_chunks = (uint32_t)(((uint64_t)B + L - 1u) / L);
+    const chunk_geom g = chunk_geom_of(c->vit, HML_VIT_DEFAULT_L, HML_VIT_DEFAULT_W, B);
+    const uint32_t L = g.L, W = g.W, n_chunks = g.n_chunks;
     const uint32_t S = std::max<uint32_t>(1u, (uint32_t)std::ceil(std::sqrt((double)n_chunks)));   // chunks per group of the back-track
     const uint32_t n_groups = (n_chunks + S - 1u) / S;
     DevBuf b_entry, b_exit, b_psi, b_match, b_list, b_words, b_maps, b_gmaps, b_gend, b_cend;
@@ -130,43 +140,35 @@ static int vit_decode(hml_ctx* c, vit_path& out) {
     HIPCHK(b_gend.alloc(n_groups));
     HIPCHK(b_cend.alloc(n_chunks));
     HIPCHK(out.q.alloc((uint64_t)B * sizeof(int16_t)));
-    long long *const entry = b_entry.as<long long>(), *const exitv = b_exit.as<long long>();
-    uint8_t *const psi = b_psi.as<uint8_t>(), *const match = b_match.as<uint8_t>();
+    uint8_t* const match = b_match.as<uint8_t>();
     uint32_t* const list = b_list.as<uint32_t>();
     unsigned long long* const words = b_words.as<unsigned long long>();
-    const hml_vit_par* const par = t.par.as<hml_vit_par>();
-    const long long *const trans = t.trans.as<long long>(), *const init = t.init.as<long long>();
-    const uint32_t* const starts = c->d_starts.get();
-    HIPCHK(hipMemsetAsync(words, 0, 4 * sizeof(unsigned long long), c->stream));
+    hml_vit_args a;
+    a.par = t.par.as<hml_vit_par>(); a.trans = t.trans.as<long long>(); a.init = t.init.as<long long>();
+    a.ia = c->d_ia; a.starts = c->d_starts.get();
+    a.L = L; a.W = W; a.n_chunks = n_chunks;
+    a.entry = b_entry.as<long long>(); a.exitv = b_exit.as<long long>(); a.psi = b_psi.as<uint8_t>();
+    HIPCHK(hipMemsetAsync(words, 0, 4 * sizeof(unsigned long long), c->stream));   // (the finishing walk adds to words[1])
 
-    by_states(K, [&](auto km) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_vit_forward<km()>), dim3((n_chunks + 63u) / 64u), dim3(64), 0, c->stream, par, trans, init, c->d_ia, starts, L, W, n_chunks, entry,
-                           exitv, psi);
-    });
+    by_states(K, [&](auto km) { hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_vit_forward<km()>), dim3((n_chunks + 63u) / 64u), dim3(64), 0, c->stream, a); });
     KLAUNCH_CHECK();
     repair_outcome rep;
-    auto verify = [&](uint64_t* stale, uint32_t* heads) { return verify_chunks(c, entry, exitv, K, n_chunks, match, list, words, stale, heads); };
+    auto verify = [&](uint64_t* stale, uint32_t* heads) { return verify_chunks(c, a.entry, a.exitv, K, n_chunks, match, list, words, stale, heads); };
     auto rerun = [&](uint32_t n_heads) {
-        by_states(K, [&](auto km) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_vit_rerun<km()>), dim3((n_heads + 63u) / 64u), dim3(64), 0, c->stream, par, trans, init, c->d_ia, starts, L, n_chunks,
-                               list, n_heads, match, entry, exitv, psi);
-        });
+        by_states(K, [&](auto km) { hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_vit_rerun<km()>), dim3((n_heads + 63u) / 64u), dim3(64), 0, c->stream, a, list, n_heads, match); });
     };
     auto finish = [&] {
-        by_states(K, [&](auto km) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_vit_finish<km()>), dim3(1), dim3(64), 0, c->stream, par, trans, init, c->d_ia, starts, L, n_chunks, match, entry,
-                               exitv, psi, words + 1);
-        });
+        by_states(K, [&](auto km) { hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_vit_finish<km()>), dim3(1), dim3(64), 0, c->stream, a, match, words + 1); });
     };
     if (int r = repair_rounds(c->vit.rounds, verify, rerun, finish, rep)) return r;
     // back-track
     const dim3 cgrid((n_chunks + 63u) / 64u), ggrid((n_groups + 63u) / 64u);
-    hipLaunchKernelGGL(hml_k_vit_chunk_maps, cgrid, dim3(64), 0, c->stream, psi, K, B, L, n_chunks, b_maps.as<uint8_t>());
+    hipLaunchKernelGGL(hml_k_vit_chunk_maps, cgrid, dim3(64), 0, c->stream, a.psi, K, B, L, n_chunks, b_maps.as<uint8_t>());
     hipLaunchKernelGGL(hml_k_vit_group_maps, ggrid, dim3(64), 0, c->stream, b_maps.as<uint8_t>(), K, n_chunks, S, n_groups, b_gmaps.as<uint8_t>());
-    hipLaunchKernelGGL(hml_k_vit_group_ends, dim3(1), dim3(64), 0, c->stream, exitv, b_gmaps.as<uint8_t>(), K, n_chunks, n_groups, b_gend.as<uint8_t>());
+    hipLaunchKernelGGL(hml_k_vit_group_ends, dim3(1), dim3(64), 0, c->stream, a.exitv, b_gmaps.as<uint8_t>(), K, n_chunks, n_groups, b_gend.as<uint8_t>());
     hipLaunchKernelGGL(hml_k_vit_chunk_ends, ggrid, dim3(64), 0, c->stream, b_maps.as<uint8_t>(), b_gend.as<uint8_t>(), K, n_chunks, S, n_groups, b_cend.as<uint8_t>());
-    hipLaunchKernelGGL(hml_k_vit_walk, cgrid, dim3(64), 0, c->stream, psi, b_cend.as<uint8_t>(), K, B, L, n_chunks, out.q.as<int16_t>());
-    hipLaunchKernelGGL(hml_k_vit_score, dim3(grid_for(B, 256, 1, 4096)), dim3(256), 0, c->stream, par, trans, init, c->d_ia, starts, out.q.as<int16_t>(), words + 2);
+    hipLaunchKernelGGL(hml_k_vit_walk, cgrid, dim3(64), 0, c->stream, a.psi, b_cend.as<uint8_t>(), K, B, L, n_chunks, out.q.as<int16_t>());
+    hipLaunchKernelGGL(hml_k_vit_score, dim3(grid_for(B, 256, 1, 4096)), dim3(256), 0, c->stream, a.par, a.trans, a.init, a.ia, a.starts, out.q.as<int16_t>(), words + 2);
     KLAUNCH_CHECK();
     unsigned long long h_words[4];
     HIPCHK(hipMemcpyAsync(h_words, words, sizeof h_words, hipMemcpyDeviceToHost, c->stream));
@@ -294,9 +296,8 @@ static int post_forward(hml_ctx* c, post_result& out, infer_tables& t, post_forw
     uint32_t B = 0;
     if (int r = post_begin(c, t, &B)) return r;
     const int K = c->K;
-    s.L = c->post.L ? c->post.L : HML_POST_DEFAULT_L;
-    s.W = c->post.W ? c->post.W : HML_POST_DEFAULT_W;
-    s.n_chunks = (uint32_t)(((uint64_t)B + s.L - 1u) / s.L);
+    const chunk_geom g = chunk_geom_of(c->post, HML_POST_DEFAULT_L, HML_POST_DEFAULT_W, B);
+    s.L = g.L; s.W = g.W; s.n_chunks = g.n_chunks;
     HIPCHK(out.alpha.alloc((uint64_t)B * K * sizeof(double)));
     HIPCHK(out.cval.alloc((uint64_t)B * sizeof(double)));
     HIPCHK(s.ell.alloc((uint64_t)B * sizeof(double)));
@@ -750,9 +751,8 @@ int hml_em_fit_many(hml_ctx* c, uint64_t R, const float* mean_var, const float* 
     }
     em_params q0;
     em_params_of(m, K, q0);
-    g.L = c->post.L ? c->post.L : HML_POST_DEFAULT_L;
-    g.W = c->post.W ? c->post.W : HML_POST_DEFAULT_W;
-    g.n_chunks = (uint32_t)(((uint64_t)g.B + g.L - 1u) / g.L);
+    const chunk_geom cg = chunk_geom_of(c->post, HML_POST_DEFAULT_L, HML_POST_DEFAULT_W, g.B);
+    g.L = cg.L; g.W = cg.W; g.n_chunks = cg.n_chunks;
     g.ncols = (uint32_t)(KK + K * (2 + 2 * g.D));
     g.n1 = ((uint64_t)g.B + 63u) / 64u; g.n2 = (g.n1 + 63u) / 64u;
     g.nfloats = 2u * P + KK + K;
@@ -1073,9 +1073,8 @@ static int sample_run(hml_ctx* c, const char* who, const sample_request& q) {
     }
     post.cval.free();
     const uint32_t B = post.B;
-    const uint32_t L = c->samp.L ? c->samp.L : HML_SAMP_DEFAULT_L;
-    const uint32_t W = c->samp.W ? c->samp.W : HML_SAMP_DEFAULT_W;
-    const uint32_t n_chunks = (uint32_t)(((uint64_t)B + L - 1u) / L);
+    const chunk_geom cg = chunk_geom_of(c->samp, HML_SAMP_DEFAULT_L, HML_SAMP_DEFAULT_W, B);
+    const uint32_t L = cg.L, W = cg.W, n_chunks = cg.n_chunks;
     const bool want_regions = q.n_regions != 0;
     const bool want_counts = q.change_count || q.state_count;
 

@@ -8,7 +8,7 @@
 // so members share nothing and no word of one depends on another or on how the batch is cut into groups.
 //   model, tables   a workgroup per member: the member's floats into a scratch model beside the context's configuration, then
 //             (a second launch) the tables of hml_k_post_tables from it (hml_vit_par_fill, A and pi widened)
-//   first / verify / rerun / finish   the smoothing's four, per direction; the counts (stale chunks, heads) lie per member in
+//   first / verify / rerun / finish   the smoothing's four (the scheme of hml_k_chunks.h), per direction; the counts lie per member in
 //             one array the host reads in one copy per round; a round's repair launch covers the stale runs of all members
 //             (a member with none has no lanes), the finishing launch has a wavefront per member (one without stale chunks
 //             returns)
@@ -76,21 +76,10 @@ HML_KERNEL __launch_bounds__(64) void hml_k_em_many_first(const hml_em_many_rec*
     hml_post_run_chunk<KM, DIR>(a, hml_post_lds, x, nullptr);
 }
 
-// hml_k_vit_verify per member, on the words of the doubles
+// hml_chunk_verify per member
 HML_KERNEL __launch_bounds__(256) void hml_k_em_many_verify(const hml_em_many_rec* __restrict__ recs, int dir, int K) {
     const hml_em_many_rec& r = recs[blockIdx.y];
-    const long long* const entry = reinterpret_cast<const long long*>(r.dir[dir].entry);
-    const long long* const exitv = reinterpret_cast<const long long*>(r.dir[dir].exitv);
-    const uint32_t n_chunks = r.dir[dir].n_chunks;
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t c = blockIdx.x * blockDim.x + threadIdx.x; c < n_chunks; c += stride) {
-        const bool eq = c == 0u || hml_vit_same(entry + (uint64_t)c * K, exitv + (uint64_t)(c - 1u) * K, K);
-        r.match[c] = eq ? 1 : 0;
-        if (!eq) {
-            atomicAdd(r.cnt, 1u);
-            if (c == 1u || hml_vit_same(entry + (uint64_t)(c - 1u) * K, exitv + (uint64_t)(c - 2u) * K, K)) r.heads[atomicAdd(r.cnt + 1, 1u)] = c;
-        }
-    }
+    hml_chunk_verify(r.dir[dir].entry, r.dir[dir].exitv, K, r.dir[dir].n_chunks, r.match, r.heads, r.cnt, r.cnt + 1);
 }
 
 // grid x covers the greatest number of heads of the round
@@ -104,7 +93,8 @@ HML_KERNEL __launch_bounds__(64) void hml_k_em_many_rerun(const hml_em_many_rec*
     hml_post_stage(a, a.par->K, hml_post_lds);
     const uint32_t i = blockIdx.x * 64u + threadIdx.x;
     if (i >= n_heads) return;
-    hml_post_rerun_walk<KM, DIR>(a, hml_post_lds, r.heads[i], r.match);
+    auto run = [&](uint32_t x, const double* from) { hml_post_run_chunk<KM, DIR>(a, hml_post_lds, x, from); };
+    hml_chunk_rerun_walk(run, a.entry, a.exitv, a.par->K, a.n_chunks, r.heads[i], r.match);
 }
 
 template <int KM, int DIR>
@@ -114,7 +104,8 @@ HML_KERNEL __launch_bounds__(64) void hml_k_em_many_finish(const hml_em_many_rec
     if (r.cnt[0] == 0u || blockIdx.x != 0u || blockDim.x != 64u) return;   // (the whole workgroup)
     const hml_post_args a = r.dir[DIR];
     hml_post_stage(a, a.par->K, hml_post_lds);
-    hml_post_finish_walk<KM, DIR>(a, hml_post_lds, r.match, r.words + HML_EMM_W_WALKED);
+    auto run = [&](uint32_t x, const double* from) { hml_post_run_chunk<KM, DIR>(a, hml_post_lds, x, from); };
+    hml_chunk_finish_walk(run, a.entry, a.exitv, a.par->K, a.n_chunks, r.match, r.words + HML_EMM_W_WALKED);
 }
 
 HML_KERNEL __launch_bounds__(256) void hml_k_em_many_degenerate(const hml_em_many_rec* __restrict__ recs, uint32_t B) {

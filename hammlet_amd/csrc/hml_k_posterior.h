@@ -4,16 +4,11 @@
 //
 // The float tables (E, m, e) are the sweep's; everything after them is IEEE double in a fixed order.  The forward and the
 // backward recursion are each one chain of B dependent steps, cut exactly as the Viterbi decode is cut (hml_k_viterbi.h):
-//   chunks    L blocks a chunk, a chunk a lane.  A CHAIN INDEX x counts the chunks in the order of the recursion: forward
-//             x = chunk, backward x = n_chunks - 1 - chunk, so that in both directions the predecessor of x is x - 1;
-//   first run chunk x starts W blocks outside its blocks from the uniform vector (exact where that reaches block 0 - pi - or the
-//             last block), records entry[x] - the normalised vector it enters its own blocks with - and exit[x], and stores
-//             the rows (alpha_b and c_b, or beta_b) of its own blocks;
-//   verify    x matches iff entry[x] == exit[x - 1] in all K doubles, bit for bit (hml_k_vit_verify on the words): two runs of
-//             a normalised recursion that have forgotten their start hold the same vector exactly, and everything a chunk
-//             stores is a function of its entry vector alone - the induction of hml_k_viterbi.h, unchanged;
-//   repair    hml_k_post_rerun / hml_k_post_finish: the rounds from the heads of the stale runs, then one lane - the walks of
-//             hml_k_vit_rerun / hml_k_vit_finish with this recursion in place of that one;
+//   first run chunk x (a chain index, hml_k_chunks.h: forward x = chunk, backward x = n_chunks - 1 - chunk) starts W blocks
+//             outside its blocks from the uniform vector (exact where that reaches block 0 - pi - or the last block), records
+//             entry[x] and exit[x] and stores the rows (alpha_b and c_b, or beta_b) of its own blocks;
+//   verify, repair   the scheme of hml_k_chunks.h on the K doubles, bit for bit: two runs of a normalised recursion that have
+//             forgotten their start hold the same vector exactly;
 //   combine   a lane per block: gamma_b, the called state and its posterior; l_b = m_b + log c_b was stored by the forward
 //             run and is reduced by the fan-in-64 tree of the definition, a lane per value of the next level.
 // W, L and the number of rounds decide which lane computes what, never a word of the result.
@@ -228,35 +223,7 @@ HML_KERNEL __launch_bounds__(64) void hml_k_post_first(const hml_post_args a) {
     hml_post_run_chunk<KM, DIR>(a, hml_post_lds, x, nullptr);
 }
 
-// the words of two vectors compared (read as doubles: the lane that compares may be the one that has just stored them)
-__device__ __forceinline__ bool hml_post_same(const double* p, const double* q, int K) {
-    bool eq = true;
-    for (int j = 0; j < K; ++j) eq = eq && hml_d2u(p[j]) == hml_d2u(q[j]);
-    return eq;
-}
-
-// A repair round: a lane per run of stale chunks, from its head - the walk of hml_k_vit_rerun (see there for why it stops
-// where it stops), over chain indices.  hml_post_rerun_walk is one lane's walk from the head x (never 0)
-template <int KM, int DIR>
-__device__ __forceinline__ void hml_post_rerun_walk(const hml_post_args& a, const double* sA, uint32_t x, const uint8_t* __restrict__ match) {
-    const int K = a.par->K;
-    for (;;) {
-        hml_post_run_chunk<KM, DIR>(a, sA, x, a.exitv + (uint64_t)(x - 1u) * K);
-        for (;;) {
-            const uint32_t nx = x + 1u;
-            if (nx >= a.n_chunks) return;
-            const bool listed = match[nx] == 0;
-            if (hml_post_same(a.entry + (uint64_t)nx * K, a.exitv + (uint64_t)x * K, K)) {
-                if (!listed) return;   // it matched before and still does
-                x = nx;                // stale before, right as stored now: on to its successor
-                continue;
-            }
-            if (!listed && nx + 1u < a.n_chunks && match[nx + 1u] == 0) return;   // nx is the predecessor another lane reads
-            x = nx;
-            break;
-        }
-    }
-}
+// a repair round: a lane per head (hml_chunk_rerun_walk, over chain indices)
 template <int KM, int DIR>
 HML_KERNEL __launch_bounds__(64) void hml_k_post_rerun(const hml_post_args a, const uint32_t* __restrict__ heads, uint32_t n_heads,
                                                        const uint8_t* __restrict__ match) {
@@ -264,50 +231,18 @@ HML_KERNEL __launch_bounds__(64) void hml_k_post_rerun(const hml_post_args a, co
     hml_post_stage(a, a.par->K, hml_post_lds);
     const uint32_t i = blockIdx.x * 64u + threadIdx.x;
     if (i >= n_heads) return;
-    hml_post_rerun_walk<KM, DIR>(a, hml_post_lds, heads[i], match);
+    auto run = [&](uint32_t x, const double* from) { hml_post_run_chunk<KM, DIR>(a, hml_post_lds, x, from); };
+    hml_chunk_rerun_walk(run, a.entry, a.exitv, a.par->K, a.n_chunks, heads[i], match);
 }
 
-// what the rounds left: one wavefront walks the chain in increasing order, its first lane runs what does not match - the walk
-// of hml_k_vit_finish.  hml_post_finish_walk is that wavefront's walk (all 64 lanes call)
-template <int KM, int DIR>
-__device__ __forceinline__ void hml_post_finish_walk(const hml_post_args& a, const double* sA, const uint8_t* __restrict__ match,
-                                                     unsigned long long* __restrict__ walked) {
-    const int K = a.par->K;
-    const int lane = threadIdx.x;
-    const uint32_t n_chunks = a.n_chunks;
-    unsigned long long n_walked = 0ull;
-    bool dirty = false;   // the predecessor was just run again: its exit vector is new
-    for (uint64_t base = 1u; base < n_chunks; base += 64u) {
-        const uint64_t mine = base + (uint32_t)lane;
-        const bool stale = mine < n_chunks && match[mine] == 0;
-        const unsigned long long mask = __ballot(stale);
-        if (mask == 0ull && !dirty) continue;
-        for (uint32_t k = 0; k < 64u && base + k < n_chunks; ++k) {
-            const uint32_t x = (uint32_t)(base + k);
-            int need = (int)((mask >> k) & 1ull);
-            if (dirty) {
-                if (lane == 0) need = hml_post_same(a.entry + (uint64_t)x * K, a.exitv + (uint64_t)(x - 1u) * K, K) ? 0 : 1;
-                need = __shfl(need, 0);
-            }
-            if (need) {
-                if (lane == 0) {
-                    hml_post_run_chunk<KM, DIR>(a, sA, x, a.exitv + (uint64_t)(x - 1u) * K);
-                    __threadfence();
-                }
-                ++n_walked;
-            }
-            dirty = need != 0;
-            if (!dirty && (mask >> k) >> 1 == 0ull) break;   // nothing stale in the rest of these 64
-        }
-    }
-    if (lane == 0) *walked += n_walked;
-}
+// what the rounds left: one wavefront (hml_chunk_finish_walk)
 template <int KM, int DIR>
 HML_KERNEL __launch_bounds__(64) void hml_k_post_finish(const hml_post_args a, const uint8_t* __restrict__ match, unsigned long long* __restrict__ walked) {
     extern __shared__ double hml_post_lds[];
     hml_post_stage(a, a.par->K, hml_post_lds);
     if (blockIdx.x != 0u || blockDim.x != 64u) return;
-    hml_post_finish_walk<KM, DIR>(a, hml_post_lds, match, walked);
+    auto run = [&](uint32_t x, const double* from) { hml_post_run_chunk<KM, DIR>(a, hml_post_lds, x, from); };
+    hml_chunk_finish_walk(run, a.entry, a.exitv, a.par->K, a.n_chunks, match, walked);
 }
 
 // a lane per block: gamma_b (stored if asked), the called state and its posterior; degenerate blocks - bad(c_b) - are counted

@@ -6,12 +6,8 @@
 //   forward   chunk c starts W blocks early from the zero vector (chunk 0, and every chunk whose warm-up reaches block 0, from
 //             `init`: exact), records entry[c] - its normalised vector at block c L - 1 - and exit[c], and stores the
 //             back-pointers psi of its own blocks;
-//   verify    chunk c matches iff entry[c] == exit[c - 1] in all K words.  Integers: two runs that have coalesced hold the
-//             same normalised vector exactly, and everything a chunk stores is a function of its entry vector alone - so when
-//             every chunk matches, induction from chunk 0 makes every stored psi the sequential recursion's;
-//   repair    in rounds, a lane per RUN of chunks that do not match: the run's head has a matching predecessor (nothing writes
-//             that exit vector during the round) and runs again from it, exactly, then its successors, as far as the change
-//             reaches; all chunks are verified again; what is left after the rounds is walked by one lane in increasing order;
+//   verify, repair   the scheme of hml_k_chunks.h on the K integer words: two runs that have coalesced hold the same normalised
+//             vector exactly; the rounds from the heads of the stale runs, then one wavefront's walk;
 //   backtrack per chunk the map [K] -> [K] from its end state to the end state of its predecessor, the maps composed over
 //             groups of chunks, one lane down the groups, then the chunks of a group, then every chunk walks its rows.
 // W, L and the number of rounds decide which lane computes what, never a word of the result.
@@ -19,6 +15,7 @@
 #define HML_K_VITERBI_H
 
 #include "hml_k_blocks.h"
+#include "hml_k_chunks.h"
 #include "hml_k_forward.h"
 #include "hml_math.h"
 #include "hml_state.h"
@@ -124,13 +121,25 @@ HML_KERNEL __launch_bounds__(256) void hml_k_vit_emit_table(const hml_vit_par* _
     }
 }
 
+// what a run over a chunk reads and writes
+struct hml_vit_args {
+    const hml_vit_par* par;
+    const long long *trans, *init;
+    const float2* ia;
+    const uint32_t* starts;
+    uint32_t L, W, n_chunks;
+    long long *entry, *exitv;    // [n_chunks][K]
+    uint8_t* psi;                // [B][K]
+};
+
 // The recursion over blocks [first, end of chunk c) by one lane.  from == nullptr: from the zero vector (from `init` if
 // first == 0); else from that normalised vector, which is then the chunk's entry.  KM: the states the vector is kept for -
 // registers up to 16 (loops unrolled), a per-lane array beyond (KM = HML_CAP_K, loops kept).
+// The tables come apart again as __restrict__ parameters: only so does the compiler know that the bytes stored to psi leave
+// them alone, and keep their loads scalar.
 template <int KM>
-__device__ __forceinline__ void hml_vit_run_chunk(const hml_vit_par* __restrict__ par, const long long* __restrict__ trans,
-                                                  const long long* __restrict__ init, const float2* __restrict__ ia,
-                                                  const uint32_t* __restrict__ starts, uint32_t L, uint32_t c, uint32_t first,
+__device__ __forceinline__ void hml_vit_recursion(const hml_vit_par* __restrict__ par, const long long* __restrict__ trans, const long long* __restrict__ init,
+                                                  const float2* __restrict__ ia, const uint32_t* __restrict__ starts, uint32_t L, uint32_t c, uint32_t first,
                                                   const long long* from, long long* entry, long long* exitv, uint8_t* psi) {
     constexpr int UF = KM <= 16 ? KM : 1;
     const int K = par->K;
@@ -183,112 +192,36 @@ __device__ __forceinline__ void hml_vit_run_chunk(const hml_vit_par* __restrict_
     for (int j = 0; j < KM; ++j)
         if (j < K) exitv[(uint64_t)c * K + j] = d[j];
 }
+// ... of the pass `a` describes: what the kernels and the walks call
+template <int KM>
+__device__ __forceinline__ void hml_vit_run_chunk(const hml_vit_args& a, uint32_t c, uint32_t first, const long long* from) {
+    hml_vit_recursion<KM>(a.par, a.trans, a.init, a.ia, a.starts, a.L, c, first, from, a.entry, a.exitv, a.psi);
+}
 
 // first pass: a lane per chunk, W blocks of warm-up
 template <int KM>
-HML_KERNEL __launch_bounds__(64) void hml_k_vit_forward(const hml_vit_par* __restrict__ par, const long long* __restrict__ trans,
-                                                        const long long* __restrict__ init, const float2* __restrict__ ia,
-                                                        const uint32_t* __restrict__ starts, uint32_t L, uint32_t W, uint32_t n_chunks,
-                                                        long long* __restrict__ entry, long long* __restrict__ exitv, uint8_t* __restrict__ psi) {
+HML_KERNEL __launch_bounds__(64) void hml_k_vit_forward(const hml_vit_args a) {
     const uint32_t c = blockIdx.x * 64u + threadIdx.x;
-    if (c >= n_chunks) return;
-    const uint64_t lo = (uint64_t)c * L;
-    hml_vit_run_chunk<KM>(par, trans, init, ia, starts, L, c, lo > W ? (uint32_t)(lo - W) : 0u, nullptr, entry, exitv, psi);
+    if (c >= a.n_chunks) return;
+    const uint64_t lo = (uint64_t)c * a.L;
+    hml_vit_run_chunk<KM>(a, c, lo > a.W ? (uint32_t)(lo - a.W) : 0u, nullptr);
 }
 
-// match[c] = (entry[c] == exit[c - 1]).  The chunks that do not match are counted; the HEADS of their runs - stale chunks whose
-// predecessor matches - are listed (in no order)
-__device__ __forceinline__ bool hml_vit_same(const long long* a, const long long* b, int K) {
-    bool eq = true;
-    for (int j = 0; j < K; ++j) eq = eq && a[j] == b[j];
-    return eq;
-}
-HML_KERNEL __launch_bounds__(256) void hml_k_vit_verify(const long long* __restrict__ entry, const long long* __restrict__ exitv, int K,
-                                                        uint32_t n_chunks, uint8_t* __restrict__ match, uint32_t* __restrict__ heads,
-                                                        uint32_t* __restrict__ n_stale, uint32_t* __restrict__ n_heads) {
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t c = blockIdx.x * blockDim.x + threadIdx.x; c < n_chunks; c += stride) {
-        const bool eq = c == 0u || hml_vit_same(entry + (uint64_t)c * K, exitv + (uint64_t)(c - 1u) * K, K);
-        match[c] = eq ? 1 : 0;
-        if (!eq) {
-            atomicAdd(n_stale, 1u);
-            if (c == 1u || hml_vit_same(entry + (uint64_t)(c - 1u) * K, exitv + (uint64_t)(c - 2u) * K, K)) heads[atomicAdd(n_heads, 1u)] = c;
-        }
-    }
-}
-
-// A repair round: a lane per run of stale chunks, from its head.  The head's predecessor matches, so nothing writes that exit
-// vector in this launch: the lane runs the head again from it, exactly, and walks on - a chunk whose entry equals the exit
-// vector its predecessor has NOW stands as stored; any other runs again from that vector.  The walk ends where a chunk that
-// matched before still matches (nothing behind it has changed), and before it would rewrite a matching chunk whose successor
-// is stale: that successor is another lane's head and reads this exit vector.  What such a stop leaves behind, the next
-// verification finds.  `match` is the last verification's and is only read here.
+// a repair round: a lane per head (hml_chunk_rerun_walk)
 template <int KM>
-HML_KERNEL __launch_bounds__(64) void hml_k_vit_rerun(const hml_vit_par* __restrict__ par, const long long* __restrict__ trans,
-                                                      const long long* __restrict__ init, const float2* __restrict__ ia,
-                                                      const uint32_t* __restrict__ starts, uint32_t L, uint32_t n_chunks,
-                                                      const uint32_t* __restrict__ heads, uint32_t n_heads, const uint8_t* __restrict__ match,
-                                                      long long* entry, long long* exitv, uint8_t* psi) {
+HML_KERNEL __launch_bounds__(64) void hml_k_vit_rerun(const hml_vit_args a, const uint32_t* __restrict__ heads, uint32_t n_heads, const uint8_t* __restrict__ match) {
     const uint32_t i = blockIdx.x * 64u + threadIdx.x;
     if (i >= n_heads) return;
-    const int K = par->K;
-    uint32_t x = heads[i];   // (never chunk 0)
-    for (;;) {
-        hml_vit_run_chunk<KM>(par, trans, init, ia, starts, L, x, (uint32_t)((uint64_t)x * L), exitv + (uint64_t)(x - 1u) * K, entry, exitv, psi);
-        for (;;) {
-            const uint32_t nx = x + 1u;
-            if (nx >= n_chunks) return;
-            const bool listed = match[nx] == 0;
-            if (hml_vit_same(entry + (uint64_t)nx * K, exitv + (uint64_t)x * K, K)) {
-                if (!listed) return;   // it matched before and still does
-                x = nx;                // stale before, right as stored now: on to its successor
-                continue;
-            }
-            if (!listed && nx + 1u < n_chunks && match[nx + 1u] == 0) return;   // nx is the predecessor another lane reads
-            x = nx;
-            break;
-        }
-    }
+    auto run = [&](uint32_t x, const long long* from) { hml_vit_run_chunk<KM>(a, x, (uint32_t)((uint64_t)x * a.L), from); };
+    hml_chunk_rerun_walk(run, a.entry, a.exitv, a.par->K, a.n_chunks, heads[i], match);
 }
 
-// what the rounds left: one wavefront walks the chunks in increasing order - 64 match bytes at a time while nothing is
-// stale - and its first lane runs every chunk that does not match its predecessor's exit vector as it stands then
+// what the rounds left: one wavefront (hml_chunk_finish_walk)
 template <int KM>
-HML_KERNEL __launch_bounds__(64) void hml_k_vit_finish(const hml_vit_par* __restrict__ par, const long long* __restrict__ trans,
-                                                       const long long* __restrict__ init, const float2* __restrict__ ia,
-                                                       const uint32_t* __restrict__ starts, uint32_t L, uint32_t n_chunks,
-                                                       const uint8_t* __restrict__ match, long long* entry, long long* exitv,
-                                                       uint8_t* psi, unsigned long long* __restrict__ walked) {
+HML_KERNEL __launch_bounds__(64) void hml_k_vit_finish(const hml_vit_args a, const uint8_t* __restrict__ match, unsigned long long* __restrict__ walked) {
     if (blockIdx.x != 0u || blockDim.x != 64u) return;
-    const int lane = threadIdx.x, K = par->K;
-    unsigned long long n_walked = 0ull;
-    bool dirty = false;   // the predecessor was just run again: its exit vector is new
-    for (uint64_t base = 1u; base < n_chunks; base += 64u) {
-        const uint64_t mine = base + (uint32_t)lane;
-        const bool bad = mine < n_chunks && match[mine] == 0;
-        const unsigned long long mask = __ballot(bad);
-        if (mask == 0ull && !dirty) continue;
-        for (uint32_t k = 0; k < 64u && base + k < n_chunks; ++k) {
-            const uint32_t c = (uint32_t)(base + k);
-            int need = (int)((mask >> k) & 1ull);
-            if (dirty) {
-                if (lane == 0) {
-                    need = hml_vit_same(entry + (uint64_t)c * K, exitv + (uint64_t)(c - 1u) * K, K) ? 0 : 1;
-                }
-                need = __shfl(need, 0);
-            }
-            if (need) {
-                if (lane == 0) {
-                    hml_vit_run_chunk<KM>(par, trans, init, ia, starts, L, c, (uint32_t)((uint64_t)c * L), exitv + (uint64_t)(c - 1u) * K, entry, exitv, psi);
-                    __threadfence();
-                }
-                ++n_walked;
-            }
-            dirty = need != 0;
-            if (!dirty && (mask >> k) >> 1 == 0ull) break;   // nothing stale in the rest of these 64
-        }
-    }
-    if (lane == 0) *walked = n_walked;
+    auto run = [&](uint32_t x, const long long* from) { hml_vit_run_chunk<KM>(a, x, (uint32_t)((uint64_t)x * a.L), from); };
+    hml_chunk_finish_walk(run, a.entry, a.exitv, a.par->K, a.n_chunks, match, walked);
 }
 
 // maps[c][j]: the state at the last block of chunk c - 1 when block (end of chunk c) is in state j  (chunk 0: unused)
