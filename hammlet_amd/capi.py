@@ -138,6 +138,9 @@ SIGNATURES = {
     "hml_posterior_sample_regions": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, _P, _P, C.c_uint32] + [_P] * 4),
     "hml_posterior_sample_info": (C.c_int, [_P] + [C.POINTER(C.c_uint64)] * 9),
     "hml_set_sample_batch_bytes": (C.c_int, [_P, C.c_uint64]),
+    "hml_posterior_region_counts": (C.c_int, [_P, C.c_uint64, _P, _P, C.c_uint32, _P, _P, _P, C.POINTER(C.c_uint64)]),
+    "hml_posterior_count_terms": (C.c_int, [_P, _P, _P]),
+    "hml_posterior_counts_info": (C.c_int, [_P] + [C.POINTER(C.c_uint64)] * 3),
     "hml_recording_payload_size": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64)]),
     "hml_recording_export": (C.c_int, [_P, C.c_int, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "hml_recording_merge_payload": (C.c_int, [_P, C.c_int, _P, C.c_uint64]),
@@ -933,6 +936,39 @@ class Chain:
     def set_sample_batch_bytes(self, n_bytes=0):
         """the device memory a group of posterior_sample's draws may take (0: the default) (hml_set_sample_batch_bytes)"""
         _check(self.lib.hml_set_sample_batch_bytes(self.h, int(n_bytes)))
+
+    # ---- count read-outs of the smoothing: exact breakpoint-count and state-avoidance posteriors ----
+    def posterior_region_counts(self, start, end, max_breaks=8):
+        """dict(hist[n, max_breaks + 1], whole_state[n, K], avoid[n, K] float64, count_degenerate): per region [start[r],
+        end[r]) the exact posterior distribution of the number of breakpoints inside it (last bin: that many or more), the
+        probability that all of it is in state j, and the probability that no position of it is in state j, under the current
+        parameters (hml_posterior_region_counts); independent of set_regions()"""
+        start, end = _region_positions(start, "start"), _region_positions(end, "end")
+        if start.shape != end.shape:
+            raise ValueError("start and end: two one-dimensional arrays of one length")
+        n, K, H = start.size, self.K, int(max_breaks)
+        if not 0 <= H < 2 ** 32:
+            raise ValueError("max_breaks: an unsigned 32-bit number")
+        out = dict(hist=np.zeros((n, min(H, 32) + 1), np.float64), whole_state=np.zeros((n, K), np.float64), avoid=np.zeros((n, K), np.float64))
+        bad = C.c_uint64()
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        _check(self.lib.hml_posterior_region_counts(self.h, n, ptr(start), ptr(end), H, ptr(out["hist"]), ptr(out["whole_state"]), ptr(out["avoid"]), C.byref(bad)))
+        out["count_degenerate"] = bad.value
+        return out
+
+    def posterior_count_terms(self):
+        """dict(v[B, K], rho[B, K] float64): the terms the call above is built from (hml_posterior_count_terms)"""
+        B, K = self.num_blocks(), self.K
+        out = dict(v=np.empty((B, K), np.float64), rho=np.empty((B, K), np.float64))
+        _check(self.lib.hml_posterior_count_terms(self.h, out["v"].ctypes.data, out["rho"].ctypes.data))
+        return out
+
+    def posterior_counts_info(self):
+        """of the last posterior_region_counts: dict(regions, steps, longest) - steps the sum over the regions of the blocks a
+        walk steps over (be - ba), longest the largest (hml_posterior_counts_info)"""
+        v = [C.c_uint64() for _ in range(3)]
+        _check(self.lib.hml_posterior_counts_info(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("regions", "steps", "longest"), (x.value for x in v)))
 
     # ---- sparse payloads of the levels, breakpoints and bands (across GPUs) -------------------
     def recording_payload_size(self, kind):

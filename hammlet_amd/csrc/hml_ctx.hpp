@@ -231,6 +231,11 @@ struct hml_ctx {
     struct {
         uint64_t batch_bytes = 0, draws = 0, groups = 0, group_size = 0;
     } samp_batch;
+    // Count read-outs (hml_posterior_region_counts; hml_k_counts.h): what the last call did (hml_posterior_counts_info).
+    struct {
+        bool done = false;
+        uint64_t regions = 0, steps = 0, longest = 0;   // steps: the sum of be - ba over the regions; longest: the largest
+    } counts;
     // Every d_* above that is not a plain pointer owns its buffer (DevBuf / DevArr, hml_host_common.hpp): deleting the context
     // frees them, whatever a call that failed half-way left allocated, and allocating one again replaces what it held.
     ~hml_ctx() { if (h_B) (void)hipHostFree(h_B); }

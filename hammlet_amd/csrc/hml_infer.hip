@@ -1,7 +1,8 @@
 // libhammlet_hip.so - exact inference under the chain's current parameters, over its current blocks (include/hml.h): the most
 // probable path (hml_viterbi*), the state posteriors and log p(y | theta) (hml_posterior*), the E-step's expected counts and
 // the fits built on them (hml_expected_counts, hml_em_*, hml_em_fit_many), and the exact breakpoint and region posteriors
-// (hml_posterior_breaks / _regions / _pair_terms), and independent draws of whole paths (hml_posterior_sample*).  Nothing here reads what a recorder wrote - those read-outs are
+// (hml_posterior_breaks / _regions / _pair_terms), independent draws of whole paths (hml_posterior_sample*), and the exact
+// breakpoint-count and state-avoidance posteriors per region (hml_posterior_region_counts).  Nothing here reads what a recorder wrote - those read-outs are
 // hml_readout.hip's - and nothing runs inside a sweep: the chain is only read, every call owns its device memory for its own
 // length, and the context keeps the launch geometry and a few numbers about the last call (hml_ctx::vit, post, em_many).
 #include <limits>
@@ -17,6 +18,7 @@
 #include "hml_k_em_many.h"
 #include "hml_k_pairs.h"   // (it brings hml_pairs_ref.h)
 #include "hml_k_sample.h"   // (it brings hml_sample_ref.h)
+#include "hml_k_counts.h"   // (it brings hml_counts_ref.h)
 
 // ---------------------------------------------------------------------------------------- what the passes share
 // f(std::integral_constant<int, KM>()) for the number of states the kernels keep a recursion's vector for
@@ -1270,6 +1272,140 @@ int hml_posterior_sample_info(hml_ctx* c, uint64_t* draws, uint64_t* groups, uin
 int hml_set_sample_batch_bytes(hml_ctx* c, uint64_t bytes) {
     if (!c) return set_err(HML_ERR_ARG, "null context");
     c->samp_batch.batch_bytes = bytes;
+    return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------- count read-outs (hml_k_counts.h)
+// Per region the exact distribution of the number of breakpoints and the probability of avoiding each state: forward
+// recursions over the region's blocks on the posterior's own transitions, whose terms v_b and rho_b follow from the row beta a
+// smoothing pass leaves behind.  The chain is only read; device memory is local to a call, as the smoothing's is.
+
+struct counts_result {
+    post_result post;   // alpha and beta (c_b, the calls and their confidences are released)
+    infer_tables t;     // A and pi in double: the walks stage them as the terms kernel does
+    DevBuf v, rho;      // [B][K] each
+    uint64_t bad = 0;
+    uint32_t B = 0;
+};
+
+// f(std::integral_constant<int, NC>()) for the cells a lane of a walk holds at the most
+template <class F>
+static void by_lane_cells(int cells, F f) {
+    switch (hml_counts_lane_cells(cells)) {
+        case 1: f(std::integral_constant<int, 1>()); break;
+        case 2: f(std::integral_constant<int, 2>()); break;
+        case 4: f(std::integral_constant<int, 4>()); break;
+        case 8: f(std::integral_constant<int, 8>()); break;
+        default: f(std::integral_constant<int, (int)HML_COUNTS_LANE_CELLS>()); break;
+    }
+}
+
+// a smoothing pass, then the terms per block
+static int counts_compute(hml_ctx* c, counts_result& out) {
+    if (int r = post_compute(c, false, out.post, out.t)) return r;
+    out.post.cval.free(); out.post.conf.free(); out.post.q.free();
+    const int K = c->K;
+    const uint32_t B = out.post.B;
+    DevBuf b_bad;
+    HIPCHK(out.v.alloc((uint64_t)B * K * sizeof(double)));
+    HIPCHK(out.rho.alloc((uint64_t)B * K * sizeof(double)));
+    HIPCHK(b_bad.alloc(sizeof(unsigned long long)));
+    HIPCHK(hipMemsetAsync(b_bad.get(), 0, sizeof(unsigned long long), c->stream));
+    const hml_post_args a = post_args_of(c, out.t);
+    by_states(K, [&](auto km) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_count_terms<km()>), dim3((B + 63u) / 64u), dim3(64), ((size_t)K * K + K) * sizeof(double), c->stream, a,
+                           out.post.beta.as<double>(), out.v.as<double>(), out.rho.as<double>(), b_bad.as<unsigned long long>());
+    });
+    KLAUNCH_CHECK();
+    unsigned long long n_bad = 0;
+    HIPCHK(hipMemcpyAsync(&n_bad, b_bad.get(), sizeof n_bad, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    out.bad = n_bad;
+    out.B = B;
+    return 0;
+}
+
+extern "C" {
+
+int hml_posterior_region_counts(hml_ctx* c, uint64_t n, const uint32_t* start, const uint32_t* end, uint32_t max_breaks, double* hist, double* whole_state, double* avoid,
+                                uint64_t* count_degenerate) {
+    NEED_MODEL();
+    if (n && (!start || !end)) return set_err(HML_ERR_ARG, "null argument");
+    const int K = c->K;
+    if (!hml_counts_h_ok(K, max_breaks)) {
+        char buf[176];
+        snprintf(buf, sizeof buf, "hml_posterior_region_counts: " HML_COUNTS_H_RULE " (K = %d, max_breaks = %u)", K, max_breaks);
+        return set_err(HML_ERR_ARG, buf);
+    }
+    for (uint64_t i = 0; i < n; ++i)
+        if (!hml_pairs_region_ok(start[i], end[i], c->T)) {
+            char buf[176];
+            snprintf(buf, sizeof buf, "hml_posterior_region_counts: region %llu is [%u, %u): it must hold a position and end at or before T = %llu", (unsigned long long)i,
+                     start[i], end[i], (unsigned long long)c->T);
+            return set_err(HML_ERR_ARG, buf);
+        }
+    counts_result cr;
+    if (int r = counts_compute(c, cr)) return r;
+    unsigned long long h_info[2] = {0ull, 0ull};
+    if (n) {
+        const uint32_t H = max_breaks;
+        const uint64_t nh = n * (uint64_t)(H + 1u), nk = n * (uint64_t)K;
+        DevBuf b_st, b_en, b_hist, b_ws, b_av, b_info;
+        HIPCHK(b_st.alloc(n * sizeof(uint32_t)));
+        HIPCHK(b_en.alloc(n * sizeof(uint32_t)));
+        HIPCHK(b_hist.alloc(nh * sizeof(double)));
+        HIPCHK(b_ws.alloc(nk * sizeof(double)));
+        HIPCHK(b_av.alloc(nk * sizeof(double)));
+        HIPCHK(b_info.alloc(sizeof h_info));
+        HIPCHK(hipMemcpyAsync(b_st.get(), start, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(b_en.get(), end, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemsetAsync(b_info.get(), 0, sizeof h_info, c->stream));
+        const hml_post_args a = post_args_of(c, cr.t);
+        hml_count_walk_args w;
+        w.alpha = cr.post.alpha.as<double>(); w.beta = cr.post.beta.as<double>(); w.v = cr.v.as<double>(); w.rho = cr.rho.as<double>();
+        w.rg_start = b_st.as<uint32_t>(); w.rg_end = b_en.as<uint32_t>(); w.n = n; w.H = H;
+        w.hist = b_hist.as<double>(); w.whole_state = b_ws.as<double>(); w.avoid = b_av.as<double>(); w.info = b_info.as<unsigned long long>();
+        const size_t staged = ((size_t)K * K + 3u * K) * sizeof(double);   // A, pi, v_b, rho_b
+        const unsigned grid = (unsigned)grid_for(n, 1, 1, 4096), slices = (unsigned)((K + HML_COUNTS_SLICE - 1) / HML_COUNTS_SLICE);
+        const int slice_states = K < HML_COUNTS_SLICE ? K : HML_COUNTS_SLICE;
+        by_lane_cells(K * (int)(H + 1u), [&](auto nc) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_count_walk<nc()>), dim3(grid), dim3(64), staged + (size_t)K * (H + 1u) * sizeof(double), c->stream, a, w);
+        });
+        by_lane_cells(K * slice_states, [&](auto nc) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(hml_k_count_avoid<nc()>), dim3(grid, slices), dim3(64), staged + (size_t)K * slice_states * sizeof(double), c->stream, a, w);
+        });
+        KLAUNCH_CHECK();
+        if (hist) HIPCHK(hipMemcpyAsync(hist, b_hist.get(), nh * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (whole_state) HIPCHK(hipMemcpyAsync(whole_state, b_ws.get(), nk * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (avoid) HIPCHK(hipMemcpyAsync(avoid, b_av.get(), nk * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(h_info, b_info.get(), sizeof h_info, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));   // (the scratch goes with this frame)
+    }
+    if (count_degenerate) *count_degenerate = cr.bad;
+    c->counts.done = true;
+    c->counts.regions = n; c->counts.steps = h_info[0]; c->counts.longest = h_info[1];
+    return 0;
+}
+
+int hml_posterior_count_terms(hml_ctx* c, double* v, double* rho) {
+    NEED_MODEL();
+    counts_result cr;
+    if (int r = counts_compute(c, cr)) return r;
+    const uint64_t words = (uint64_t)cr.B * c->K;
+    if (v) HIPCHK(hipMemcpyAsync(v, cr.v.get(), words * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (rho) HIPCHK(hipMemcpyAsync(rho, cr.rho.get(), words * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int hml_posterior_counts_info(hml_ctx* c, uint64_t* regions, uint64_t* steps, uint64_t* longest) {
+    if (!c) return set_err(HML_ERR_ARG, "null context");
+    if (!c->counts.done) return set_err(HML_ERR_ARG, "hml_posterior_counts_info: nothing was computed yet");
+    if (regions) *regions = c->counts.regions;
+    if (steps) *steps = c->counts.steps;
+    if (longest) *longest = c->counts.longest;
     return 0;
 }
 

@@ -7,7 +7,7 @@
 // means.  Their files are described where they are written: include/hammlet/Recorded.hpp (`-O L`, R, BP, CS, LB, LC, RG: what the
 // contexts recorded over their sweeps - levels, the chains' agreement on them, breakpoints, the consensus segmentation, level
 // bands and their calls, joint posteriors over the regions of `-regions FILE`), Viterbi.hpp (`-O V`), Posterior.hpp (`-O PD`, PB,
-// PR: exact under the chain's final parameters), Fit.hpp (`-em`, `-em-starts`, `-O EM`, EMS: the fit runs before the other
+// PR, PC: exact under the chain's final parameters), Fit.hpp (`-em`, `-em-starts`, `-O EM`, EMS: the fit runs before the other
 // end-of-run outputs, which are then under the fitted parameters), History.hpp (`-O H`, HS) and Records.hpp (the reference's files
 // and `-O X`, PREFIXmaxsegmentationSUFFIX).  -raw FILE reads float32 values instead of text; -device N selects
 // the GPU; -chain N selects the Philox sub-key of an independent chain; -chains N runs N independent chains (sub-keys
@@ -77,6 +77,10 @@ static const char* kHelp =
     "                                 number of breakpoints; then per draw: index, segments, score in nats; with -regions, then\n"
     "                                 per region: start, end, the mean number of breakpoints inside it over the draws, the draws\n"
     "                                 with 0, 1, ... 7 and with 8 or more of them, the label (extension; needs -psample)\n"
+    "                    PC           posteriorcounts: per region of -regions, tab-separated: start, end, the exact posterior\n"
+    "                                 probabilities of 0, 1, ... H - 1 and of H or more breakpoints inside it (H of -pcounts),\n"
+    "                                 then per state the probability that no position of the region is in it; under the\n"
+    "                                 parameters of -O PD; with -chains N one file per chain (extension)\n"
     "                    EM           em: the fit of -em - one line per step: step, objective; then the reason it stopped, the\n"
     "                                 parameters kept for want of support, and the fitted means, variances, A and pi; with\n"
     "                                 -chains N one file per chain (extension; needs -em); with -em-starts the winner's\n"
@@ -141,7 +145,9 @@ static const char* kHelp =
     "  -psample R [SEED]              R independent draws (1 to 2^24) of whole state paths from p(q|y,theta) under the chain's\n"
     "                                 final (or -em fitted) parameters for -O PS and -O PSS; draw r depends on SEED (default: the\n"
     "                                 seed of -R) and r alone (extension)\n"
-    "  -regions FILE                  the regions of -O RG and -O PR, one per line: start end [label ...], positions counted from 0, the\n"
+    "  -pcounts H                     the bins of -O PC: 0, 1, ... H - 1 and H or more breakpoints; 1 to 32, and the number of\n"
+    "                                 states times (H + 1) at most 1024 (default 8) (extension)\n"
+    "  -regions FILE                  the regions of -O RG, -O PR and -O PC, one per line: start end [label ...], positions counted from 0, the\n"
     "                                 end not included; lines that begin with # and blank lines are skipped.  Regions may\n"
     "                                 overlap, nest and repeat (extension)\n"
     "  -em STEPS [TOL]                once the scheme has run, fit theta, A and pi by expectation-maximisation over the last block\n"
@@ -179,7 +185,7 @@ struct Step {
 // job wants, every file name and the refusal to overwrite.  The long flag is the file's stem: PREFIX[chainK.]nameSUFFIX.
 enum Output {
     oMarginals, oSequences, oParameters, oBlocks, oCompression, oMapping, oSegments, oMaxSegmentation, oViterbi, oPosterior, oEm, oEmStarts,
-    oPosteriorBreaks, oPosteriorRegions, oPosteriorSample, oPosteriorSampleSummary, oLevels, oBreakpoints, oConsensus, oBands, oBandCalls, oRhat, oRegions, oHistory, oHistorySummary, nrOutputs
+    oPosteriorBreaks, oPosteriorRegions, oPosteriorSample, oPosteriorSampleSummary, oPosteriorCounts, oLevels, oBreakpoints, oConsensus, oBands, oBandCalls, oRhat, oRegions, oHistory, oHistorySummary, nrOutputs
 };
 struct OutputSpec {
     Output id;
@@ -205,6 +211,7 @@ static constexpr OutputSpec kOutputs[nrOutputs] = {
     {oPosteriorRegions, "PR", "posteriorregions", true, true},
     {oPosteriorSample, "PS", "posteriorsample", true, true},
     {oPosteriorSampleSummary, "PSS", "posteriorsamplesummary", true, true},
+    {oPosteriorCounts, "PC", "posteriorcounts", true, true},
     {oLevels, "L", "levels", false, true},
     {oBreakpoints, "BP", "breakpoints", false, true},   // (B and C are the reference's blocks and compression)
     {oConsensus, "CS", "consensus", false, true},
@@ -234,6 +241,7 @@ struct Job {
     double bandCall = 0;             // -bandcall P
     double posteriorBreak = 0.5;     // -pbreak P (-O PB)
     uint64_t sampleDraws = 0, sampleSeed = 0;   // -psample R [SEED] (-O PS, PSS); 0: none
+    uint32_t countBreaks = 8;        // -pcounts H (-O PC)
     Regions regions;                 // -regions FILE (recorded when -O RG asks for them)
     vector<float> regionEdges;       // ... and their edges: those of -bands
     uint64_t historyEvery = 1;       // -history-every N (-O H, HS)
@@ -404,6 +412,8 @@ static void finishChain(const Job& job, int index, hml_ctx* ctx) {
     if (job.wants(oPosteriorSampleSummary))
         posterior.writeSampleSummaryFile(job.fileName(oPosteriorSampleSummary, index), job.sampleDraws, job.sampleSeed, job.regions.start, job.regions.end, job.regions.label,
                                          (int)job.nrStates);
+    if (job.wants(oPosteriorCounts))
+        posterior.writeCountsFile(job.fileName(oPosteriorCounts, index), job.regions.start, job.regions.end, job.countBreaks, (int)job.nrStates);
 }
 
 // the chains' histories, in chain order (hammlet/History.hpp): read through the host, whichever GPUs the chains are on
@@ -774,6 +784,17 @@ static Job parseJob(Parser& args, vector<real_t>& inputValues) {
             throw std::runtime_error("The outputs posteriorsample (PS) and posteriorsamplesummary (PSS) need a model with transitions: the scheme has mixture sweeps only!");
         if (!args.isSet("-psample")) throw std::runtime_error("The outputs posteriorsample (PS) and posteriorsamplesummary (PSS) need the draws: ask for them with -psample R [SEED]!");
     }
+    if (job.wants(oPosteriorCounts)) {
+        // an exact function of the smoothing's rows: it needs what -O PD needs
+        if (!anyFB) throw std::runtime_error("The output posteriorcounts (PC) needs a model with transitions: the scheme has mixture sweeps only!");
+        if (!args.isSet("-regions")) throw std::runtime_error("The output posteriorcounts (PC) needs the regions: give them with -regions FILE!");
+    }
+    if (job.wants(oPosteriorCounts) || args.isSet("-pcounts")) {
+        if (args.nrTokens("-pcounts") != 1) throw std::runtime_error("Not enough arguments for flag -pcounts!");
+        const char* const rule = "The argument of -pcounts must be a whole number of breakpoints, 1 to 32, and the number of states times that number plus one at most 1024!";
+        job.countBreaks = (uint32_t)wholeNumber(args.parse<double>("-pcounts", 0), 1, 32, rule);
+        if (job.nrStates * ((size_t)job.countBreaks + 1) > 1024) throw std::runtime_error(rule);
+    }
     if (args.isSet("-psample")) {
         if (args.nrTokens("-psample") < 1) throw std::runtime_error("Not enough arguments for flag -psample!");
         if (args.nrTokens("-psample") > 2) throw std::runtime_error("Too many arguments for flag -psample: R and, optionally, SEED!");
@@ -954,6 +975,7 @@ int main(int argc, const char* argv[]) {
         args.registerFlags({"-em"});
         args.registerFlags({"-em-prior"});
         args.registerFlags({"-em-starts"});
+        args.registerFlags({"-pcounts"}, "8");
         args.parseArgs();
 
         if (args.isSet("-g")) args.print();

@@ -14,6 +14,9 @@
 //   PREFIXposteriorsamplesummarySUFFIX  `-O PSS`: "draws<TAB>seed<TAB>viterbi_score<TAB>expected_breaks", then per draw
 //                           "index<TAB>segments<TAB>score" (nats); with `-regions FILE`, then per region start, end, the mean number
 //                           of breakpoints inside it, its histogram over the draws and the label
+//   PREFIXposteriorcountsSUFFIX   `-O PC` with `-pcounts H`: per region of `-regions FILE`, tab-separated: start, end, the H + 1
+//                           exact probabilities of 0, 1, ... H - 1 and of H or more breakpoints inside it, then per state the
+//                           probability that no position of the region is in it (%.17g) (hml_posterior_region_counts)
 // A thin handle over a context that something else owns (the chain's rng_t), next to Viterbi.  Every call computes anew; the
 // chain is only read.
 #ifndef HAMMLET_POSTERIOR_HPP
@@ -49,6 +52,13 @@ public:
         std::vector<double> wholeState, share;       // [n][K], row-major
         uint64_t pairDegenerate = 0;
     };
+    struct RegionCounts {
+        uint32_t maxBreaks = 0;
+        std::vector<double> hist;                 // [n][maxBreaks + 1], row-major: exactly h breakpoints; the last bin: that many or more
+        std::vector<double> wholeState, avoid;    // [n][K]: all of it in state j; no position of it in state j
+        uint64_t countDegenerate = 0;
+    };
+    struct CountsInfo { uint64_t regions = 0, steps = 0, longest = 0; };
     struct Info { uint64_t chunks = 0, L = 0, W = 0, staleForward = 0, staleBackward = 0, rounds = 0, serialChunks = 0; };
     struct Sample {
         uint64_t first = 0, blocks = 0;
@@ -118,6 +128,22 @@ public:
         check(hml_posterior_regions(mCtx, n, start.data(), end.data(), r.whole.data(), r.wholeState.data(), r.expectedBreaks.data(), r.share.data(), nullptr,
                                     &r.pairDegenerate));
         return r;
+    }
+    // per region [start[r], end[r]): the exact distribution of the number of breakpoints inside it, all of it in state j, none of
+    // it in state j (hml_posterior_region_counts); maxBreaks 1 ... 32 with K (maxBreaks + 1) <= 1024
+    RegionCounts regionCounts(const std::vector<uint32_t>& start, const std::vector<uint32_t>& end, uint32_t maxBreaks, int K) const {
+        if (start.size() != end.size()) throw std::runtime_error("Posterior::regionCounts: as many starts as ends");
+        RegionCounts r;
+        const size_t n = start.size();
+        r.maxBreaks = maxBreaks;
+        r.hist.resize(n * ((size_t)(maxBreaks <= 32u ? maxBreaks : 32u) + 1)); r.wholeState.resize(n * (size_t)K); r.avoid.resize(n * (size_t)K);
+        check(hml_posterior_region_counts(mCtx, n, start.data(), end.data(), maxBreaks, r.hist.data(), r.wholeState.data(), r.avoid.data(), &r.countDegenerate));
+        return r;
+    }
+    CountsInfo countsInfo() const {
+        CountsInfo i;
+        check(hml_posterior_counts_info(mCtx, &i.regions, &i.steps, &i.longest));
+        return i;
     }
     Info info() const {
         Info i;
@@ -248,6 +274,19 @@ public:
             for (int j = 0; j < K; ++j) out.printf("\t%.17g", r.wholeState[i * (size_t)K + j]);
             for (int j = 0; j < K; ++j) out.printf("\t%.17g", r.share[i * (size_t)K + j]);
             out.printf("\t%s\n", i < label.size() ? label[i].c_str() : "");
+        }
+        out.close();
+    }
+
+    // `-O PC`: per region "start<TAB>end<TAB>hist[0 ... maxBreaks]<TAB>avoid[0 ... K - 1]", %.17g
+    void writeCountsFile(const std::string& fn, const std::vector<uint32_t>& start, const std::vector<uint32_t>& end, uint32_t maxBreaks, int K) const {
+        const RegionCounts r = regionCounts(start, end, maxBreaks, K);
+        TextFile out(fn);
+        for (size_t i = 0; i < start.size(); ++i) {
+            out.printf("%u\t%u", start[i], end[i]);
+            for (uint32_t h = 0; h <= maxBreaks; ++h) out.printf("\t%.17g", r.hist[i * ((size_t)maxBreaks + 1) + h]);
+            for (int j = 0; j < K; ++j) out.printf("\t%.17g", r.avoid[i * (size_t)K + j]);
+            out.printf("\n");
         }
         out.close();
     }

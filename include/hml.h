@@ -670,8 +670,9 @@ int hml_posterior_pair_terms(hml_ctx* ctx, double* p /*B*/, double* r /*B*K*/, u
 
 /* ---- sampled paths: independent draws of whole state paths from p(q | y, theta) under the current parameters.  No counterpart
  * in the reference (its `sequences` file holds the dependent paths of the sweeps, each under its own parameters). ----
- * What has no closed form under a fitted model is read off such draws: the distribution of the number of breakpoints in a
- * region, how far a breakpoint can move, whether two regions change together.  A sweep cannot serve: it redraws the parameters
+ * What no exact read-out answers under a fitted model is read off such draws: how far a breakpoint can move, whether two
+ * regions change together.  (The distribution of the number of breakpoints in a region is exact: hml_posterior_region_counts
+ * below.)  A sweep cannot serve: it redraws the parameters
  * and yields one dependent path.  With alpha as smoothing defines it (forward rows, degenerate restarts included) and A widened
  * exactly to double:
  *   uniform of draw r at block b:  o = Philox4x32-10 words of hml_stream4(hml_make_key(seed, 0), HML_KIND_PSAMPLE = 8, epoch r,
@@ -708,6 +709,48 @@ int hml_posterior_sample_regions(hml_ctx* ctx, uint64_t first, uint64_t count, u
 int hml_posterior_sample_info(hml_ctx* ctx, uint64_t* draws, uint64_t* groups, uint64_t* group_size, uint64_t* chunks, uint64_t* L, uint64_t* W,
                               uint64_t* stale_first, uint64_t* rounds, uint64_t* serial_chunks);
 int hml_set_sample_batch_bytes(hml_ctx* ctx, uint64_t bytes /*0: the default, 4 GiB*/);
+
+/* ---- count read-outs of the smoothing: per region the exact distribution of the number of breakpoints, and the probability
+ * that no part of it is in a given state.  No counterpart in the reference. ----
+ * "How many breakpoints does this region hold?" as a distribution, not an expectation, and "does any part of it touch state j?" -
+ * for a copy-number user "is any part of this gene deleted?".  whole_state is "all of it is in j", share an expectation, gamma per
+ * block: none answers either.  Under fixed parameters the posterior over paths is a Markov chain over the blocks with the
+ * transitions p(q_b = j | q_{b-1} = i, y, theta) = A_ij v_b(j) / u_b(i), v and u as the pairwise read-outs above define them, and
+ * both answers are short forward recursions over the region's blocks on those transitions: exact, no draws, no Monte-Carlo
+ * error - a probability of 1e-12 is resolved.  IEEE double, + x / only, sums from 0.0 in ascending index:
+ *   per boundary b = 1 ... B - 1:  v_b(j) = e_b(j) beta_b(j);  u_b(i) = sum_k A_ik v_b(k);  rho_b(i) = 1 / u_b(i), and 0 where
+ *     u_b(i) is not a positive finite number - for this purpose: not a finite number of at least 2^-1000, so that no later
+ *     product can overflow: the pair (b, i) is counted in count_degenerate and the mass leaving state i there is lost rather
+ *     than turned into a not-a-number.  A v_b(j) that is not a finite non-negative number (e_b(j) is a not-a-number) is
+ *     replaced by 0 once u_b is formed - every rho_b is 0 then.  Block 0 has no boundary: v_0 = rho_0 = 0.
+ *   per region [start, end), ba and be as in hml_posterior_regions, H = max_breaks:
+ *     count cells   f(j, 0) = gamma_ba(j), f(j, h > 0) = 0;  for b = ba + 1 ... be, with phi(i, h) = f(i, h) rho_b(i):
+ *                   f'(j, h) = (A_jj phi(j, h) + s(j, h)) v_b(j);  s(j, 0) = 0, s(j, h) = sum_{i != j} A_ij src(i, h);
+ *                   src(i, h) = phi(i, h - 1) for 1 <= h < H, src(i, H) = phi(i, H - 1) + phi(i, H): the last bin absorbs
+ *     hist[h]        = sum_j f(j, h) after block be: the probability of exactly h breakpoints inside the region; h = H: H or more
+ *     whole_state[j] = f(j, 0): all of it in state j - the unquantised sibling of hml_posterior_regions' value
+ *     avoidance cells, per struck-out state x:  g_x(i) = gamma_ba(i) for i != x, 0 at x;
+ *                   g'_x(i) = (sum_{k != x} A_ki (g_x(k) rho_b(k))) v_b(i) for i != x, 0 at x
+ *     avoid[x]       = sum_{i != x} g_x(i) after block be: the probability that no position of the region is in state x.  That
+ *                      it touches x is 1 - avoid[x], exact to 2^-53 absolute; a small avoid[x] keeps its relative precision.
+ *   Every operation is on non-negative numbers: nothing cancels, and a value is off by about its chain's operation count times
+ *   2^-53 relative.  Without degenerate boundaries sum_h hist[h] = 1 up to rounding; otherwise the shortfall is the lost mass.
+ *   No output holds a not-a-number.  hammlet_amd/csrc/hml_counts_ref.h states every step and restates it for one host thread;
+ *   the device gives those very words.
+ * The regions are arguments, as hml_posterior_regions' are: in any order, overlapping or repeated; start >= end or end > T is
+ * HML_ERR_ARG naming the region; n = 0 succeeds; any output may be NULL.  max_breaks must be 1 ... 32 with
+ * K (max_breaks + 1) <= 1024 - 32 up to 31 states, 15 at 64 - and is HML_ERR_ARG otherwise.  The other refusals are
+ * hml_posterior's (a halted chain, no blocks, no model).  The chain is only read.  Device memory - 2 K 8 bytes per block on top of
+ * the smoothing's - is local to a call and released before it returns.  Options "posterior_L", "posterior_W" and
+ * "posterior_rounds" stay launch geometry only: no output word depends on them.
+ * Cost: a region is a serial chain of be - ba steps, one wavefront walking it.  The call is meant for many regions of gene or
+ * segment size; one region over a whole trace of 10^6 blocks is legal and slow.
+ * hml_posterior_count_terms: v and rho themselves (probe; either may be NULL).  hml_posterior_counts_info: of the last
+ * hml_posterior_region_counts - its regions, the sum of be - ba over them and the largest be - ba. */
+int hml_posterior_region_counts(hml_ctx* ctx, uint64_t n, const uint32_t* start /*n*/, const uint32_t* end /*n*/, uint32_t max_breaks /*H*/,
+                                double* hist /*n*(H+1)*/, double* whole_state /*n*K*/, double* avoid /*n*K*/, uint64_t* count_degenerate);
+int hml_posterior_count_terms(hml_ctx* ctx, double* v /*B*K*/, double* rho /*B*K*/);                    /* probe */
+int hml_posterior_counts_info(hml_ctx* ctx, uint64_t* regions, uint64_t* steps, uint64_t* longest);     /* of the last call */
 
 /* ---- sparse payloads: levels, breakpoints and bands across GPUs.  No counterpart in the reference. ----
  * The three recordings above keep a cell and a boundary bit per change of state, so what another GPU needs of one is a list:
